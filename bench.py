@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: CLEVR questions/sec of one joint_training step on MI355X (BASELINE.json `metric`).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` and the headline step's own figures); every other measurement below
+(roofline, CPU baseline, kernel reports, collectives, side configurations) runs only with `--full`.
+`--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy (dump_outputs).
 
 (N > 1: one process per GPU over RCCL -- under torch.distributed.run as the driver starts it, or on its own: without
 WORLD_SIZE in the environment the script launches its N ranks itself.)
@@ -26,7 +31,7 @@ the NMN skips -- a step without its heaviest part).  `config.valid_program_fract
 Inputs are resident in HBM before the timed region; the sampled programs travel device -> host every
 step because they decide the NMN launch schedule (the one sync the algorithm itself requires).
 
-Besides the contract fields the JSON line carries
+With --full the JSON line also carries
   roofline       for the kernel family with the largest share of step time (conv_nhwc: forward +
                  data gradients of every 3x3 / 1x1 conv of the NMN): algorithmic FLOPs / launch time
                  measured with events on the launch stream in separate instrumented steps, against
@@ -736,6 +741,48 @@ def extraction_side(dev, n=128, k=5):
                         "70 000 training images = %.0f s" % (n, 70000 * dt / n)}
 
 
+DUMP_SAMPLE = 4096  # parameter elements per tensor in the dump (all of a smaller tensor)
+
+
+def dump_outputs(directory, out, models, rank):
+    """--dump-outputs: what the timed path computed in its last step, as DIR/<name>.npy -- the arrays JointTrainingStep.step
+    returned (losses, ELBO terms, objective: float64; the sampled programs: float32 token ids) and, per trained model, a
+    fixed sample of the parameters that step updated (float32; per tensor in named_parameters order, DUMP_SAMPLE indices
+    drawn from a generator seeded 0, so two builds dump the same elements).  Rank r > 0 writes under DIR/rank<r>."""
+    import numpy as np
+
+    if rank:
+        directory = os.path.join(directory, "rank%d" % rank)
+    os.makedirs(directory, exist_ok=True)
+    arrays = {}
+
+    def walk(prefix, v):
+        if isinstance(v, dict):
+            for k, x in v.items():
+                walk(prefix + [k], x)
+        elif torch.is_tensor(v):
+            a = v.detach().cpu()
+            arrays[".".join(prefix)] = a.double().numpy() if a.dim() == 0 else a.float().numpy()
+
+    walk([], {k: v for k, v in out.items() if k != "pg"})  # ("pg": the generator's loss and the same programs again)
+    for name, model in models:
+        g = torch.Generator().manual_seed(0)
+        parts = []
+        for p in model.parameters():
+            if not p.requires_grad:
+                continue
+            flat = p.detach().reshape(-1)
+            if flat.numel() > DUMP_SAMPLE:
+                flat = flat[torch.randint(0, flat.numel(), (DUMP_SAMPLE,), generator=g).to(flat.device)]
+            parts.append(flat.float().cpu())
+        arrays["params.%s" % name] = torch.cat(parts).numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, total
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    log("outputs of the last timed step: %d arrays, %.1f MB -> %s" % (len(arrays), total / 1e6, directory))
+
+
 def self_launch(args):
     """`python bench.py --gpus N` outside torch.distributed.run: start the N ranks ourselves (one process per GPU,
     rendezvous on 127.0.0.1) with the same arguments, pass their output through and exit with their status."""
@@ -923,6 +970,11 @@ def main():
     ap.add_argument("--no-extras-but-ingest", action="store_true", help="of the side measurements only joint_training_ingest")
     ap.add_argument("--sides", default=None, help="comma-separated side measurements to run (default: all); A/B aid")
     ap.add_argument("--extras", action="store_true", help="N > 1: run the single-GPU side measurements too (default: N = 1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: collectives (N > 1), roofline, CPU baseline, kernel reports and the "
+                         "side measurements (the --no-* / --sides options select among them); off: the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (see dump_outputs)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -995,7 +1047,7 @@ def main():
     trainer = JointTrainingStep(pg, qr, prior, nmn, **JOINT)
     parallel.broadcast_parameters(trainer.optimizer.arenas, trainer.optimizer.loose)
     sds = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sds = {"pg": cpu_state(pg), "qr": cpu_state(qr), "prior": cpu_state(prior), "nmn": cpu_state(nmn)}
 
     # set-up, like the generator fit above: a few iterations so that what only happens at the start of a
@@ -1013,19 +1065,23 @@ def main():
         trainer.step(batch)
     torch.cuda.synchronize()
     log("joint_training: warmup + %d timed steps" % args.steps)
-    elapsed, host, blocked = timed(lambda: trainer.step(batch), args.steps, args.warmup, dev, world, trainer)
+    last = {}  # (--dump-outputs: what the last step returned)
+    step_fn = (lambda: last.update(out=trainer.step(batch))) if args.dump_outputs else (lambda: trainer.step(batch))
+    elapsed, host, blocked = timed(step_fn, args.steps, args.warmup, dev, world, trainer)
     log("timed region: %.3f s for %d steps" % (elapsed, args.steps))
+    if args.dump_outputs:  # (before --full's instrumented steps move the parameters)
+        dump_outputs(args.dump_outputs, last["out"], (("pg", pg), ("qr", qr), ("nmn", nmn)), rank)
     prims = nmn.engine.last_plan.n_prims if nmn.engine.last_plan else None
 
     collectives = None
-    if world > 1:
+    if args.full and world > 1:
         try:  # every rank takes part
             collectives = collective_report(trainer, lambda: trainer.step(batch), dev, world)
         except Exception as exc:
             collectives = {"error": "%s: %s" % (type(exc).__name__, exc)}
 
     roof = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         # every rank runs the instrumented steps (they contain the step's collectives); rank 0 reports
         agg = kernel_rooflines(nmn.engine, lambda: (launch_guard.beat(), trainer.step(batch)), passes=args.roofline_passes, trainer=trainer)
         if rank == 0:
@@ -1042,13 +1098,13 @@ def main():
             cpu1 = {"error": "%s: %s" % (type(exc).__name__, exc)}
 
     recurrent = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         try:
             recurrent = recurrent_kernel_report(dev)
         except Exception as exc:  # a side report must not take the headline line down
             recurrent = {"error": "%s: %s" % (type(exc).__name__, exc)}
     hbm_kernels = None
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         try:  # (after every timed run of the headline: the optimiser steps below move its parameters)
             # (the optimiser is timed at N = 1 only: stepping rank 0 alone would let its replica drift from the others)
             hbm_kernels = hbm_kernel_report(dev, trainer.optimizer if world == 1 else None)
@@ -1061,7 +1117,7 @@ def main():
     def on(name):
         return chosen is None or name in chosen
 
-    want_extras = not args.no_extras and not args.no_extras_but_ingest and (world == 1 or args.extras)
+    want_extras = args.full and not args.no_extras and not args.no_extras_but_ingest and (world == 1 or args.extras)
 
     def side(name, metric, workload, n, make, k=10):
         if not on(name):
@@ -1080,7 +1136,7 @@ def main():
         except Exception as exc:  # the headline line must survive a failure of a side measurement
             extras[name] = {"error": "%s: %s" % (type(exc).__name__, exc)}
 
-    if not args.no_extras and world > 1 and args.scaling == "strong":
+    if args.full and not args.no_extras and world > 1 and args.scaling == "strong":
         # weak scaling beside the strong-scaling headline: the one-GPU workload (all of --batch) on EVERY rank
         side("weak_scaling", "CLEVR questions/sec (joint_training step)",
              "joint_training_ours.yml, %d questions per GPU (global batch %d): per-GPU work fixed as N grows" % (total, total * world),
@@ -1099,7 +1155,7 @@ def main():
                 log("joint_training_28x28: %.1f questions/s" % extras["joint_training_28x28"]["value"])
         except Exception as exc:
             extras["joint_training_28x28"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
-    if not args.no_extras and args.ingest_rows > 0 and on("joint_training_ingest"):
+    if args.full and not args.no_extras and args.ingest_rows > 0 and on("joint_training_ingest"):
         try:
             extras["joint_training_ingest"] = ingest_side(vocab, trainer, dev, rank, world, args, elapsed / args.steps * 1e3)
             log("joint_training_ingest: %.1f questions/s" % extras["joint_training_ingest"]["value"])

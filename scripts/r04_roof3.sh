@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 python -c "import torch" >/dev/null 2>&1
 for i in 1 2 3; do
-timeout 500 python bench.py --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+timeout 500 python bench.py --full --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])
 r=d['roofline']

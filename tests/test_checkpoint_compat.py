@@ -1,31 +1,49 @@
-"""a checkpoint written by the REFERENCE (its NeuralModuleNetwork + the torch.optim.Adam and
+"""a checkpoint in the REFERENCE's layout (its NeuralModuleNetwork + the torch.optim.Adam and
 ReduceLROnPlateau its trainer builds, saved in CheckpointManager's layout -- probnmn/utils/checkpointing.py
 :68-105, trainers/_trainer.py:103-130) loads into this build's NMN and ModuleTrainingStep: parameters by name,
-Adam moments by position (same parameter order), step count, learning rate and scheduler state.  Build
-container only (needs /root/reference); in a fresh interpreter because it installs import stand-ins."""
+Adam moments by position (same parameter order), step count, learning rate and scheduler state; and this build's
+checkpoint loads back into that layout.  The reference's model is stood in for by a module of exactly its layout
+(tests/golden/nmn_reference_layout.json, written from the real reference by oracle/make_checkpoint_layout.py: every
+state_dict key and shape in order, parameters in parameters() order) -- the model's values play no part, the optimizer
+and scheduler are torch's own.  In a fresh interpreter, as the product package is imported there."""
 import os
 import subprocess
 import sys
 import textwrap
 
-import pytest
-
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+LAYOUT = os.path.join(ROOT, "tests", "golden", "nmn_reference_layout.json")
 
 SCRIPT = textwrap.dedent('''
     import os, sys
     ROOT = sys.argv[1]
     sys.path[:0] = [ROOT, os.path.join(ROOT, "probnmn-clevr_amd")]
+    import json
     import torch
-    from oracle import make_golden as mg
-    mg._install_shims()
-    mg._load("probnmn.modules.nmn_modules", "probnmn/modules/nmn_modules.py")
-    ref_nmn = mg._load("probnmn.models.nmn", "probnmn/models/nmn.py")
-    dims = dict(class_projection_channels=128, classifier_linear_size=32)
-    vocab = mg._Vocab(mg.namespaces())
+    layout = json.load(open(sys.argv[3]))
+    dims = layout["dims"]
+
+    def reference_layout_module():
+        """An nn.Module whose state_dict keys, shapes and parameters() order are the reference NMN's."""
+        root = torch.nn.Module()
+        for key, shape, dtype in layout["state_dict"]:
+            *path, leaf = key.split(".")
+            mod = root
+            for part in path:
+                if not hasattr(mod, part):
+                    mod.add_module(part, torch.nn.Module())
+                mod = getattr(mod, part)
+            t = torch.randn(shape).to(getattr(torch, dtype))
+            if key in layout["parameters"]:
+                mod.register_parameter(leaf, torch.nn.Parameter(t))
+            else:
+                mod.register_buffer(leaf, t)
+        assert [k for k, _ in root.named_parameters()] == layout["parameters"]
+        assert [k for k in root.state_dict()] == [e[0] for e in layout["state_dict"]]
+        return root
+
     torch.manual_seed(3)
-    ref = ref_nmn.NeuralModuleNetwork(vocab, **dims)
+    ref = reference_layout_module()
     adam = torch.optim.Adam(ref.parameters(), lr=1e-4, weight_decay=0.0)
     sched = torch.optim.lr_scheduler.ReduceLROnPlateau(adam, mode="max", factor=0.5, patience=0, threshold=1e-3)
     g = torch.Generator().manual_seed(4)
@@ -67,8 +85,8 @@ SCRIPT = textwrap.dedent('''
     assert torch.equal(eng.arena.view_of(m, name), ref_state[0]["exp_avg"])
     # and the way back: this build's checkpoint loads into the reference's model and optimizer
     ck = step.state_dict()
-    ref2 = ref_nmn.NeuralModuleNetwork(vocab, **dims)
-    ref2.load_state_dict(ck["nmn"])
+    ref2 = reference_layout_module()
+    ref2.load_state_dict(ck["nmn"])  # (strict: the same keys, each of the reference's shape)
     adam2 = torch.optim.Adam(ref2.parameters(), lr=1.0)
     adam2.load_state_dict(ck["optimizer"])
     assert adam2.param_groups[0]["lr"] == 5e-5
@@ -77,7 +95,6 @@ SCRIPT = textwrap.dedent('''
 ''')
 
 
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "probnmn")), reason="needs the reference (build container only)")
 def test_reference_checkpoint_round_trip(tmp_path):
-    r = subprocess.run([sys.executable, "-c", SCRIPT, ROOT, str(tmp_path)], capture_output=True, text=True, timeout=600)
+    r = subprocess.run([sys.executable, "-c", SCRIPT, ROOT, str(tmp_path), LAYOUT], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0 and "CKPT-OK" in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
