@@ -470,7 +470,9 @@ int pnmn_cluster_reserve_cus(int cus);
  *             LSTM cell; [sample != 0: logits = h W_p^T + b_p, token choice, next xe from etable]
  *   W_ih of the reference's LSTMCell is [W_c | W_e] (input = cat(ctx, embedding)); xe / etable carry
  *   the embedding half plus both biases.  sample: 0 teacher forced (xe; or xe == NULL and step t's
- *   input taken as row in_tokens[b * in_token_stride + t] of etable), 1 sample, 2 greedy.
+ *   input taken as row in_tokens[b * in_token_stride + t] of etable), 1 sample, 2 greedy: the token choice of
+ *   pnmn_sample_tokens (same Philox stream, counter (row_offset + b, t); same rule for rows that are not all finite,
+ *   so a token is always in [0, V)).
  *   saved for backward: act, cs, hs, ctx, probs (softmax before masking).
  * backward: dhs (gradient wrt every h_t) -> dgates (= d xe), denc (+=, zero on entry), dh0.
  * S <= 64 encoder positions, V <= 128 sampled vocabulary.
@@ -561,6 +563,14 @@ int pnmn_attn_denc(const float* weights, const float* dscore, const float* dctx,
  *             (row_offset + b, step) -- shard-invariant under data parallelism)
  *   logprobs[b] = log_softmax(logits[b])[tokens[b]]            (unmodified distribution)
  * V <= 512.
+ * Token choice is always an index in [0, V), also for rows that are not all finite (the same rule in the decoder kernels):
+ *   greedy:   torch.argmax semantics -- a NaN counts as the maximum, the first index wins.
+ *   sampling, no NaN or +inf in the row but the allowed weights underflow to a total of 0: the weights are recomputed
+ *             relative to the largest allowed logit (the same distribution without the underflow).
+ *   sampling, a NaN or +inf in the row, or every allowed logit -inf: the first allowed index with the largest logit,
+ *             a NaN counting as the largest; logprobs stays log_softmax(logits[b])[tokens[b]] (NaN propagates).
+ *   no allowed token (V <= 3, pad / unk / start cover the row): the greedy choice.
+ * A finite row with a positive allowed total never reaches these rules (its draw does not change).
  * ------------------------------------------------------------------------------------------- */
 int pnmn_sample_tokens(const float* logits, int64_t* tokens, float* logprobs, int B, int V,
                        int greedy, uint64_t seed, uint64_t row_offset, uint32_t step, int pad_index,

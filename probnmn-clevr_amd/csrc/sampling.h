@@ -55,9 +55,93 @@ __device__ inline float philox_uniform(uint64_t seed, uint64_t row, uint32_t ste
     return (float)(ctr[0] >> 8) * (1.0f / 16777216.0f);
 }
 
+// Inverse-CDF scan of one row's weights `w` (chunk k of a lane = index lane + 64k, index order): the first index with
+// w > 0 whose inclusive prefix sum exceeds `target`; the last index with w > 0 when round-off leaves the target past the
+// end; -1 when no weight is > 0.  Wave-uniform.
+template <int K>
+__device__ __forceinline__ int inverse_cdf(const float (&w)[K], float target) {
+    const int lane = threadIdx.x & 63;
+    float before = 0.f;
+    int choice = -1, last_ok = -1;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        float inc = w[k];  // inclusive prefix sum over lanes
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const float tt = __shfl_up(inc, o);
+            if (lane >= o) inc += tt;
+        }
+        const unsigned long long hit = __ballot((w[k] > 0.f) && (before + inc > target));
+        if (choice < 0 && hit) choice = 64 * k + (int)__ffsll((long long)hit) - 1;
+        const unsigned long long pos = __ballot(w[k] > 0.f);
+        if (pos) last_ok = 64 * k + 63 - __clzll((long long)pos);
+        before += __shfl(inc, 63);
+    }
+    return choice < 0 ? last_ok : choice;
+}
+
+// First index j < V with ok(j) of the largest v, a NaN counting as larger than any number (torch.argmax); -1 when no
+// index is ok.  Wave-uniform.
+template <int K, typename Ok>
+__device__ inline int first_argmax(const float (&v)[K], Ok ok) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const unsigned long long nan = __ballot(ok(lane + 64 * k) && v[k] != v[k]);
+        if (nan) return 64 * k + (int)__ffsll((long long)nan) - 1;
+    }
+    float m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < K; ++k)
+        if (ok(lane + 64 * k)) m = fmaxf(m, v[k]);
+    m = wmax(m);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const unsigned long long hit = __ballot(ok(lane + 64 * k) && v[k] == m);
+        if (hit) return 64 * k + (int)__ffsll((long long)hit) - 1;
+    }
+    return -1;
+}
+
+// The token of a row the common path cannot serve (the rule is documented beside pnmn_sample_tokens in
+// include/probnmn_hip.h): greedy over a row with a NaN; sampling over a row with a NaN or +inf, or whose allowed weights
+// sum to 0.  `v` holds the row (entries j >= V are -inf), `u` the row's uniform.  Reached only through a wave-uniform
+// branch that a finite row with positive allowed mass never takes.
+template <int K>
+__device__ inline int choose_token_fallback(const float (&v)[K], int V, bool greedy, int pad, int unk, int start, float u) {
+    const int lane = threadIdx.x & 63;
+    const auto in_row = [V](int j) { return j < V; };
+    const auto allowed = [=](int j) { return j < V && j != pad && j != unk && j != start; };
+    if (!greedy) {
+        bool bad = false;  // a NaN or +inf in the row
+        float m = -INFINITY;  // largest allowed logit
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const int j = lane + 64 * k;
+            if (j < V) bad |= !(v[k] < INFINITY);
+            if (allowed(j)) m = fmaxf(m, v[k]);
+        }
+        m = wmax(m);
+        if (!__ballot(bad) && m > -INFINITY) {
+            // finite row whose allowed weights underflowed: the same distribution relative to its largest allowed logit
+            float w[K], tot = 0.f;
+#pragma unroll
+            for (int k = 0; k < K; ++k) {
+                w[k] = allowed(lane + 64 * k) ? expf(v[k] - m) : 0.f;
+                tot += w[k];
+            }
+            return inverse_cdf(w, u * wsum(tot));
+        }
+        const int c = first_argmax(v, allowed);
+        if (c >= 0) return c;
+    }
+    return first_argmax(v, in_row);  // greedy, or no allowed token at all
+}
+
 // One wave picks one row's token from `logits` (LDS, V <= 128 entries): mode 2 = first arg-max,
 // mode 1 = inverse-CDF draw from softmax(logits) with pad / unk / start removed (reference
-// seq2seq_base.py:203-220).  The result is wave-uniform.
+// seq2seq_base.py:203-220); rows that are not all finite follow choose_token_fallback.  The result is
+// wave-uniform and always in [0, V).
 __device__ inline int choose_row_token(const float* logits, int V, int mode, int pad, int unk, int start, uint64_t seed,
                                        uint64_t global_row, uint32_t t) {
     const int lane = threadIdx.x & 63;
@@ -82,6 +166,7 @@ __device__ inline int choose_row_token(const float* logits, int V, int mode, int
             best = other < best ? other : best;
         }
         choice = best;
+        if (__ballot(v[0] != v[0] || v[1] != v[1])) choice = choose_token_fallback(v, V, true, pad, unk, start, 0.f);
     } else {
         float se = 0.f;
 #pragma unroll
@@ -96,27 +181,13 @@ __device__ inline int choose_row_token(const float* logits, int V, int mode, int
             tot += w[k];
         }
         tot = wsum(tot);
-        const float target = philox_uniform(seed, global_row, t) * tot;
-        float before = 0.f;
-        choice = -1;
-        int last_ok = -1;
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            float inc = w[k];
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const float tt = __shfl_up(inc, o);
-                if (lane >= o) inc += tt;
-            }
-            const unsigned long long hit = __ballot((w[k] > 0.f) && (before + inc > target));
-            if (choice < 0 && hit) choice = 64 * k + (int)__ffsll((long long)hit) - 1;
-            const unsigned long long pos = __ballot(w[k] > 0.f);
-            if (pos) last_ok = 64 * k + 63 - __clzll((long long)pos);
-            before += __shfl(inc, 63);
-        }
-        if (choice < 0) choice = last_ok;
+        const float u = philox_uniform(seed, global_row, t);
+        if (tot > 0.f)  // (a NaN or +inf anywhere in the row makes the total NaN)
+            choice = inverse_cdf(w, u * tot);
+        else
+            choice = choose_token_fallback(v, V, false, pad, unk, start, u);
     }
-    return choice;
+    return min(max(choice, 0), V - 1);
 }
 
 }  // namespace pnmn

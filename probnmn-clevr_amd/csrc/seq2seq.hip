@@ -66,30 +66,7 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* __restr
     dc_prev[idx] = dc * f;
 }
 
-// ---- Philox4x32-10 (Salmon et al. 2011), one draw per (seed, row, step) ------------------------------
-__device__ __forceinline__ void philox_round(uint32_t (&ctr)[4], uint32_t k0, uint32_t k1) {
-    const uint64_t p0 = (uint64_t)0xD2511F53u * ctr[0];
-    const uint64_t p1 = (uint64_t)0xCD9E8D57u * ctr[2];
-    const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
-    const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-    ctr[0] = hi1 ^ ctr[1] ^ k0;
-    ctr[1] = lo1;
-    ctr[2] = hi0 ^ ctr[3] ^ k1;
-    ctr[3] = lo0;
-}
-
-__device__ float philox_uniform(uint64_t seed, uint64_t row, uint32_t step) {
-    uint32_t ctr[4] = {(uint32_t)row, (uint32_t)(row >> 32), step, 0x9E3779B9u};
-    uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        philox_round(ctr, k0, k1);
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return (float)(ctr[0] >> 8) * (1.0f / 16777216.0f);  // [0, 1)
-}
-
+// one draw per (seed, row, step): pnmn::philox_uniform (sampling.h), the stream the decoder kernels draw from
 __device__ __forceinline__ float wave_max(float v) { return pnmn::wmax(v); }  // (the decoder kernels' DPP reductions:
 __device__ __forceinline__ float wave_sum(float v) { return pnmn::wsum(v); }  //  same summation order, same tokens)
 
@@ -132,6 +109,8 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
             best = other < best ? other : best;
         }
         choice = best;
+        if (!(lse == lse))  // a NaN, +inf or nothing but -inf in the row: a NaN, if any, is the maximum
+            choice = pnmn::choose_token_fallback(v, V, true, pad, unk, start, 0.f);
     } else {
         // weights = softmax with the forbidden tokens zeroed (seq2seq_base.py:212-214); inverse CDF
         float w[MAXV];
@@ -144,29 +123,14 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
             tot += w[k];
         }
         tot = wave_sum(tot);
-        const float target = philox_uniform(seed, row_offset + (uint64_t)row, step) * tot;
-        // token order = index order: chunk k holds indices [64k, 64k+64); scan chunk by chunk
-        float before = 0.f;
-        choice = -1;
-        int last_ok = -1;
-#pragma unroll
-        for (int k = 0; k < MAXV; ++k) {
-            // inclusive prefix sum over lanes
-            float inc = w[k];
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const float t = __shfl_up(inc, o);
-                if (lane >= o) inc += t;
-            }
-            const bool hit = (w[k] > 0.f) && (before + inc > target);
-            const unsigned long long m = __ballot(hit);
-            if (choice < 0 && m) choice = 64 * k + (int)__ffsll((long long)m) - 1;
-            const unsigned long long pos = __ballot(w[k] > 0.f);
-            if (pos) last_ok = 64 * k + 63 - __clzll((long long)pos);
-            before += __shfl(inc, 63);
-        }
-        if (choice < 0) choice = last_ok;  // round-off at the very end of the CDF
+        // token order = index order: chunk k holds indices [64k, 64k+64)
+        const float u = pnmn::philox_uniform(seed, row_offset + (uint64_t)row, step);
+        if (tot > 0.f)  // (a NaN or +inf anywhere in the row makes the total NaN)
+            choice = pnmn::inverse_cdf(w, u * tot);
+        else
+            choice = pnmn::choose_token_fallback(v, V, false, pad, unk, start, u);
     }
+    choice = min(max(choice, 0), V - 1);
     if (lane == 0) {
         tokens[row] = choice;
         logprobs[row] = z[choice] - lse;  // from the UNMODIFIED log-softmax (seq2seq_base.py:204,220)
