@@ -800,6 +800,34 @@ int pnmn_lstm_stack_fwd(const pnmn_lstm_stack_job* jobs /* HOST */, int n, void*
 int pnmn_lstm_stack_bwd(const pnmn_lstm_stack_job* jobs /* HOST */, int n, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * LSTM dropout between an encoder's layers (csrc/lstm_dropout.hip, csrc/lstm_stack.hip, csrc/dropout.h).
+ * Replaces: nn.LSTM(..., dropout=p) in training mode (reference probnmn/modules/seq2seq_base.py:57,78;
+ *           probnmn/models/program_prior.py:42,56): the output of every layer but the last, at every step, times a mask on
+ *           its way to the next layer's input.
+ * Mask: y = x * keep * scale with scale = 1.0f / (1.0f - p) (fp32) and keep(row, t, u) from Philox4x32-10 (the generator of
+ *   pnmn_sample_tokens): key {seed lo, seed hi}, counter {row lo, row hi, t, u}, output word 0 -> u01 = (x0 >> 8) * 2^-24;
+ *   keep iff u01 < 1.0f - p (fp32).  row = row_offset + the row's index in the pass.  A dropped element is x * 0 (p = 1:
+ *   zeros).  Backward applies the same call to the gradient (the same seed and row_offset regenerate the mask).
+ * pnmn_lstm_dropout: y = mask(x) over [rows][T][H] (H % 4 == 0, 16-byte aligned; y == x allowed).
+ * pnmn_lstm_stack_{fwd,bwd}_dropout: pnmn_lstm_stack_{fwd,bwd} with one descriptor per job (drops[k] for jobs[k]; p = 0:
+ *   none).  Forward, p > 0 only on a job with dep < 0 that has a dependant: it also writes hsd = mask(hs) and the dependant
+ *   reads hsd instead of hs.  Backward, p > 0 only on a job with dep >= 0: the gradient arriving from the layer above is
+ *   masked.  When no job has p > 0 these run exactly the kernels of pnmn_lstm_stack_{fwd,bwd}.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct pnmn_lstm_dropout_desc {
+    float*   hsd;           /* forward: [B][T][H] out, the job's hs after the mask */
+    uint64_t seed;
+    int64_t  row_offset;
+    float    p;             /* in [0, 1]; 0 = no dropout on this job */
+    int32_t  reserved;
+} pnmn_lstm_dropout_desc;   /* 32 bytes */
+int pnmn_lstm_dropout(const float* x, float* y, int rows, int T, int H, float p, uint64_t seed, int64_t row_offset, void* stream);
+int pnmn_lstm_stack_fwd_dropout(const pnmn_lstm_stack_job* jobs /* HOST */, const pnmn_lstm_dropout_desc* drops /* HOST */, int n,
+                                void* workspace, void* stream);
+int pnmn_lstm_stack_bwd_dropout(const pnmn_lstm_stack_job* jobs /* HOST */, const pnmn_lstm_dropout_desc* drops /* HOST */, int n,
+                                void* workspace, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * fp32 GEMM, up to PNMN_GEMM_MAX independent problems per launch (csrc/gemm.hip).
  * Replaces: every product over all time steps that the reference reaches through nn.LSTM / nn.Linear / autograd in
  *           the seq2seq models (probnmn/modules/seq2seq_base.py:101-155 via allennlp's SimpleSeq2Seq: encoder input

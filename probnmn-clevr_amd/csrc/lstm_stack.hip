@@ -27,6 +27,7 @@
 
 #include "../../include/probnmn_hip.h"
 #include "cluster.h"
+#include "dropout.h"
 #include "lds_optin.h"
 
 namespace {
@@ -43,6 +44,18 @@ struct Jobs {
     int consumer[MAXJ];   // job that depends on this one, or -1
     float* px[MAXJ];      // backward: the job's exchange buffer [tiles][2][S][16][H]
     int n;
+};
+
+// Dropout between an encoder's layers (pnmn_lstm_stack_{fwd,bwd}_dropout), per job; read only by the DROP instantiations.
+// Forward: a FIRST job with on[k] also writes hsd = hs * keep * scale, which its consumer stages instead of hs.  Backward: a
+// BELOW job with on[k] multiplies the gradient arriving from the layer above by keep * scale (the same bits: dropout.h).
+struct Drop {
+    float* hsd[MAXJ];
+    uint64_t seed[MAXJ];
+    int64_t row_offset[MAXJ];
+    float keep_below[MAXJ];  // 1 - p
+    float scale[MAXJ];       // 1 / (1 - p)
+    int on[MAXJ];
 };
 
 // ---- hand-offs ----------------------------------------------------------------------------------------------------------
@@ -155,7 +168,8 @@ __device__ __forceinline__ void stage_rows(const float* src, int row0, int B, in
 // =========================================================================================================================
 // forward
 // =========================================================================================================================
-__global__ __launch_bounds__(512) void lstm_stack_fwd_kernel(const Jobs jobs, int* sync) {
+template <bool DROP>
+__global__ __launch_bounds__(512) void lstm_stack_fwd_kernel(const Jobs jobs, int* sync, const Drop drop) {
     constexpr int GLD = UW + 4;
     __shared__ float gl[4][LROWS][GLD];
     __shared__ __attribute__((aligned(16))) float hl[LROWS][HLD];   // h_{t-1} of this layer
@@ -186,7 +200,10 @@ __global__ __launch_bounds__(512) void lstm_stack_fwd_kernel(const Jobs jobs, in
                          : f32x4_{0.f, 0.f, 0.f, 0.f};
     }
     float creg = 0.f;  // J = UW * 16 / 512 = 1 (row, unit) pair per thread
-    const float* below = second ? jobs.j[jb.dep].hs : nullptr;
+    const float* below = second ? ((DROP && drop.on[jb.dep]) ? drop.hsd[jb.dep] : jobs.j[jb.dep].hs) : nullptr;
+    // FIRST with dropout: this thread's (row, unit) pair of the epilogue, its Philox key and the dropped copy of hs
+    const bool dp = DROP && !second && drop.on[ji];
+    float* const hsd = dp ? drop.hsd[ji] : nullptr;
     const float bias = second ? jb.bias[gate * LH + u0 + 16 * ub + li] : 0.f;
 
     // FIRST: this lane's four rows of the step inputs (see lstm_seq_fwd_cluster_kernel for the token look-ahead)
@@ -249,6 +266,10 @@ __global__ __launch_bounds__(512) void lstm_stack_fwd_kernel(const Jobs jobs, in
             if (row < B) {
                 const size_t o = ((size_t)row * T + t) * LH + u;
                 jb.hs[o] = h;
+                if (DROP && dp)  // (before the step's hand-off: the consumer's cross wait covers it)
+                    hsd[o] = pnmn::dropout_apply(h, pnmn::dropout_keep(drop.seed[ji], (uint64_t)(drop.row_offset[ji] + row), (uint32_t)t,
+                                                                       (uint32_t)u, drop.keep_below[ji]),
+                                                 drop.scale[ji]);
                 jb.cs[o] = c;
                 if (jb.act) {
                     float* ar = jb.act + ((size_t)row * T + t) * (4 * LH);
@@ -269,7 +290,8 @@ __global__ __launch_bounds__(512) void lstm_stack_fwd_kernel(const Jobs jobs, in
 // =========================================================================================================================
 // backward
 // =========================================================================================================================
-__global__ __launch_bounds__(512) void lstm_stack_bwd_kernel(const Jobs jobs, int* sync) {
+template <bool DROP>
+__global__ __launch_bounds__(512) void lstm_stack_bwd_kernel(const Jobs jobs, int* sync, const Drop drop) {
     constexpr int KB = 4 * UW / 16;      // k blocks of this workgroup's gate columns (recurrence product)
     constexpr int DLD = 4 * UW + 4;
     constexpr int XLD = 4 * LH + 4;
@@ -350,6 +372,10 @@ __global__ __launch_bounds__(512) void lstm_stack_bwd_kernel(const Jobs jobs, in
         float sum = 0.f;
 #pragma unroll
         for (int w = 0; w < 8; ++w) sum += red[w][rl][ul];  // K slices in ascending order
+        if (DROP && drop.on[ji] && row < B)  // the mask the forward pass applied between the layers (regenerated, not stored)
+            sum = pnmn::dropout_apply(sum, pnmn::dropout_keep(drop.seed[ji], (uint64_t)(drop.row_offset[ji] + row), (uint32_t)t,
+                                                              (uint32_t)u, drop.keep_below[ji]),
+                                      drop.scale[ji]);
         return sum;
     };
 
@@ -463,7 +489,32 @@ extern "C" int64_t pnmn_lstm_stack_workspace_bytes(const pnmn_lstm_stack_job* jo
     return bytes;
 }
 
-extern "C" int pnmn_lstm_stack_fwd(const pnmn_lstm_stack_job* jobs, int n, void* workspace, void* stream) {
+namespace {
+
+// Per-job dropout descriptors -> the kernels' Drop block; `any` = some job drops (else the plain instantiation runs).
+// Forward: p > 0 only on a FIRST job with a consumer, with `hsd`; backward: only on a BELOW job.
+int drop_block(const Layout& L, const pnmn_lstm_stack_job* jobs, const pnmn_lstm_dropout_desc* drops, int n, bool backward, Drop* D,
+               bool* any) {
+    *D = Drop{};
+    *any = false;
+    if (!drops) return 0;
+    for (int k = 0; k < n; ++k) {
+        const float p = drops[k].p;
+        if (!(p >= 0.f && p <= 1.f) || drops[k].row_offset < 0) return PNMN_EINVAL;
+        if (p == 0.f) continue;
+        if (backward ? jobs[k].dep < 0 : (jobs[k].dep >= 0 || L.jobs.consumer[k] < 0 || !drops[k].hsd)) return PNMN_EINVAL;
+        D->hsd[k] = drops[k].hsd;
+        D->seed[k] = drops[k].seed;
+        D->row_offset[k] = drops[k].row_offset;
+        D->keep_below[k] = 1.0f - p;
+        D->scale[k] = 1.0f / D->keep_below[k];
+        D->on[k] = 1;
+        *any = true;
+    }
+    return 0;
+}
+
+int stack_fwd(const pnmn_lstm_stack_job* jobs, const pnmn_lstm_dropout_desc* drops, int n, void* workspace, void* stream) {
     if (n <= 0) return 0;
     if (!jobs || !workspace) return PNMN_EINVAL;
     const Layout L = lay_out(jobs, n);
@@ -473,15 +524,21 @@ extern "C" int pnmn_lstm_stack_fwd(const pnmn_lstm_stack_job* jobs, int n, void*
         if (!j.w_hh || !j.hs || !j.cs) return PNMN_EINVAL;
         if (j.dep >= 0 ? (!j.w_ih || !j.bias) : !j.xp) return PNMN_EINVAL;
     }
+    Drop D;
+    bool any;
+    if (const int rc = drop_block(L, jobs, drops, n, false, &D, &any)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int* sync = nullptr;
     hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
     if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL(lstm_stack_fwd_kernel, dim3(S * L.vtiles), dim3(512), 0, st, L.jobs, sync);
+    if (any)
+        hipLaunchKernelGGL(lstm_stack_fwd_kernel<true>, dim3(S * L.vtiles), dim3(512), 0, st, L.jobs, sync, D);
+    else
+        hipLaunchKernelGGL(lstm_stack_fwd_kernel<false>, dim3(S * L.vtiles), dim3(512), 0, st, L.jobs, sync, D);
     return (int)hipGetLastError();
 }
 
-extern "C" int pnmn_lstm_stack_bwd(const pnmn_lstm_stack_job* jobs, int n, void* workspace, void* stream) {
+int stack_bwd(const pnmn_lstm_stack_job* jobs, const pnmn_lstm_dropout_desc* drops, int n, void* workspace, void* stream) {
     if (n <= 0) return 0;
     if (!jobs || !workspace) return PNMN_EINVAL;
     const Layout L = lay_out(jobs, n);
@@ -491,6 +548,9 @@ extern "C" int pnmn_lstm_stack_bwd(const pnmn_lstm_stack_job* jobs, int n, void*
         if (!j.w_hh || !j.act || !j.cs || !j.dgates) return PNMN_EINVAL;
         if (j.dep >= 0 ? !j.w_ih : !j.dhs) return PNMN_EINVAL;
     }
+    Drop D;
+    bool any;
+    if (const int rc = drop_block(L, jobs, drops, n, true, &D, &any)) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     int* sync = nullptr;
     hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
@@ -502,8 +562,34 @@ extern "C" int pnmn_lstm_stack_bwd(const pnmn_lstm_stack_job* jobs, int n, void*
         J.px[k] = reinterpret_cast<float*>(at);
         at += (size_t)((jobs[k].B + LROWS - 1) / LROWS) * 2 * S * LROWS * LH * sizeof(float);
     }
-    static std::atomic<uint64_t> cfg{0};
-    if (const int rc = pnmn::opt_in_lds(reinterpret_cast<const void*>(lstm_stack_bwd_kernel), BWD_DYN_LDS, cfg)) return rc;
-    hipLaunchKernelGGL(lstm_stack_bwd_kernel, dim3(S * L.vtiles), dim3(512), BWD_DYN_LDS, st, J, sync);
+    if (any) {
+        static std::atomic<uint64_t> cfg{0};
+        if (const int rc = pnmn::opt_in_lds(reinterpret_cast<const void*>(lstm_stack_bwd_kernel<true>), BWD_DYN_LDS, cfg)) return rc;
+        hipLaunchKernelGGL(lstm_stack_bwd_kernel<true>, dim3(S * L.vtiles), dim3(512), BWD_DYN_LDS, st, J, sync, D);
+    } else {
+        static std::atomic<uint64_t> cfg{0};
+        if (const int rc = pnmn::opt_in_lds(reinterpret_cast<const void*>(lstm_stack_bwd_kernel<false>), BWD_DYN_LDS, cfg)) return rc;
+        hipLaunchKernelGGL(lstm_stack_bwd_kernel<false>, dim3(S * L.vtiles), dim3(512), BWD_DYN_LDS, st, J, sync, D);
+    }
     return (int)hipGetLastError();
+}
+
+}  // namespace
+
+extern "C" int pnmn_lstm_stack_fwd(const pnmn_lstm_stack_job* jobs, int n, void* workspace, void* stream) {
+    return stack_fwd(jobs, nullptr, n, workspace, stream);
+}
+
+extern "C" int pnmn_lstm_stack_bwd(const pnmn_lstm_stack_job* jobs, int n, void* workspace, void* stream) {
+    return stack_bwd(jobs, nullptr, n, workspace, stream);
+}
+
+extern "C" int pnmn_lstm_stack_fwd_dropout(const pnmn_lstm_stack_job* jobs, const pnmn_lstm_dropout_desc* drops, int n, void* workspace,
+                                           void* stream) {
+    return stack_fwd(jobs, drops, n, workspace, stream);
+}
+
+extern "C" int pnmn_lstm_stack_bwd_dropout(const pnmn_lstm_stack_job* jobs, const pnmn_lstm_dropout_desc* drops, int n, void* workspace,
+                                           void* stream) {
+    return stack_bwd(jobs, drops, n, workspace, stream);
 }

@@ -113,6 +113,9 @@ SIGNATURES: Dict[str, tuple] = {
     "pnmn_lstm_stack_workspace_bytes": (_P, _I, _I),
     "pnmn_lstm_stack_fwd": (_P, _I, _P, _P),
     "pnmn_lstm_stack_bwd": (_P, _I, _P, _P),
+    "pnmn_lstm_dropout": (_P, _P, _I, _I, _I, _F, ctypes.c_uint64, ctypes.c_int64, _P),
+    "pnmn_lstm_stack_fwd_dropout": (_P, _P, _I, _P, _P),
+    "pnmn_lstm_stack_bwd_dropout": (_P, _P, _I, _P, _P),
     "pnmn_gemm": (_P, _I, _P),
     "pnmn_gemm_cus": (_P, _I, _I, _P),
     "pnmn_gemm_workspace_bytes": (_I, _I, _I),
@@ -262,6 +265,7 @@ GEMM_MAX, GEMM_A_T, GEMM_B_T, GEMM_ACC = 8, 1, 2, 4
 LSTM_STACK_JOB = np.dtype([("xp", _u64), ("tokens", _u64), ("token_stride", np.int64)] + [(n, _u64) for n in ("w_hh", "w_ih", "bias", "hs", "cs", "act", "dhs", "dgates")]
                           + [(n, _i32) for n in ("B", "T", "dep", "reserved")])  # pnmn_lstm_stack_job
 LSTM_STACK_JOBS = 6
+LSTM_DROPOUT_DESC = np.dtype([("hsd", _u64), ("seed", _u64), ("row_offset", np.int64), ("p", np.float32), ("reserved", _i32)])  # pnmn_lstm_dropout_desc
 TOKEN_SEG = np.dtype([("src", _u64), ("index", _u64), ("row_stride", np.int64), ("rows", _i32), ("width", _i32)])  # pnmn_token_seg
 EINVAL, ESHAPE, EAGAIN = -1, -2, -3  # PNMN_EINVAL / PNMN_ESHAPE / PNMN_EAGAIN
 ADAM_ITEM = np.dtype([("param", _u64), ("grad", _u64), ("exp_avg", _u64), ("exp_avg_sq", _u64), ("n", np.int64),
@@ -323,6 +327,7 @@ ITEM_SIZES = {
     "pnmn_gemm_desc": (GEMM_DESC, 120),
     "pnmn_token_seg": (TOKEN_SEG, 32),
     "pnmn_lstm_stack_job": (LSTM_STACK_JOB, 104),
+    "pnmn_lstm_dropout_desc": (LSTM_DROPOUT_DESC, 32),
 }
 
 

@@ -10,7 +10,7 @@ from torch.nn import functional as F
 
 from probnmn import _hip
 from probnmn.modules.seq2seq_base import (DerivedParams, _Encoder, _TokenEmbedder, _TokenPrep, lstm_derived_params,
-                                          lstm_derived_specs,
+                                          lstm_derived_specs, lstm_dropout_seed,
                                           sequence_nll)
 from probnmn.running_metrics import Average
 
@@ -31,6 +31,8 @@ class ProgramPrior(nn.Module):
         self._output_layer = nn.Linear(input_size, vocab_size, bias=False)
         self._output_layer.weight = self._embedder.embedding.weight  # tied
         self._log2_perplexity = Average()
+        # row offset of this rank's shard in the global batch: the row key of the dropout masks (as Seq2SeqBase's)
+        self.sample_row_offset = 0
         self.__dict__["_derived_cache"] = DerivedParams()  # (packed recurrent weights; not part of the state_dict)
 
     def _derived(self):
@@ -54,7 +56,9 @@ class ProgramPrior(nn.Module):
             raise _hip.HipLibraryError("program prior input on %s: the HIP path needs a ROCm device" % program_tokens.device)
         toks, fmask, _ = _TokenPrep.run(program_tokens, self._pad_index, self._start_index, self._end_index,
                                         drop_first=False, want_mask=True)
-        encoded = self._encoder.forward_tokens(self._embedder.embedding, toks, fmask, derived=self._derived())
+        seed = lstm_dropout_seed(self._encoder._module)
+        encoded = self._encoder.forward_tokens(self._embedder.embedding, toks, fmask, derived=self._derived(), dropout_seed=seed,
+                                               row_offset=self.sample_row_offset)
         logits = self._output_layer(self._projection_layer(encoded))
         loss = sequence_nll(logits[:, :-1], toks[:, 1:], toks[:, 1:], self._pad_index, 1e-13)
         if not need_predictions:  # (the trainers' reward path: no samples, no validation metric)

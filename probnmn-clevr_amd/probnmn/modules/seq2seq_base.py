@@ -477,6 +477,40 @@ class _LSTMLayerSeq(torch.autograd.Function):
         return dxp, dw_hh, None, None, None
 
 
+class _LSTMDropout(torch.autograd.Function):
+    """``nn.LSTM(dropout=p)``'s mask between two layers, in training mode (``pnmn_lstm_dropout``): y = x * keep * scale over
+    [B,T,H] with keep(row, t, u) drawn from Philox under ``seed`` (row = ``row_offset`` + the row's index; the stream is
+    documented beside the entry point in include/probnmn_hip.h).  Backward regenerates the same mask on the gradient."""
+
+    @staticmethod
+    def forward(ctx, x, p, seed, row_offset):
+        x = x.contiguous()
+        B, T, Hd = x.shape
+        y = torch.empty_like(x)
+        _hip.check(_hip.lib().pnmn_lstm_dropout(x.data_ptr(), y.data_ptr(), B, T, Hd, p, seed, row_offset, _hip.stream_ptr(x.device)),
+                   "lstm_dropout")
+        ctx.args = (p, seed, row_offset)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        p, seed, row_offset = ctx.args
+        dy = dy.contiguous()
+        B, T, Hd = dy.shape
+        dx = torch.empty_like(dy)
+        _hip.check(_hip.lib().pnmn_lstm_dropout(dy.data_ptr(), dx.data_ptr(), B, T, Hd, p, seed, row_offset, _hip.stream_ptr(dy.device)),
+                   "lstm_dropout backward")
+        return dx, None, None, None
+
+
+def lstm_dropout_seed(lstm: nn.LSTM) -> Optional[int]:
+    """The seed of one encoder pass's dropout masks: drawn from torch's CPU generator (as ``decode`` draws its sampler
+    seeds) only when the pass drops anything -- training mode and p > 0; None otherwise, drawing nothing."""
+    if lstm.training and lstm.dropout > 0 and lstm.num_layers > 1:
+        return int(torch.randint(0, 2 ** 62, (1,)).item())  # CPU generator: no device sync
+    return None
+
+
 def _table_grad(dy: torch.Tensor, tokens: torch.Tensor, vocab: int, padding_idx: Optional[int] = None) -> torch.Tensor:
     """Gradient of ``F.embedding(tokens, table)`` wrt the table, from the gradient ``dy`` [B,T,C] of its output."""
     if vocab <= 128 and dy.size(-1) % 64 == 0 and tokens.dim() == 2:
@@ -934,7 +968,7 @@ def lstm_bias(lstm: nn.LSTM, layer: int, derived: Optional[Dict[str, torch.Tenso
 
 def masked_lstm(lstm: nn.LSTM, x: torch.Tensor, mask: torch.Tensor, first_projection: Optional[torch.Tensor] = None,
                 derived: Optional[Dict[str, torch.Tensor]] = None, last: Optional[torch.Tensor] = None,
-                first_tokens: Optional[torch.Tensor] = None):
+                first_tokens: Optional[torch.Tensor] = None, dropout_seed: Optional[int] = None, row_offset: int = 0):
     """``PytorchSeq2SeqWrapper(nn.LSTM)(x, mask)``: zero initial state, outputs zero past each row's
     length.  Rows are run over all T steps (a unidirectional state never sees later steps) with the
     input GEMM batched over time and the recurrence in one persistent HIP kernel per layer.
@@ -942,9 +976,13 @@ def masked_lstm(lstm: nn.LSTM, x: torch.Tensor, mask: torch.Tensor, first_projec
     ; ``x`` is then unused -- with ``first_tokens`` it is the [V,4H] per-token TABLE and the
     layer kernel looks the rows up itself.  ``derived``: the model's ``DerivedParams`` output (packed
     weights, bias sums).  ``last`` ([B] int32, ``mask`` then being the float mask): also return each row's
-    state at that step -- (outputs, last states) from one launch."""
+    state at that step -- (outputs, last states) from one launch.  In training mode with ``lstm.dropout`` > 0 the output of
+    every layer but the last passes through ``_LSTMDropout`` under ``dropout_seed`` (drawn here when not given) with row keys
+    from ``row_offset``."""
     B, T = mask.shape
     inp = x
+    if dropout_seed is None:
+        dropout_seed = lstm_dropout_seed(lstm)
     for layer in range(lstm.num_layers):
         w_ih = getattr(lstm, "weight_ih_l%d" % layer)
         w_hh = getattr(lstm, "weight_hh_l%d" % layer)
@@ -975,6 +1013,8 @@ def masked_lstm(lstm: nn.LSTM, x: torch.Tensor, mask: torch.Tensor, first_projec
                 h, c = lstm_cell_pointwise(gates, c)
                 outs.append(h)
             inp = torch.stack(outs, 1)
+        if dropout_seed is not None and layer + 1 < lstm.num_layers:
+            inp = _LSTMDropout.apply(inp, float(lstm.dropout), dropout_seed, row_offset)
     if last is not None:
         return _MaskAndLast.apply(inp, mask, last)
     return inp * mask.unsqueeze(-1).to(inp.dtype)
@@ -1009,12 +1049,14 @@ class _Encoder(nn.Module):
         return masked_lstm(self._module, x, mask)
 
     def forward_tokens(self, embedding: nn.Embedding, tokens: torch.Tensor, mask: torch.Tensor,
-                       derived: Optional[Dict[str, torch.Tensor]] = None, last: Optional[torch.Tensor] = None):
+                       derived: Optional[Dict[str, torch.Tensor]] = None, last: Optional[torch.Tensor] = None,
+                       dropout_seed: Optional[int] = None, row_offset: int = 0):
         """``forward(embedding(tokens), mask)`` with the first layer's input projection taken from a
         per-token table (``_TokenTable``: V < 100 projected rows instead of a GEMM over all B x T); with ``last`` also each row's state at that step."""
         lstm = self._module
         table = _TokenTable.apply(embedding.weight, lstm.weight_ih_l0, lstm_bias(lstm, 0, derived), embedding.padding_idx)
-        return masked_lstm(lstm, None, mask, first_projection=table, derived=derived, last=last, first_tokens=tokens)
+        return masked_lstm(lstm, None, mask, first_projection=table, derived=derived, last=last, first_tokens=tokens,
+                           dropout_seed=dropout_seed, row_offset=row_offset)
 
 
 class Seq2SeqBase(nn.Module):
@@ -1038,8 +1080,6 @@ class Seq2SeqBase(nn.Module):
         self._start_index = vocabulary.get_token_index("@start@", namespace=target_namespace)
         self._max_decoding_steps = max_decoding_steps
         self._scheduled_sampling_ratio = 0.0
-        if dropout != 0.0:
-            raise NotImplementedError("dropout != 0 is not used by any reference config and not built")
 
         v_src = vocabulary.get_vocab_size(namespace=source_namespace)
         v_tgt = vocabulary.get_vocab_size(namespace=target_namespace)
@@ -1096,7 +1136,10 @@ class Seq2SeqBase(nn.Module):
         pad, bos, eos = self._pad_index, self._start_index, self._end_index
         # boundaries (@start@ is not encoded), mask and index of the last real token: one launch
         src, fmask, last = _TokenPrep.run(source_tokens, pad, bos, eos, drop_first=True, want_mask=True)
-        enc, h = self._encoder.forward_tokens(self._source_embedder.embedding, src, fmask, derived=self._derived(), last=last)
+        # (the dropout seed of this pass, if it drops anything, is drawn before any seed of the decodes that follow)
+        seed = lstm_dropout_seed(self._encoder._module)
+        enc, h = self._encoder.forward_tokens(self._source_embedder.embedding, src, fmask, derived=self._derived(), last=last,
+                                              dropout_seed=seed, row_offset=self.sample_row_offset)
         return {"enc": enc, "h": h, "fmask": fmask}
 
     @staticmethod

@@ -71,6 +71,10 @@ class _Calls(list):
     def add(self, name: str, *args) -> None:
         self.append((getattr(_hip.lib(), name), args, name))
 
+    def add_fn(self, name: str, fn) -> None:
+        """A call whose arguments are read when it runs (a dropout mask's seed changes every iteration)."""
+        self.append((fn, (), name))
+
     def run(self) -> None:
         for fn, args, name in self:
             rc = fn(*args)
@@ -83,6 +87,11 @@ def _supported(model) -> bool:
     return (lstm.hidden_size == 256 and lstm.num_layers == 2 and lstm.input_size == 256 and cell.hidden_size == 256
             and cell.input_size == 512 and model._output_projection_layer.weight.size(0) <= 128
             and model._source_embedder.embedding.weight.size(0) <= 128)
+
+
+def _dropout_p(lstm) -> float:
+    """p of the mask between an encoder's layers in a training-mode pass (0: none)."""
+    return float(lstm.dropout) if lstm.num_layers > 1 else 0.0
 
 
 class _Model:
@@ -127,10 +136,14 @@ class Seq2SeqPlan:
             pl = prior._encoder._module
             if pl.hidden_size != 256 or pl.num_layers != 2 or pl.input_size != 256:
                 raise PlanUnsupported("prior shapes")
+            if pl.training and _dropout_p(pl) > 0:  # (the trainers keep the prior in eval mode: its pass drops nothing)
+                raise PlanUnsupported("prior in training mode with dropout")
         lib = _hip.lib()
         self.dev, self.n, self.m, self.tq, self.tp = dev, n, m, tq, tp
         self.stream = _hip.stream_ptr(dev)
         self.pg, self.qr, self.prior = _Model(pg, dev), _Model(qr, dev), prior
+        # the masks between the encoders' layers (the plan serves training-mode passes only)
+        self.drop_p = (_dropout_p(pg._encoder._module), _dropout_p(qr._encoder._module))
         self.with_prior = with_prior
         B = n + m
         self.B = B
@@ -208,8 +221,10 @@ class Seq2SeqPlan:
             calls.add("pnmn_gemm_cus", rec.ctypes.data, len(rec), GEMM_WORKGROUPS, self.stream)
 
     def _encoder_prepare(self, calls: _Calls, tag: str, mm: Optional[_Model], derived, tokens: torch.Tensor, width: int, rows: int,
-                         drop_first: bool, emb: torch.Tensor, pad_idx, lstm, want_last: bool = True) -> Dict:
-        """Buffers of one encoder pass + what precedes its recurrence: token_prep and the per-token table of layer 1."""
+                         drop_first: bool, emb: torch.Tensor, pad_idx, lstm, want_last: bool = True, p: float = 0.0) -> Dict:
+        """Buffers of one encoder pass + what precedes its recurrence: token_prep and the per-token table of layer 1.  ``p`` > 0:
+        dropout between the layers -- "hsd" holds layer 1's output after the mask (layer 2's input), and every call that
+        applies the mask finds this iteration's seed in "seed" / the records listed in "drop_recs" (``_set_dropout``)."""
         st = self.stream
         model = mm.model if mm is not None else self.prior
         pad, bos, eos = model._pad_index, model._start_index, model._end_index
@@ -221,7 +236,9 @@ class Seq2SeqPlan:
                  src=f(tag + ".src", rows, T, dtype=torch.long), fmask=f(tag + ".fmask", rows, T), last=f(tag + ".last", rows, dtype=torch.int32),
                  table=f(tag + ".table", V, 1024), hs1=f(tag + ".hs1", rows, T, 256), cs1=f(tag + ".cs1", rows, T, 256),
                  act1=f(tag + ".act1", rows, T, 1024), hs2=f(tag + ".hs2", rows, T, 256), cs2=f(tag + ".cs2", rows, T, 256),
-                 act2=f(tag + ".act2", rows, T, 1024))
+                 act2=f(tag + ".act2", rows, T, 1024), p=p, seed=0, row_offset=0, drop_recs=[])
+        if p > 0:
+            e["hsd"] = f(tag + ".hsd", rows, T, 256)
         calls.add("pnmn_token_prep", tokens.data_ptr(), tokens.stride(0), rows, width, pad, bos, eos, int(drop_first), e["src"].data_ptr(),
                   e["fmask"].data_ptr(), e["last"].data_ptr(), st)
         calls.add("pnmn_token_table_fwd", emb.data_ptr(), lstm.weight_ih_l0.data_ptr(), lstm.weight_ih_l0.stride(0),
@@ -265,7 +282,22 @@ class Seq2SeqPlan:
             jobs = self._stack_jobs(group, backward)
             ws = self.bytes_buf("%s.stack_ws%d" % (name, len(self._keep)), lib.pnmn_lstm_stack_workspace_bytes(jobs.ctypes.data, len(jobs), int(backward)))
             self._keep.append(jobs)
-            calls.add("pnmn_lstm_stack_bwd" if backward else "pnmn_lstm_stack_fwd", jobs.ctypes.data, len(jobs), ws.data_ptr(), self.stream)
+            if any(e["p"] > 0 for e in group):
+                # dropout descriptors: on layer 1's job (forward: the FIRST job writes hsd; backward: the BELOW job masks the
+                # gradient from above); seeds are written into them per iteration
+                drops = np.zeros(len(jobs), _hip.LSTM_DROPOUT_DESC)
+                for k, e in enumerate(group):
+                    if e["p"] > 0:
+                        i = 2 * k + int(backward)
+                        drops[i]["p"] = e["p"]
+                        if not backward:
+                            drops[i]["hsd"] = e["hsd"].data_ptr()
+                        e["drop_recs"].append((drops, i))
+                self._keep.append(drops)
+                calls.add("pnmn_lstm_stack_bwd_dropout" if backward else "pnmn_lstm_stack_fwd_dropout", jobs.ctypes.data, drops.ctypes.data,
+                          len(jobs), ws.data_ptr(), self.stream)
+            else:
+                calls.add("pnmn_lstm_stack_bwd" if backward else "pnmn_lstm_stack_fwd", jobs.ctypes.data, len(jobs), ws.data_ptr(), self.stream)
             del group[:]
 
         for e in encs:
@@ -285,6 +317,17 @@ class Seq2SeqPlan:
         flush()
         return left
 
+    def _dropout_call(self, calls: _Calls, e: Dict, src: torch.Tensor, dst: torch.Tensor) -> None:
+        """pnmn_lstm_dropout over one of the encoder's [rows][T][256] tensors with the iteration's seed (y == x allowed)."""
+        fn, st = _hip.lib().pnmn_lstm_dropout, self.stream
+        x, y, rows, T, p = src.data_ptr(), dst.data_ptr(), e["rows"], e["T"], e["p"]
+        calls.add_fn("pnmn_lstm_dropout", lambda: fn(x, y, rows, T, 256, p, e["seed"], e["row_offset"], st))
+
+    def _set_dropout(self, e: Dict, seed: int, row_offset: int) -> None:
+        e["seed"], e["row_offset"] = seed, row_offset
+        for rec, i in e["drop_recs"]:
+            rec[i]["seed"], rec[i]["row_offset"] = seed, row_offset
+
     def _encoders_fwd(self, calls: _Calls, name: str, encs: List[Dict], most: Optional[int] = None) -> None:
         lib, st = _hip.lib(), self.stream
         for e in self._stack_launches(calls, name, encs, False, most):
@@ -293,7 +336,11 @@ class Seq2SeqPlan:
             ws = self.bytes_buf(e["tag"] + ".lstm_ws", lib.pnmn_lstm_seq_workspace_bytes(rows, 0))
             calls.add("pnmn_lstm_seq_fwd", e["table"].data_ptr(), e["src"].data_ptr(), e["src"].stride(0), d["l0.hh"].data_ptr(),
                       e["hs1"].data_ptr(), e["cs1"].data_ptr(), e["act1"].data_ptr(), rows, T, 256, ws.data_ptr(), st)
-            self._gemm(calls, e["tag"] + ".xp2g", [dict(a=e["hs1"].data_ptr(), b=lstm.weight_ih_l1.data_ptr(), c=xp2.data_ptr(), M=rows * T,
+            x2 = e["hs1"]
+            if e["p"] > 0:
+                self._dropout_call(calls, e, e["hs1"], e["hsd"])
+                x2 = e["hsd"]
+            self._gemm(calls, e["tag"] + ".xp2g", [dict(a=x2.data_ptr(), b=lstm.weight_ih_l1.data_ptr(), c=xp2.data_ptr(), M=rows * T,
                                                         N=1024, K=256, lda=256, ldb=256, ldc=1024, tb=1, bias=d["l1.b"].data_ptr())])
             calls.add("pnmn_lstm_seq_fwd", xp2.data_ptr(), None, 0, d["l1.hh"].data_ptr(), e["hs2"].data_ptr(), e["cs2"].data_ptr(),
                       e["act2"].data_ptr(), rows, T, 256, ws.data_ptr(), st)
@@ -320,6 +367,8 @@ class Seq2SeqPlan:
                       e["dg2"].data_ptr(), rows, T, 256, ws.data_ptr(), st)
             self._gemm(calls, tag + ".dx", [dict(a=e["dg2"].data_ptr(), b=lstm.weight_ih_l1.data_ptr(), c=dhs1.data_ptr(), M=rows * T, N=256,
                                                  K=1024, lda=1024, ldb=256, ldc=256, split="auto")])
+            if e["p"] > 0:
+                self._dropout_call(calls, e, dhs1, dhs1)
             calls.add("pnmn_lstm_seq_bwd", dhs1.data_ptr(), e["act1"].data_ptr(), e["cs1"].data_ptr(), d["l0.hhT"].data_ptr(),
                       e["dg1"].data_ptr(), rows, T, 256, ws.data_ptr(), st)
 
@@ -344,8 +393,8 @@ class Seq2SeqPlan:
             deferred += [
                 dict(a=dg2.data_ptr(), b=e["hs2"].data_ptr(), c=g(lstm.weight_hh_l1).data_ptr(), M=1024, N=256, K=K, lda=1024, ldb=256,
                      ldc=256, ta=1, split="auto", shift_t=T, colsum=g(lstm.bias_ih_l1).data_ptr(), colsum2=g(lstm.bias_hh_l1).data_ptr()),
-                dict(a=dg2.data_ptr(), b=e["hs1"].data_ptr(), c=g(lstm.weight_ih_l1).data_ptr(), M=1024, N=256, K=K, lda=1024, ldb=256,
-                     ldc=256, ta=1, split="auto"),
+                dict(a=dg2.data_ptr(), b=(e["hsd"] if e["p"] > 0 else e["hs1"]).data_ptr(), c=g(lstm.weight_ih_l1).data_ptr(), M=1024,
+                     N=256, K=K, lda=1024, ldb=256, ldc=256, ta=1, split="auto"),  # (layer 2's input: after the mask)
                 dict(a=dg1.data_ptr(), b=e["hs1"].data_ptr(), c=g(lstm.weight_hh_l0).data_ptr(), M=1024, N=256, K=K, lda=1024, ldb=256,
                      ldc=256, ta=1, split="auto", shift_t=T),
             ]
@@ -375,11 +424,11 @@ class Seq2SeqPlan:
         ques = f("ques", B, tq, dtype=torch.long)
         prog_sup = f("prog_sup", m, tp, dtype=torch.long)
         e_pg = self._encoder_prepare(self.fwd_pg_enc, "pg.e", pg, dpg, ques, tq, B, True, pg.emb_src,
-                                     pg.model._source_embedder.embedding.padding_idx, pg.lstm)
+                                     pg.model._source_embedder.embedding.padding_idx, pg.lstm, p=self.drop_p[0])
         self._encoders_fwd(self.fwd_pg_enc, "pg.e", [e_pg], most=STACK_PG_ENCODER)
         #: workgroups of the generator's encoder launch (0: a launch per layer): a trainer that runs the NMN's stem beside it
         #: cuts the stem's launches for the CUs this leaves (JointTrainingStep)
-        self.pg_encoder_workgroups = 16 * (-(-B // 16)) if any(n == "pnmn_lstm_stack_fwd" for _, _, n in self.fwd_pg_enc) else 0
+        self.pg_encoder_workgroups = 16 * (-(-B // 16)) if any(n.startswith("pnmn_lstm_stack_fwd") for _, _, n in self.fwd_pg_enc) else 0
         S = e_pg["T"]
         if S > 64 or D > 64:
             raise PlanUnsupported("more than 64 source positions / decoding steps")
@@ -437,7 +486,8 @@ class Seq2SeqPlan:
         c = self.fwd_qr
         c.add("pnmn_token_rows", segs.ctypes.data, 2, source.data_ptr(), Wq, 0, st)
         e_qr = self._encoder_prepare(c, "qr.e", qr, dqr, source, Wq, B, True, qr.emb_src, qr.model._source_embedder.embedding.padding_idx,
-                                     qr.lstm)
+                                     qr.lstm, p=self.drop_p[1])
+        self.e_pg, self.e_qr = e_pg, e_qr
         # the prior reads the same samples: its two LSTM layers ride in the reconstructor encoder's launch (its projections
         # and loss follow in `fwd_prior`, behind the trunk's launch)
         e_pr = None
@@ -616,6 +666,10 @@ class Seq2SeqPlan:
                 return False
         if self.with_prior and tuple(p.data_ptr() for p in self.prior.parameters()) != self.prior_sig:
             return False
+        if (_dropout_p(self.pg.lstm), _dropout_p(self.qr.lstm)) != self.drop_p:
+            return False
+        if self.with_prior and self.prior.training and _dropout_p(self.prior._encoder._module) > 0:
+            return False
         return self._sig() == self._derived_sig
 
     # ---- one iteration -------------------------------------------------------------------------------------------------------
@@ -635,9 +689,14 @@ class Seq2SeqPlan:
             program.data_ptr(), sup_d.data_ptr(), program.stride(0), self.m, self.tp
         _hip.check(lib.pnmn_token_rows(segs.ctypes.data, 1, self.out["prog_sup"].data_ptr(), self.tp, 0, st), "token_rows")
         # one seed per pass, drawn as Seq2SeqBase.decode_prepare draws them (sampling, teacher-forced, reconstructor): the
-        # eager and the planned iteration sample the same programs from the same torch seed
+        # eager and the planned iteration sample the same programs from the same torch seed -- with an encoder's dropout seed
+        # (Seq2SeqBase.encode) where the eager iteration draws it: before its model's decode seeds
+        if self.drop_p[0] > 0:
+            self._set_dropout(self.e_pg, int(torch.randint(0, 2 ** 62, (1,)).item()), self.pg.model.sample_row_offset)
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
         torch.randint(0, 2 ** 62, (1,))
+        if self.drop_p[1] > 0:
+            self._set_dropout(self.e_qr, int(torch.randint(0, 2 ** 62, (1,)).item()), self.qr.model.sample_row_offset)
         torch.randint(0, 2 ** 62, (1,))
         self.pair_jobs[0]["seed"] = seed
         self.pair_jobs[0]["row_offset"] = self.pg.model.sample_row_offset
