@@ -489,6 +489,28 @@ int pnmn_attn_lstm_bwd(const float* dhs, const float* act, const float* cs, cons
                        const float* h0, const float* w_c_t, const float* w_hh_t, float* dgates,
                        float* denc, float* dh0, int B, int T, int S, int hidden, void* stream);
 
+/* Beam-search decoding with the same per-step arithmetic (decoder_beam.hip): inference only, nothing saved, no backward.
+ * One workgroup owns 16 / beam questions x beam hypotheses for all T steps.  enc [B][S][H], mask [B][S] and h0 [B][H] are
+ * per QUESTION (never repeated per hypothesis); etable / w_c / w_hh / w_p / b_p as for pnmn_attn_lstm_fwd (w_c, w_hh in
+ * fragment order).  Selection rule, per question b:
+ *   score[b][0] = 0, score[b][k>0] = -inf, last[b][k] = start_index                 (step 0 expands one state)
+ *   each step: logp[k][v] = log_softmax(h_k W_p^T + b_p)[v]; logp[k][pad|unk|start] = -inf;
+ *              last[b][k] == end_index: logp[k][:] = -inf, logp[k][end] = 0         (a finished hypothesis keeps its score)
+ *              cand[k*V+v] = score[b][k] + logp[k][v]                               (a non-finite cand counts as -inf)
+ *              new beams = the `beam` largest cand, best first; equal cand: the smaller k*V+v first;
+ *              a slot left without a finite candidate: token end_index, back-pointer 0, score -inf
+ *   Scores are plain sums of log-probabilities (fp32).  The survivors' h, c and last token follow the back-pointers.
+ * outputs: tokens [B][beam][T] (back-tracked, best first, every token in [0, V), @end@ after a hypothesis's first @end@),
+ *          scores [B][beam]; optional trace of every step, [B][T][beam] each (all three or none): the token, the
+ *          back-pointer (slot of the previous step) and the running score of every slot.
+ * Limits: hidden = 256, 1 <= S <= 64, 1 <= V <= 128, T <= 64, beam in {1, 2, 4, 8, 16}, start / end index inside [0, V);
+ * anything else (or a missing pointer) returns PNMN_EINVAL. */
+int pnmn_attn_lstm_beam(const float* etable, const float* enc, const float* mask, const float* h0,
+                        const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
+                        int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
+                        float* trace_scores, int B, int T, int S, int V, int hidden, int beam,
+                        int pad_index, int unk_index, int start_index, int end_index, void* stream);
+
 /* Multi-CU variants of the two kernels above (decoder_multi.hip): eight workgroups per 16-row tile,
  * each keeping its rows' encoder outputs in LDS and its slices of W_c / W_hh in registers, two L2
  * hand-offs per step.  Same arguments and saved tensors, plus a device `workspace` of

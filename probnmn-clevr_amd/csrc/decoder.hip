@@ -26,6 +26,7 @@
 #include <stdint.h>
 
 #include "../../include/probnmn_hip.h"
+#include "decoder_stages.h"
 #include "lds_optin.h"
 #include "sampling.h"
 
@@ -116,12 +117,8 @@ __global__ __launch_bounds__(512) void attn_lstm_fwd_kernel(const FwdArgs a) {
                     }
                 }
                 const float m = lane < S ? a.mask[(size_t)row * S + lane] : 0.f;
-                const float v = myscore * m;  // allennlp masked_softmax: softmax(vector * mask) ...
-                const float mx = wmax(lane < S ? v : -INFINITY);
-                const float ex = lane < S ? expf(v - mx) : 0.f;
-                const float p = ex / wsum(ex);
-                const float q = p * m;        // ... * mask, renormalised with 1e-13
-                const float wgt = q / (wsum(q) + 1e-13f);
+                float p;  // (the softmax before masking: saved for the backward)
+                const float wgt = pnmn::attention_weight(myscore, m, S, lane, p);
                 if (lane < S) {
                     wl[rl][lane] = wgt;
                     a.probs[((size_t)row * T + t) * S + lane] = p;
@@ -168,27 +165,7 @@ __global__ __launch_bounds__(512) void attn_lstm_fwd_kernel(const FwdArgs a) {
                     }
                     acc[gate][ut][r] = v;
                 }
-#pragma unroll 2
-        for (int kb = 0; kb < H / 16; ++kb) {
-            const f32x4 ac = *reinterpret_cast<const f32x4*>(&cl[li][kb * 16 + 4 * g]);
-            const f32x4 ah = *reinterpret_cast<const f32x4*>(&hl[cur][li][kb * 16 + 4 * g]);
-#pragma unroll
-            for (int gate = 0; gate < 4; ++gate)
-#pragma unroll
-                for (int ut = 0; ut < 2; ++ut) {
-                    const size_t fo = ((size_t)((gate * (H / 16) + 2 * wave + ut) * (H / 16) + kb) * 64 + lane) * 4;
-                    const f32x4 bc = *reinterpret_cast<const f32x4*>(a.w_c + fo);  // weights are packed in
-                    const f32x4 bh = *reinterpret_cast<const f32x4*>(a.w_hh + fo);  // fragment order (seq2seq.hip)
-                    acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac.x, bc.x, acc[gate][ut], 0, 0, 0);
-                    acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac.y, bc.y, acc[gate][ut], 0, 0, 0);
-                    acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac.z, bc.z, acc[gate][ut], 0, 0, 0);
-                    acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ac.w, bc.w, acc[gate][ut], 0, 0, 0);
-                    acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.x, bh.x, acc[gate][ut], 0, 0, 0);
-                    acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.y, bh.y, acc[gate][ut], 0, 0, 0);
-                    acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.z, bh.z, acc[gate][ut], 0, 0, 0);
-                    acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.w, bh.w, acc[gate][ut], 0, 0, 0);
-                }
-        }
+        pnmn::gates_mfma<H, LD>(acc, cl, hl[cur], a.w_c, a.w_hh, wave, lane);
         // ---------------- cell ----------------
 #pragma unroll
         for (int ut = 0; ut < 2; ++ut)
@@ -220,19 +197,9 @@ __global__ __launch_bounds__(512) void attn_lstm_fwd_kernel(const FwdArgs a) {
         if (a.sample) {
             const int V = a.V;
             if (16 * wave < V) {  // logits tile: 16 rows x 16 vocabulary entries per wave
-                f32x4 lacc = f32x4{0.f, 0.f, 0.f, 0.f};
                 const int vn = 16 * wave + li;
                 const bool vok = vn < V;
-#pragma unroll 4
-                for (int kb = 0; kb < H / 16; ++kb) {
-                    const f32x4 ah = *reinterpret_cast<const f32x4*>(&hl[nxt][li][kb * 16 + 4 * g]);
-                    f32x4 bp = f32x4{0.f, 0.f, 0.f, 0.f};
-                    if (vok) bp = *reinterpret_cast<const f32x4*>(a.w_p + (size_t)vn * H + kb * 16 + 4 * g);  // (row-major: tiny)
-                    lacc = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.x, bp.x, lacc, 0, 0, 0);
-                    lacc = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.y, bp.y, lacc, 0, 0, 0);
-                    lacc = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.z, bp.z, lacc, 0, 0, 0);
-                    lacc = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.w, bp.w, lacc, 0, 0, 0);
-                }
+                const f32x4 lacc = pnmn::logits_tile<H, LD>(hl[nxt], a.w_p, V, wave, lane);
                 const float bias = vok ? a.b_p[vn] : 0.f;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) logl[4 * g + r][vn < MAXV ? vn : 0] = vok ? lacc[r] + bias : -INFINITY;

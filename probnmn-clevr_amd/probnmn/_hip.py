@@ -82,6 +82,7 @@ SIGNATURES: Dict[str, tuple] = {
     "pnmn_token_rows": (_P, _I, _P, _I, ctypes.c_int64, _P),
     "pnmn_lstm_seq_workspace_bytes": (_I, _I),
     "pnmn_cluster_reserve_cus": (_I,),
+    "pnmn_attn_lstm_beam": (_P,) * 13 + (_I,) * 10 + (_P,),
     "pnmn_attn_lstm_fwd": (_P,) * 15 + (_I,) * 9 + (ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.c_int64, _P),
     "pnmn_attn_lstm_bwd": (_P,) * 14 + (_I,) * 4 + (_P,),
     "pnmn_attn_lstm_multi_workspace_bytes": (_I, _I),

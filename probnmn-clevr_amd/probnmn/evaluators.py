@@ -9,7 +9,8 @@ Stand-alone layout only (when the models are grafted onto the reference's packag
     predictions are the arg-max of the teacher-forced distributions (seq2seq_base.py:188-198), and the NMN
     answers on those; accuracy = #(prediction == answer) / N (an invalid program predicts @@UNKNOWN@@);
   * inference samples programs (``program_generator(question)`` with the default strategy, in eval mode)
-    and lets the NMN answer without gold answers.
+    and lets the NMN answer without gold answers; with ``beam_size`` it beam-searches them instead (not in the
+    reference) and can prefer the best-ranked hypothesis that is a valid program.
 Batches are dicts of DEVICE tensors with the reference's keys (a ``PrefetchingLoader`` yields them)."""
 from typing import Any, Callable, Dict, Iterable, List, Optional
 
@@ -120,9 +121,16 @@ def evaluate_answer_accuracy(program_generator, nmn, batches: Iterable[Dict[str,
 
 
 @torch.no_grad()
-def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary) -> List[Dict[str, Any]]:
+def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary,
+                    beam_size: Optional[int] = None, prefer_valid: bool = True) -> List[Dict[str, Any]]:
     """scripts/inference.py:76-91: sampled programs -> NMN -> answer strings, one record per question
-    (``question_index`` from the batch when present, else a running index)."""
+    (``question_index`` from the batch when present, else a running index).
+
+    ``beam_size`` (1, 2, 4, 8 or 16): the generator decodes with beam search instead (``decoding_strategy="beam"``) and
+    the NMN gets, per question, the most probable hypothesis -- or, with ``prefer_valid``, the best-ranked hypothesis
+    that the program compiler accepts (the most probable one when none is valid).  Validity is decided on the host from
+    the [B, K, T] tokens the loop copies out anyway.  Each record then also names ``"program"`` (token strings of the
+    chosen hypothesis, without padding), its ``"beam_rank"`` and whether it is a ``"program_valid"`` one."""
     was_training = (program_generator.training, nmn.training)
     program_generator.eval()
     nmn.eval()
@@ -130,9 +138,13 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
     try:
         # (as in answering_evaluator: batch i + 1's generator pass is queued before batch i's programs are awaited on the host)
         pinned: Dict[Any, torch.Tensor] = {}
+        pad = getattr(program_generator, "_pad_index", 0)
 
         def queue(batch, iteration):
-            programs = program_generator(batch["question"])["predictions"]
+            if beam_size is None:
+                programs = program_generator(batch["question"])["predictions"]
+            else:
+                programs = program_generator(batch["question"], decoding_strategy="beam", beam_size=beam_size)["beam_predictions"]
             if not (programs.is_cuda and batch["image"].is_cuda):
                 return programs, None
             key = (iteration & 1, tuple(programs.shape), programs.dtype)
@@ -143,14 +155,38 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
             copied.record()
             return pinned[key], copied
 
+        def choose(beams):
+            """[B, K, T] host tokens -> (programs [B, T], rank per question, validity of the chosen program)."""
+            B, K, T = beams.shape
+            arr = beams.cpu().numpy()
+            # (the NMN decides the validity of the B chosen programs again on its own: host work, microseconds per program)
+            if prefer_valid:
+                compiled = nmn.engine.compiler.compile_batch(arr.reshape(B * K, T))
+                ok = [[compiled[b * K + k].valid for k in range(K)] for b in range(B)]
+                ranks = [row.index(True) if True in row else 0 for row in ok]
+                valid = [row[r] for row, r in zip(ok, ranks)]
+            else:
+                ranks = [0] * B
+                valid = [c.valid for c in nmn.engine.compiler.compile_batch(arr[:, 0])]
+            return beams[torch.arange(B), torch.tensor(ranks, dtype=torch.long)], ranks, valid
+
         def finish(batch, queued):
             programs, copied = queued
             if copied is not None:
                 copied.synchronize()
+            extra = None
+            if beam_size is not None:
+                programs, ranks, valid = choose(programs)
+                extra = (programs.tolist(), ranks, valid)
             answers = nmn(batch["image"], programs)["predictions"].cpu().tolist()
             index = batch["question_index"].cpu().tolist() if "question_index" in batch else range(len(records), len(records) + len(answers))
-            for qi, a in zip(index, answers):
-                records.append({"question_index": int(qi), "answer": vocabulary.get_token_from_index(int(a), namespace="answers")})
+            for i, (qi, a) in enumerate(zip(index, answers)):
+                record = {"question_index": int(qi), "answer": vocabulary.get_token_from_index(int(a), namespace="answers")}
+                if extra is not None:
+                    record["program"] = [vocabulary.get_token_from_index(int(t), namespace="programs") for t in extra[0][i] if t != pad]
+                    record["beam_rank"] = int(extra[1][i])
+                    record["program_valid"] = bool(extra[2][i])
+                records.append(record)
 
         pending = None
         for iteration, batch in enumerate(batches):

@@ -17,6 +17,10 @@ hidden sizes fall back to a GEMM per step plus the cell kernel (``pnmn_lstm_cell
 ``pnmn_sample_tokens``).  Everything that the reference does with per-row Python loops and ``.cpu()``
 round trips (sentence boundaries, trimming at ``@end@``) is vectorised on the device: a forward pass
 performs no host synchronisation.
+
+Not in the reference: ``decoding_strategy="beam"`` (``Seq2SeqBase.decode_beam``), beam search for inference as one launch
+of a persistent kernel that keeps the K hypotheses of a question in one workgroup (``pnmn_attn_lstm_beam``,
+csrc/decoder_beam.hip).
 """
 import os
 from typing import Dict, Optional
@@ -968,7 +972,8 @@ def lstm_bias(lstm: nn.LSTM, layer: int, derived: Optional[Dict[str, torch.Tenso
 
 def masked_lstm(lstm: nn.LSTM, x: torch.Tensor, mask: torch.Tensor, first_projection: Optional[torch.Tensor] = None,
                 derived: Optional[Dict[str, torch.Tensor]] = None, last: Optional[torch.Tensor] = None,
-                first_tokens: Optional[torch.Tensor] = None, dropout_seed: Optional[int] = None, row_offset: int = 0):
+                first_tokens: Optional[torch.Tensor] = None, dropout_seed: Optional[int] = None, row_offset: int = 0,
+                dropout: bool = True):
     """``PytorchSeq2SeqWrapper(nn.LSTM)(x, mask)``: zero initial state, outputs zero past each row's
     length.  Rows are run over all T steps (a unidirectional state never sees later steps) with the
     input GEMM batched over time and the recurrence in one persistent HIP kernel per layer.
@@ -978,10 +983,12 @@ def masked_lstm(lstm: nn.LSTM, x: torch.Tensor, mask: torch.Tensor, first_projec
     weights, bias sums).  ``last`` ([B] int32, ``mask`` then being the float mask): also return each row's
     state at that step -- (outputs, last states) from one launch.  In training mode with ``lstm.dropout`` > 0 the output of
     every layer but the last passes through ``_LSTMDropout`` under ``dropout_seed`` (drawn here when not given) with row keys
-    from ``row_offset``."""
+    from ``row_offset``.  ``dropout=False``: no mask and no seed drawn whatever the mode (inference inside a training run)."""
     B, T = mask.shape
     inp = x
-    if dropout_seed is None:
+    if not dropout:
+        dropout_seed = None
+    elif dropout_seed is None:
         dropout_seed = lstm_dropout_seed(lstm)
     for layer in range(lstm.num_layers):
         w_ih = getattr(lstm, "weight_ih_l%d" % layer)
@@ -1050,13 +1057,13 @@ class _Encoder(nn.Module):
 
     def forward_tokens(self, embedding: nn.Embedding, tokens: torch.Tensor, mask: torch.Tensor,
                        derived: Optional[Dict[str, torch.Tensor]] = None, last: Optional[torch.Tensor] = None,
-                       dropout_seed: Optional[int] = None, row_offset: int = 0):
+                       dropout_seed: Optional[int] = None, row_offset: int = 0, dropout: bool = True):
         """``forward(embedding(tokens), mask)`` with the first layer's input projection taken from a
         per-token table (``_TokenTable``: V < 100 projected rows instead of a GEMM over all B x T); with ``last`` also each row's state at that step."""
         lstm = self._module
         table = _TokenTable.apply(embedding.weight, lstm.weight_ih_l0, lstm_bias(lstm, 0, derived), embedding.padding_idx)
         return masked_lstm(lstm, None, mask, first_projection=table, derived=derived, last=last, first_tokens=tokens,
-                           dropout_seed=dropout_seed, row_offset=row_offset)
+                           dropout_seed=dropout_seed, row_offset=row_offset, dropout=dropout)
 
 
 class Seq2SeqBase(nn.Module):
@@ -1124,22 +1131,31 @@ class Seq2SeqBase(nn.Module):
         target_tokens: Optional[torch.LongTensor] = None,
         decoding_strategy: str = "sampling",
         need_predictions: bool = True,
+        beam_size: int = 4,
     ) -> Dict[str, torch.Tensor]:
+        """``decoding_strategy``: "sampling" / "greedy" as the reference; "beam": beam search of width ``beam_size`` (free
+        running only, no gradients -- see ``decode_beam``).  ``beam_size`` is ignored by the other strategies."""
+        if decoding_strategy == "beam":
+            self._check_beam_arguments(target_tokens, beam_size)
+            with torch.no_grad():  # (the encoder without its dropout: the search is the same in train() and eval() mode)
+                return self.decode_beam(self.encode(source_tokens, dropout=False), beam_size)
         return self.decode(self.encode(source_tokens), target_tokens, decoding_strategy, need_predictions)
 
-    def encode(self, source_tokens: torch.LongTensor) -> Dict[str, torch.Tensor]:
+    def encode(self, source_tokens: torch.LongTensor, dropout: bool = True) -> Dict[str, torch.Tensor]:
         """Encoder half of ``forward`` (reference seq2seq_base.py ``_encode`` + ``_init_decoder_state``).
         Rows are independent, so a trainer may encode one batch once and ``decode`` row subsets of
-        the state in different modes (``select_rows``)."""
+        the state in different modes (``select_rows``).  ``dropout=False``: the encoder's LSTM dropout is off whatever the
+        mode and no seed is drawn for it -- what ``decoding_strategy="beam"`` encodes with, and what a caller of
+        ``decode(state, decoding_strategy="beam")`` on a model in ``train()`` mode wants its state from."""
         if source_tokens.device.type != "cuda":
             raise _hip.HipLibraryError("seq2seq input on %s: the HIP path needs a ROCm device" % source_tokens.device)
         pad, bos, eos = self._pad_index, self._start_index, self._end_index
         # boundaries (@start@ is not encoded), mask and index of the last real token: one launch
         src, fmask, last = _TokenPrep.run(source_tokens, pad, bos, eos, drop_first=True, want_mask=True)
         # (the dropout seed of this pass, if it drops anything, is drawn before any seed of the decodes that follow)
-        seed = lstm_dropout_seed(self._encoder._module)
+        seed = lstm_dropout_seed(self._encoder._module) if dropout else None
         enc, h = self._encoder.forward_tokens(self._source_embedder.embedding, src, fmask, derived=self._derived(), last=last,
-                                              dropout_seed=seed, row_offset=self.sample_row_offset)
+                                              dropout_seed=seed, row_offset=self.sample_row_offset, dropout=dropout)
         return {"enc": enc, "h": h, "fmask": fmask}
 
     @staticmethod
@@ -1165,13 +1181,18 @@ class Seq2SeqBase(nn.Module):
         decoding_strategy: str = "sampling",
         need_predictions: bool = True,
         seed: Optional[int] = None,
+        beam_size: int = 4,
     ) -> Dict[str, torch.Tensor]:
         """``need_predictions=False`` (teacher forcing only): skip drawing the per-step predictions from the
         teacher-forced distributions (reference :196-220) -- training iterations never read them.  ``seed``: the sampler
         seed a ``decode_prepare`` of this pass already drew (its pairing fell through): one draw per pass either way, so
-        paired and unpaired schedules sample the same programs from the same torch seed."""
+        paired and unpaired schedules sample the same programs from the same torch seed.  ``decoding_strategy="beam"``:
+        ``decode_beam`` with ``beam_size`` (which the other strategies ignore)."""
+        if decoding_strategy == "beam":
+            self._check_beam_arguments(target_tokens, beam_size)
+            return self.decode_beam(state, beam_size)
         if decoding_strategy not in ("sampling", "greedy"):
-            raise ValueError("decoding_strategy must be 'sampling' or 'greedy'")
+            raise ValueError("decoding_strategy must be 'sampling', 'greedy' or 'beam'")
         pad, bos, eos = self._pad_index, self._start_index, self._end_index
         enc, h, fmask = state["enc"], state["h"], state["fmask"]
         tgt = None
@@ -1239,6 +1260,74 @@ class Seq2SeqBase(nn.Module):
                 self._record_metrics(predictions, tgt[:, 1:], ce)
                 self._bleu(predictions, tgt)  # (reference :260: against the targets WITH their @start@, as allennlp)
         return output_dict
+
+    # ---- beam search (inference) ---------------------------------------------------------------------------------------
+    BEAM_SIZES = (1, 2, 4, 8, 16)
+
+    @staticmethod
+    def _check_beam_arguments(target_tokens, beam_size) -> None:
+        if target_tokens is not None:
+            raise ValueError("decoding_strategy='beam' is free running: it takes no target_tokens")
+        if isinstance(beam_size, bool) or not isinstance(beam_size, int) or beam_size not in Seq2SeqBase.BEAM_SIZES:
+            raise ValueError("beam_size must be one of %s, got %r" % (Seq2SeqBase.BEAM_SIZES, beam_size))
+
+    @torch.no_grad()
+    def decode_beam(self, state: Dict[str, torch.Tensor], beam_size: int = 4, trace: bool = False) -> Dict[str, torch.Tensor]:
+        """Beam search over ``max_decoding_steps`` steps in ONE launch of the persistent beam kernel
+        (``pnmn_attn_lstm_beam``, csrc/decoder_beam.hip; the selection rule is stated in include/probnmn_hip.h).  Inference
+        only: no graph, no seed drawn from the torch generator, the same in ``train()`` and ``eval()`` mode given a ``state``
+        encoded without dropout (``encode(..., dropout=False)``, as ``forward`` does for this strategy).  Returns
+        ``beam_predictions`` [B, K, T] (best first, each row trimmed at its first @end@), ``beam_log_probabilities`` [B, K]
+        (sums of token log-probabilities), ``predictions`` = the best hypothesis and ``loss`` [B] = its negative
+        log-probability over its number of non-padding tokens (the free-running sampled path's quantity).  ``trace=True``
+        adds ``beam_trace``: (token, back-pointer, score) of every slot at every step, [B, T, K] each.  There is no
+        step-by-step path for this mode: shapes outside the kernel's limits raise ``NotImplementedError``."""
+        self._check_beam_arguments(None, beam_size)
+        enc, h, fmask = state["enc"].detach(), state["h"].detach(), state["fmask"].detach()
+        dev = enc.device
+        if dev.type != "cuda":
+            raise _hip.HipLibraryError("beam decoder on %s: the HIP path needs a ROCm device (no CPU fallback)" % dev)
+        B, S, Hd = enc.shape
+        K, T = beam_size, self._max_decoding_steps
+        w_p, b_p = self._output_projection_layer.weight.detach(), self._output_projection_layer.bias.detach()
+        V = w_p.size(0)
+        for what, value, ok, limit in (("hidden size", Hd, Hd == 256, "256"), ("source positions", S, S <= 64, "<= 64"),
+                                       ("target vocabulary", V, V <= 128, "<= 128"), ("decoding steps", T, T <= 64, "<= 64")):
+            if not ok:
+                raise NotImplementedError("beam search: %s = %d, the beam kernel is built for %s" % (what, value, limit))
+        derived = self._derived()
+        w_ih = self._decoder_cell.weight_ih.detach()
+        if derived is not None:
+            bias, w_c_p, w_hh_p = derived["d.b"], derived["d.c"], derived["d.hh"]
+        else:
+            bias = self._decoder_cell.bias_ih.detach() + self._decoder_cell.bias_hh.detach()
+            w_c_p, w_hh_p = pack_fragments(w_ih[:, :Hd]), pack_fragments(self._decoder_cell.weight_hh)
+        # (the token table is rebuilt per call, as the free-running path does: one small GEMM, ~0.01 ms, that a timing of this
+        #  method includes; without DerivedParams -- never on a ROCm device at hidden 256 -- so are the two weight packs)
+        etable = F.linear(self._target_embedder.weight.detach(), w_ih[:, Hd:], bias).contiguous()
+        enc, h, fmask, w_p, b_p = enc.contiguous(), h.contiguous(), fmask.contiguous(), w_p.contiguous(), b_p.contiguous()
+        raw = torch.empty(B, K, T, dtype=torch.long, device=dev)
+        scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+        tr = None
+        if trace:
+            tr = (torch.empty(B, T, K, dtype=torch.int32, device=dev), torch.empty(B, T, K, dtype=torch.int32, device=dev),
+                  torch.empty(B, T, K, dtype=torch.float32, device=dev))
+        if B > 0 and T > 0:
+            _hip.check(_hip.lib().pnmn_attn_lstm_beam(
+                etable.data_ptr(), enc.data_ptr(), fmask.data_ptr(), h.data_ptr(), w_c_p.data_ptr(), w_hh_p.data_ptr(),
+                w_p.data_ptr(), b_p.data_ptr(), raw.data_ptr(), scores.data_ptr(),
+                tr[0].data_ptr() if tr else None, tr[1].data_ptr() if tr else None, tr[2].data_ptr() if tr else None,
+                B, T, S, V, Hd, K, self._pad_index, self._unk_index, self._start_index, self._end_index,
+                _hip.stream_ptr(dev)), "attn_lstm_beam")
+        beams = self._trim_predictions(raw.view(B * K, T)).view(B, K, T)
+        best = beams[:, 0]
+        n = (best != self._pad_index).sum(-1).to(scores.dtype)
+        # (an empty best hypothesis, n = 0: the sampled path sums no log-probability and returns 0)
+        loss = torch.where(n > 0, -scores[:, 0] / (n + 1e-12), torch.zeros_like(n))
+        out = {"predictions": best, "loss": loss, "beam_predictions": beams, "beam_log_probabilities": scores}
+        if tr:
+            out["beam_trace"] = {"tokens": tr[0], "backpointers": tr[1], "scores": tr[2]}
+        return out
 
     # ---- two teacher-forced decodes of a training iteration side by side -------------------------------------------
     def decode_prepare(self, state: Dict[str, torch.Tensor], target_tokens: Optional[torch.LongTensor] = None,
