@@ -120,7 +120,15 @@ int pnmn_conv_wgrad(const pnmn_wgrad_item* items, const pnmn_wgrad_job* jobs, in
                     int W, int ntaps, int cin_blocks, int cout_blocks, int x_stride,
                     int dy_stride, void* stream);
 /* The same with a CU budget (0 = none; 14x14 maps): at most `cus` workgroups, each walking several (job, slab) units --
- * for launches that share the chip with other streams' kernels.  In a pnmn_launch entry p[7] of a WGRAD carries it. */
+ * for launches that share the chip with other streams' kernels.  In a pnmn_launch entry p[7] of a WGRAD carries it.
+ * The budget only changes how the work is cut, never the sums.  What a value means, path by path:
+ *   3x3 at 14x14 and classifier-shaped 1x1 (one input block, even cout_blocks, at most 512 jobs; either map size):
+ *     1..256 is the budget; anything else (0, negative, larger) sizes the launch for the whole chip;
+ *   other 1x1 at 14x14: any cus >= 1 below the number of (job, slab) units is the number of workgroups, which walk the
+ *     units (values above 256 included); anything else gives one workgroup per unit;
+ *   the banded 28x28 kernels (3x3, and every 1x1 launch that is not classifier-shaped) ignore it.
+ * A job may be empty (item_begin == item_end: nothing is added), and every item carries its own dilation -- the items of
+ * one job need not share it. */
 int pnmn_conv_wgrad_cus(const pnmn_wgrad_item* items, const pnmn_wgrad_job* jobs, int n_jobs, int H, int W, int ntaps,
                         int cin_blocks, int cout_blocks, int x_stride, int dy_stride, int cus, void* stream);
 

@@ -475,7 +475,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     struct Cursor {
         int job, item, st;  // job, absolute item index, stage within the item
     };
-    // (a range of more items than the LDS holds records of goes in pieces: one more flush per 511 items)
+    // (a range of more items than the LDS holds records of goes in pieces of G1_MAX_ITEMS - 1 = 255 items' stages: one more
+    // flush per piece)
     for (long t0 = r0; t0 < r1;) {
     const long t1 = r1 - t0 > (long)(G1_MAX_ITEMS - 1) * spi ? t0 + (long)(G1_MAX_ITEMS - 1) * spi : r1;
     __syncthreads();  // (the previous piece's records and stage buffers are no longer read)
@@ -651,8 +652,8 @@ int launch_wgrad_1x1_gemm(const pnmn_wgrad_item* items, const pnmn_wgrad_job* jo
     if (const int e = pnmn::opt_in_lds(reinterpret_cast<const void*>(conv_wgrad_1x1_gemm_kernel), G1_LDS_ALL, configured)) return e;
     const int n_cob = cout_blocks / 2;
     // workgroups per output block: two per CU the launch may use, shared out among the blocks -- but a range of at least
-    // ~2 stages each (n_jobs x HW / 28 stages is a lower bound that needs no look at the device records: every job holds
-    // at least one item)
+    // ~2 stages each (n_jobs x HW / 28 stages is an estimate that needs no look at the device records: the planners' jobs
+    // hold at least one item.  Where jobs are empty it is too high and some workgroups get an empty range, which they skip)
     const int budget = (cus >= 1 && cus <= 256) ? cus : pnmn::default_conv_cus();
     int wpc = 2 * budget / n_cob;
     const long least = (long)n_jobs * (HW / G1_PX);

@@ -27,6 +27,10 @@
 //     sub-tiles; B = x: one ds_read_u16 of the row table, one v_xad, one ds_read_b32 per tap) with the next step's
 //     operands requested one step ahead and the row entries two steps ahead.
 //
+//   * The row table holds ONE dilation.  It is rebuilt behind an extra barrier pair at a unit's end (the next job may have
+//     another) and wherever an item's dilation differs from the item's before it inside a job (pnmn_wgrad_item carries
+//     its own): loaders and contraction waves read the same item records and so agree on where that is.
+//
 // LDS: 4 x-slots (106 496 B) + 2 dy half slots (51 200 B) + row table at conv_stream's offset = Geom::LDS_BYTES.
 #pragma once
 #include "conv_stream.h"
@@ -206,6 +210,15 @@ __device__ __forceinline__ void loader(const Launch& L, const pnmn_wgrad_item* i
                 fill_table<14, 14, 14>(lds, 0, dil, 1, 9, lane, LW, NLOAD);
                 tab_dil = dil;
             }
+        } else if (C.half == 0) {
+            // the dilation is the ITEM's: where it changes inside a job the table is rebuilt behind the same extra barrier
+            // (the contraction waves take theirs on the same comparison of the same item records)
+            const int dil = items[C.item].dilation;
+            if (dil != tab_dil) {
+                lds_barrier();  // the item before this one is contracted
+                fill_table<14, 14, 14>(lds, 0, dil, 1, 9, lane, LW, NLOAD);
+                tab_dil = dil;
+            }
         }
         lds_barrier();  // hand-over: the stage is the contraction waves'; every stage before it is finished
         const int half = C.half;
@@ -239,7 +252,10 @@ __device__ __forceinline__ void contraction(const Launch& L, const pnmn_wgrad_it
     const int li = lane & 15, g = lane >> 4;
     Walker Wk;
     Wk.start(L, jobs);
-    start_up(lds, Wk.valid() ? items[Wk.item].dilation : 1, Wk.valid(), wave, lane);
+    // dilation the row table holds (the loaders keep the same record: a unit's first item sets it, an item of another
+    // dilation inside the job rebuilds the table behind one more barrier)
+    int tab_dil = Wk.valid() ? items[Wk.item].dilation : 1;
+    start_up(lds, tab_dil, Wk.valid(), wave, lane);
 
     const uint32_t lds0 = (uint32_t)(uintptr_t)(lchar*)lds;
     // this lane's channel li of a 16-channel sub-slot row: piece (li >> 2) at its permuted position (conv_stream.h),
@@ -259,8 +275,17 @@ __device__ __forceinline__ void contraction(const Launch& L, const pnmn_wgrad_it
         const int slab = Wk.slab;
         float* const dw = Wk.dw;
         bool more = true;
+        int next_dil = tab_dil;  // dilation of the item behind the one in flight (fetched during its second half)
         while (more) {
             const int half = Wk.half;
+            if (half == 0) {
+                if (next_dil != tab_dil) {
+                    lds_barrier();  // this item's dilation differs: the loaders rebuild the row table behind this barrier
+                    tab_dil = next_dil;
+                }
+            } else if (Wk.item + 1 < Wk.item_end) {
+                next_dil = items[Wk.item + 1].dilation;
+            }
             const uint32_t xbase = xsub + (uint32_t)((cnt & 1) * XBUF_BYTES);
             const int nk = half ? KSTEPS - K_HALF0 : K_HALF0;
             uint32_t dyp = dylane + (uint32_t)(half * DY_SLOT);
@@ -346,6 +371,7 @@ __device__ __forceinline__ void contraction(const Launch& L, const pnmn_wgrad_it
             }
         }
         Wk.next_unit();
+        if (Wk.valid()) tab_dil = items[Wk.item].dilation;
     }
 }
 
