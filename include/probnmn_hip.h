@@ -521,35 +521,27 @@ int pnmn_attn_lstm_beam(const float* etable, const float* enc, const float* mask
 
 /* Multi-CU variants of the two kernels above (decoder_multi.hip): eight workgroups per 16-row tile,
  * each keeping its rows' encoder outputs in LDS and its slices of W_c / W_hh in registers, two L2
- * hand-offs per step.  Same arguments and saved tensors, plus a device `workspace` of
- * pnmn_attn_lstm_multi_workspace_bytes(B, backward) bytes (0 = device too small: use the kernels
- * above).  Batches beyond what fits the chip at once (512 rows on 256 CUs) run as successive launches.
+ * hand-offs per step.  A job = the arguments and saved tensors of pnmn_attn_lstm_fwd / _bwd for one pass; every call
+ * also takes a device `workspace` of pnmn_attn_lstm_group_workspace_bytes(rows, n, backward) bytes, rows[i] = B of
+ * job i (n = 1: 0 = device too small, use the kernels above).
  * The backward emits dctx [B,T,H] (gradient wrt every context vector) and dscore [B,T,S] (gradient
  * wrt the attention scores) instead of accumulating denc; the caller forms
  *     denc = w^T dctx + dscore^T h_prev      (two GEMMs per row over the T steps; w = the masked, renormalised
  *                                             attention weights, which the kernel writes to `weights` [B,T,S])
  * Sums over source positions / gate columns are associated differently from the one-workgroup
- * kernels: results agree to fp32 round-off, not bit for bit. */
-int64_t pnmn_attn_lstm_multi_workspace_bytes(int B, int backward);
-int pnmn_attn_lstm_fwd_multi(const float* xe, const float* etable, const float* enc, const float* mask,
-                             const float* h0, const float* w_c, const float* w_hh, const float* w_p,
-                             const float* b_p, float* hs, float* cs, float* act, float* ctx,
-                             float* probs, int64_t* tokens, int B, int T, int S, int V, int hidden,
-                             int sample, int pad_index, int unk_index, int start_index,
-                             uint64_t seed, uint64_t row_offset, const int64_t* in_tokens,
-                             int64_t in_token_stride, void* workspace, void* stream);
-int pnmn_attn_lstm_bwd_multi(const float* dhs, const float* act, const float* cs, const float* hs,
-                             const float* probs, const float* enc, const float* mask,
-                             const float* h0, const float* w_c_t, const float* w_hh_t,
-                             float* dgates, float* dctx, float* dscore, float* weights, float* dh0,
-                             int B, int T, int S, int hidden, void* workspace, void* stream);
-
-/* Two independent decoder passes side by side in ONE launch (a training iteration's teacher-forced decodes: the
- * reconstructor over the questions and the generator over the supervised programs -- question_coding_trainer.py:128-160,
- * joint_training_trainer.py:150-190 call them one after the other): these kernels are bound by their per-step hand-off
- * latency, so two passes that fit the chip together take as long as the longer one instead of the sum.  A job = the
- * arguments of pnmn_attn_lstm_fwd_multi / _bwd_multi.  Passes that do not fit one launch together run one after the
- * other (identical results).  Workspace: pnmn_attn_lstm_pair_workspace_bytes(Ba, Bb, backward). */
+ * kernels: results agree to fp32 round-off, not bit for bit.
+ *
+ * `jobs` is an array of n INDEPENDENT passes (forward n = 1..2, backward n = 1..3) that go out side by side in ONE
+ * launch.  These kernels are bound by their per-step hand-off latency, so passes that fit the chip together take as
+ * long as the longest instead of the sum.  Forward: a training iteration's teacher-forced decodes, the reconstructor
+ * over the questions and the generator over the supervised programs (question_coding_trainer.py:128-160,
+ * joint_training_trainer.py:150-190 call them one after the other).  Backward: those two and the generator's decode of
+ * the sampled programs (the samples are discrete, no gradient flows from the reconstruction back into the generator).
+ * Fit: every job has B > 0 and T > 0 and the jobs' tiles, each job rounded up to whole groups of 8 tiles, are resident
+ * together (512 rows on 256 CUs, at most 128 tiles).  Jobs that do not fit go out as the first n - 1 by the same rule,
+ * then the last alone (identical results): three -> pair + single, pair -> single, single.  A single job beyond what
+ * fits the chip at once runs as successive launches over its rows; one with B <= 0 or T <= 0 is skipped.
+ * n out of range or a missing jobs / workspace pointer returns PNMN_EINVAL (the workspace query: 0). */
 typedef struct pnmn_decoder_fwd_job {
     const float *xe, *etable, *enc, *mask, *h0, *w_c, *w_hh, *w_p, *b_p;
     float *hs, *cs, *act, *ctx, *probs;
@@ -564,20 +556,10 @@ typedef struct pnmn_decoder_bwd_job {
     float *dgates, *dctx, *dscore, *weights, *dh0;
     int32_t B, T, S, reserved;
 } pnmn_decoder_bwd_job;    /* 136 bytes */
-int64_t pnmn_attn_lstm_pair_workspace_bytes(int Ba, int Bb, int backward);
-int pnmn_attn_lstm_fwd_multi_pair(const pnmn_decoder_fwd_job* a, const pnmn_decoder_fwd_job* b, int hidden, void* workspace,
-                                  void* stream);
-int pnmn_attn_lstm_bwd_multi_pair(const pnmn_decoder_bwd_job* a, const pnmn_decoder_bwd_job* b, int hidden, void* workspace,
-                                  void* stream);
-/* ... of THREE passes: in the backward pass of a training iteration the ProgramGenerator's two decodes and the
- * QuestionReconstructor's are independent (question_coding_trainer.py:128-160, joint_training_trainer.py:150-190: the sampled
- * programs are discrete, no gradient flows from the reconstruction back into the generator) -- side by side the launch takes as
- * long as the longest.  Falls back to pair + single when the three do not fit the chip together (identical results).
- * Workspace: pnmn_attn_lstm_group3_workspace_bytes(Ba, Bb, Bc, backward). */
-int64_t pnmn_attn_lstm_group3_workspace_bytes(int Ba, int Bb, int Bc, int backward);
-int pnmn_attn_lstm_bwd_multi_group3(const pnmn_decoder_bwd_job* a, const pnmn_decoder_bwd_job* b, const pnmn_decoder_bwd_job* c,
-                                    int hidden, void* workspace, void* stream);
-/* The encoder-output gradient from what pnmn_attn_lstm_bwd_multi emits, in one bandwidth-bound launch instead of two
+int64_t pnmn_attn_lstm_group_workspace_bytes(const int32_t* rows, int n, int backward);
+int pnmn_attn_lstm_fwd_group(const pnmn_decoder_fwd_job* jobs, int n, int hidden, void* workspace, void* stream);
+int pnmn_attn_lstm_bwd_group(const pnmn_decoder_bwd_job* jobs, int n, int hidden, void* workspace, void* stream);
+/* The encoder-output gradient from what pnmn_attn_lstm_bwd_group emits, in one bandwidth-bound launch instead of two
  * strided-batched library GEMMs of B tiny [S x T].[T x 256] products (allennlp SimpleSeq2Seq._prepare_attended_input /
  * DotProductAttention under autograd; seq2seq_base.py:201):
  *   denc[b][s][:] = sum_t weights[b][t][s] * dctx[b][t][:] + dscore[b][t][s] * h_{t-1}[b][:]   (h_{-1} = h0)

@@ -873,267 +873,202 @@ int rows_per_launch() {
     return cus >= 8 * MEMBERS ? (cus / (8 * MEMBERS)) * 8 * ROWS : 0;
 }
 
+
+// ---- host side: one to three independent passes per launch ---------------------------------------------------------
+constexpr size_t LDS_LIMIT = 160 * 1024;
+constexpr int MAX_JOBS = 3;
+
+inline int padded_tiles(int B) { return 8 * ((((B + ROWS - 1) / ROWS) + 7) / 8); }  // (whole groups of 8 tiles)
+
+// all n passes in one launch?  (their tile groups must be resident together)
+bool fits(const int* rows, int n) {
+    const int chunk = rows_per_launch();
+    int tiles = 0;
+    for (int i = 0; i < n; ++i) {
+        if (rows[i] <= 0) return false;
+        tiles += padded_tiles(rows[i]);
+    }
+    return chunk > 0 && tiles * ROWS <= chunk && tiles <= 128;
+}
+template <class Job>
+bool jobs_fit(const Job* j, int n) {
+    int rows[MAX_JOBS];
+    for (int i = 0; i < n; ++i) {
+        if (j[i].T <= 0) return false;
+        rows[i] = j[i].B;
+    }
+    return fits(rows, n);
+}
+
+// tiles of exchange buffers behind the counters: a lone pass takes its own tiles (of one row chunk), passes side by
+// side whole groups of 8 tiles each
+int exchange_tiles(const int* rows, int n, int chunk) {
+    if (n == 1) return ((rows[0] < chunk ? rows[0] : chunk) + ROWS - 1) / ROWS;
+    int tiles = 0;
+    for (int i = 0; i < n; ++i) tiles += padded_tiles(rows[i]);
+    return tiles;
+}
+
+// passes that do not fit one launch together: the first n - 1 by the same rule, then the last alone
+int64_t workspace_bytes(const int* rows, int n, bool backward) {
+    if (n > 1 && !fits(rows, n)) {
+        const int64_t a = workspace_bytes(rows, n - 1, backward), b = workspace_bytes(rows + n - 1, 1, backward);
+        return a > b ? a : b;
+    }
+    const int chunk = rows_per_launch();
+    if (chunk <= 0 || rows[0] <= 0) return 0;
+    int64_t bytes = (int64_t)pnmn::CLUSTER_SYNC_BYTES;
+    if (backward) bytes += (int64_t)exchange_tiles(rows, n, chunk) * (2 * MEMBERS * 2 + 2) * ROWS * H * sizeof(float);
+    return bytes;
+}
+
+int check_job(const pnmn_decoder_fwd_job& j, int hidden) {
+    if (!j.enc || !j.mask || !j.h0 || !j.w_c || !j.w_hh || !j.hs || !j.cs || !j.act || !j.ctx || !j.probs) return PNMN_EINVAL;
+    if (j.sample ? (!j.etable || !j.w_p || !j.b_p || !j.tokens) : (!j.xe && !(j.etable && j.in_tokens))) return PNMN_EINVAL;
+    if (hidden != H || j.S < 1 || j.S > MAXS || (j.sample && (j.V < 1 || j.V > MAXV))) return PNMN_ESHAPE;
+    return 0;
+}
+int check_job(const pnmn_decoder_bwd_job& j, int hidden) {
+    if (!j.dhs || !j.act || !j.cs || !j.hs || !j.probs || !j.enc || !j.mask || !j.h0 || !j.w_c_t || !j.w_hh_t || !j.dgates ||
+        !j.dctx || !j.dscore || !j.weights || !j.dh0)
+        return PNMN_EINVAL;
+    if (hidden != H || j.S < 1 || j.S > MAXS) return PNMN_ESHAPE;
+    return 0;
+}
+
+// the kernel's arguments for `rows` rows of a pass from row r on; tile0 = the pass's first tile in the launch (its
+// counters and exchange buffers)
+MFwdArgs kernel_args(const pnmn_decoder_fwd_job& j, size_t r, int rows, int* sync, int tile0) {
+    const int T = j.T, S = j.S;
+    return MFwdArgs{j.xe ? j.xe + r * T * G4 : nullptr, j.etable, j.enc + r * S * H, j.mask + r * S, j.h0 + r * H, j.w_c, j.w_hh,
+                    j.w_p, j.b_p, j.hs + r * T * H, j.cs + r * T * H, j.act + r * T * G4, j.ctx + r * T * H, j.probs + r * T * S,
+                    j.tokens ? j.tokens + r * T : nullptr, (!j.sample && !j.xe) ? j.in_tokens + r * j.in_token_stride : nullptr,
+                    (long)j.in_token_stride, sync + tile0 * pnmn::CLUSTER_COUNTER_STRIDE, rows, T, S, j.V, (rows + ROWS - 1) / ROWS,
+                    j.sample, j.pad_index, j.unk_index, j.start_index, j.seed, j.row_offset + r};
+}
+MBwdArgs kernel_args(const pnmn_decoder_bwd_job& j, size_t r, int rows, int* sync, int tile0, float* x1, float* x2) {
+    const int T = j.T, S = j.S;
+    return MBwdArgs{j.dhs + r * T * H, j.act + r * T * G4, j.cs + r * T * H, j.hs + r * T * H, j.probs + r * T * S,
+                    j.enc + r * S * H, j.mask + r * S, j.h0 + r * H, j.w_c_t, j.w_hh_t, j.dgates + r * T * G4, j.dctx + r * T * H,
+                    j.dscore + r * T * S, j.weights + r * T * S, j.dh0 + r * H, x1 + (size_t)tile0 * 2 * MEMBERS * 2 * ROWS * H,
+                    x2 + (size_t)tile0 * 2 * ROWS * H, sync + tile0 * pnmn::CLUSTER_COUNTER_STRIDE, rows, T, S,
+                    (rows + ROWS - 1) / ROWS};
+}
+
+// What a group of passes needs before its launch, the same in both directions: every job checked, the longest source
+// (the LDS size follows it), every pass's first tile (tile0[n] = all tiles).
+template <class Job>
+int plan_group(const Job* j, int n, int hidden, int& smax, int& chunk, int* rows, int* tile0) {
+    smax = 0;
+    tile0[0] = 0;
+    for (int i = 0; i < n; ++i) {
+        if (const int e = check_job(j[i], hidden)) return e;
+        smax = j[i].S > smax ? j[i].S : smax;
+        rows[i] = j[i].B;
+        tile0[i + 1] = tile0[i] + padded_tiles(rows[i]);
+    }
+    chunk = rows_per_launch();
+    return chunk > 0 ? 0 : PNMN_ESHAPE;
+}
+
+// Passes that fit the chip together go out as ONE launch; otherwise the first n - 1 by the same rule and then the last
+// alone (identical results).  A lone pass beyond one launch runs in row chunks.
+int launch_fwd(const pnmn_decoder_fwd_job* j, int n, int hidden, void* workspace, hipStream_t st) {
+    if (n > 1 && !jobs_fit(j, n)) {
+        const int rc = launch_fwd(j, n - 1, hidden, workspace, st);
+        return rc != 0 ? rc : launch_fwd(j + n - 1, 1, hidden, workspace, st);
+    }
+    if (j[0].B <= 0 || j[0].T <= 0) return 0;  // (a lone pass only: passes side by side have rows and steps, see jobs_fit)
+    int smax, chunk, rows[MAX_JOBS], tile0[MAX_JOBS + 1];
+    if (const int e = plan_group(j, n, hidden, smax, chunk, rows, tile0)) return e;
+    const bool overlap = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + FWD_OVERLAP_LDS <= LDS_LIMIT;
+    const size_t lds = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + (overlap ? FWD_OVERLAP_LDS : 0);
+    const bool s0 = j[0].sample != 0, s1 = n > 1 && j[1].sample != 0;
+    const void* kernel = n == 1 ? fwd_multi_variant(overlap, s0) : fwd_pair_variant(overlap, s0, s1);
+    {   // (the opt-in is per device and per kernel: lds_optin.h; the limit itself, whatever this launch uses)
+        static std::atomic<uint64_t> cfg[2][8];
+        if (const int e = pnmn::opt_in_lds(kernel, LDS_LIMIT, cfg[n - 1][4 * overlap + 2 * s0 + s1])) return e;
+    }
+    int* sync = nullptr;
+    if (n > 1) {
+        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
+        if (e != hipSuccess) return (int)e;
+        const auto pair = reinterpret_cast<void (*)(const MFwdArgs, const MFwdArgs, const int)>(const_cast<void*>(kernel));
+        const MFwdArgs a0 = kernel_args(j[0], 0, rows[0], sync, 0), a1 = kernel_args(j[1], 0, rows[1], sync, tile0[1]);
+        hipLaunchKernelGGL(pair, dim3(MEMBERS * tile0[2]), dim3(512), lds, st, a0, a1, tile0[1]);
+        return (int)hipGetLastError();
+    }
+    const auto multi = reinterpret_cast<void (*)(const MFwdArgs)>(const_cast<void*>(kernel));
+    for (int r0 = 0; r0 < rows[0]; r0 += chunk) {
+        const int part = rows[0] - r0 < chunk ? rows[0] - r0 : chunk;
+        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
+        if (e != hipSuccess) return (int)e;
+        const MFwdArgs a = kernel_args(j[0], (size_t)r0, part, sync, 0);
+        hipLaunchKernelGGL(multi, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a);
+        e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
+int launch_bwd(const pnmn_decoder_bwd_job* j, int n, int hidden, void* workspace, hipStream_t st) {
+    if (n > 1 && !jobs_fit(j, n)) {
+        const int rc = launch_bwd(j, n - 1, hidden, workspace, st);
+        return rc != 0 ? rc : launch_bwd(j + n - 1, 1, hidden, workspace, st);
+    }
+    if (j[0].B <= 0 || j[0].T <= 0) return 0;  // (a lone pass only: passes side by side have rows and steps, see jobs_fit)
+    int smax, chunk, rows[MAX_JOBS], tile0[MAX_JOBS + 1];
+    if (const int e = plan_group(j, n, hidden, smax, chunk, rows, tile0)) return e;
+    const size_t lds = BWD_FIXED_LDS + sizeof(float) * RW * smax * H;
+    {
+        const void* const kernels[MAX_JOBS] = {reinterpret_cast<const void*>(attn_lstm_bwd_multi_kernel),
+                                               reinterpret_cast<const void*>(attn_lstm_bwd_pair_kernel),
+                                               reinterpret_cast<const void*>(attn_lstm_bwd_group3_kernel)};
+        static std::atomic<uint64_t> cfg[MAX_JOBS];  // (per kernel and device: lds_optin.h)
+        if (const int e = pnmn::opt_in_lds(kernels[n - 1], LDS_LIMIT, cfg[n - 1])) return e;
+    }
+    float* x1 = reinterpret_cast<float*>(static_cast<char*>(workspace) + pnmn::CLUSTER_SYNC_BYTES);
+    float* x2 = x1 + (size_t)exchange_tiles(rows, n, chunk) * 2 * MEMBERS * 2 * ROWS * H;
+    int* sync = nullptr;
+    if (n > 1) {
+        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
+        if (e != hipSuccess) return (int)e;
+        MBwdArgs a[MAX_JOBS];
+        for (int i = 0; i < n; ++i) a[i] = kernel_args(j[i], 0, rows[i], sync, tile0[i], x1, x2);
+        const dim3 grid(MEMBERS * tile0[n]);
+        if (n == 2) hipLaunchKernelGGL(attn_lstm_bwd_pair_kernel, grid, dim3(512), lds, st, a[0], a[1], tile0[1]);
+        else hipLaunchKernelGGL(attn_lstm_bwd_group3_kernel, grid, dim3(512), lds, st, a[0], a[1], a[2], tile0[1], tile0[2]);
+        return (int)hipGetLastError();
+    }
+    for (int r0 = 0; r0 < rows[0]; r0 += chunk) {
+        const int part = rows[0] - r0 < chunk ? rows[0] - r0 : chunk;
+        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
+        if (e != hipSuccess) return (int)e;
+        const MBwdArgs a = kernel_args(j[0], (size_t)r0, part, sync, 0, x1, x2);
+        hipLaunchKernelGGL(attn_lstm_bwd_multi_kernel, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a);
+        e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
 
-int64_t pnmn_attn_lstm_multi_workspace_bytes(int B, int backward) {
-    const int chunk = rows_per_launch();
-    if (chunk <= 0 || B <= 0) return 0;
-    const int tiles = ((B < chunk ? B : chunk) + ROWS - 1) / ROWS;
-    int64_t n = (int64_t)pnmn::CLUSTER_SYNC_BYTES;
-    if (backward) n += (int64_t)tiles * (2 * MEMBERS * 2 + 2) * ROWS * H * sizeof(float);
-    return n;
+int64_t pnmn_attn_lstm_group_workspace_bytes(const int32_t* rows, int n, int backward) {
+    if (!rows || n < 1 || n > MAX_JOBS) return 0;
+    return workspace_bytes(rows, n, backward != 0);
 }
 
-int pnmn_attn_lstm_fwd_multi(const float* xe, const float* etable, const float* enc, const float* mask, const float* h0,
-                             const float* w_c, const float* w_hh, const float* w_p, const float* b_p, float* hs, float* cs,
-                             float* act, float* ctx, float* probs, int64_t* tokens, int B, int T, int S, int V, int hidden,
-                             int sample, int pad_index, int unk_index, int start_index, uint64_t seed, uint64_t row_offset,
-                             const int64_t* in_tokens, int64_t in_token_stride, void* workspace, void* stream) {
-    if (B <= 0 || T <= 0) return 0;
-    if (!enc || !mask || !h0 || !w_c || !w_hh || !hs || !cs || !act || !ctx || !probs || !workspace) return PNMN_EINVAL;
-    if (sample ? (!etable || !w_p || !b_p || !tokens) : (!xe && !(etable && in_tokens))) return PNMN_EINVAL;
-    if (hidden != H || S < 1 || S > MAXS || (sample && (V < 1 || V > MAXV))) return PNMN_ESHAPE;
-    const int chunk = rows_per_launch();
-    if (chunk <= 0) return PNMN_ESHAPE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    constexpr size_t LDS_LIMIT = 160 * 1024;
-    const bool overlap = FWD_FIXED_LDS + sizeof(float) * RW * S * H + FWD_OVERLAP_LDS <= LDS_LIMIT;
-    const size_t lds = FWD_FIXED_LDS + sizeof(float) * RW * S * H + (overlap ? FWD_OVERLAP_LDS : 0);
-    {   // (the opt-in is per device and per kernel: lds_optin.h; the limit itself, whatever this launch uses)
-        static std::atomic<uint64_t> cfg[4] = {{0}, {0}, {0}, {0}};
-        if (const int e = pnmn::opt_in_lds(fwd_multi_variant(overlap, sample != 0), LDS_LIMIT, cfg[2 * overlap + (sample != 0)])) return e;
-    }
-    const auto kernel = reinterpret_cast<void (*)(const MFwdArgs)>(const_cast<void*>(fwd_multi_variant(overlap, sample != 0)));
-    for (int r0 = 0; r0 < B; r0 += chunk) {
-        const int rows = B - r0 < chunk ? B - r0 : chunk;
-        const int tiles = (rows + ROWS - 1) / ROWS;
-        int* sync = nullptr;
-        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
-        if (e != hipSuccess) return (int)e;
-        const size_t r = (size_t)r0;
-        MFwdArgs a{xe ? xe + r * T * G4 : nullptr, etable, enc + r * S * H, mask + r * S, h0 + r * H, w_c, w_hh, w_p, b_p,
-                   hs + r * T * H, cs + r * T * H, act + r * T * G4, ctx + r * T * H, probs + r * T * S,
-                   tokens ? tokens + r * T : nullptr, (!sample && !xe) ? in_tokens + r * in_token_stride : nullptr,
-                   (long)in_token_stride, sync, rows, T, S, V, tiles, sample,
-                   pad_index, unk_index, start_index, seed, row_offset + r};
-        hipLaunchKernelGGL(kernel, dim3(8 * MEMBERS * ((tiles + 7) / 8)), dim3(512), lds, st, a);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
+int pnmn_attn_lstm_fwd_group(const pnmn_decoder_fwd_job* jobs, int n, int hidden, void* workspace, void* stream) {
+    if (!jobs || !workspace || n < 1 || n > 2) return PNMN_EINVAL;
+    return launch_fwd(jobs, n, hidden, workspace, static_cast<hipStream_t>(stream));
 }
 
-int pnmn_attn_lstm_bwd_multi(const float* dhs, const float* act, const float* cs, const float* hs, const float* probs,
-                             const float* enc, const float* mask, const float* h0, const float* w_c_t,
-                             const float* w_hh_t, float* dgates, float* dctx, float* dscore, float* weights, float* dh0, int B,
-                             int T,
-                             int S, int hidden, void* workspace, void* stream) {
-    if (B <= 0 || T <= 0) return 0;
-    if (!dhs || !act || !cs || !hs || !probs || !enc || !mask || !h0 || !w_c_t || !w_hh_t || !dgates || !dctx ||
-        !dscore || !weights || !dh0 || !workspace)
-        return PNMN_EINVAL;
-    if (hidden != H || S < 1 || S > MAXS) return PNMN_ESHAPE;
-    const int chunk = rows_per_launch();
-    if (chunk <= 0) return PNMN_ESHAPE;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t lds = BWD_FIXED_LDS + sizeof(float) * RW * S * H;
-    {
-        static std::atomic<uint64_t> cfg{0};  // (per device: lds_optin.h)
-        if (const int e = pnmn::opt_in_lds(reinterpret_cast<const void*>(attn_lstm_bwd_multi_kernel), 160 * 1024, cfg)) return e;
-    }
-    char* ws = static_cast<char*>(workspace);
-    float* x1 = reinterpret_cast<float*>(ws + pnmn::CLUSTER_SYNC_BYTES);
-    const int max_tiles = chunk / ROWS;
-    float* x2 = x1 + (size_t)((B < chunk ? (B + ROWS - 1) / ROWS : max_tiles)) * 2 * MEMBERS * 2 * ROWS * H;
-    for (int r0 = 0; r0 < B; r0 += chunk) {
-        const int rows = B - r0 < chunk ? B - r0 : chunk;
-        const int tiles = (rows + ROWS - 1) / ROWS;
-        int* sync = nullptr;
-        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
-        if (e != hipSuccess) return (int)e;
-        const size_t r = (size_t)r0;
-        MBwdArgs a{dhs + r * T * H, act + r * T * G4, cs + r * T * H, hs + r * T * H, probs + r * T * S, enc + r * S * H,
-                   mask + r * S, h0 + r * H, w_c_t, w_hh_t, dgates + r * T * G4, dctx + r * T * H, dscore + r * T * S,
-                   weights + r * T * S,
-                   dh0 + r * H, x1, x2, sync, rows, T, S, tiles};
-        hipLaunchKernelGGL(attn_lstm_bwd_multi_kernel, dim3(8 * MEMBERS * ((tiles + 7) / 8)), dim3(512), lds, st, a);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
-
-
-// ---- two passes side by side -----------------------------------------------------------------------------------
-static inline int padded_tiles(int B) { return 8 * ((((B + ROWS - 1) / ROWS) + 7) / 8); }  // (whole groups of 8 tiles)
-
-// both passes in one launch?  (their tile groups must be resident together)
-static bool pair_fits(int Ba, int Bb) {
-    const int chunk = rows_per_launch();
-    return chunk > 0 && Ba > 0 && Bb > 0 && (padded_tiles(Ba) + padded_tiles(Bb)) * ROWS <= chunk + 0 &&
-           (padded_tiles(Ba) + padded_tiles(Bb)) <= 128;
-}
-
-int64_t pnmn_attn_lstm_pair_workspace_bytes(int Ba, int Bb, int backward) {
-    if (!pair_fits(Ba, Bb)) {
-        const int64_t a = pnmn_attn_lstm_multi_workspace_bytes(Ba, backward), b = pnmn_attn_lstm_multi_workspace_bytes(Bb, backward);
-        return a > b ? a : b;
-    }
-    int64_t n = (int64_t)pnmn::CLUSTER_SYNC_BYTES;
-    if (backward) n += (int64_t)(padded_tiles(Ba) + padded_tiles(Bb)) * (2 * MEMBERS * 2 + 2) * ROWS * H * sizeof(float);
-    return n;
-}
-
-int pnmn_attn_lstm_fwd_multi_pair(const pnmn_decoder_fwd_job* ja, const pnmn_decoder_fwd_job* jb, int hidden, void* workspace,
-                                  void* stream) {
-    if (!ja || !jb || !workspace) return PNMN_EINVAL;
-    auto single = [&](const pnmn_decoder_fwd_job* j) {
-        return pnmn_attn_lstm_fwd_multi(j->xe, j->etable, j->enc, j->mask, j->h0, j->w_c, j->w_hh, j->w_p, j->b_p, j->hs, j->cs,
-                                        j->act, j->ctx, j->probs, j->tokens, j->B, j->T, j->S, j->V, hidden, j->sample, j->pad_index,
-                                        j->unk_index, j->start_index, j->seed, j->row_offset, j->in_tokens, j->in_token_stride,
-                                        workspace, stream);
-    };
-    if (!pair_fits(ja->B, jb->B) || ja->T <= 0 || jb->T <= 0) {  // (one after the other: same results)
-        const int rc = single(ja);
-        return rc != 0 ? rc : single(jb);
-    }
-    const pnmn_decoder_fwd_job* jobs[2] = {ja, jb};
-    for (const pnmn_decoder_fwd_job* j : jobs) {
-        if (!j->enc || !j->mask || !j->h0 || !j->w_c || !j->w_hh || !j->hs || !j->cs || !j->act || !j->ctx || !j->probs) return PNMN_EINVAL;
-        if (j->sample ? (!j->etable || !j->w_p || !j->b_p || !j->tokens) : (!j->xe && !(j->etable && j->in_tokens))) return PNMN_EINVAL;
-        if (hidden != H || j->S < 1 || j->S > MAXS || (j->sample && (j->V < 1 || j->V > MAXV))) return PNMN_ESHAPE;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    constexpr size_t LDS_LIMIT = 160 * 1024;
-    const int smax = ja->S > jb->S ? ja->S : jb->S;
-    const bool overlap = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + FWD_OVERLAP_LDS <= LDS_LIMIT;
-    const size_t lds = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + (overlap ? FWD_OVERLAP_LDS : 0);
-    {   // (the opt-in is per device and per kernel: lds_optin.h; the limit itself, whatever this launch uses)
-        static std::atomic<uint64_t> cfg[8] = {{0}, {0}, {0}, {0}, {0}, {0}, {0}, {0}};
-        const int v = 4 * overlap + 2 * (ja->sample != 0) + (jb->sample != 0);
-        if (const int e = pnmn::opt_in_lds(fwd_pair_variant(overlap, ja->sample != 0, jb->sample != 0), LDS_LIMIT, cfg[v])) return e;
-    }
-    const auto kernel = reinterpret_cast<void (*)(const MFwdArgs, const MFwdArgs, const int)>(
-        const_cast<void*>(fwd_pair_variant(overlap, ja->sample != 0, jb->sample != 0)));
-    int* sync = nullptr;
-    hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
-    if (e != hipSuccess) return (int)e;
-    const int tiles0 = padded_tiles(ja->B);
-    auto args = [&](const pnmn_decoder_fwd_job* j, int* sy) {
-        return MFwdArgs{j->xe, j->etable, j->enc, j->mask, j->h0, j->w_c, j->w_hh, j->w_p, j->b_p, j->hs, j->cs, j->act, j->ctx,
-                        j->probs, j->tokens, (!j->sample && !j->xe) ? j->in_tokens : nullptr, (long)j->in_token_stride, sy, j->B,
-                        j->T, j->S, j->V, (j->B + ROWS - 1) / ROWS, j->sample, j->pad_index, j->unk_index, j->start_index,
-                        j->seed, j->row_offset};
-    };
-    const MFwdArgs a0 = args(ja, sync), a1 = args(jb, sync + tiles0 * pnmn::CLUSTER_COUNTER_STRIDE);
-    const int groups = (tiles0 + padded_tiles(jb->B)) / 8;
-    hipLaunchKernelGGL(kernel, dim3(8 * MEMBERS * groups), dim3(512), lds, st, a0, a1, tiles0);
-    return (int)hipGetLastError();
-}
-
-int pnmn_attn_lstm_bwd_multi_pair(const pnmn_decoder_bwd_job* ja, const pnmn_decoder_bwd_job* jb, int hidden, void* workspace,
-                                  void* stream) {
-    if (!ja || !jb || !workspace) return PNMN_EINVAL;
-    auto single = [&](const pnmn_decoder_bwd_job* j) {
-        return pnmn_attn_lstm_bwd_multi(j->dhs, j->act, j->cs, j->hs, j->probs, j->enc, j->mask, j->h0, j->w_c_t, j->w_hh_t, j->dgates,
-                                        j->dctx, j->dscore, j->weights, j->dh0, j->B, j->T, j->S, hidden, workspace, stream);
-    };
-    if (!pair_fits(ja->B, jb->B) || ja->T <= 0 || jb->T <= 0) {
-        const int rc = single(ja);
-        return rc != 0 ? rc : single(jb);
-    }
-    const pnmn_decoder_bwd_job* jobs[2] = {ja, jb};
-    for (const pnmn_decoder_bwd_job* j : jobs) {
-        if (!j->dhs || !j->act || !j->cs || !j->hs || !j->probs || !j->enc || !j->mask || !j->h0 || !j->w_c_t || !j->w_hh_t ||
-            !j->dgates || !j->dctx || !j->dscore || !j->weights || !j->dh0)
-            return PNMN_EINVAL;
-        if (hidden != H || j->S < 1 || j->S > MAXS) return PNMN_ESHAPE;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int smax = ja->S > jb->S ? ja->S : jb->S;
-    const size_t lds = BWD_FIXED_LDS + sizeof(float) * RW * smax * H;
-    {
-        static std::atomic<uint64_t> cfg{0};  // (per device: lds_optin.h)
-        if (const int e = pnmn::opt_in_lds(reinterpret_cast<const void*>(attn_lstm_bwd_pair_kernel), 160 * 1024, cfg)) return e;
-    }
-    int* sync = nullptr;
-    hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
-    if (e != hipSuccess) return (int)e;
-    const int tiles0 = padded_tiles(ja->B), total = tiles0 + padded_tiles(jb->B);
-    char* ws = static_cast<char*>(workspace);
-    float* x1 = reinterpret_cast<float*>(ws + pnmn::CLUSTER_SYNC_BYTES);
-    float* x2 = x1 + (size_t)total * 2 * MEMBERS * 2 * ROWS * H;
-    auto args = [&](const pnmn_decoder_bwd_job* j, int first_tile) {
-        return MBwdArgs{j->dhs, j->act, j->cs, j->hs, j->probs, j->enc, j->mask, j->h0, j->w_c_t, j->w_hh_t, j->dgates, j->dctx,
-                        j->dscore, j->weights, j->dh0, x1 + (size_t)first_tile * 2 * MEMBERS * 2 * ROWS * H,
-                        x2 + (size_t)first_tile * 2 * ROWS * H, sync + first_tile * pnmn::CLUSTER_COUNTER_STRIDE, j->B, j->T, j->S,
-                        (j->B + ROWS - 1) / ROWS};
-    };
-    const MBwdArgs a0 = args(ja, 0), a1 = args(jb, tiles0);
-    hipLaunchKernelGGL(attn_lstm_bwd_pair_kernel, dim3(8 * MEMBERS * (total / 8)), dim3(512), lds, st, a0, a1, tiles0);
-    return (int)hipGetLastError();
-}
-
-// ---- three backward passes side by side ----------------------------------------------------------------------
-static bool group3_fits(int Ba, int Bb, int Bc) {
-    const int chunk = rows_per_launch();
-    const int tiles = padded_tiles(Ba) + padded_tiles(Bb) + padded_tiles(Bc);
-    return chunk > 0 && Ba > 0 && Bb > 0 && Bc > 0 && tiles * ROWS <= chunk && tiles <= 128;
-}
-
-int64_t pnmn_attn_lstm_group3_workspace_bytes(int Ba, int Bb, int Bc, int backward) {
-    if (!group3_fits(Ba, Bb, Bc)) {
-        const int64_t ab = pnmn_attn_lstm_pair_workspace_bytes(Ba, Bb, backward), c = pnmn_attn_lstm_multi_workspace_bytes(Bc, backward);
-        return ab > c ? ab : c;
-    }
-    int64_t n = (int64_t)pnmn::CLUSTER_SYNC_BYTES;
-    if (backward) n += (int64_t)(padded_tiles(Ba) + padded_tiles(Bb) + padded_tiles(Bc)) * (2 * MEMBERS * 2 + 2) * ROWS * H * sizeof(float);
-    return n;
-}
-
-int pnmn_attn_lstm_bwd_multi_group3(const pnmn_decoder_bwd_job* ja, const pnmn_decoder_bwd_job* jb, const pnmn_decoder_bwd_job* jc,
-                                    int hidden, void* workspace, void* stream) {
-    if (!ja || !jb || !jc || !workspace) return PNMN_EINVAL;
-    if (!group3_fits(ja->B, jb->B, jc->B) || ja->T <= 0 || jb->T <= 0 || jc->T <= 0) {  // (pair + single: same results)
-        const int rc = pnmn_attn_lstm_bwd_multi_pair(ja, jb, hidden, workspace, stream);
-        return rc != 0 ? rc
-                       : pnmn_attn_lstm_bwd_multi(jc->dhs, jc->act, jc->cs, jc->hs, jc->probs, jc->enc, jc->mask, jc->h0, jc->w_c_t,
-                                                  jc->w_hh_t, jc->dgates, jc->dctx, jc->dscore, jc->weights, jc->dh0, jc->B, jc->T, jc->S,
-                                                  hidden, workspace, stream);
-    }
-    const pnmn_decoder_bwd_job* jobs[3] = {ja, jb, jc};
-    int smax = 0;
-    for (const pnmn_decoder_bwd_job* j : jobs) {
-        if (!j->dhs || !j->act || !j->cs || !j->hs || !j->probs || !j->enc || !j->mask || !j->h0 || !j->w_c_t || !j->w_hh_t ||
-            !j->dgates || !j->dctx || !j->dscore || !j->weights || !j->dh0)
-            return PNMN_EINVAL;
-        if (hidden != H || j->S < 1 || j->S > MAXS) return PNMN_ESHAPE;
-        smax = j->S > smax ? j->S : smax;
-    }
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t lds = BWD_FIXED_LDS + sizeof(float) * RW * smax * H;
-    {
-        static std::atomic<uint64_t> cfg{0};  // (per device: lds_optin.h)
-        if (const int e = pnmn::opt_in_lds(reinterpret_cast<const void*>(attn_lstm_bwd_group3_kernel), 160 * 1024, cfg)) return e;
-    }
-    int* sync = nullptr;
-    hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
-    if (e != hipSuccess) return (int)e;
-    const int tiles0 = padded_tiles(ja->B), tiles01 = tiles0 + padded_tiles(jb->B), total = tiles01 + padded_tiles(jc->B);
-    char* ws = static_cast<char*>(workspace);
-    float* x1 = reinterpret_cast<float*>(ws + pnmn::CLUSTER_SYNC_BYTES);
-    float* x2 = x1 + (size_t)total * 2 * MEMBERS * 2 * ROWS * H;
-    auto args = [&](const pnmn_decoder_bwd_job* j, int first_tile) {
-        return MBwdArgs{j->dhs, j->act, j->cs, j->hs, j->probs, j->enc, j->mask, j->h0, j->w_c_t, j->w_hh_t, j->dgates, j->dctx,
-                        j->dscore, j->weights, j->dh0, x1 + (size_t)first_tile * 2 * MEMBERS * 2 * ROWS * H,
-                        x2 + (size_t)first_tile * 2 * ROWS * H, sync + first_tile * pnmn::CLUSTER_COUNTER_STRIDE, j->B, j->T, j->S,
-                        (j->B + ROWS - 1) / ROWS};
-    };
-    const MBwdArgs a0 = args(ja, 0), a1 = args(jb, tiles0), a2 = args(jc, tiles01);
-    hipLaunchKernelGGL(attn_lstm_bwd_group3_kernel, dim3(8 * MEMBERS * (total / 8)), dim3(512), lds, st, a0, a1, a2, tiles0, tiles01);
-    return (int)hipGetLastError();
+int pnmn_attn_lstm_bwd_group(const pnmn_decoder_bwd_job* jobs, int n, int hidden, void* workspace, void* stream) {
+    if (!jobs || !workspace || n < 1 || n > MAX_JOBS) return PNMN_EINVAL;
+    return launch_bwd(jobs, n, hidden, workspace, static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

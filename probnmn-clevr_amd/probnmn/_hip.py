@@ -85,14 +85,9 @@ SIGNATURES: Dict[str, tuple] = {
     "pnmn_attn_lstm_beam": (_P,) * 13 + (_I,) * 10 + (_P,),
     "pnmn_attn_lstm_fwd": (_P,) * 15 + (_I,) * 9 + (ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.c_int64, _P),
     "pnmn_attn_lstm_bwd": (_P,) * 14 + (_I,) * 4 + (_P,),
-    "pnmn_attn_lstm_multi_workspace_bytes": (_I, _I),
-    "pnmn_attn_lstm_fwd_multi": (_P,) * 15 + (_I,) * 9 + (ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.c_int64, _P, _P),
-    "pnmn_attn_lstm_bwd_multi": (_P,) * 15 + (_I,) * 4 + (_P, _P),
-    "pnmn_attn_lstm_pair_workspace_bytes": (_I, _I, _I),
-    "pnmn_attn_lstm_fwd_multi_pair": (_P, _P, _I, _P, _P),
-    "pnmn_attn_lstm_bwd_multi_pair": (_P, _P, _I, _P, _P),
-    "pnmn_attn_lstm_group3_workspace_bytes": (_I, _I, _I, _I),
-    "pnmn_attn_lstm_bwd_multi_group3": (_P, _P, _P, _I, _P, _P),
+    "pnmn_attn_lstm_group_workspace_bytes": (_P, _I, _I),
+    "pnmn_attn_lstm_fwd_group": (_P, _I, _I, _P, _P),
+    "pnmn_attn_lstm_bwd_group": (_P, _I, _I, _P, _P),
     "pnmn_attn_denc": (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P),
     "pnmn_conv_nhwc_launches": (_I, _I, _I, _I, _I, _I),
     "pnmn_conv_force_split": (_I,),
@@ -126,7 +121,7 @@ SIGNATURES: Dict[str, tuple] = {
 }
 
 
-ABI_VERSION = 12  # pnmn_abi_version() of the library these signatures describe (include/probnmn_hip.h)
+ABI_VERSION = 13  # pnmn_abi_version() of the library these signatures describe (include/probnmn_hip.h)
 
 
 def lib() -> ctypes.CDLL:
@@ -330,6 +325,12 @@ ITEM_SIZES = {
     "pnmn_lstm_stack_job": (LSTM_STACK_JOB, 104),
     "pnmn_lstm_dropout_desc": (LSTM_DROPOUT_DESC, 32),
 }
+
+
+def decoder_workspace_bytes(rows, backward: bool) -> int:
+    """``pnmn_attn_lstm_group_workspace_bytes`` for decoder passes of ``rows[i]`` rows each in one call (1-3 of them)."""
+    r = np.asarray(rows, np.int32)
+    return int(lib().pnmn_attn_lstm_group_workspace_bytes(r.ctypes.data, len(r), 1 if backward else 0))
 
 
 def stream_ptr(device: torch.device) -> int:

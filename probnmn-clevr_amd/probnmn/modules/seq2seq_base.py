@@ -23,7 +23,7 @@ of a persistent kernel that keeps the K hypotheses of a question in one workgrou
 csrc/decoder_beam.hip).
 """
 import os
-from typing import Dict, Optional
+from typing import Dict, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -415,12 +415,18 @@ def _lstm_workspace(batch: int, backward: bool, device) -> Optional[torch.Tensor
     return torch.empty(n, dtype=torch.uint8, device=device) if n > 0 else None
 
 
-def _decoder_workspace(batch: int, backward: bool, device) -> Optional[torch.Tensor]:
-    """Scratch of the multi-CU decoder kernels; ``None`` = use the one-workgroup-per-tile kernels
+def _decoder_workspace_bytes(rows, backward: bool) -> int:
+    """Bytes of scratch the multi-CU decoder kernels want for passes of ``rows[i]`` rows each in one call (the library's fit /
+    fall-back rule: include/probnmn_hip.h); 0 = a single pass runs on the one-workgroup-per-tile kernels
     (PNMN_DECODER_CLUSTER=0, or a device too small for eight resident workgroups per tile)."""
-    if os.environ.get("PNMN_DECODER_CLUSTER", "1") == "0":
-        return None
-    n = int(_hip.lib().pnmn_attn_lstm_multi_workspace_bytes(batch, 1 if backward else 0))
+    if len(rows) == 1 and os.environ.get("PNMN_DECODER_CLUSTER", "1") == "0":
+        return 0
+    return _hip.decoder_workspace_bytes(rows, backward)
+
+
+def _decoder_workspace(rows, backward: bool, device) -> Optional[torch.Tensor]:
+    """That scratch, or ``None`` for 0 bytes.  A fresh allocation per launch, as ``_lstm_workspace``."""
+    n = _decoder_workspace_bytes(rows, backward)
     return torch.empty(n, dtype=torch.uint8, device=device) if n > 0 else None
 
 
@@ -528,310 +534,219 @@ def _table_grad(dy: torch.Tensor, tokens: torch.Tensor, vocab: int, padding_idx:
     return dw
 
 
-class _AttnLSTMDecoder(torch.autograd.Function):
-    """The decoding loop as one persistent kernel launch (``pnmn_attn_lstm_fwd`` / ``_bwd``).
+_SIDE_SAVED = 11  # tensors a decoder pass saves: hs, cs, act, cx, probs, enc, mask, h0, w_c, w_hh, step tokens
 
-    inputs : xe [B,T,4H] (teacher forcing) or etable [V,4H] (free running), enc [B,S,H], mask [B,S] float,
-             h0 [B,H], W_c [4H,H], W_hh [4H,H], W_p [V,H], b_p [V]
-    outputs: hidden states [B,T,H], tokens [B,T] (free running only)
-    Weight gradients are batched GEMMs over what the kernels saved."""
 
-    @staticmethod
-    def forward(ctx, xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, mode, T, seed, row_offset, pad, unk, start,
-                packs=None, in_tokens=None):
-        dev = enc.device
-        if dev.type != "cuda":
-            raise _hip.HipLibraryError("decoder on %s: the HIP path needs a ROCm device (no CPU fallback)" % dev)
-        enc, mask, h0 = enc.contiguous(), mask.contiguous(), h0.contiguous()
-        w_c, w_hh = w_c.detach(), w_hh.detach()
-        if packs is not None:  # (w_c, w_hh, w_c^T, w_hh^T in fragment order, from the model's DerivedParams)
-            w_c_p, w_hh_p = packs[0], packs[1]
-            ctx.packs_t = (packs[2], packs[3])
-        else:
-            w_c_p, w_hh_p = pack_fragments(w_c), pack_fragments(w_hh)
-            ctx.packs_t = None
-        B, S, Hd = enc.shape
-        f = dict(dtype=torch.float32, device=dev)
-        hs, cs, cx = torch.empty(B, T, Hd, **f), torch.empty(B, T, Hd, **f), torch.empty(B, T, Hd, **f)
-        act = torch.empty(B, T, 4 * Hd, **f)
-        probs = torch.empty(B, T, S, **f)
-        tokens = None
-        V = 0
-        if mode != 0:
-            etable, w_p, b_p = etable.contiguous(), w_p.detach().contiguous(), b_p.detach().contiguous()
-            tokens = torch.empty(B, T, dtype=torch.long, device=dev)
-            V = w_p.size(0)
-        elif in_tokens is not None:  # teacher forcing from the [V,4H] table: step t's input is row in_tokens[b,t]
-            etable = etable.contiguous()
-            if in_tokens.dtype != torch.long or in_tokens.stride(1) != 1:
-                in_tokens = in_tokens.long().contiguous()
-            xe = None
-        else:
-            xe = xe.contiguous()
-        ptr = lambda t: None if t is None else t.data_ptr()  # noqa: E731
-        args = (ptr(xe if mode == 0 else None), ptr(etable if (mode != 0 or in_tokens is not None) else None),
-                enc.data_ptr(), mask.data_ptr(),
-                h0.data_ptr(), w_c_p.data_ptr(), w_hh_p.data_ptr(), ptr(w_p if mode != 0 else None),
-                ptr(b_p if mode != 0 else None), hs.data_ptr(), cs.data_ptr(), act.data_ptr(), cx.data_ptr(),
-                probs.data_ptr(), ptr(tokens), B, T, S, V, Hd, mode, pad, unk, start, seed, row_offset,
-                ptr(in_tokens) if mode == 0 else None, in_tokens.stride(0) if (mode == 0 and in_tokens is not None) else 0)
-        ws = _decoder_workspace(B, False, dev)
-        if ws is not None:
-            _hip.check(_hip.lib().pnmn_attn_lstm_fwd_multi(*args, ws.data_ptr(), _hip.stream_ptr(dev)), "attn_lstm_fwd_multi")
-        else:
-            _hip.check(_hip.lib().pnmn_attn_lstm_fwd(*args, _hip.stream_ptr(dev)), "attn_lstm_fwd")
-        ctx.save_for_backward(hs, cs, act, cx, probs, enc, mask, h0, w_c, w_hh,
-                              tokens if tokens is not None else torch.empty(0, device=dev))
-        ctx.mode, ctx.start, ctx.vocab = mode, start, (etable.size(0) if etable is not None else 0)
-        ctx.in_tokens = in_tokens if mode == 0 else None
-        if tokens is not None:
-            ctx.mark_non_differentiable(tokens)
-            return hs, tokens
-        return hs, torch.empty(0, dtype=torch.long, device=dev)
+class _DecoderLaunch(NamedTuple):
+    """What the forward launch of some decoder passes leaves behind.  Per pass: two ``outs`` (hidden states [B,T,H] and the
+    chosen tokens [B,T], empty when teacher forced), ``_SIDE_SAVED`` tensors in ``saved`` and one entry of ``side_meta``
+    (vocab, (W_c^T, W_hh^T) in fragment order or None, mode, start index, fed projected inputs?)."""
 
-    @staticmethod
-    def backward(ctx, dhs, _):
-        hs, cs, act, cx, probs, enc, mask, h0, w_c, w_hh, tokens = ctx.saved_tensors
-        B, T, Hd = hs.shape
-        S = enc.size(1)
-        dev = hs.device
-        dgates = torch.empty_like(act)
-        dh0 = torch.empty_like(h0)
+    outs: tuple
+    saved: tuple
+    side_meta: tuple
+
+
+def _prepare_decoder_side(jobs, k, source, enc, mask, h0, w_c, w_hh, m):
+    """Everything one decoder pass needs before its launch; fills row ``k`` of ``jobs`` (``DECODER_FWD_JOB``).
+    Tensor inputs: ``source``, enc [B,S,H], mask [B,S] float, h0 [B,H], W_c [4H,H], W_hh [4H,H]; ``m`` carries the rest:
+    ``mode`` 0 teacher forced -- ``source`` is the per-token table [V,4H] and step t's input its row ``in_tokens[b,t]``, or
+    (no ``in_tokens``) ``source`` is the projected inputs xe [B,T,4H] themselves; 1 sampling / 2 greedy: free running, the
+    kernel picks each step's token (``source`` = the projected embedding table; ``w_p`` [V,H], ``b_p``, ``pad``, ``unk``,
+    ``seed``, ``row_offset``); ``T``, ``start``, ``packs`` = (W_c, W_hh, W_c^T, W_hh^T) in fragment order from the model's
+    DerivedParams, or None.  Returns (outs, saved, side meta) as ``_DecoderLaunch`` lists them, and the tensors that must
+    outlive the launch call."""
+    dev = enc.device
+    if dev.type != "cuda":
+        raise _hip.HipLibraryError("decoder on %s: the HIP path needs a ROCm device (no CPU fallback)" % dev)
+    source, enc, mask, h0 = source.contiguous(), enc.contiguous(), mask.contiguous(), h0.contiguous()
+    w_c, w_hh = w_c.detach(), w_hh.detach()
+    packs = m.get("packs")
+    if packs is None:
+        packs = (pack_fragments(w_c), pack_fragments(w_hh), None, None)
+    mode, T = m["mode"], m["T"]
+    B, S, Hd = enc.shape
+    f = dict(dtype=torch.float32, device=dev)
+    hs, cs, cx = torch.empty(B, T, Hd, **f), torch.empty(B, T, Hd, **f), torch.empty(B, T, Hd, **f)
+    act, probs = torch.empty(B, T, 4 * Hd, **f), torch.empty(B, T, S, **f)
+    in_tokens = tokens = w_p = b_p = None
+    projected = mode == 0 and m.get("in_tokens") is None
+    if mode != 0:
+        w_p, b_p = m["w_p"].detach().contiguous(), m["b_p"].detach().contiguous()
+        tokens = torch.empty(B, T, dtype=torch.long, device=dev)
+    elif not projected:
+        in_tokens = m["in_tokens"]
+        if in_tokens.dtype != torch.long or in_tokens.stride(1) != 1:
+            in_tokens = in_tokens.long().contiguous()
+    ptr = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+    jobs[k] = (source.data_ptr() if projected else 0, 0 if projected else source.data_ptr(), enc.data_ptr(), mask.data_ptr(),
+               h0.data_ptr(), packs[0].data_ptr(), packs[1].data_ptr(), ptr(w_p), ptr(b_p), hs.data_ptr(), cs.data_ptr(),
+               act.data_ptr(), cx.data_ptr(), probs.data_ptr(), ptr(tokens), ptr(in_tokens),
+               0 if in_tokens is None else in_tokens.stride(0), m.get("seed", 0), m.get("row_offset", 0), B, T, S,
+               0 if w_p is None else w_p.size(0), mode, m.get("pad", 0), m.get("unk", 0), m["start"])
+    empty = torch.empty(0, dtype=torch.long, device=dev)
+    step_tokens = tokens if mode != 0 else in_tokens
+    saved = (hs, cs, act, cx, probs, enc, mask, h0, w_c, w_hh, step_tokens if step_tokens is not None else hs.new_empty(0))
+    side_meta = (0 if projected else source.size(0), (packs[2], packs[3]) if packs[2] is not None else None, mode, m["start"],
+                 projected)
+    return (hs, tokens if tokens is not None else empty), saved, side_meta, (source, packs, w_p, b_p)
+
+
+def _decoder_forward(tensors, metas) -> _DecoderLaunch:
+    """The forward of one or two decoder passes as ONE launch (``pnmn_attn_lstm_fwd_group``: side by side when they fit the
+    chip together, else one after the other -- bit for bit the same either way, the kernels' bodies are shared).
+    ``tensors[k]`` / ``metas[k]``: pass k's inputs as ``_prepare_decoder_side`` takes them.  A single pass without the
+    multi-CU kernels (``_decoder_workspace``) runs on ``pnmn_attn_lstm_fwd``."""
+    n = len(metas)
+    jobs = np.zeros(n, _hip.DECODER_FWD_JOB)
+    sides = [_prepare_decoder_side(jobs, k, *tensors[k], metas[k]) for k in range(n)]  # (alive until the launch is queued)
+    hs = sides[0][0][0]
+    dev, Hd = hs.device, hs.size(2)
+    ws = _decoder_workspace([sd[0][0].size(0) for sd in sides], False, dev)
+    lib = _hip.lib()
+    if ws is not None:
+        _hip.check(lib.pnmn_attn_lstm_fwd_group(jobs.ctypes.data, n, Hd, ws.data_ptr(), _hip.stream_ptr(dev)), "attn_lstm_fwd_group")
+    elif n == 1:
+        j = jobs[0].item()  # (the record's fields in order: 16 pointers, stride, seed, row offset, 8 ints)
+        _hip.check(lib.pnmn_attn_lstm_fwd(*j[:15], *j[19:23], Hd, *j[23:27], j[17], j[18], j[15], j[16], _hip.stream_ptr(dev)),
+                   "attn_lstm_fwd")
+    else:
+        raise _hip.HipLibraryError("decoder passes side by side need the multi-CU decoder kernels (none on this device)")
+    return _DecoderLaunch(tuple(t for sd in sides for t in sd[0]), tuple(t for sd in sides for t in sd[1]),
+                          tuple(sd[2] for sd in sides))
+
+
+def _decoder_sides_backward(saved, side_meta, dhs_list, needs_input_grad):
+    """Backward of 1-3 decoder passes whose forward saved ``_SIDE_SAVED`` tensors each (``_DecoderLaunch``): ONE launch for
+    all of them (``pnmn_attn_lstm_bwd_group``), then per pass the encoder-output gradient, the two weight-gradient GEMMs
+    and the gradient of what fed the steps (the table, or the projected inputs).  Returns six gradients per pass, in the
+    order of ``_prepare_decoder_side``'s tensor inputs (source, enc, mask, h0, w_c, w_hh); ``needs_input_grad`` likewise.
+    A single pass without the multi-CU kernels runs on ``pnmn_attn_lstm_bwd``, which accumulates ``denc`` itself."""
+    dev = saved[0].device
+    n = len(dhs_list)
+    lib, Hd = _hip.lib(), saved[0].size(2)
+    ws = _decoder_workspace([saved[_SIDE_SAVED * k].size(0) for k in range(n)], True, dev)
+    if ws is None and n > 1:
+        raise _hip.HipLibraryError("decoder passes side by side need the multi-CU decoder kernels (none on this device)")
+    jobs = np.zeros(n, _hip.DECODER_BWD_JOB)
+    sides = []
+    for k, dhs in enumerate(dhs_list):
+        hs, cs, act, cx, probs, enc, mask, h0, w_c, w_hh, step_tokens = saved[_SIDE_SAVED * k: _SIDE_SAVED * (k + 1)]
+        packs_t = side_meta[k][1]
+        B, T, S = hs.size(0), hs.size(1), enc.size(1)
         # (named temporaries: a tensor that dies right after .data_ptr() may be recycled by the next allocation)
-        dhs_c = dhs.contiguous()
-        w_c_t, w_hh_t = ctx.packs_t if ctx.packs_t is not None else (pack_fragments(w_c.t()), pack_fragments(w_hh.t()))
-        hprev = torch.cat((h0.unsqueeze(1), hs[:, :-1]), 1)  # h_{t-1} of every (row, step)
-        ws = _decoder_workspace(B, True, dev)
+        dhs_c = torch.zeros_like(hs) if dhs is None else dhs.contiguous()
+        w_c_t, w_hh_t = packs_t if packs_t is not None else (pack_fragments(w_c.t()), pack_fragments(w_hh.t()))
+        dgates, dh0 = torch.empty_like(act), torch.empty_like(h0)
         if ws is not None:
-            dctx, dscore, weights = torch.empty_like(hs), torch.empty_like(probs), torch.empty_like(probs)
-            _hip.check(_hip.lib().pnmn_attn_lstm_bwd_multi(
-                dhs_c.data_ptr(), act.data_ptr(), cs.data_ptr(), hs.data_ptr(), probs.data_ptr(), enc.data_ptr(),
-                mask.data_ptr(), h0.data_ptr(), w_c_t.data_ptr(), w_hh_t.data_ptr(), dgates.data_ptr(), dctx.data_ptr(),
-                dscore.data_ptr(), weights.data_ptr(), dh0.data_ptr(), B, T, S, Hd, ws.data_ptr(), _hip.stream_ptr(dev)),
-                "attn_lstm_bwd_multi")
+            dctx, dscore, weights, denc = torch.empty_like(hs), torch.empty_like(probs), torch.empty_like(probs), None
+            jobs[k] = (dhs_c.data_ptr(), act.data_ptr(), cs.data_ptr(), hs.data_ptr(), probs.data_ptr(), enc.data_ptr(),
+                       mask.data_ptr(), h0.data_ptr(), w_c_t.data_ptr(), w_hh_t.data_ptr(), dgates.data_ptr(), dctx.data_ptr(),
+                       dscore.data_ptr(), weights.data_ptr(), dh0.data_ptr(), B, T, S, 0)
+        else:
+            dctx = dscore = weights = None
+            denc = torch.zeros_like(enc)
+            _hip.check(lib.pnmn_attn_lstm_bwd(
+                dhs_c.data_ptr(), act.data_ptr(), cs.data_ptr(), hs.data_ptr(), cx.data_ptr(), probs.data_ptr(),
+                enc.data_ptr(), mask.data_ptr(), h0.data_ptr(), w_c_t.data_ptr(), w_hh_t.data_ptr(), dgates.data_ptr(),
+                denc.data_ptr(), dh0.data_ptr(), B, T, S, Hd, _hip.stream_ptr(dev)), "attn_lstm_bwd")
+        sides.append(dict(hs=hs, cx=cx, enc=enc, h0=h0, step_tokens=step_tokens, dgates=dgates, dh0=dh0, dctx=dctx, dscore=dscore,
+                          weights=weights, denc=denc, keep=(dhs_c, w_c_t, w_hh_t), B=B, T=T, S=S))
+    if ws is not None:
+        _hip.check(lib.pnmn_attn_lstm_bwd_group(jobs.ctypes.data, n, Hd, ws.data_ptr(), _hip.stream_ptr(dev)), "attn_lstm_bwd_group")
+    grads = []
+    for k, sd in enumerate(sides):
+        B, T, S = sd["B"], sd["T"], sd["S"]
+        vocab, _, mode, start, projected = side_meta[k]
+        need = needs_input_grad[6 * k: 6 * k + 6]
+        hprev = None
+        if need[5] or (need[1] and sd["denc"] is None and T > 64):
+            hprev = torch.cat((sd["h0"].unsqueeze(1), sd["hs"][:, :-1]), 1)  # h_{t-1} of every (row, step)
+        denc = sd["denc"] if need[1] else None
+        if need[1] and denc is None:
             # encoder-output gradient as two GEMMs per row over the T steps: enc_s enters step t through
             # the context (weight w_ts = masked, renormalised attention, written out by the kernel) and through the
             # score (gradient dscore_ts, times h_{t-1})
             if T <= 64:
-                denc = torch.empty_like(enc)
-                _hip.check(_hip.lib().pnmn_attn_denc(weights.data_ptr(), dscore.data_ptr(), dctx.data_ptr(), hs.data_ptr(),
-                                                     h0.data_ptr(), denc.data_ptr(), B, T, S, Hd, _hip.stream_ptr(dev)),
-                           "attn_denc")
-            else:
-                denc = torch.baddbmm(torch.bmm(weights.transpose(1, 2), dctx), dscore.transpose(1, 2), hprev)
-        else:
-            denc = torch.zeros_like(enc)
-            _hip.check(_hip.lib().pnmn_attn_lstm_bwd(
-                dhs_c.data_ptr(), act.data_ptr(), cs.data_ptr(), hs.data_ptr(), cx.data_ptr(), probs.data_ptr(),
-                enc.data_ptr(), mask.data_ptr(), h0.data_ptr(), w_c_t.data_ptr(), w_hh_t.data_ptr(), dgates.data_ptr(),
-                denc.data_ptr(), dh0.data_ptr(), B, T, S, Hd, _hip.stream_ptr(dev)), "attn_lstm_bwd")
-        flat = dgates.reshape(B * T, 4 * Hd)
-        dw_c = wgrad_gemm(flat, cx.reshape(B * T, Hd))
-        dw_hh = wgrad_gemm(flat, hprev.reshape(B * T, Hd))
-        dxe = detable = None
-        if ctx.mode == 0 and ctx.in_tokens is not None:
-            detable = _table_grad(dgates, ctx.in_tokens, ctx.vocab) if ctx.needs_input_grad[1] else None
-        elif ctx.mode == 0:
-            dxe = dgates
-        else:
-            if ctx.vocab <= 128:  # step t's input is the token chosen at step t - 1 (@start@ first)
-                detable = embedding_grad(dgates, tokens, ctx.vocab, shift=True, start=ctx.start)
-            else:
-                tok_in = torch.cat((tokens.new_full((B, 1), ctx.start), tokens[:, :-1]), 1).reshape(-1)
-                detable = torch.zeros(ctx.vocab, 4 * Hd, dtype=dgates.dtype, device=dev).index_add_(0, tok_in, flat)
-        return (dxe, detable, denc, None, dh0, dw_c, dw_hh) + (None,) * 11
-
-
-class _AttnLSTMDecoderPair(torch.autograd.Function):
-    """TWO independent decoder passes in one launch each way (``pnmn_attn_lstm_fwd_multi_pair`` / ``_bwd_multi_pair``):
-    the persistent decoder kernels are bound by their per-step hand-off latency, so side by side they take as long as
-    the longer pass.  Either side may be teacher forced (mode 0: step inputs ``in_tokens`` [B,T] index the per-token
-    table) or free running (mode 1 sampling / 2 greedy: the kernel picks each step's token; ``etable`` then is the
-    projected embedding table).  Per side the tensor inputs are etable [V,4H], enc [B,S,H], mask [B,S], h0 [B,H], W_c,
-    W_hh; ``meta`` carries the rest.  Same arithmetic as two ``_AttnLSTMDecoder`` calls (bit for bit: the kernels'
-    bodies are shared; the library runs the passes one after the other when they do not fit the chip together)."""
-
-    @staticmethod
-    def forward(ctx, etable_a, enc_a, mask_a, h0_a, w_c_a, w_hh_a, etable_b, enc_b, mask_b, h0_b, w_c_b, w_hh_b, meta):
-        dev = enc_a.device
-        sides, jobs = [], np.zeros(2, _hip.DECODER_FWD_JOB)
-        for k, (etable, enc, mask, h0, w_c, w_hh, m) in enumerate(((etable_a, enc_a, mask_a, h0_a, w_c_a, w_hh_a, meta[0]),
-                                                                  (etable_b, enc_b, mask_b, h0_b, w_c_b, w_hh_b, meta[1]))):
-            etable, enc, mask, h0 = etable.contiguous(), enc.contiguous(), mask.contiguous(), h0.contiguous()
-            w_c, w_hh = w_c.detach(), w_hh.detach()
-            packs = m["packs"] if m["packs"] is not None else (pack_fragments(w_c), pack_fragments(w_hh), None, None)
-            mode, T = m["mode"], m["T"]
-            B, S, Hd = enc.shape
-            f = dict(dtype=torch.float32, device=dev)
-            hs, cs, cx = torch.empty(B, T, Hd, **f), torch.empty(B, T, Hd, **f), torch.empty(B, T, Hd, **f)
-            act, probs = torch.empty(B, T, 4 * Hd, **f), torch.empty(B, T, S, **f)
-            j = jobs[k]
-            j["etable"], j["enc"], j["mask"], j["h0"] = etable.data_ptr(), enc.data_ptr(), mask.data_ptr(), h0.data_ptr()
-            j["w_c"], j["w_hh"] = packs[0].data_ptr(), packs[1].data_ptr()
-            j["hs"], j["cs"], j["act"], j["ctx"], j["probs"] = hs.data_ptr(), cs.data_ptr(), act.data_ptr(), cx.data_ptr(), probs.data_ptr()
-            j["B"], j["T"], j["S"], j["start_index"] = B, T, S, m["start"]
-            in_tokens = tokens = None
-            keep = [etable, packs]
-            if mode == 0:
-                in_tokens = m["in_tokens"]
-                if in_tokens.dtype != torch.long or in_tokens.stride(1) != 1:
-                    in_tokens = in_tokens.long().contiguous()
-                j["in_tokens"], j["in_token_stride"] = in_tokens.data_ptr(), in_tokens.stride(0)
-            else:
-                w_p, b_p = m["w_p"].detach().contiguous(), m["b_p"].detach().contiguous()
-                tokens = torch.empty(B, T, dtype=torch.long, device=dev)
-                j["w_p"], j["b_p"], j["tokens"], j["V"], j["sample"] = w_p.data_ptr(), b_p.data_ptr(), tokens.data_ptr(), w_p.size(0), mode
-                j["pad_index"], j["unk_index"], j["seed"], j["row_offset"] = m["pad"], m["unk"], m["seed"], m["row_offset"]
-                keep += [w_p, b_p]
-            sides.append(dict(hs=hs, cs=cs, act=act, cx=cx, probs=probs, enc=enc, mask=mask, h0=h0, w_c=w_c, w_hh=w_hh,
-                              in_tokens=in_tokens, tokens=tokens, vocab=etable.size(0), mode=mode, start=m["start"],
-                              packs_t=(packs[2], packs[3]) if packs[2] is not None else None, keep=keep))
-        Ba, Bb = sides[0]["hs"].size(0), sides[1]["hs"].size(0)
-        ws = torch.empty(int(_hip.lib().pnmn_attn_lstm_pair_workspace_bytes(Ba, Bb, 0)), dtype=torch.uint8, device=dev)
-        _hip.check(_hip.lib().pnmn_attn_lstm_fwd_multi_pair(jobs[0:1].ctypes.data, jobs[1:2].ctypes.data, sides[0]["hs"].size(2),
-                                                            ws.data_ptr(), _hip.stream_ptr(dev)), "attn_lstm_fwd_multi_pair")
-        saved, outs = [], []
-        empty = torch.empty(0, dtype=torch.long, device=dev)
-        for sd in sides:
-            step_tokens = sd["in_tokens"] if sd["mode"] == 0 else sd["tokens"]
-            saved += [sd["hs"], sd["cs"], sd["act"], sd["cx"], sd["probs"], sd["enc"], sd["mask"], sd["h0"], sd["w_c"], sd["w_hh"],
-                      step_tokens]
-            toks = sd["tokens"] if sd["tokens"] is not None else empty
-            outs += [sd["hs"], toks]
-        ctx.save_for_backward(*saved)
-        ctx.side_meta = [(sd["vocab"], sd["packs_t"], sd["mode"], sd["start"]) for sd in sides]
-        ctx.mark_non_differentiable(outs[1], outs[3])
-        return tuple(outs)
-
-    @staticmethod
-    def backward(ctx, dhs_a, _ta, dhs_b, _tb):
-        return (*_decoder_sides_backward(ctx.saved_tensors, ctx.side_meta, (dhs_a, dhs_b), ctx.needs_input_grad), None)
-
-
-def _decoder_sides_backward(saved, side_meta, dhs_list, needs_input_grad):
-    """Backward of 1-3 decoder passes whose forward saved (hs, cs, act, cx, probs, enc, mask, h0, w_c, w_hh, step tokens) each:
-    ONE launch for all of them (``pnmn_attn_lstm_bwd_multi`` / ``_pair`` / ``_group3``), then per pass the encoder-output
-    gradient, the two weight-gradient GEMMs and the table gradient.  Returns six gradients per pass, in the order of the
-    forward's tensor inputs (etable, enc, mask, h0, w_c, w_hh)."""
-    dev = saved[0].device
-    n = len(dhs_list)
-    jobs = np.zeros(n, _hip.DECODER_BWD_JOB)
-    sides = []
-    for k, dhs in enumerate(dhs_list):
-        hs, cs, act, cx, probs, enc, mask, h0, w_c, w_hh, step_tokens = saved[11 * k: 11 * k + 11]
-        vocab, packs_t, mode, start = side_meta[k]
-        B, T, Hd = hs.shape
-        S = enc.size(1)
-        dhs_c = torch.zeros_like(hs) if dhs is None else dhs.contiguous()
-        w_c_t, w_hh_t = packs_t if packs_t is not None else (pack_fragments(w_c.t()), pack_fragments(w_hh.t()))
-        dgates, dh0 = torch.empty_like(act), torch.empty_like(h0)
-        dctx, dscore, weights = torch.empty_like(hs), torch.empty_like(probs), torch.empty_like(probs)
-        j = jobs[k]
-        for name, t in (("dhs", dhs_c), ("act", act), ("cs", cs), ("hs", hs), ("probs", probs), ("enc", enc), ("mask", mask),
-                        ("h0", h0), ("w_c_t", w_c_t), ("w_hh_t", w_hh_t), ("dgates", dgates), ("dctx", dctx),
-                        ("dscore", dscore), ("weights", weights), ("dh0", dh0)):
-            j[name] = t.data_ptr()
-        j["B"], j["T"], j["S"] = B, T, S
-        sides.append(dict(hs=hs, cx=cx, enc=enc, h0=h0, step_tokens=step_tokens, vocab=vocab, mode=mode, start=start,
-                          dgates=dgates, dh0=dh0, dctx=dctx, dscore=dscore, weights=weights, keep=(dhs_c, w_c_t, w_hh_t),
-                          B=B, T=T, S=S, Hd=Hd))
-    lib, Hd = _hip.lib(), sides[0]["Hd"]
-    rows = [sd["B"] for sd in sides]
-    if n == 1:
-        ws = torch.empty(int(lib.pnmn_attn_lstm_multi_workspace_bytes(rows[0], 1)), dtype=torch.uint8, device=dev)
-        j = jobs[0]
-        _hip.check(lib.pnmn_attn_lstm_bwd_multi(*(int(j[f]) for f in ("dhs", "act", "cs", "hs", "probs", "enc", "mask", "h0", "w_c_t",
-                                                                      "w_hh_t", "dgates", "dctx", "dscore", "weights", "dh0")),
-                                                rows[0], sides[0]["T"], sides[0]["S"], Hd, ws.data_ptr(), _hip.stream_ptr(dev)),
-                   "attn_lstm_bwd_multi")
-    elif n == 2:
-        ws = torch.empty(int(lib.pnmn_attn_lstm_pair_workspace_bytes(rows[0], rows[1], 1)), dtype=torch.uint8, device=dev)
-        _hip.check(lib.pnmn_attn_lstm_bwd_multi_pair(jobs[0:1].ctypes.data, jobs[1:2].ctypes.data, Hd, ws.data_ptr(),
-                                                     _hip.stream_ptr(dev)), "attn_lstm_bwd_multi_pair")
-    else:
-        ws = torch.empty(int(lib.pnmn_attn_lstm_group3_workspace_bytes(rows[0], rows[1], rows[2], 1)), dtype=torch.uint8, device=dev)
-        _hip.check(lib.pnmn_attn_lstm_bwd_multi_group3(jobs[0:1].ctypes.data, jobs[1:2].ctypes.data, jobs[2:3].ctypes.data, Hd,
-                                                       ws.data_ptr(), _hip.stream_ptr(dev)), "attn_lstm_bwd_multi_group3")
-    grads = []
-    for k, sd in enumerate(sides):
-        B, T, S, Hd = sd["B"], sd["T"], sd["S"], sd["Hd"]
-        need = needs_input_grad[6 * k: 6 * k + 6]
-        denc = None
-        if need[1]:
-            if T <= 64:
                 denc = torch.empty_like(sd["enc"])
-                _hip.check(_hip.lib().pnmn_attn_denc(sd["weights"].data_ptr(), sd["dscore"].data_ptr(), sd["dctx"].data_ptr(),
-                                                     sd["hs"].data_ptr(), sd["h0"].data_ptr(), denc.data_ptr(), B, T, S, Hd,
-                                                     _hip.stream_ptr(dev)), "attn_denc")
+                _hip.check(lib.pnmn_attn_denc(sd["weights"].data_ptr(), sd["dscore"].data_ptr(), sd["dctx"].data_ptr(),
+                                              sd["hs"].data_ptr(), sd["h0"].data_ptr(), denc.data_ptr(), B, T, S, Hd,
+                                              _hip.stream_ptr(dev)), "attn_denc")
             else:
-                hprev = torch.cat((sd["h0"].unsqueeze(1), sd["hs"][:, :-1]), 1)
                 denc = torch.baddbmm(torch.bmm(sd["weights"].transpose(1, 2), sd["dctx"]), sd["dscore"].transpose(1, 2), hprev)
         flat = sd["dgates"].reshape(B * T, 4 * Hd)
         dw_c = wgrad_gemm(flat, sd["cx"].reshape(B * T, Hd)) if need[4] else None
-        dw_hh = None
-        if need[5]:
-            hprev = torch.cat((sd["h0"].unsqueeze(1), sd["hs"][:, :-1]), 1)
-            dw_hh = wgrad_gemm(flat, hprev.reshape(B * T, Hd))
-        detable = None
+        dw_hh = wgrad_gemm(flat, hprev.reshape(B * T, Hd)) if need[5] else None
+        dsource = None
         if need[0]:
-            if sd["mode"] == 0:
-                detable = _table_grad(sd["dgates"], sd["step_tokens"], sd["vocab"])
-            elif sd["vocab"] <= 128:  # step t's input is the token chosen at step t - 1 (@start@ first)
-                detable = embedding_grad(sd["dgates"], sd["step_tokens"], sd["vocab"], shift=True, start=sd["start"])
+            if projected:
+                dsource = sd["dgates"]
+            elif mode == 0:
+                dsource = _table_grad(sd["dgates"], sd["step_tokens"], vocab)
+            elif vocab <= 128:  # step t's input is the token chosen at step t - 1 (@start@ first)
+                dsource = embedding_grad(sd["dgates"], sd["step_tokens"], vocab, shift=True, start=start)
             else:
-                tok_in = torch.cat((sd["step_tokens"].new_full((B, 1), sd["start"]), sd["step_tokens"][:, :-1]), 1).reshape(-1)
-                detable = torch.zeros(sd["vocab"], 4 * Hd, dtype=flat.dtype, device=dev).index_add_(0, tok_in, flat)
-        grads += [detable, denc, None, sd["dh0"], dw_c, dw_hh]
+                tok_in = torch.cat((sd["step_tokens"].new_full((B, 1), start), sd["step_tokens"][:, :-1]), 1).reshape(-1)
+                dsource = torch.zeros(vocab, 4 * Hd, dtype=flat.dtype, device=dev).index_add_(0, tok_in, flat)
+        grads += [dsource, denc, None, sd["dh0"], dw_c, dw_hh]
     return grads
 
 
-class _Capture:
-    """Stands in for an autograd context where a Function's ``forward`` is run for its launches only (the graph node that
-    owns what it saved is created later: ``_AttnLSTMDecoderGroup``)."""
+class _AttnLSTMDecoder(torch.autograd.Function):
+    """One decoding loop as one persistent kernel launch each way, with every input positional.
 
-    needs_input_grad = ()
+    inputs : xe [B,T,4H] (teacher forcing) or etable [V,4H] (free running; teacher forcing with ``in_tokens``), enc [B,S,H],
+             mask [B,S] float, h0 [B,H], W_c [4H,H], W_hh [4H,H], W_p [V,H], b_p [V]
+    outputs: hidden states [B,T,H], tokens [B,T] (free running only)
+    An adaptor over ``_decoder_forward`` / ``_decoder_sides_backward``, which say what runs."""
 
-    def save_for_backward(self, *tensors):
-        self.saved = tensors
+    @staticmethod
+    def forward(ctx, xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, mode, T, seed, row_offset, pad, unk, start,
+                packs=None, in_tokens=None):
+        m = dict(mode=mode, T=T, seed=seed, row_offset=row_offset, pad=pad, unk=unk, start=start, packs=packs, w_p=w_p, b_p=b_p,
+                 in_tokens=in_tokens if mode == 0 else None)
+        ctx.projected = mode == 0 and in_tokens is None
+        got = _decoder_forward([(xe if ctx.projected else etable, enc, mask, h0, w_c, w_hh)], [m])
+        ctx.save_for_backward(*got.saved)
+        ctx.side_meta = got.side_meta
+        ctx.mark_non_differentiable(got.outs[1])
+        return got.outs
 
-    def mark_non_differentiable(self, *tensors):
-        pass
+    @staticmethod
+    def backward(ctx, dhs, _):
+        need = ctx.needs_input_grad
+        d = _decoder_sides_backward(ctx.saved_tensors, ctx.side_meta, (dhs,), (need[0 if ctx.projected else 1], *need[2:7]))
+        return ((d[0], None) if ctx.projected else (None, d[0])) + tuple(d[1:]) + (None,) * 11
 
 
 class _AttnLSTMDecoderGroup(torch.autograd.Function):
-    """ONE graph node for up to three decoder passes whose forward launches happened at different times, so that their
-    BACKWARD is one launch (``pnmn_attn_lstm_bwd_multi_group3``).  In a training iteration the generator's two decodes
-    run first (their samples are the reconstructor's input), the reconstructor's decode later -- but backward the three are
-    independent, and on one stream they add their step counts on the iteration's critical chain (at 128 questions per GPU
-    the seq2seq backward IS that chain: 275 + 470 us of decoder kernels become 470).  Inputs: per pass etable, enc, mask,
-    h0, W_c, W_hh (as ``_AttnLSTMDecoderPair``), then ``meta`` (one dict per pass; ``meta[k]["pre"]`` = index of the pass in
-    ``pre``, the ``_Capture`` of an earlier ``decode_pair_launch``, or None: launched here) and ``pre``."""
+    """ONE graph node for up to three independent decoder passes, so that their BACKWARD is one launch
+    (``pnmn_attn_lstm_bwd_group``): the persistent decoder kernels are bound by their per-step hand-off latency, so side by
+    side they take as long as the longest pass.  A pass is launched here -- those that are, side by side in one forward
+    launch per two (``_decoder_forward``) -- or was launched earlier (``decode_pair_launch``).  In a training iteration the
+    generator's two decodes run first (their samples are the reconstructor's input), the reconstructor's decode later -- but
+    backward the three are independent, and on one stream they add their step counts on the iteration's critical chain (at
+    128 questions per GPU the seq2seq backward IS that chain: 275 + 470 us of decoder kernels become 470).  Inputs: per pass
+    the six tensors of ``_prepare_decoder_side``, then ``meta`` (its dict per pass; ``meta[k]["pre"]`` = index of the pass in
+    ``pre``, or None / absent: launched here) and ``pre`` (the ``_DecoderLaunch`` of the earlier launch, or None).  Outputs:
+    per pass the hidden states and the tokens.  Same arithmetic as one ``_AttnLSTMDecoder`` per pass, bit for bit."""
 
     @staticmethod
     def forward(ctx, *args):
         meta, pre = args[-2], args[-1]
         tens = args[:-2]
+        now = [k for k, m in enumerate(meta) if m.get("pre") is None]
+        where = {k: (pre, m["pre"]) for k, m in enumerate(meta) if m.get("pre") is not None}
+        for i in range(0, len(now), 2):
+            ks = now[i: i + 2]
+            got = _decoder_forward([tens[6 * k: 6 * k + 6] for k in ks], [meta[k] for k in ks])
+            where.update((k, (got, j)) for j, k in enumerate(ks))
         saved, side_meta, outs = [], [], []
-        for k, m in enumerate(meta):
-            etable, enc, mask, h0, w_c, w_hh = tens[6 * k: 6 * k + 6]
-            if m.get("pre") is not None:
-                j = m["pre"]
-                saved += list(pre.saved[11 * j: 11 * j + 11])
-                side_meta.append(pre.side_meta[j])
-                outs += [pre.outs[2 * j], pre.outs[2 * j + 1]]
-                continue
-            cap = _Capture()
-            if m["mode"] == 0:
-                hs, tok = _AttnLSTMDecoder.forward(cap, None, etable, enc, mask, h0, w_c, w_hh, None, None, 0, m["T"], 0, 0, 0, 0,
-                                                   m["start"], m["packs"], m["in_tokens"])
-                step_tokens = cap.in_tokens
-            else:
-                hs, tok = _AttnLSTMDecoder.forward(cap, None, etable, enc, mask, h0, w_c, w_hh, m["w_p"], m["b_p"], m["mode"], m["T"],
-                                                   m["seed"], m["row_offset"], m["pad"], m["unk"], m["start"], m["packs"])
-                step_tokens = cap.saved[10]
-            saved += list(cap.saved[:10]) + [step_tokens]
-            side_meta.append((cap.vocab, cap.packs_t, cap.mode, cap.start))
-            outs += [hs, tok]
+        for k in range(len(meta)):
+            launch, j = where[k]
+            saved += launch.saved[_SIDE_SAVED * j: _SIDE_SAVED * (j + 1)]
+            side_meta.append(launch.side_meta[j])
+            outs += launch.outs[2 * j: 2 * j + 2]
         ctx.save_for_backward(*saved)
         ctx.side_meta = side_meta
         ctx.mark_non_differentiable(*outs[1::2])
@@ -1205,47 +1120,21 @@ class Seq2SeqBase(nn.Module):
         if seed is None:
             seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # CPU generator: no device sync
         Hd = h.size(1)
-        w_ih = self._decoder_cell.weight_ih
-        # the cell's input is cat(attended, embedding)
-        w_c, w_e = _SplitColumns.apply(w_ih, Hd) if w_ih.requires_grad and torch.is_grad_enabled() else (w_ih[:, :Hd], w_ih[:, Hd:])
-        w_p, b_p = self._output_projection_layer.weight, self._output_projection_layer.bias
-        fused = Hd == 256 and enc.size(1) <= 64 and w_p.size(0) <= 128
-        derived = self._derived() if fused else None
-        if derived is not None:
-            bias = _Alias.apply(self._decoder_cell.bias_ih, self._decoder_cell.bias_hh, derived["d.b"])
-            packs = (derived["d.c"], derived["d.hh"], derived["d.cT"], derived["d.hhT"])
-        else:
-            bias = self._decoder_cell.bias_ih + self._decoder_cell.bias_hh
-            packs = None
+        fused = Hd == 256 and enc.size(1) <= 64 and self._output_projection_layer.weight.size(0) <= 128
         if fused:
-            args = (pad, self._unk_index, bos, packs)
-            if tgt is not None:  # teacher forcing: every step's input embedding is known up front
-                emb = self._target_embedder
-                etable = _TokenTable.apply(emb.weight, w_e, bias, emb.padding_idx)
-                hs, _ = _AttnLSTMDecoder.apply(None, etable, enc, fmask, h, w_c, self._decoder_cell.weight_hh, w_p, b_p,
-                                               0, steps, seed, self.sample_row_offset, *args, tgt[:, :steps])
-            else:  # free running: the kernel also picks each step's token
-                etable = F.linear(self._target_embedder.weight, w_e, bias)
-                hs, raw = _AttnLSTMDecoder.apply(None, etable, enc, fmask, h, w_c, self._decoder_cell.weight_hh, w_p,
-                                                 b_p, 2 if greedy else 1, steps, seed, self.sample_row_offset, *args)
-            # one GEMM for all steps; its weight gradient [V, B*T] x [B*T, H] -- 44-100 output rows over a 13 000-47 000 long
-            # reduction -- through the K-split of wgrad_gemm (as a plain mm: 80-144 us at 3-17 TFLOP/s, scripts/r05_gemm_sites.py)
-            logits_all = linear_rows(hs, w_p, b_p)
-            if tgt is not None:
-                output_dict = {"loss": sequence_nll(logits_all, tgt[:, 1:], tgt[:, 1:], pad, 1e-13)}
-                if need_predictions or not self.training:
-                    # predictions are drawn / arg-maxed from the teacher-forced distributions (reference :196-220)
-                    raw, _ = choose_tokens(logits_all.reshape(B * steps, -1), greedy, seed, self.sample_row_offset * steps,
-                                           0, pad, self._unk_index, bos)
-                    output_dict["predictions"] = self._trim_predictions(raw.view(B, steps))
-            else:
-                predictions = self._trim_predictions(raw)
-                output_dict = {"predictions": predictions, "loss": sequence_nll(logits_all, raw, predictions, pad, 1e-12)}
+            prep = self._fused_prep(state, tgt, greedy, seed, self._derived())
+            hs, raw = _AttnLSTMDecoderGroup.apply(*_prep_tensors(prep), [prep["meta"]], None)
+            output_dict, logits_all = self._finish(prep, hs, raw)
+            if tgt is not None and (need_predictions or not self.training):
+                # predictions are drawn / arg-maxed from the teacher-forced distributions (reference :196-220)
+                raw, _ = choose_tokens(logits_all.reshape(B * steps, -1), greedy, seed, self.sample_row_offset * steps,
+                                       0, pad, self._unk_index, bos)
+                output_dict["predictions"] = self._trim_predictions(raw.view(B, steps))
             ce = output_dict["loss"]
             predictions = output_dict.get("predictions")
         else:
             _note_slow_path("decoder", "hidden size %d, %d source positions, %d target tokens (the persistent decoder kernel is "
-                            "built for 256 / <= 64 / <= 128)" % (Hd, enc.size(1), w_p.size(0)))
+                            "built for 256 / <= 64 / <= 128)" % (Hd, enc.size(1), self._output_projection_layer.weight.size(0)))
             raw, logits_all, logprobs = self._decode_stepwise(enc, fmask, h, torch.zeros_like(h), tgt, steps, greedy, seed)
             predictions = self._trim_predictions(raw)
             pmask = (predictions != pad).float()
@@ -1343,45 +1232,67 @@ class Seq2SeqBase(nn.Module):
             return None
         # the pair kernels are multi-CU only: PNMN_DECODER_CLUSTER=0, or a device that cannot host eight resident
         # workgroups per tile (the library then reports no workspace), leave both passes to decode()
-        if os.environ.get("PNMN_DECODER_CLUSTER", "1") == "0" or \
-                int(_hip.lib().pnmn_attn_lstm_multi_workspace_bytes(enc.size(0), 0)) <= 0:
+        if _decoder_workspace_bytes([enc.size(0)], False) <= 0:
             return None
         derived = self._derived()
         if derived is None:
             return None
-        pad, bos, eos = self._pad_index, self._start_index, self._end_index
-        w_ih = self._decoder_cell.weight_ih
-        w_c, w_e = _SplitColumns.apply(w_ih, Hd) if w_ih.requires_grad else (w_ih[:, :Hd], w_ih[:, Hd:])
-        bias = _Alias.apply(self._decoder_cell.bias_ih, self._decoder_cell.bias_hh, derived["d.b"])
-        emb = self._target_embedder
-        meta = {"packs": (derived["d.c"], derived["d.hh"], derived["d.cT"], derived["d.hhT"]), "start": bos}
         tgt = None
         if target_tokens is not None:
-            tgt = _TokenPrep.run(target_tokens, pad, bos, eos, drop_first=False, want_mask=False)[0]
+            tgt = _TokenPrep.run(target_tokens, self._pad_index, self._start_index, self._end_index, drop_first=False,
+                                 want_mask=False)[0]
+        # (decode() draws one seed per pass, used or not: keep the generator in step)
+        seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # CPU generator: no device sync
+        return self._fused_prep(state, tgt, decoding_strategy == "greedy", seed, derived)
+
+    def _fused_prep(self, state: Dict[str, torch.Tensor], tgt: Optional[torch.Tensor], greedy: bool, seed: int,
+                    derived: Optional[Dict[str, torch.Tensor]]):
+        """The inputs of one pass through the persistent decoder kernels: the six tensors and the ``meta`` of
+        ``_prepare_decoder_side`` (``_prep_tensors``), and what ``decode_finish`` reads.  ``tgt`` (targets with their
+        boundary tokens): teacher forced; None: free running under ``seed``.  ``derived``: the model's ``DerivedParams``
+        output, or None (the bias sum and the weight packs are then computed per call)."""
+        Hd = state["h"].size(1)
+        w_ih = self._decoder_cell.weight_ih
+        # the cell's input is cat(attended, embedding)
+        w_c, w_e = _SplitColumns.apply(w_ih, Hd) if w_ih.requires_grad and torch.is_grad_enabled() else (w_ih[:, :Hd], w_ih[:, Hd:])
+        if derived is not None:
+            bias = _Alias.apply(self._decoder_cell.bias_ih, self._decoder_cell.bias_hh, derived["d.b"])
+            packs = (derived["d.c"], derived["d.hh"], derived["d.cT"], derived["d.hhT"])
+        else:
+            bias = self._decoder_cell.bias_ih + self._decoder_cell.bias_hh
+            packs = None
+        emb = self._target_embedder
+        meta = {"packs": packs, "start": self._start_index}
+        if tgt is not None:  # teacher forcing: every step's input embedding is known up front
             steps = tgt.size(1) - 1
             etable = _TokenTable.apply(emb.weight, w_e, bias, emb.padding_idx)
-            torch.randint(0, 2 ** 62, (1,))  # (decode() draws one seed per pass, used or not: keep the generator in step)
             meta.update(mode=0, in_tokens=tgt[:, :steps], T=steps)
-        else:
+        else:  # free running: the kernel also picks each step's token
             steps = self._max_decoding_steps
             etable = F.linear(emb.weight, w_e, bias)
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # CPU generator: no device sync
-            meta.update(mode=2 if decoding_strategy == "greedy" else 1, T=steps, pad=pad, unk=self._unk_index, seed=seed,
-                        row_offset=self.sample_row_offset, w_p=w_p, b_p=b_p)
-        return {"model": self, "tgt": tgt, "steps": steps, "etable": etable, "enc": enc, "fmask": fmask, "h": h, "w_c": w_c,
-                "w_hh": self._decoder_cell.weight_hh, "meta": meta}
+            meta.update(mode=2 if greedy else 1, T=steps, pad=self._pad_index, unk=self._unk_index, seed=seed,
+                        row_offset=self.sample_row_offset, w_p=self._output_projection_layer.weight,
+                        b_p=self._output_projection_layer.bias)
+        return {"model": self, "tgt": tgt, "steps": steps, "etable": etable, "enc": state["enc"], "fmask": state["fmask"],
+                "h": state["h"], "w_c": w_c, "w_hh": self._decoder_cell.weight_hh, "meta": meta}
 
     def decode_finish(self, prep, hs: torch.Tensor, raw: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
         """Second half: the output projection over all steps and the per-row loss -- the cross entropy of the targets
         (reference :235-254) or, free running, the length-normalised negative log-probability of the trimmed samples
         (reference :222-233)."""
+        return self._finish(prep, hs, raw)[0]
+
+    def _finish(self, prep, hs, raw):
+        """``decode_finish`` and the logits [B,T,V] it took the loss from."""
         proj = self._output_projection_layer
-        logits_all = linear_rows(hs, proj.weight, proj.bias)  # (weight gradient through wgrad_gemm's K-split, see decode)
+        # one GEMM for all steps; its weight gradient [V, B*T] x [B*T, H] -- 44-100 output rows over a 13 000-47 000 long
+        # reduction -- through the K-split of wgrad_gemm (as a plain mm: 80-144 us at 3-17 TFLOP/s, scripts/r05_gemm_sites.py)
+        logits_all = linear_rows(hs, proj.weight, proj.bias)
         tgt = prep["tgt"]
         if tgt is not None:
-            return {"loss": sequence_nll(logits_all, tgt[:, 1:], tgt[:, 1:], self._pad_index, 1e-13)}
+            return {"loss": sequence_nll(logits_all, tgt[:, 1:], tgt[:, 1:], self._pad_index, 1e-13)}, logits_all
         predictions = self._trim_predictions(raw)
-        return {"predictions": predictions, "loss": sequence_nll(logits_all, raw, predictions, self._pad_index, 1e-12)}
+        return {"predictions": predictions, "loss": sequence_nll(logits_all, raw, predictions, self._pad_index, 1e-12)}, logits_all
 
     def _decode_stepwise(self, enc, fmask, h, c, tgt, steps, greedy, seed):
         """Step-by-step decoding for shapes the persistent kernel is not built for (hidden != 256,
@@ -1451,26 +1362,22 @@ class Seq2SeqBase(nn.Module):
         }
 
 
+def _prep_tensors(prep):
+    """A prepared decode's tensor inputs, in ``_prepare_decoder_side``'s order."""
+    return prep["etable"], prep["enc"], prep["fmask"], prep["h"], prep["w_c"], prep["w_hh"]
+
+
 def decode_pair(prep_a, prep_b):
     """The launches of two prepared decodes (``Seq2SeqBase.decode_prepare``) as one, then each model's second half.
     Returns the two output dicts ({"loss": per-row loss[, "predictions"]})."""
-    hs_a, tok_a, hs_b, tok_b = _AttnLSTMDecoderPair.apply(
-        prep_a["etable"], prep_a["enc"], prep_a["fmask"], prep_a["h"], prep_a["w_c"], prep_a["w_hh"],
-        prep_b["etable"], prep_b["enc"], prep_b["fmask"], prep_b["h"], prep_b["w_c"], prep_b["w_hh"],
-        (prep_a["meta"], prep_b["meta"]))
-    return prep_a["model"].decode_finish(prep_a, hs_a, tok_a), prep_b["model"].decode_finish(prep_b, hs_b, tok_b)
+    return tuple(decode_group([prep_a, prep_b], None, [None, None]))
 
 
-def decode_pair_launch(prep_a, prep_b):
+def decode_pair_launch(prep_a, prep_b) -> _DecoderLaunch:
     """The forward launch of two prepared decodes NOW, without a graph node: returns what ``decode_group`` needs to create
     the node later (``.outs`` = (hidden states a, tokens a, hidden states b, tokens b))."""
-    cap = _Capture()
     with torch.no_grad():
-        cap.outs = _AttnLSTMDecoderPair.forward(
-            cap, prep_a["etable"], prep_a["enc"], prep_a["fmask"], prep_a["h"], prep_a["w_c"], prep_a["w_hh"],
-            prep_b["etable"], prep_b["enc"], prep_b["fmask"], prep_b["h"], prep_b["w_c"], prep_b["w_hh"],
-            (prep_a["meta"], prep_b["meta"]))
-    return cap
+        return _decoder_forward([_prep_tensors(prep_a), _prep_tensors(prep_b)], [prep_a["meta"], prep_b["meta"]])
 
 
 def decode_group(preps, pre, pre_index):
@@ -1479,9 +1386,7 @@ def decode_group(preps, pre, pre_index):
     passes' output dicts."""
     flat, metas = [], []
     for p, j in zip(preps, pre_index):
-        flat += [p["etable"], p["enc"], p["fmask"], p["h"], p["w_c"], p["w_hh"]]
-        m = dict(p["meta"])
-        m["pre"] = j
-        metas.append(m)
+        flat += _prep_tensors(p)
+        metas.append(dict(p["meta"], pre=j))
     outs = _AttnLSTMDecoderGroup.apply(*flat, metas, pre)
     return [p["model"].decode_finish(p, outs[2 * k], outs[2 * k + 1]) for k, p in enumerate(preps)]

@@ -149,7 +149,7 @@ class Seq2SeqPlan:
         self.B = B
         D = pg._max_decoding_steps
         self.D = D
-        if int(lib.pnmn_attn_lstm_pair_workspace_bytes(n, m, 0)) <= 0 or int(lib.pnmn_attn_lstm_multi_workspace_bytes(B, 0)) <= 0 \
+        if _hip.decoder_workspace_bytes([n, m], False) <= 0 or _hip.decoder_workspace_bytes([B], False) <= 0 \
                 or int(lib.pnmn_lstm_seq_workspace_bytes(B, 0)) <= 0:
             raise PlanUnsupported("batch does not fit the multi-CU recurrent kernels in one launch")
         self._bufs: Dict[str, torch.Tensor] = {}
@@ -410,6 +410,15 @@ class Seq2SeqPlan:
         v.update(rows=rows, T=T, S=S, row0=row0, R=R)
         return v
 
+    @staticmethod
+    def _decoder_fwd_job(j, sd: Dict[str, torch.Tensor], table: torch.Tensor, e: Dict[str, torch.Tensor], r0: int, derived, start: int) -> None:
+        """What every pass's ``DECODER_FWD_JOB`` holds: the table, the encoder's rows from ``r0`` on, the weight packs, the pass's
+        saved tensors (``_decoder_side``) and its shape; the caller adds the step tokens or the sampler's fields."""
+        j["etable"], j["enc"], j["mask"], j["h0"] = table.data_ptr(), e["enc"][r0:].data_ptr(), e["fmask"][r0:].data_ptr(), e["h"][r0:].data_ptr()
+        j["w_c"], j["w_hh"] = derived["d.c"].data_ptr(), derived["d.hh"].data_ptr()
+        j["hs"], j["cs"], j["act"], j["ctx"], j["probs"] = (sd[k].data_ptr() for k in ("hs", "cs", "act", "cx", "probs"))
+        j["B"], j["T"], j["S"], j["start_index"] = sd["rows"], sd["T"], sd["S"], start
+
     # ---- the plan ----------------------------------------------------------------------------------------------------------
     def _build(self) -> None:
         lib, st = _hip.lib(), self.stream
@@ -452,19 +461,15 @@ class Seq2SeqPlan:
         w_e_ptr = cell.weight_ih.data_ptr() + 4 * 256  # columns [256, 512): the embedding half of cat(attended, embedded)
         c.add("pnmn_token_table_fwd", pg.emb_tgt.data_ptr(), w_e_ptr, 512, dpg["d.b"].data_ptr(), Vp, 256, 1024, table_d.data_ptr(), st)
         jobs = np.zeros(2, _hip.DECODER_FWD_JOB)
-        enc, fmask, h = e_pg["enc"], e_pg["fmask"], e_pg["h"]
-        for j, sd, r0 in ((jobs[0], side_s, 0), (jobs[1], side_t, n)):
-            j["etable"], j["enc"], j["mask"], j["h0"] = table_d.data_ptr(), enc[r0:].data_ptr(), fmask[r0:].data_ptr(), h[r0:].data_ptr()
-            j["w_c"], j["w_hh"] = dpg["d.c"].data_ptr(), dpg["d.hh"].data_ptr()
-            j["hs"], j["cs"], j["act"], j["ctx"], j["probs"] = (sd[k].data_ptr() for k in ("hs", "cs", "act", "cx", "probs"))
-            j["B"], j["T"], j["S"], j["start_index"] = sd["rows"], sd["T"], S, bos
+        self._decoder_fwd_job(jobs[0], side_s, table_d, e_pg, 0, dpg, bos)
+        self._decoder_fwd_job(jobs[1], side_t, table_d, e_pg, n, dpg, bos)
         js = jobs[0]
         js["w_p"], js["b_p"], js["tokens"], js["V"], js["sample"] = pg.proj.weight.data_ptr(), pg.proj.bias.data_ptr(), raw.data_ptr(), Vp, 1
         js["pad_index"], js["unk_index"] = pad, pg.model._unk_index
         jobs[1]["in_tokens"], jobs[1]["in_token_stride"] = tgt.data_ptr(), tgt.stride(0)
         self.pair_jobs = jobs
-        pws = self.bytes_buf("pg.pair_ws", lib.pnmn_attn_lstm_pair_workspace_bytes(n, m, 0))
-        c.add("pnmn_attn_lstm_fwd_multi_pair", jobs[0:1].ctypes.data, jobs[1:2].ctypes.data, 256, pws.data_ptr(), st)
+        pws = self.bytes_buf("pg.pair_ws", _hip.decoder_workspace_bytes([n, m], False))
+        c.add("pnmn_attn_lstm_fwd_group", jobs.ctypes.data, 2, 256, pws.data_ptr(), st)
         c.add("pnmn_trim_predictions", raw.data_ptr(), n, D, eos, z.data_ptr(), st)
         # (the output projection and the losses follow in `fwd_pg_finish`: the samples are what the host waits for)
         self.fwd_pg_finish = _Calls()
@@ -515,11 +520,12 @@ class Seq2SeqPlan:
         qcell = qr.cell
         c.add("pnmn_token_table_fwd", qr.emb_tgt.data_ptr(), qcell.weight_ih.data_ptr() + 4 * 256, 512, dqr["d.b"].data_ptr(), Vq, 256, 1024,
               table_q.data_ptr(), st)
-        qws = self.bytes_buf("qr.dec_ws", lib.pnmn_attn_lstm_multi_workspace_bytes(B, 0))
-        c.add("pnmn_attn_lstm_fwd_multi", None, table_q.data_ptr(), e_qr["enc"].data_ptr(), e_qr["fmask"].data_ptr(), e_qr["h"].data_ptr(),
-              dqr["d.c"].data_ptr(), dqr["d.hh"].data_ptr(), None, None, side_q["hs"].data_ptr(), side_q["cs"].data_ptr(),
-              side_q["act"].data_ptr(), side_q["cx"].data_ptr(), side_q["probs"].data_ptr(), None, B, Tq, Sq, 0, 256, 0, pad,
-              qr.model._unk_index, bos, 0, 0, qtgt.data_ptr(), qtgt.stride(0), qws.data_ptr(), st)
+        qjob = np.zeros(1, _hip.DECODER_FWD_JOB)
+        self._decoder_fwd_job(qjob[0], side_q, table_q, e_qr, 0, dqr, bos)
+        qjob[0]["in_tokens"], qjob[0]["in_token_stride"] = qtgt.data_ptr(), qtgt.stride(0)
+        self._keep.append(qjob)
+        qws = self.bytes_buf("qr.dec_ws", _hip.decoder_workspace_bytes([B], False))
+        c.add("pnmn_attn_lstm_fwd_group", qjob.ctypes.data, 1, 256, qws.data_ptr(), st)
         self._gemm(c, "qr.logits_g", [dict(a=qbase["hs"].data_ptr(), b=qr.proj.weight.data_ptr(), c=qlogits.data_ptr(), M=B * Tq, N=Vq, K=256,
                                            lda=256, ldb=256, ldc=Vq, tb=1, bias=qr.proj.bias.data_ptr())])
         c.add("pnmn_seq_nll_fwd", qlogits.data_ptr(), Tq * Vq, qtgt.data_ptr() + 8, qtgt.stride(0), qtgt.data_ptr() + 8, qtgt.stride(0), pad,
@@ -567,20 +573,14 @@ class Seq2SeqPlan:
             j["B"], j["T"], j["S"] = sd["rows"], sd["T"], sd["S"]
         self._keep.append(bj)
         if DECODER_BWD_GROUP >= 3:
-            gws = self.bytes_buf("group_ws", lib.pnmn_attn_lstm_group3_workspace_bytes(n, m, B, 1))
-            c.add("pnmn_attn_lstm_bwd_multi_group3", bj[0:1].ctypes.data, bj[1:2].ctypes.data, bj[2:3].ctypes.data, 256, gws.data_ptr(), st)
+            groups = [("group_ws", [0, 1, 2])]
+        elif DECODER_BWD_GROUP == 2:
+            groups = [("pair_bws", [0, 1]), ("single_bws2", [2])]
         else:
-            singles = [0, 1, 2]
-            if DECODER_BWD_GROUP == 2:
-                gws = self.bytes_buf("pair_bws", lib.pnmn_attn_lstm_pair_workspace_bytes(n, m, 1))
-                c.add("pnmn_attn_lstm_bwd_multi_pair", bj[0:1].ctypes.data, bj[1:2].ctypes.data, 256, gws.data_ptr(), st)
-                singles = [2]
-            for k in singles:
-                j = bj[k]
-                sws = self.bytes_buf("single_bws%d" % k, lib.pnmn_attn_lstm_multi_workspace_bytes(int(j["B"]), 1))
-                c.add("pnmn_attn_lstm_bwd_multi", *(int(j[fld]) for fld in ("dhs", "act", "cs", "hs", "probs", "enc", "mask", "h0", "w_c_t", "w_hh_t",
-                                                                            "dgates", "dctx", "dscore", "weights", "dh0")),
-                      int(j["B"]), int(j["T"]), int(j["S"]), 256, sws.data_ptr(), st)
+            groups = [("single_bws%d" % k, [k]) for k in range(3)]
+        for name, ks in groups:  # (each a run of consecutive jobs of `bj`)
+            gws = self.bytes_buf(name, _hip.decoder_workspace_bytes([int(bj[k]["B"]) for k in ks], True))
+            c.add("pnmn_attn_lstm_bwd_group", bj[ks[0]:ks[-1] + 1].ctypes.data, len(ks), 256, gws.data_ptr(), st)
         for sd, e, r0, denc in ((side_s, e_pg, 0, denc_pg), (side_t, e_pg, n, denc_pg), (side_q, e_qr, 0, denc_qr)):
             c.add("pnmn_attn_denc", sd["weights"].data_ptr(), sd["dscore"].data_ptr(), sd["dctx"].data_ptr(), sd["hs"].data_ptr(),
                   e["h"][r0:].data_ptr(), denc[r0:].data_ptr(), sd["rows"], sd["T"], sd["S"], 256, st)

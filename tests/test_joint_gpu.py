@@ -250,7 +250,7 @@ def test_joint_training_step_at_config5_shapes_with_the_full_classifier():
 
 def test_grouped_decoder_backward_is_the_pair_and_single_backward():
     """The backward passes of the generator's two decodes and the reconstructor's in ONE launch (round 5,
-    ``_AttnLSTMDecoderGroup`` / ``pnmn_attn_lstm_bwd_multi_group3``) against pair + single launches: same kernels' bodies,
+    ``_AttnLSTMDecoderGroup`` / ``pnmn_attn_lstm_bwd_group``) against pair + single launches: same kernels' bodies,
     same operands -- the decoders' own gradients are bit-identical and everything else agrees to the order of the embedding gradient's
     atomic adds, for a question-coding iteration (no NMN: nothing
     atomic in the step) at two batch sizes, one of them with a shard the three passes do not fit the chip for together."""

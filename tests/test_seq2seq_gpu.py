@@ -396,7 +396,7 @@ def test_multi_cu_hand_off_counters_per_stream_and_under_capture():
 @pytest.mark.parametrize("batch,steps,positions", [(7, 5, 3), (128, 27, 46), (530, 9, 27), (1024, 12, 64)])
 @pytest.mark.parametrize("mode", [0, 1, 2])
 def test_multi_cu_decoder_matches_one_workgroup_per_tile(batch, steps, positions, mode, monkeypatch):
-    """pnmn_attn_lstm_fwd_multi / _bwd_multi (eight workgroups per tile, batches beyond 512 rows in
+    """pnmn_attn_lstm_fwd_group / _bwd_group with one job (eight workgroups per tile, batches beyond 512 rows in
     several launches) against pnmn_attn_lstm_fwd / _bwd: hidden states, chosen tokens and every gradient."""
     from probnmn.modules.seq2seq_base import _AttnLSTMDecoder
 

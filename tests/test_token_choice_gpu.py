@@ -183,7 +183,7 @@ def test_decoder_draws_the_reference_token(B, T, S, V, cluster, monkeypatch):
 def test_paired_decoder_draws_the_reference_token(rows_s, rows_t):
     """The paired launch (a sampling side beside a teacher-forced one) draws what the reference draws from its own
     hidden states."""
-    from probnmn.modules.seq2seq_base import _AttnLSTMDecoderPair
+    from probnmn.modules.seq2seq_base import _AttnLSTMDecoderGroup
 
     T, S, V = 26, 30, 44
     a, b = _decoder_inputs(rows_s, S, V, 1 + rows_s), _decoder_inputs(rows_t, S, V, 2 + rows_t)
@@ -193,9 +193,9 @@ def test_paired_decoder_draws_the_reference_token(rows_s, rows_t):
                       b_p=a["b_p"])
         meta_b = dict(packs=None, mode=0, T=T, start=START, in_tokens=tf_tokens)
         with torch.no_grad():
-            hs_a, tok_a, hs_b, _ = _AttnLSTMDecoderPair.apply(
+            hs_a, tok_a, hs_b, _ = _AttnLSTMDecoderGroup.apply(
                 a["etable"], a["enc"], a["mask"], a["h0"], a["w_c"], a["w_hh"],
-                b["etable"], b["enc"], b["mask"], b["h0"], b["w_c"], b["w_hh"], (meta_a, meta_b))
+                b["etable"], b["enc"], b["mask"], b["h0"], b["w_c"], b["w_hh"], (meta_a, meta_b), None)
         torch.cuda.synchronize()
         what = "pair rows %d + %d seed=%d offset=%d" % (rows_s, rows_t, seed, row_offset)
         _check_decoder_tokens(hs_a, tok_a, a["w_p"], a["b_p"], 1, seed, row_offset, what)
@@ -361,7 +361,7 @@ def _recorded_draws():
     training batches), the paired launch and the standalone kernel.  tests/golden/token_choice_draws.npz holds them as
     drawn by the library before non-finite rows had a rule of their own; ``python tests/test_token_choice_gpu.py record``
     rewrites it, for a change that is meant to change the draws."""
-    from probnmn.modules.seq2seq_base import _AttnLSTMDecoderPair, choose_tokens
+    from probnmn.modules.seq2seq_base import _AttnLSTMDecoderGroup, choose_tokens
 
     out = {}
     saved = os.environ.get("PNMN_DECODER_CLUSTER")
@@ -383,8 +383,8 @@ def _recorded_draws():
     meta_a = dict(packs=None, mode=1, T=26, start=START, pad=PAD, unk=UNK, seed=99, row_offset=5, w_p=a["w_p"], b_p=a["b_p"])
     meta_b = dict(packs=None, mode=0, T=26, start=START, in_tokens=tf)
     with torch.no_grad():
-        _, tok_a, _, _ = _AttnLSTMDecoderPair.apply(a["etable"], a["enc"], a["mask"], a["h0"], a["w_c"], a["w_hh"],
-                                                    b["etable"], b["enc"], b["mask"], b["h0"], b["w_c"], b["w_hh"], (meta_a, meta_b))
+        _, tok_a, _, _ = _AttnLSTMDecoderGroup.apply(a["etable"], a["enc"], a["mask"], a["h0"], a["w_c"], a["w_hh"],
+                                                     b["etable"], b["enc"], b["mask"], b["h0"], b["w_c"], b["w_hh"], (meta_a, meta_b), None)
     out["pair"] = tok_a.cpu().numpy().astype(np.uint8)
     for V in (44, 100, 512):
         logits = _standalone_logits(8192, V, 5 + V)
