@@ -519,6 +519,35 @@ int pnmn_attn_lstm_beam(const float* etable, const float* enc, const float* mask
                         float* trace_scores, int B, int T, int S, int V, int hidden, int beam,
                         int pad_index, int unk_index, int start_index, int end_index, void* stream);
 
+/* pnmn_attn_lstm_beam under a token automaton: only hypotheses the automaton accepts leave the decoder.
+ *   token_class [V]                    class of every target token, each < n_classes
+ *   next_state  [n_states][n_classes]  each < n_states; state 0 is the start state
+ *   min_left    [n_states]             fewest further tokens from the state to an accepting one: 0 = accepting,
+ *                                      255 = no completion exists
+ * The three tables are HOST pointers; every entry is checked, and they travel by value in the launch arguments (no device
+ * allocation, no copy, no synchronisation; the caller's arrays are free again when the call returns).  Every slot carries
+ * a state, state[b][k] = 0 at the start.  The selection rule above changes at the candidates only; at step t (0-based) a
+ * hypothesis k that has not finished, in state s, offers
+ *   token v (not pad / unk / start, v != end)  only if  min_left[next_state[s][token_class[v]]] <= T - 1 - t
+ *   end_index                                  only if  min_left[s] == 0
+ * and every other candidate of it is -inf; a finished hypothesis offers only end_index at its own score, as above.
+ * A survivor's state is the one reached from its parent's (by back-pointer) on its token; on end_index, the parent's.
+ * Selection, ties, the slot without a finite candidate, the back-track and the trace are those of pnmn_attn_lstm_beam.
+ * Consequence: every hypothesis with a finite score, cut at its first end_index, is accepted by the automaton; when
+ * min_left[0] <= T, slot 0 of every question is finite.  With one state, one class and min_left = {0} the call computes
+ * what pnmn_attn_lstm_beam computes, bit for bit.
+ * Limits: those of pnmn_attn_lstm_beam, 1 <= n_states <= 32, 1 <= n_classes <= 16; a null table or an entry out of range
+ * returns PNMN_EINVAL. */
+#define PNMN_BEAM_MAX_STATES 32
+#define PNMN_BEAM_MAX_CLASSES 16
+int pnmn_attn_lstm_beam_constrained(const float* etable, const float* enc, const float* mask, const float* h0,
+                                    const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
+                                    int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
+                                    float* trace_scores, int B, int T, int S, int V, int hidden, int beam,
+                                    int pad_index, int unk_index, int start_index, int end_index,
+                                    const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left,
+                                    int n_states, int n_classes, void* stream);
+
 /* Multi-CU variants of the two kernels above (decoder_multi.hip): eight workgroups per 16-row tile,
  * each keeping its rows' encoder outputs in LDS and its slices of W_c / W_hh in registers, two L2
  * hand-offs per step.  A job = the arguments and saved tensors of pnmn_attn_lstm_fwd / _bwd for one pass; every call

@@ -19,6 +19,13 @@
 // attn_lstm_fwd_kernel (decoder.hip) runs too; the loops over the encoder rows and the cell are restated here without that
 // kernel's stores for the backward.
 // Nothing is saved for a backward pass: the only global writes are tokens / scores and the optional per-step trace.
+//
+// Constrained variant (pnmn_attn_lstm_beam_constrained, template parameter C): every slot also carries one byte, the state
+// of a token automaton (class of every token, next state per class, fewest further tokens to an accepting state).  The
+// three tables arrive by value in the launch arguments and are staged into LDS once; the candidate stage alone differs:
+// a live hypothesis offers a token only if an accepting state stays reachable in the steps that remain, and @end@ only in
+// an accepting state.  Selection, gather, early stop and back-track are the unconstrained ones; the survivors' states
+// follow the back-pointers like their last tokens.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -59,6 +66,27 @@ struct BeamArgs {
     float* trace_scores;    // [B][T][K] or nullptr
     int B, T, S, V;
     int pad, unk, start, end;
+};
+
+constexpr int MAX_STATES = PNMN_BEAM_MAX_STATES;    // token automaton of the constrained search
+constexpr int MAX_CLASSES = PNMN_BEAM_MAX_CLASSES;
+constexpr int DEAD = 255;  // min_left: no completion exists
+static_assert(MAX_STATES * MAX_CLASSES == 512 && MAXV <= 512 && (MAXV & (MAXV - 1)) == 0, "staged by 512 threads, one entry each");
+
+struct ConstrainedBeamArgs : BeamArgs {
+    unsigned char token_class[MAXV];                     // [V], < n_classes
+    unsigned char next_state[MAX_STATES * MAX_CLASSES];  // [n_states][n_classes] packed, < n_states
+    unsigned char min_left[MAX_STATES];                  // [n_states]
+    int n_classes;
+};
+
+template <bool C>
+struct beam_args {
+    using type = BeamArgs;
+};
+template <>
+struct beam_args<true> {
+    using type = ConstrainedBeamArgs;
 };
 
 // Attention of NH hypotheses that share one question's encoder rows (`er` = enc row 0 of the question + 4 * lane):
@@ -146,8 +174,8 @@ __device__ __forceinline__ void wave_top(float (&val)[N], const int (&idx)[N], f
     }
 }
 
-template <int K>
-__global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const BeamArgs a) {
+template <int K, bool C>
+__global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const typename beam_args<C>::type a) {
     constexpr int Q = ROWS / K;  // questions per workgroup
     __shared__ __attribute__((aligned(16))) float hl[2][ROWS][LD];  // [0]: h the step reads, [1]: h the cell wrote
     __shared__ __attribute__((aligned(16))) float cl[ROWS][LD];     // ctx; after the cell: c on its way through the gather
@@ -158,6 +186,9 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const BeamArgs a) {
     __shared__ unsigned char tok_hist[MAXT][ROWS], bp_hist[MAXT][ROWS];
     __shared__ float top_val[8][ROWS];                              // selection: every wave's K best (value, candidate)
     __shared__ int top_idx[8][ROWS];
+    // constrained search only: the automaton, and the state of every slot ([0]: the step reads, [1]: the survivors')
+    __shared__ unsigned char clsl[C ? MAXV : 1], nextl[C ? MAX_STATES * MAX_CLASSES : 1], leftl[C ? MAX_STATES : 1];
+    __shared__ unsigned char statel[2][C ? ROWS : 1];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int q0 = blockIdx.x * Q;  // first question of this tile
     const int T = a.T, S = a.S, V = a.V;
@@ -170,6 +201,14 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const BeamArgs a) {
         const bool live = q0 + tid / K < a.B;
         tokl[tid] = live ? a.start : a.end;  // (a tile row past the batch counts as finished)
         scorel[tid] = (tid % K == 0) ? 0.f : -INFINITY;  // step 0 expands ONE state per question
+    }
+    int ncls = 1;
+    if constexpr (C) {
+        ncls = a.n_classes;
+        clsl[tid & (MAXV - 1)] = a.token_class[tid & (MAXV - 1)];  // (512 threads: every entry, some four times over)
+        nextl[tid] = a.next_state[tid];                            // (MAX_STATES * MAX_CLASSES = 512)
+        if (tid < MAX_STATES) leftl[tid] = a.min_left[tid];
+        if (tid < ROWS) statel[0][tid] = statel[1][tid] = 0;  // the start state
     }
     float creg[2][4];
 #pragma unroll
@@ -261,6 +300,8 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const BeamArgs a) {
             const float lse = mx + logf(wsum(se));
             const float score = scorel[rl];
             const bool finished = tokl[rl] == a.end;
+            int st = 0;
+            if constexpr (C) st = statel[0][rl];
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const int j = lane + 64 * k;
@@ -269,6 +310,12 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const BeamArgs a) {
                     if (j == a.end) cand = score;  // a finished hypothesis keeps its score
                 } else if (j < V && j != a.pad && j != a.unk && j != a.start) {
                     cand = score + (v[k] - lse);
+                    if constexpr (C) {
+                        // @end@: only in an accepting state; any other token: an accepting state must stay reachable in
+                        // the T - 1 - t steps after this one (DEAD = 255 > any step count)
+                        const int left = j == a.end ? (leftl[st] == 0 ? 0 : DEAD) : leftl[nextl[st * ncls + clsl[j]]];
+                        if (left > T - 1 - t) cand = -INFINITY;
+                    }
                 }
                 if (!(cand > -INFINITY && cand < INFINITY)) cand = -INFINITY;  // a non-finite candidate counts as -inf
                 logl[rl][j] = cand;
@@ -288,6 +335,10 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const BeamArgs a) {
             tokl[rl] = tok;
             tok_hist[t][rl] = (unsigned char)tok;
             bp_hist[t][rl] = (unsigned char)bp;
+            if constexpr (C) {  // the state reached from the parent's on the token; @end@ leaves it where it is
+                const int ps = statel[0][(rl / K) * K + bp];
+                statel[1][rl] = tok == a.end ? (unsigned char)ps : nextl[ps * ncls + clsl[tok]];
+            }
             if (a.trace_tokens) {
                 const size_t o = ((size_t)(q0 + rl / K) * T + t) * K + rl % K;
                 a.trace_tokens[o] = tok;
@@ -356,6 +407,9 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const BeamArgs a) {
                 const int src = (q0 + rl / K < a.B) ? bpl[rl] : rl;
                 creg[ut][r] = cl[src][32 * wave + 16 * ut + li];
             }
+        if constexpr (C) {
+            if (tid < ROWS) statel[0][tid] = statel[1][tid];  // (tile rows past the batch: never read)
+        }
         // (also the barrier between this gather and the next step's writes to cl)
         if (__syncthreads_and(tid < ROWS ? tokl[tid] == a.end : 1)) {
             done = t + 1;
@@ -394,11 +448,39 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const BeamArgs a) {
     }
 }
 
-template <int K>
-int launch_beam(const BeamArgs& a, hipStream_t stream) {
+template <int K, bool C>
+int launch_beam(const typename beam_args<C>::type& a, hipStream_t stream) {
     constexpr int Q = ROWS / K;
-    hipLaunchKernelGGL(attn_lstm_beam_kernel<K>, dim3((a.B + Q - 1) / Q), dim3(512), 0, stream, a);
+    hipLaunchKernelGGL((attn_lstm_beam_kernel<K, C>), dim3((a.B + Q - 1) / Q), dim3(512), 0, stream, a);
     return (int)hipGetLastError();
+}
+
+template <bool C>
+int launch_beam_width(int beam, const typename beam_args<C>::type& a, hipStream_t stream) {
+    switch (beam) {
+        case 1: return launch_beam<1, C>(a, stream);
+        case 2: return launch_beam<2, C>(a, stream);
+        case 4: return launch_beam<4, C>(a, stream);
+        case 8: return launch_beam<8, C>(a, stream);
+        case 16: return launch_beam<16, C>(a, stream);
+        default: return PNMN_EINVAL;
+    }
+}
+
+// The argument checks both entry points share: 0 = launch, 1 = nothing to do, PNMN_EINVAL.
+int check_beam_arguments(const float* etable, const float* enc, const float* mask, const float* h0, const float* w_c,
+                         const float* w_hh, const float* w_p, const float* b_p, const int64_t* tokens, const float* scores,
+                         const int32_t* trace_tokens, const int32_t* trace_backptr, const float* trace_scores, int B, int T, int S,
+                         int V, int hidden, int beam, int start_index, int end_index) {
+    if (B < 0 || T < 0) return PNMN_EINVAL;
+    if (!etable || !enc || !mask || !h0 || !w_c || !w_hh || !w_p || !b_p || !tokens || !scores) return PNMN_EINVAL;
+    const int traced = (trace_tokens != nullptr) + (trace_backptr != nullptr) + (trace_scores != nullptr);
+    if (traced != 0 && traced != 3) return PNMN_EINVAL;
+    if (hidden != H || S < 1 || S > MAXS || V < 1 || V > MAXV || T > MAXT) return PNMN_EINVAL;
+    // every index the kernel looks a table row up by, or writes as a token, is inside the vocabulary
+    if (start_index < 0 || start_index >= V || end_index < 0 || end_index >= V) return PNMN_EINVAL;
+    if (beam != 1 && beam != 2 && beam != 4 && beam != 8 && beam != 16) return PNMN_EINVAL;
+    return B == 0 || T == 0 ? 1 : 0;
 }
 
 }  // namespace
@@ -408,23 +490,40 @@ extern "C" int pnmn_attn_lstm_beam(const float* etable, const float* enc, const 
                                    int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
                                    float* trace_scores, int B, int T, int S, int V, int hidden, int beam, int pad_index,
                                    int unk_index, int start_index, int end_index, void* stream) {
-    if (B < 0 || T < 0) return PNMN_EINVAL;
-    if (!etable || !enc || !mask || !h0 || !w_c || !w_hh || !w_p || !b_p || !tokens || !scores) return PNMN_EINVAL;
-    const int traced = (trace_tokens != nullptr) + (trace_backptr != nullptr) + (trace_scores != nullptr);
-    if (traced != 0 && traced != 3) return PNMN_EINVAL;
-    if (hidden != H || S < 1 || S > MAXS || V < 1 || V > MAXV || T > MAXT) return PNMN_EINVAL;
-    // every index the kernel looks a table row up by, or writes as a token, is inside the vocabulary
-    if (start_index < 0 || start_index >= V || end_index < 0 || end_index >= V) return PNMN_EINVAL;
-    if (B == 0 || T == 0) return beam == 1 || beam == 2 || beam == 4 || beam == 8 || beam == 16 ? 0 : PNMN_EINVAL;
+    const int todo = check_beam_arguments(etable, enc, mask, h0, w_c, w_hh, w_p, b_p, tokens, scores, trace_tokens, trace_backptr,
+                                          trace_scores, B, T, S, V, hidden, beam, start_index, end_index);
+    if (todo != 0) return todo < 0 ? todo : 0;
     const BeamArgs a{etable, enc, mask, h0, w_c, w_hh, w_p, b_p, tokens, scores, trace_tokens, trace_backptr, trace_scores,
                      B, T, S, V, pad_index, unk_index, start_index, end_index};
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    switch (beam) {
-        case 1: return launch_beam<1>(a, st);
-        case 2: return launch_beam<2>(a, st);
-        case 4: return launch_beam<4>(a, st);
-        case 8: return launch_beam<8>(a, st);
-        case 16: return launch_beam<16>(a, st);
-        default: return PNMN_EINVAL;
+    return launch_beam_width<false>(beam, a, static_cast<hipStream_t>(stream));
+}
+
+extern "C" int pnmn_attn_lstm_beam_constrained(const float* etable, const float* enc, const float* mask, const float* h0,
+                                               const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
+                                               int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
+                                               float* trace_scores, int B, int T, int S, int V, int hidden, int beam,
+                                               int pad_index, int unk_index, int start_index, int end_index,
+                                               const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left,
+                                               int n_states, int n_classes, void* stream) {
+    const int todo = check_beam_arguments(etable, enc, mask, h0, w_c, w_hh, w_p, b_p, tokens, scores, trace_tokens, trace_backptr,
+                                          trace_scores, B, T, S, V, hidden, beam, start_index, end_index);
+    if (todo < 0) return todo;
+    if (!token_class || !next_state || !min_left) return PNMN_EINVAL;
+    if (n_states < 1 || n_states > MAX_STATES || n_classes < 1 || n_classes > MAX_CLASSES) return PNMN_EINVAL;
+    // every table entry the kernel indexes with stays inside the tables (min_left is only compared)
+    ConstrainedBeamArgs a{};
+    for (int v = 0; v < V; ++v) {
+        if (token_class[v] >= n_classes) return PNMN_EINVAL;
+        a.token_class[v] = token_class[v];
     }
+    for (int i = 0; i < n_states * n_classes; ++i) {
+        if (next_state[i] >= n_states) return PNMN_EINVAL;
+        a.next_state[i] = next_state[i];
+    }
+    for (int s = 0; s < n_states; ++s) a.min_left[s] = min_left[s];
+    if (todo != 0) return 0;
+    static_cast<BeamArgs&>(a) = BeamArgs{etable, enc, mask, h0, w_c, w_hh, w_p, b_p, tokens, scores, trace_tokens, trace_backptr,
+                                         trace_scores, B, T, S, V, pad_index, unk_index, start_index, end_index};
+    a.n_classes = n_classes;
+    return launch_beam_width<true>(beam, a, static_cast<hipStream_t>(stream));
 }

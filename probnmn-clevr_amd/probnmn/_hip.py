@@ -83,6 +83,7 @@ SIGNATURES: Dict[str, tuple] = {
     "pnmn_lstm_seq_workspace_bytes": (_I, _I),
     "pnmn_cluster_reserve_cus": (_I,),
     "pnmn_attn_lstm_beam": (_P,) * 13 + (_I,) * 10 + (_P,),
+    "pnmn_attn_lstm_beam_constrained": (_P,) * 13 + (_I,) * 10 + (_P,) * 3 + (_I,) * 2 + (_P,),
     "pnmn_attn_lstm_fwd": (_P,) * 15 + (_I,) * 9 + (ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.c_int64, _P),
     "pnmn_attn_lstm_bwd": (_P,) * 14 + (_I,) * 4 + (_P,),
     "pnmn_attn_lstm_group_workspace_bytes": (_P, _I, _I),

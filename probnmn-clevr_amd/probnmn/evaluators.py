@@ -122,7 +122,8 @@ def evaluate_answer_accuracy(program_generator, nmn, batches: Iterable[Dict[str,
 
 @torch.no_grad()
 def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary,
-                    beam_size: Optional[int] = None, prefer_valid: bool = True) -> List[Dict[str, Any]]:
+                    beam_size: Optional[int] = None, prefer_valid: bool = True,
+                    constrained: bool = False) -> List[Dict[str, Any]]:
     """scripts/inference.py:76-91: sampled programs -> NMN -> answer strings, one record per question
     (``question_index`` from the batch when present, else a running index).
 
@@ -130,7 +131,13 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
     the NMN gets, per question, the most probable hypothesis -- or, with ``prefer_valid``, the best-ranked hypothesis
     that the program compiler accepts (the most probable one when none is valid).  Validity is decided on the host from
     the [B, K, T] tokens the loop copies out anyway.  Each record then also names ``"program"`` (token strings of the
-    chosen hypothesis, without padding), its ``"beam_rank"`` and whether it is a ``"program_valid"`` one."""
+    chosen hypothesis, without padding), its ``"beam_rank"`` and whether it is a ``"program_valid"`` one.
+
+    ``constrained`` (needs ``beam_size``): the beam kernel searches under the program compiler's validity rule
+    (``nmn.engine.compiler.decoding_automaton``), so every hypothesis it returns is a valid program: ``program_valid`` is
+    always true, and ``beam_rank`` is 0 under ``prefer_valid``.  The record layout is the same."""
+    if constrained and beam_size is None:
+        raise ValueError("constrained=True constrains the beam search: give a beam_size")
     was_training = (program_generator.training, nmn.training)
     program_generator.eval()
     nmn.eval()
@@ -139,12 +146,18 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
         # (as in answering_evaluator: batch i + 1's generator pass is queued before batch i's programs are awaited on the host)
         pinned: Dict[Any, torch.Tensor] = {}
         pad = getattr(program_generator, "_pad_index", 0)
+        constraint = None
+        if constrained:  # built once (and cached on the compiler): the tokens the decoder never emits do not count
+            exclude = [getattr(program_generator, name) for name in ("_pad_index", "_unk_index", "_start_index", "_end_index")]
+            constraint = nmn.engine.compiler.decoding_automaton(exclude=exclude)
 
         def queue(batch, iteration):
             if beam_size is None:
                 programs = program_generator(batch["question"])["predictions"]
             else:
-                programs = program_generator(batch["question"], decoding_strategy="beam", beam_size=beam_size)["beam_predictions"]
+                extra = {} if constraint is None else {"constraint": constraint}
+                programs = program_generator(batch["question"], decoding_strategy="beam", beam_size=beam_size,
+                                             **extra)["beam_predictions"]
             if not (programs.is_cuda and batch["image"].is_cuda):
                 return programs, None
             key = (iteration & 1, tuple(programs.shape), programs.dtype)

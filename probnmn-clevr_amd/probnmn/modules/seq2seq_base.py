@@ -1047,13 +1047,17 @@ class Seq2SeqBase(nn.Module):
         decoding_strategy: str = "sampling",
         need_predictions: bool = True,
         beam_size: int = 4,
+        constraint=None,
     ) -> Dict[str, torch.Tensor]:
         """``decoding_strategy``: "sampling" / "greedy" as the reference; "beam": beam search of width ``beam_size`` (free
-        running only, no gradients -- see ``decode_beam``).  ``beam_size`` is ignored by the other strategies."""
+        running only, no gradients -- see ``decode_beam``).  ``beam_size`` is ignored by the other strategies;
+        ``constraint`` (a token automaton, beam search only) is refused by them."""
         if decoding_strategy == "beam":
             self._check_beam_arguments(target_tokens, beam_size)
             with torch.no_grad():  # (the encoder without its dropout: the search is the same in train() and eval() mode)
-                return self.decode_beam(self.encode(source_tokens, dropout=False), beam_size)
+                return self.decode_beam(self.encode(source_tokens, dropout=False), beam_size, constraint=constraint)
+        if constraint is not None:
+            raise ValueError("constraint: only decoding_strategy='beam' decodes under a token automaton")
         return self.decode(self.encode(source_tokens), target_tokens, decoding_strategy, need_predictions)
 
     def encode(self, source_tokens: torch.LongTensor, dropout: bool = True) -> Dict[str, torch.Tensor]:
@@ -1097,15 +1101,18 @@ class Seq2SeqBase(nn.Module):
         need_predictions: bool = True,
         seed: Optional[int] = None,
         beam_size: int = 4,
+        constraint=None,
     ) -> Dict[str, torch.Tensor]:
         """``need_predictions=False`` (teacher forcing only): skip drawing the per-step predictions from the
         teacher-forced distributions (reference :196-220) -- training iterations never read them.  ``seed``: the sampler
         seed a ``decode_prepare`` of this pass already drew (its pairing fell through): one draw per pass either way, so
         paired and unpaired schedules sample the same programs from the same torch seed.  ``decoding_strategy="beam"``:
-        ``decode_beam`` with ``beam_size`` (which the other strategies ignore)."""
+        ``decode_beam`` with ``beam_size`` (which the other strategies ignore) and ``constraint`` (which they refuse)."""
         if decoding_strategy == "beam":
             self._check_beam_arguments(target_tokens, beam_size)
-            return self.decode_beam(state, beam_size)
+            return self.decode_beam(state, beam_size, constraint=constraint)
+        if constraint is not None:
+            raise ValueError("constraint: only decoding_strategy='beam' decodes under a token automaton")
         if decoding_strategy not in ("sampling", "greedy"):
             raise ValueError("decoding_strategy must be 'sampling', 'greedy' or 'beam'")
         pad, bos, eos = self._pad_index, self._start_index, self._end_index
@@ -1161,7 +1168,8 @@ class Seq2SeqBase(nn.Module):
             raise ValueError("beam_size must be one of %s, got %r" % (Seq2SeqBase.BEAM_SIZES, beam_size))
 
     @torch.no_grad()
-    def decode_beam(self, state: Dict[str, torch.Tensor], beam_size: int = 4, trace: bool = False) -> Dict[str, torch.Tensor]:
+    def decode_beam(self, state: Dict[str, torch.Tensor], beam_size: int = 4, trace: bool = False,
+                    constraint=None) -> Dict[str, torch.Tensor]:
         """Beam search over ``max_decoding_steps`` steps in ONE launch of the persistent beam kernel
         (``pnmn_attn_lstm_beam``, csrc/decoder_beam.hip; the selection rule is stated in include/probnmn_hip.h).  Inference
         only: no graph, no seed drawn from the torch generator, the same in ``train()`` and ``eval()`` mode given a ``state``
@@ -1170,8 +1178,24 @@ class Seq2SeqBase(nn.Module):
         (sums of token log-probabilities), ``predictions`` = the best hypothesis and ``loss`` [B] = its negative
         log-probability over its number of non-padding tokens (the free-running sampled path's quantity).  ``trace=True``
         adds ``beam_trace``: (token, back-pointer, score) of every slot at every step, [B, T, K] each.  There is no
-        step-by-step path for this mode: shapes outside the kernel's limits raise ``NotImplementedError``."""
+        step-by-step path for this mode: shapes outside the kernel's limits raise ``NotImplementedError``.
+
+        ``constraint``: a token automaton (``token_class`` [V], ``next_state`` [n_states, n_classes], ``min_left``
+        [n_states] as uint8 numpy arrays -- ``ProgramCompiler.decoding_automaton``).  The search then runs in
+        ``pnmn_attn_lstm_beam_constrained``: a hypothesis offers a token only while an accepted completion stays reachable
+        in the steps that remain, so every hypothesis with a finite score is accepted by the automaton.  The same keys
+        come back.  ``None``: ``pnmn_attn_lstm_beam``, unconstrained."""
         self._check_beam_arguments(None, beam_size)
+        tables = None
+        if constraint is not None:
+            tables = [np.ascontiguousarray(getattr(constraint, name), dtype=np.uint8)
+                      for name in ("token_class", "next_state", "min_left")]
+            n_vocab = self._output_projection_layer.weight.size(0)
+            if tables[0].ndim != 1 or tables[0].shape[0] != n_vocab:
+                raise ValueError("constraint: token_class covers %s tokens, the target vocabulary has %d"
+                                 % (tables[0].shape, n_vocab))
+            if tables[1].ndim != 2 or tables[2].shape != (tables[1].shape[0],):
+                raise ValueError("constraint: next_state must be [n_states, n_classes] and min_left [n_states]")
         enc, h, fmask = state["enc"].detach(), state["h"].detach(), state["fmask"].detach()
         dev = enc.device
         if dev.type != "cuda":
@@ -1202,12 +1226,16 @@ class Seq2SeqBase(nn.Module):
             tr = (torch.empty(B, T, K, dtype=torch.int32, device=dev), torch.empty(B, T, K, dtype=torch.int32, device=dev),
                   torch.empty(B, T, K, dtype=torch.float32, device=dev))
         if B > 0 and T > 0:
-            _hip.check(_hip.lib().pnmn_attn_lstm_beam(
-                etable.data_ptr(), enc.data_ptr(), fmask.data_ptr(), h.data_ptr(), w_c_p.data_ptr(), w_hh_p.data_ptr(),
-                w_p.data_ptr(), b_p.data_ptr(), raw.data_ptr(), scores.data_ptr(),
-                tr[0].data_ptr() if tr else None, tr[1].data_ptr() if tr else None, tr[2].data_ptr() if tr else None,
-                B, T, S, V, Hd, K, self._pad_index, self._unk_index, self._start_index, self._end_index,
-                _hip.stream_ptr(dev)), "attn_lstm_beam")
+            common = (etable.data_ptr(), enc.data_ptr(), fmask.data_ptr(), h.data_ptr(), w_c_p.data_ptr(), w_hh_p.data_ptr(),
+                      w_p.data_ptr(), b_p.data_ptr(), raw.data_ptr(), scores.data_ptr(),
+                      tr[0].data_ptr() if tr else None, tr[1].data_ptr() if tr else None, tr[2].data_ptr() if tr else None,
+                      B, T, S, V, Hd, K, self._pad_index, self._unk_index, self._start_index, self._end_index)
+            if tables is None:
+                _hip.check(_hip.lib().pnmn_attn_lstm_beam(*common, _hip.stream_ptr(dev)), "attn_lstm_beam")
+            else:  # (the tables are host arrays: the library checks every entry and passes them by value)
+                _hip.check(_hip.lib().pnmn_attn_lstm_beam_constrained(
+                    *common, tables[0].ctypes.data, tables[1].ctypes.data, tables[2].ctypes.data,
+                    tables[1].shape[0], tables[1].shape[1], _hip.stream_ptr(dev)), "attn_lstm_beam_constrained")
         beams = self._trim_predictions(raw.view(B * K, T)).view(B, K, T)
         best = beams[:, 0]
         n = (best != self._pad_index).sum(-1).to(scores.dtype)

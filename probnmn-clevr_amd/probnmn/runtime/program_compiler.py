@@ -115,6 +115,7 @@ class ProgramCompiler:
         self._bytes_cache: Dict[bytes, CompiledProgram] = {}
         self._kinds_array = None
         self._invalid = CompiledProgram(False, (), FEAT)
+        self._automata: Dict[Tuple[int, ...], "DecodingAutomaton"] = {}
 
     def compile(self, tokens: Sequence[int]) -> CompiledProgram:
         key = tuple(int(t) for t in tokens)
@@ -193,28 +194,166 @@ class ProgramCompiler:
             if tok < 0 or tok >= nkinds:
                 return invalid  # the reference's vocabulary lookup would raise KeyError
             kind = self.kinds[tok]
-            if kind == SKIP:
+            step = register_step(kind, out_c, saved_c if saved is not None else None, D)
+            if step is None:
+                return invalid
+            if step is _UNCHANGED:
                 continue
+            oc, _ = step
             if kind == SCENE:
                 saved, saved_c = out, out_c
                 out, out_c = ONES, 1
                 continue
-            if kind in (AND, OR):
-                if saved is None:
-                    return invalid
-                oc = max(out_c, saved_c)  # torch.min/max broadcast 1 <-> D channels
+            if kind in (AND, OR, CMP):
                 calls.append(ModuleCall(kind, tok, out, saved, out_c, saved_c, oc))
-            elif kind == CMP:
-                if saved is None or out_c != D or saved_c != D:
-                    return invalid
-                calls.append(ModuleCall(kind, tok, out, saved, D, D, D))
-                oc = D
             else:  # ATT / QUERY / REL / SAME take (FEAT, attention)
-                if out_c != 1:
-                    return invalid
-                oc = D if kind == QUERY else 1
                 calls.append(ModuleCall(kind, tok, out, FEAT, 1, D, oc))
             out, out_c = len(calls) + 1, oc
         if out_c != D:
             return invalid
         return CompiledProgram(True, tuple(calls), out)
+
+    # ---------------------------------------------------------------------------------
+    def decoding_automaton(self, exclude: Sequence[int] = ()) -> "DecodingAutomaton":
+        """The validity rule as a left-to-right automaton over token classes, for grammar-constrained beam search
+        (``pnmn_attn_lstm_beam_constrained``): a token string is accepted exactly when ``compile`` calls it valid.
+
+        ``_compile`` reads a program right to left and its verdict depends on the channel counts of the two registers
+        alone -- a small deterministic machine over ``register_step``.  A decoder emits left to right, so this is the
+        reversed machine, determinised by subset construction: the subset after a prefix is the set of register states
+        from which reading the prefix reversed ends with D output channels.  It starts as the set of accepting register
+        states, is accepting when it holds the initial register state (D channels, nothing saved), and the empty subset
+        is the dead state.  Token kinds with the same column share a class.  ``min_left`` counts only tokens a decoder
+        may emit: every vocabulary index outside ``exclude`` (pad / unk / start / end)."""
+        key = tuple(sorted(set(int(t) for t in exclude)))
+        hit = self._automata.get(key)
+        if hit is None:
+            hit = self._automata[key] = _build_automaton(self.kinds, self.module_channels, key)
+        return hit
+
+
+_UNCHANGED = object()  # register_step: the token leaves both registers as they are
+
+
+def register_step(kind: int, out_c: int, saved_c: Optional[int], D: int):
+    """One token of the interpreter on the channel counts of its two registers (``saved_c`` None: nothing saved yet):
+    ``None`` when the token is invalid here, ``_UNCHANGED`` for a skipped token, else the new (out_c, saved_c)."""
+    if kind == SKIP:
+        return _UNCHANGED
+    if kind == SCENE:
+        return 1, out_c
+    if kind in (AND, OR):
+        if saved_c is None:
+            return None
+        return max(out_c, saved_c), saved_c  # torch.min/max broadcast 1 <-> D channels
+    if kind == CMP:
+        if saved_c is None or out_c != D or saved_c != D:
+            return None
+        return D, saved_c
+    # ATT / QUERY / REL / SAME take (FEAT, attention)
+    if out_c != 1:
+        return None
+    return (D if kind == QUERY else 1), saved_c
+
+
+MAX_AUTOMATON_STATES = 32   # PNMN_BEAM_MAX_STATES / PNMN_BEAM_MAX_CLASSES of include/probnmn_hip.h
+MAX_AUTOMATON_CLASSES = 16
+NO_COMPLETION = 255
+
+
+class DecodingAutomaton:
+    """``token_class`` [V], ``next_state`` [n_states, n_classes], ``min_left`` [n_states]: read-only contiguous uint8
+    arrays, state 0 the start state (the layout ``pnmn_attn_lstm_beam_constrained`` takes)."""
+
+    __slots__ = ("token_class", "next_state", "min_left")
+
+    def __init__(self, token_class, next_state, min_left):
+        import numpy as np
+
+        arrays = []
+        for a in (token_class, next_state, min_left):
+            a = np.array(a, dtype=np.uint8, order="C")
+            a.setflags(write=False)
+            arrays.append(a)
+        tc, ns, ml = arrays
+        if tc.ndim != 1 or ns.ndim != 2 or ml.ndim != 1 or ns.shape[0] != ml.shape[0]:
+            raise ValueError("token_class [V], next_state [n_states, n_classes], min_left [n_states]")
+        if not (1 <= ns.shape[0] <= MAX_AUTOMATON_STATES and 1 <= ns.shape[1] <= MAX_AUTOMATON_CLASSES):
+            raise ValueError("decoding automaton of %d states x %d classes: the beam kernel takes at most %d x %d"
+                             % (ns.shape[0], ns.shape[1], MAX_AUTOMATON_STATES, MAX_AUTOMATON_CLASSES))
+        if (tc.size and int(tc.max()) >= ns.shape[1]) or int(ns.max()) >= ns.shape[0]:
+            raise ValueError("decoding automaton: a table entry is out of range")
+        object.__setattr__(self, "token_class", tc)
+        object.__setattr__(self, "next_state", ns)
+        object.__setattr__(self, "min_left", ml)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("DecodingAutomaton is immutable")
+
+    @property
+    def n_states(self) -> int:
+        return self.next_state.shape[0]
+
+    @property
+    def n_classes(self) -> int:
+        return self.next_state.shape[1]
+
+    def accepts(self, tokens: Sequence[int]) -> bool:
+        s = 0
+        for t in tokens:
+            if t < 0 or t >= self.token_class.size:
+                return False
+            s = int(self.next_state[s, self.token_class[t]])
+        return int(self.min_left[s]) == 0
+
+
+def _build_automaton(kinds: Sequence[int], D: int, exclude: Tuple[int, ...]) -> DecodingAutomaton:
+    n_kinds = len(KIND_NAMES)
+    # the register states _compile can be in: (out_c, saved_c), saved_c None before the first `scene`
+    regs = [(o, s) for o in (1, D) for s in (None, 1, D)] if D != 1 else [(1, None), (1, 1)]
+    initial = (D, None)
+
+    def after(kind, reg):
+        step = register_step(kind, reg[0], reg[1], D)
+        return reg if step is _UNCHANGED else step
+
+    # reading a prefix reversed = its LAST token first: extending the prefix by token x puts x in front of the reversed
+    # string, so the new subset is {r : step(x, r) is in the old subset}
+    start = frozenset(r for r in regs if r[0] == D)
+    subsets, table = [start], []
+    index = {start: 0}
+    i = 0
+    while i < len(subsets):
+        row = []
+        for kind in range(n_kinds):
+            nxt = frozenset(r for r in regs if after(kind, r) in subsets[i])
+            if nxt not in index:
+                index[nxt] = len(subsets)
+                subsets.append(nxt)
+            row.append(index[nxt])
+        table.append(row)
+        i += 1
+    n_states = len(subsets)
+    # kinds with identical columns share a class
+    columns = [tuple(table[s][k] for s in range(n_states)) for k in range(n_kinds)]
+    class_of_column: Dict[Tuple[int, ...], int] = {}
+    kind_class = [class_of_column.setdefault(col, len(class_of_column)) for col in columns]
+    n_classes = len(class_of_column)
+    if n_states > MAX_AUTOMATON_STATES or n_classes > MAX_AUTOMATON_CLASSES:
+        raise ValueError("decoding automaton of %d states x %d classes: the beam kernel takes at most %d x %d"
+                         % (n_states, n_classes, MAX_AUTOMATON_STATES, MAX_AUTOMATON_CLASSES))
+    next_state = [[0] * n_classes for _ in range(n_states)]
+    for k in range(n_kinds):
+        for s in range(n_states):
+            next_state[s][kind_class[k]] = table[s][k]
+    token_class = [kind_class[k] for k in kinds]
+    # fewest further tokens to an accepting subset, over the classes of tokens a decoder may emit
+    emitted = sorted({token_class[t] for t in range(len(kinds)) if t not in exclude})
+    min_left = [0 if initial in subsets[s] else NO_COMPLETION for s in range(n_states)]
+    for _ in range(n_states):
+        for s in range(n_states):
+            for c in emitted:
+                via = min_left[next_state[s][c]]
+                if via != NO_COMPLETION and via + 1 < min_left[s]:
+                    min_left[s] = via + 1
+    return DecodingAutomaton(token_class, next_state, min_left)

@@ -1,6 +1,7 @@
 """What beam-search decoding costs against the existing greedy free-running decode of as many rows.
 
 usage: python scripts/beam_decode_rate.py [--questions 256] [--steps 30] [--beams 1,4,8,16] [--rounds 5] [--window 0.5]
+                                          [--constrained | --variants beam,...]
 
 For every beam width K: ``ProgramGenerator.decode_beam`` of B questions (one launch of the beam kernel: B*K hypotheses,
 the encoder outputs read per question) against ``decode(..., "greedy")`` of the same encoder state repeated K times
@@ -11,7 +12,12 @@ inside each round; a measurement is the host clock around as many decodes as fil
 short trial of the variant), ending in a device synchronise, after a warm-up of every shape.  The "beam" figure is the
 whole ``decode_beam`` call -- the per-call token table, the trim and the loss with the kernel -- as "greedy" is the whole
 ``decode`` call.  Prints one JSON line per K: median ms per decode of each variant over the rounds, the spread
-(min, max) and the ratios beam / greedy."""
+(min, max) and the ratios beam / greedy.
+
+``--constrained``: what the grammar constraint costs.  The variants are then "beam" and "beam_constrained" -- the same
+``decode_beam`` under the program compiler's decoding automaton (``pnmn_attn_lstm_beam_constrained``) -- alternating
+inside each round, and the ratio printed is constrained / unconstrained.  ``--variants``: any subset, in the order given
+(e.g. ``beam`` alone, to compare two builds of the library process against process)."""
 import argparse
 import json
 import os
@@ -30,12 +36,19 @@ def main() -> None:
     ap.add_argument("--beams", default="1,4,8,16")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--window", type=float, default=0.5, help="seconds of decodes per measurement")
+    ap.add_argument("--constrained", action="store_true", help="time beam against beam under the decoding automaton")
+    ap.add_argument("--variants", default=None, help="comma-separated subset of beam, beam_constrained, greedy, greedy_one_workgroup")
     args = ap.parse_args()
+    if args.variants is not None:
+        chosen = args.variants.split(",")
+    else:
+        chosen = ["beam", "beam_constrained"] if args.constrained else ["beam", "greedy", "greedy_one_workgroup"]
 
     import torch
 
     from probnmn.data.synthetic import synthetic_batch
     from probnmn.models import ProgramGenerator
+    from probnmn.runtime.program_compiler import ProgramCompiler
     from probnmn.vocabulary import Vocabulary
 
     if not torch.cuda.is_available():
@@ -45,6 +58,10 @@ def main() -> None:
     torch.manual_seed(0)
     pg = ProgramGenerator(vocab, max_decoding_steps=args.steps).to(dev).eval()
     questions = synthetic_batch(vocab, args.questions, seed=1)["question"].to(dev)
+    automaton = None
+    if "beam_constrained" in chosen:
+        compiler = ProgramCompiler(vocab.get_index_to_token_vocabulary("programs"))
+        automaton = compiler.decoding_automaton(exclude=(pg._pad_index, pg._unk_index, pg._start_index, pg._end_index))
 
     def timed(fn, calls: int) -> float:
         torch.cuda.synchronize()
@@ -57,10 +74,15 @@ def main() -> None:
     with torch.no_grad():
         state = pg.encode(questions)
         for K in [int(k) for k in args.beams.split(",")]:
-            wide = {k: v.repeat_interleave(K, 0).contiguous() for k, v in state.items()}
+            wide = None
+            if "greedy" in chosen or "greedy_one_workgroup" in chosen:
+                wide = {k: v.repeat_interleave(K, 0).contiguous() for k, v in state.items()}
 
             def beam():
                 pg.decode_beam(state, K)
+
+            def beam_constrained():
+                pg.decode_beam(state, K, constraint=automaton)
 
             def greedy():
                 pg.decode(wide, decoding_strategy="greedy")
@@ -72,7 +94,9 @@ def main() -> None:
                 finally:
                     del os.environ["PNMN_DECODER_CLUSTER"]
 
-            variants = (("beam", beam), ("greedy", greedy), ("greedy_one_workgroup", greedy_one_workgroup))
+            known = {"beam": beam, "beam_constrained": beam_constrained, "greedy": greedy,
+                     "greedy_one_workgroup": greedy_one_workgroup}
+            variants = tuple((name, known[name]) for name in chosen)
             for _, fn in variants:  # warm-up of every shape
                 for _ in range(3):
                     fn()
@@ -82,13 +106,17 @@ def main() -> None:
                 for name, fn in variants:
                     ms[name].append(timed(fn, calls[name]))
             med = {name: statistics.median(v) for name, v in ms.items()}
-            print(json.dumps({
+            line = {
                 "questions": args.questions, "beam": K, "steps": args.steps, "rows": args.questions * K, "calls": calls,
                 "ms": {name: round(med[name], 4) for name in ms},
-                "spread_ms": {name: [round(min(v), 4), round(max(v), 4)] for name, v in ms.items()},
-                "beam_over_greedy": round(med["beam"] / med["greedy"], 3),
-                "beam_over_greedy_one_workgroup": round(med["beam"] / med["greedy_one_workgroup"], 3),
-                "us_per_step": {name: round(med[name] / args.steps * 1e3, 2) for name in ms}}), flush=True)
+                "spread_ms": {name: [round(min(v), 4), round(max(v), 4)] for name, v in ms.items()}}
+            for key, over, under in (("beam_over_greedy", "beam", "greedy"),
+                                     ("beam_over_greedy_one_workgroup", "beam", "greedy_one_workgroup"),
+                                     ("constrained_over_beam", "beam_constrained", "beam")):
+                if over in med and under in med:
+                    line[key] = round(med[over] / med[under], 3)
+            line["us_per_step"] = {name: round(med[name] / args.steps * 1e3, 2) for name in ms}
+            print(json.dumps(line), flush=True)
 
 
 if __name__ == "__main__":
