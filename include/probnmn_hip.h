@@ -16,6 +16,15 @@
  *   - return 0 on success, a negative PNMN_E* for argument errors, a positive hipError_t
  *     otherwise.
  * No torch types appear anywhere in this interface.
+ *
+ * Declaration conventions.  The Python binding (probnmn/_hip.py) is derived from this file when it is imported: an
+ * entry point, record or constant is added HERE (and defined in csrc), nowhere else.  Its reader relies on:
+ *   - a prototype starts its line with the return type, `int` or `int64_t`, and ends with `);`
+ *   - a record is one `typedef struct [tag] { ... } pnmn_x;` of pointers, fixed-width scalars (int32_t, uint32_t,
+ *     int64_t, uint64_t, float, double) and arrays of them -- no nested records, unions or bit fields
+ *   - scalar parameters are int, int32_t, uint32_t, int64_t, uint64_t, float or double; anything with a `*` is a pointer
+ *   - a constant is `#define PNMN_NAME <integer>` or `(<negative integer>)`
+ * A pnmn_ declaration written any other way makes the import fail with its text (tests/test_abi.py).
  */
 #ifndef PROBNMN_HIP_H
 #define PROBNMN_HIP_H
@@ -922,6 +931,7 @@ int64_t pnmn_colsum_workspace_bytes(int R, int C);
 /* Library self-description (no GPU needed).  12: pnmn_gemm_desc gains colsum / colsum2 (120 bytes), pnmn_gemm_workspace_bytes includes the column-sum partials.  11 = round 6: pnmn_gemm / pnmn_colsum / pnmn_token_rows, an accumulate flag on pnmn_embedding_grad, row stride + second bias output on pnmn_token_table_bwd.  10 = round 5.  8 = round 4: the trunk executor of version 7 removed again (pnmn_trunk_exec, pnmn_plan_batch_owners, the EXEC launch op; pnmn_trunk_io shrinks to 224 bytes), streamed convolution kernel behind the same pnmn_conv_nhwc entry points (split 16 gone).  7: the trunk executor (pnmn_trunk_exec, EXEC launch op, pnmn_trunk_io grows to 232 bytes), conv segments in one launch; 6 = round 3: pnmn_conv_nhwc_cus, paired decoder launches, pnmn_attn_denc, pnmn_joint_objective, ingest by copy engine; 5: the trunk planner (pnmn_trunk_*), pnmn_set_rows, SET_ROWS / ACCUMULATE / ZERO launch ops; 4: pnmn_cluster_reserve_cus.  3 = round 2: 28x28 maps in the conv / weight-gradient / layout /
  * pool entry points, pnmn_conv_nhwc_launches takes H and W, sequence-loss / ELBO / feature-ingest entry points
  * added, the persistent dataflow executor (pnmn_dataflow) removed. */
+#define PNMN_ABI_VERSION 13   /* what pnmn_abi_version() returns; the binding refuses a library built from another */
 int pnmn_abi_version(void);
 
 #ifdef __cplusplus

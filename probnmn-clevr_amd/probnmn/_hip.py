@@ -1,4 +1,10 @@
-"""ctypes binding of ``libprobnmn_hip.so`` (include/probnmn_hip.h).
+"""ctypes binding of ``libprobnmn_hip.so``, derived from its C header (include/probnmn_hip.h).
+
+The header is the one statement of the ABI.  ``read_header`` parses it when this module is imported and everything the
+package binds comes out of that: ``SIGNATURES`` / ``RESTYPES`` (every ``pnmn_*`` prototype), one numpy record dtype per
+``typedef struct ... pnmn_x;`` (``pnmn_conv_item`` -> ``CONV_ITEM``) and one integer per ``#define PNMN_NAME``
+(``PNMN_OP_CONV`` -> ``OP_CONV``).  A new entry point, record or constant is therefore added in the header and in its
+``.hip`` file, nowhere else; tests/test_abi.py holds the result against the C++ compiler's own view of the header.
 
 The library is the product: if it is missing, or a call fails, this module raises -- there is no
 CPU or eager-PyTorch fallback anywhere in the package.  ``torch`` is imported first on purpose:
@@ -7,6 +13,7 @@ that torch's stream handles and device pointers are valid inside it.
 """
 import ctypes
 import os
+import re
 import time
 from typing import Dict, Optional
 
@@ -15,12 +22,7 @@ import torch  # noqa: F401  (must precede the dlopen below)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PNMN_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libprobnmn_hip.so")
-
-CHANNELS = 128
-CONV_ACCUMULATE = 1
-CONV_ATOMIC = 2
-CONV_MASKBWD = 4
-CONV_DATTN = 16
+HEADER_PATH = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "probnmn_hip.h")
 
 
 class HipLibraryError(RuntimeError):
@@ -29,100 +31,96 @@ class HipLibraryError(RuntimeError):
 
 _lib: Optional[ctypes.CDLL] = None
 
-# name -> (restype, argtypes); kept in one table so tests can check every symbol the header
-# declares is exported.
-_P = ctypes.c_void_p
-_I = ctypes.c_int
-_D = ctypes.c_double
-_F = ctypes.c_float
-SIGNATURES: Dict[str, tuple] = {
-    "pnmn_abi_version": (),
-    "pnmn_conv_nhwc": (_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P),
-    "pnmn_conv_nhwc_cus": (_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P),
-    "pnmn_conv_wgrad_cus": (_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P),
-    "pnmn_conv_wgrad": (_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P),
-    "pnmn_transpose_weights": (_P, _I, _P),
-    "pnmn_dot1_sigmoid_fwd": (_P, _I, _I, _P),
-    "pnmn_dot1_sigmoid_bwd": (_P, _I, _I, _P),
-    "pnmn_same_fwd": (_P, _I, _I, _P),
-    "pnmn_same_bwd": (_P, _I, _I, _P),
-    "pnmn_minmax_fwd": (_P, _I, _I, _I, _P),
-    "pnmn_minmax_bwd": (_P, _I, _I, _I, _P),
-    "pnmn_mask_bwd": (_P, _I, _I, _P),
-    "pnmn_feat_grad_gather": (_P, _P, _I, _I, _I, _P),
-    "pnmn_accumulate": (_P, _I, _P),
-    "pnmn_nchw_to_nhwc": (_P, _P, _I, _I, _I, _P),
-    "pnmn_nchw_to_nhwc_rows": (_P, _P, _P, _I, _I, _I, _P),
-    "pnmn_nhwc_to_nchw": (_P, _P, _I, _I, _I, _P),
-    "pnmn_copy_rows_h2d": (_P, _P, _P, _I, ctypes.c_int64, ctypes.c_int64, _P),
-    "pnmn_gather_features": (_P, _P, _P, _I, ctypes.c_int64, _I, _I, _P),
-    "pnmn_maxpool2_flatten_fwd": (_P, _P, _I, _I, _I, _I, _P),
-    "pnmn_maxpool2_flatten_bwd": (_P, _P, _P, _I, _I, _I, _I, _P),
-    "pnmn_answer_loss": (_P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P),
-    "pnmn_seq_nll_fwd": (_P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64, _I, _P, _P, _I, _I, _I, _F, _P),
-    "pnmn_seq_nll_bwd": (_P, ctypes.c_int64, _P, ctypes.c_int64, _P, ctypes.c_int64, _I, _P, _P, _P, ctypes.c_int64,
-                         _I, _I, _I, _F, _P),
-    "pnmn_token_prep": (_P, ctypes.c_int64, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P),
-    "pnmn_trim_predictions": (_P, _I, _I, _I, _P, _P),
-    "pnmn_mask_last_fwd": (_P, _P, _P, _I, _I, _I, _P, _P, _P),
-    "pnmn_mask_last_bwd": (_P, _P, _P, _P, _I, _I, _I, _P, _P),
-    "pnmn_embedding_grad": (_P, _P, ctypes.c_int64, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P),
-    "pnmn_embedding_grad_workspace_bytes": (_I, _I, _I),
-    "pnmn_derive_params": (_P, _I, _I, _P),
-    "pnmn_elbo_rows": (_P, _P, _P, _P, _P, _F, _F, _I, _P, _P, _P),
-    "pnmn_joint_objective": (_P, _P, _P, _P, _P, _P, _P, _P, _F, _F, _F, _F, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P),
-    "pnmn_clamp_adam": (_P, _I, _D, _D, _D, _D, _D, _D, _P),
-    "pnmn_clamp_adam_blocks": (_P, _I, _D, _D, _D, _D, _D, _D, _I, _P),
-    "pnmn_lstm_cell_fwd": (_P, _P, _P, _P, _P, _I, _I, _P),
-    "pnmn_lstm_cell_bwd": (_P, _P, _P, _P, _P, _P, _P, _I, _I, _P),
-    "pnmn_lstm_seq_fwd": (_P, _P, ctypes.c_int64, _P, _P, _P, _P, _I, _I, _I, _P, _P),
-    "pnmn_lstm_seq_bwd": (_P, _P, _P, _P, _P, _I, _I, _I, _P, _P),
-    "pnmn_token_table_fwd": (_P, _P, ctypes.c_int64, _P, _I, _I, _I, _P, _P),
-    "pnmn_token_table_bwd": (_P, _P, _P, ctypes.c_int64, _I, _I, _I, _I, _P, _P, ctypes.c_int64, _P, _P, _P),
-    "pnmn_token_rows": (_P, _I, _P, _I, ctypes.c_int64, _P),
-    "pnmn_lstm_seq_workspace_bytes": (_I, _I),
-    "pnmn_cluster_reserve_cus": (_I,),
-    "pnmn_attn_lstm_beam": (_P,) * 13 + (_I,) * 10 + (_P,),
-    "pnmn_attn_lstm_beam_constrained": (_P,) * 13 + (_I,) * 10 + (_P,) * 3 + (_I,) * 2 + (_P,),
-    "pnmn_attn_lstm_fwd": (_P,) * 15 + (_I,) * 9 + (ctypes.c_uint64, ctypes.c_uint64, _P, ctypes.c_int64, _P),
-    "pnmn_attn_lstm_bwd": (_P,) * 14 + (_I,) * 4 + (_P,),
-    "pnmn_attn_lstm_group_workspace_bytes": (_P, _I, _I),
-    "pnmn_attn_lstm_fwd_group": (_P, _I, _I, _P, _P),
-    "pnmn_attn_lstm_bwd_group": (_P, _I, _I, _P, _P),
-    "pnmn_attn_denc": (_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P),
-    "pnmn_conv_nhwc_launches": (_I, _I, _I, _I, _I, _I),
-    "pnmn_conv_force_split": (_I,),
-    "pnmn_run_launches": (_P, _I, _P),
-    "pnmn_conv2d_nhwc": (_P, _P),
-    "pnmn_conv2d_weight_floats": (_I, _I, _I, _I),
-    "pnmn_maxpool3x3s2_nhwc": (_P, _P, _I, _I, _I, _I, _P),
-    "pnmn_launch_trace_begin": (),
-    "pnmn_launch_trace_end": (_P, _I, _P),
-    "pnmn_set_rows": (_P, _I, _P),
-    "pnmn_trunk_planner_create": (_P, _P),
-    "pnmn_trunk_planner_destroy": (_P,),
-    "pnmn_trunk_plan_and_launch": (_P, _P, _P),
-    "pnmn_trunk_last_forward": (_P, _P, _I),
-    "pnmn_trunk_last_records_bytes": (_P, _P, ctypes.c_int64),
-    "pnmn_plan_batch": (_P, _P, ctypes.c_int64, _P, _P, _I),
-    "pnmn_compile_programs": (_P, _I, _I, _P, _I, _I, _P, _P, _P, _P),
-    "pnmn_sample_tokens": (_P, _P, _P, _I, _I, _I, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_uint32, _I, _I, _I, _P),
-    "pnmn_lstm_stack_workspace_bytes": (_P, _I, _I),
-    "pnmn_lstm_stack_fwd": (_P, _I, _P, _P),
-    "pnmn_lstm_stack_bwd": (_P, _I, _P, _P),
-    "pnmn_lstm_dropout": (_P, _P, _I, _I, _I, _F, ctypes.c_uint64, ctypes.c_int64, _P),
-    "pnmn_lstm_stack_fwd_dropout": (_P, _P, _I, _P, _P),
-    "pnmn_lstm_stack_bwd_dropout": (_P, _P, _I, _P, _P),
-    "pnmn_gemm": (_P, _I, _P),
-    "pnmn_gemm_cus": (_P, _I, _I, _P),
-    "pnmn_gemm_workspace_bytes": (_I, _I, _I),
-    "pnmn_gemm_split_k": (_I, _I, _I, _I),
-    "pnmn_colsum": (_P, ctypes.c_int64, _I, _I, _P, _P, _I, _P, _P),
-    "pnmn_colsum_workspace_bytes": (_I, _I),
+# C scalar type -> (ctypes type as a parameter or return value, numpy type as a record field).  Closed on purpose: a type
+# that is not listed here fails the import, it is never guessed.  Anything declared with a `*` is a pointer.
+_C_SCALARS = {
+    "int": (ctypes.c_int, np.int32),
+    "int32_t": (ctypes.c_int32, np.int32),
+    "uint32_t": (ctypes.c_uint32, np.uint32),
+    "int64_t": (ctypes.c_int64, np.int64),
+    "uint64_t": (ctypes.c_uint64, np.uint64),
+    "float": (ctypes.c_float, np.float32),
+    "double": (ctypes.c_double, np.float64),
 }
 
 
-ABI_VERSION = 13  # pnmn_abi_version() of the library these signatures describe (include/probnmn_hip.h)
+def read_header(path: str = HEADER_PATH, text: Optional[str] = None):
+    """(signatures, restypes, records, constants) of the C header at ``path`` (or of ``text``), following the declaration
+    conventions stated at its top: prototype name -> argtypes tuple and -> return type, struct name -> aligned numpy
+    dtype (pointer fields as uint64), ``PNMN_*`` -> int.  A ``pnmn_`` declaration it cannot read raises, naming it."""
+    if text is None:
+        try:
+            with open(path) as f:
+                text = f.read()
+        except OSError as e:
+            raise HipLibraryError("cannot read %s (%s): the binding is derived from this header" % (path, e))
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+
+    def scalar(ctype: str, decl: str, which: int):
+        if ctype not in _C_SCALARS:
+            raise HipLibraryError("probnmn_hip.h: type `%s` in `%s` is not one the binding knows (%s)"
+                                  % (ctype, " ".join(decl.split()), ", ".join(_C_SCALARS)))
+        return _C_SCALARS[ctype][which]
+
+    constants: Dict[str, int] = {}
+    for line in re.findall(r"^[ \t]*#[ \t]*define[ \t]+PNMN_.*$", text, flags=re.M):
+        m = re.fullmatch(r"\s*#\s*define\s+(PNMN_\w+)\s+(?:(\d+)|\((-\d+)\))\s*", line)
+        if m is None:
+            raise HipLibraryError("probnmn_hip.h: `%s` is not an integer constant" % line.strip())
+        constants[m[1]] = int(m[2] or m[3])
+
+    records: Dict[str, np.dtype] = {}
+    for m in re.finditer(r"\btypedef\b(?:\s+struct\s*\w*\s*\{([^{}]*)\}\s*(pnmn_\w+)\s*;)?", text):
+        if m[2] is None:
+            raise HipLibraryError("probnmn_hip.h: cannot read the record at `%s`: a record is `typedef struct [tag] { ... } "
+                                  "pnmn_x;`" % " ".join(text[m.start():m.start() + 60].split()))
+        fields = []
+        for decl in filter(None, (d.strip() for d in m[1].split(";"))):
+            # `const float *a, *b` or `int32_t n, p[8]`: a type, then declarators; a `*` makes its declarator a pointer
+            words = re.sub(r"\bconst\b", " ", decl).replace("*", " * ").split(None, 1)
+            declarators = [re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[\s*(\w+)\s*\])?\s*", d) for d in words[-1].split(",")]
+            if len(words) != 2 or None in declarators:
+                raise HipLibraryError("probnmn_hip.h: cannot read the field `%s` of %s" % (decl, m[2]))
+            for star, name, length in (d.groups() for d in declarators):
+                kind = np.uint64 if star else scalar(words[0], "%s; /* %s */" % (decl, m[2]), 1)
+                if length is None:
+                    fields.append((name, kind))
+                elif length.isdigit() or length in constants:
+                    fields.append((name, kind, (int(length) if length.isdigit() else constants[length],)))
+                else:
+                    raise HipLibraryError("probnmn_hip.h: array length `%s` of `%s` in %s is neither a number nor a "
+                                          "#define above it" % (length, decl, m[2]))
+        records[m[2]] = np.dtype(fields, align=True)
+
+    signatures: Dict[str, tuple] = {}
+    restypes = {}
+    for m in re.finditer(r"^(int|int64_t)\s+(pnmn_\w+)\s*\(([^()]*)\)\s*;", text, flags=re.M):
+        params = [p.strip() for p in m[3].split(",")]
+        argtypes = []
+        for p in [] if params in (["void"], [""]) else params:
+            words = re.sub(r"\bconst\b", " ", p).split()
+            if "*" in p:
+                argtypes.append(ctypes.c_void_p)
+            elif len(words) == 2:
+                argtypes.append(scalar(words[0], "%s /* %s */" % (p, m[2]), 0))
+            else:
+                raise HipLibraryError("probnmn_hip.h: cannot read the parameter `%s` of %s" % (p, m[2]))
+        signatures[m[2]] = tuple(argtypes)
+        restypes[m[2]] = _C_SCALARS[m[1]][0]
+    for m in re.finditer(r"\b(pnmn_\w+)\s*\(", text):
+        if m[1] not in signatures:
+            raise HipLibraryError("probnmn_hip.h: cannot read the declaration of %s: a prototype is `int` or `int64_t` at "
+                                  "the start of a line, the name, the parameters, `);`" % m[1])
+    return signatures, restypes, records, constants
+
+
+# name -> argtypes / restype of every entry point, C struct name -> record dtype, PNMN_* -> value
+SIGNATURES, RESTYPES, RECORDS, CONSTANTS = read_header()
+globals().update({name[len("pnmn_"):].upper(): dtype for name, dtype in RECORDS.items()})  # pnmn_conv_item -> CONV_ITEM
+globals().update({name[len("PNMN_"):]: value for name, value in CONSTANTS.items()})        # PNMN_OP_CONV -> OP_CONV, ...
+GEMM_A_T, GEMM_B_T, GEMM_ACC = (CONSTANTS["PNMN_GEMM_" + n] for n in ("A_TRANSPOSED", "B_TRANSPOSED", "ACCUMULATE"))
+ABI_VERSION = CONSTANTS["PNMN_ABI_VERSION"]  # what pnmn_abi_version() of a library built from this header returns
+ITEM_SIZES = {name: (dtype, dtype.itemsize) for name, dtype in RECORDS.items()}
 
 
 def lib() -> ctypes.CDLL:
@@ -137,7 +135,7 @@ def lib() -> ctypes.CDLL:
         handle = ctypes.CDLL(LIB_PATH)
         for name, argtypes in SIGNATURES.items():
             fn = getattr(handle, name)  # AttributeError if the symbol is not exported
-            fn.restype = ctypes.c_int64 if name.endswith("_bytes") else ctypes.c_int
+            fn.restype = RESTYPES[name]
             fn.argtypes = list(argtypes)
         if handle.pnmn_abi_version() != ABI_VERSION:  # (same symbol names, other argument lists: never call into it)
             raise HipLibraryError("%s has ABI version %d, this package binds version %d -- rebuild the library"
@@ -200,84 +198,6 @@ if os.environ.get("PNMN_TRACE_LAUNCHES"):
     _start_trace(float(os.environ["PNMN_TRACE_LAUNCHES"]))
 
 
-# ---- item record layouts (must match include/probnmn_hip.h byte for byte) -------------------------
-_u64 = np.uint64
-_i32 = np.int32
-CONV_ITEM = np.dtype(
-    [("in", _u64), ("in2", _u64), ("mask", _u64), ("gate", _u64), ("weight", _u64), ("bias", _u64),
-     ("out", _u64), ("dilation", _i32), ("flags", _i32), ("mb_feats", _u64), ("mb_attn", _u64),
-     ("mb_dfeats", _u64), ("mb_dattn", _u64)]
-)
-WGRAD_ITEM = np.dtype(
-    [("x", _u64), ("x2", _u64), ("xmask", _u64), ("dy", _u64), ("gate", _u64), ("dilation", _i32),
-     ("reserved", _i32)]
-)
-WGRAD_JOB = np.dtype([("dw", _u64), ("dbias", _u64), ("item_begin", _i32), ("item_end", _i32)])
-WTRANS_ITEM = np.dtype(
-    [("src", _u64), ("dst", _u64), ("cout", _i32), ("cin", _i32), ("ntaps", _i32), ("reserved", _i32)]
-)
-DOT1_ITEM = np.dtype(
-    [("in", _u64), ("w", _u64), ("b", _u64), ("out", _u64), ("dout", _u64), ("din", _u64),
-     ("dw", _u64), ("db", _u64)]
-)
-SAME_ITEM = np.dtype(
-    [("feats", _u64), ("attn", _u64), ("w", _u64), ("b", _u64), ("out", _u64), ("dout", _u64),
-     ("dfeats", _u64), ("dattn", _u64), ("dw", _u64), ("db", _u64)]
-)
-MINMAX_ITEM = np.dtype(
-    [("a", _u64), ("b", _u64), ("out", _u64), ("dout", _u64), ("da", _u64), ("db", _u64),
-     ("a_channels", _i32), ("b_channels", _i32), ("is_max", _i32), ("reserved", _i32)]
-)
-MASKBWD_ITEM = np.dtype([("dx", _u64), ("feats", _u64), ("attn", _u64), ("dfeats", _u64), ("dattn", _u64)])
-AXPY_ITEM = np.dtype([("src", _u64), ("dst", _u64), ("n", np.int64)])
-DERIVE_JOB = np.dtype([("src", _u64), ("src2", _u64), ("dst", _u64), ("n", _i32), ("k", _i32), ("ld", _i32), ("kind", _i32)])
-PLAN_IN = np.dtype([(n, _u64) for n in ("tables", "nprims", "tids", "examples", "base", "tokens", "w3", "b3", "wt3",
-                                         "dotw", "dotb", "params", "grads", "wt", "act", "gact", "feat", "gfeat",
-                                         "final_", "gfinal", "ones")]
-                   + [(n, _i32) for n in ("n_templates", "pmax", "nv", "cmax", "hw", "channels", "wgrad_chunk",
-                                          "wgrad_groups", "fuse_mask_bwd", "sole_writer", "sort_by_weight", "reserved")])
-TRUNK_CONFIG = np.dtype([(n, _u64) for n in ("kinds", "w3", "b3", "wt3", "dotw", "dotb")]
-                        + [(n, _i32) for n in ("n_kinds", "channels", "H", "W", "wgrad_chunk", "wgrad_groups", "fuse_mask_bwd",
-                                               "sole_writer", "sort_by_weight", "reserved")])
-TRUNK_IO = np.dtype([(n, _u64) for n in ("programs", "params", "grads", "wt", "act", "gact", "feat", "gfeat", "final_", "gfinal",
-                                          "ones")]
-                    + [("act_capacity", np.int64)]
-                    + [(n, _u64) for n in ("fwd_tail", "bwd_head", "bwd_tail", "bwd", "valid")]
-                    + [("arena_floats", np.int64)]
-                    + [(n, _i32) for n in ("n_programs", "length", "n_fwd_tail", "n_bwd_head", "n_bwd_tail", "bwd_capacity",
-                                           "need_backward", "launch", "n_bwd", "bwd_piece_cut", "n_prims", "n_fwd", "depth",
-                                           "n_invalid", "n_feat_result", "conv_cus", "wgrad_cus", "n_conv", "n_proj", "reserved")]
-                    + [("touched_tokens", _u64, (4,))])
-DECODER_FWD_JOB = np.dtype([(n, _u64) for n in ("xe", "etable", "enc", "mask", "h0", "w_c", "w_hh", "w_p", "b_p", "hs", "cs", "act",
-                                                  "ctx", "probs", "tokens", "in_tokens")]
-                           + [("in_token_stride", np.int64), ("seed", _u64), ("row_offset", _u64)]
-                           + [(n, _i32) for n in ("B", "T", "S", "V", "sample", "pad_index", "unk_index", "start_index")])
-DECODER_BWD_JOB = np.dtype([(n, _u64) for n in ("dhs", "act", "cs", "hs", "probs", "enc", "mask", "h0", "w_c_t", "w_hh_t", "dgates",
-                                                  "dctx", "dscore", "weights", "dh0")]
-                           + [(n, _i32) for n in ("B", "T", "S", "reserved")])
-GEMM_DESC = np.dtype([(n, _u64) for n in ("a", "b", "c", "bias")] + [(n, np.int64) for n in ("lda", "ldb", "ldc")]
-                     + [(n, _i32) for n in ("M", "N", "K", "flags", "split_k", "shift_t")]
-                     + [("shift_h0", _u64), ("ld_h0", np.int64), ("workspace", _u64), ("colsum", _u64), ("colsum2", _u64)])  # pnmn_gemm_desc
-GEMM_MAX, GEMM_A_T, GEMM_B_T, GEMM_ACC = 8, 1, 2, 4
-LSTM_STACK_JOB = np.dtype([("xp", _u64), ("tokens", _u64), ("token_stride", np.int64)] + [(n, _u64) for n in ("w_hh", "w_ih", "bias", "hs", "cs", "act", "dhs", "dgates")]
-                          + [(n, _i32) for n in ("B", "T", "dep", "reserved")])  # pnmn_lstm_stack_job
-LSTM_STACK_JOBS = 6
-LSTM_DROPOUT_DESC = np.dtype([("hsd", _u64), ("seed", _u64), ("row_offset", np.int64), ("p", np.float32), ("reserved", _i32)])  # pnmn_lstm_dropout_desc
-TOKEN_SEG = np.dtype([("src", _u64), ("index", _u64), ("row_stride", np.int64), ("rows", _i32), ("width", _i32)])  # pnmn_token_seg
-EINVAL, ESHAPE, EAGAIN = -1, -2, -3  # PNMN_EINVAL / PNMN_ESHAPE / PNMN_EAGAIN
-ADAM_ITEM = np.dtype([("param", _u64), ("grad", _u64), ("exp_avg", _u64), ("exp_avg_sq", _u64), ("n", np.int64),
-                      ("bc1", np.float32), ("bc2_sqrt", np.float32)])
-
-LAUNCH = np.dtype([("a", _u64), ("b", _u64), ("c", _u64), ("op", _i32), ("n", _i32), ("p", _i32, (8,))])
-CONV2D_DESC = np.dtype([("x", _u64), ("w", _u64), ("scale", _u64), ("shift", _u64), ("residual", _u64), ("y", _u64),
-                        ("N", _i32), ("H", _i32), ("W", _i32), ("Cin", _i32), ("Ho", _i32), ("Wo", _i32), ("Cout", _i32),
-                        ("kh", _i32), ("kw", _i32), ("stride", _i32), ("pad", _i32), ("relu", _i32)])  # pnmn_conv2d_desc
-LAUNCH_TIMING = np.dtype([("op", _i32), ("n", _i32), ("p", _i32, (8,)), ("n_items", _i32), ("ms", np.float32),
-                          ("flops", np.float64), ("bytes", np.float64)])  # pnmn_launch_timing
-(OP_CONV, OP_WGRAD, OP_TRANSPOSE_WEIGHTS, OP_DOT_FWD, OP_DOT_BWD, OP_SAME_FWD, OP_SAME_BWD, OP_MINMAX_FWD, OP_MINMAX_BWD,
- OP_MASK_BWD, OP_MAXPOOL_FWD, OP_MAXPOOL_BWD, OP_NCHW_TO_NHWC, OP_SET_ROWS, OP_ACCUMULATE, OP_ZERO, OP_FEAT_GATHER) = range(17)
-
-
 class LaunchList:
     """A sequence of grouped launches for ``pnmn_run_launches`` (one binding call instead of one per launch).
     Rows are kept as tuples of eight 64-bit words -- the byte image of ``pnmn_launch`` (a, b, c, op | n << 32,
@@ -299,33 +219,6 @@ class LaunchList:
             rec = np.array(self._rows, dtype=np.uint64)
             check(lib().pnmn_run_launches(rec.ctypes.data, len(self._rows), stream), what)
             self._rows = []
-
-
-ITEM_SIZES = {
-    "pnmn_launch": (LAUNCH, 64),
-    "pnmn_launch_timing": (LAUNCH_TIMING, 64),
-    "pnmn_conv2d_desc": (CONV2D_DESC, 96),
-    "pnmn_conv_item": (CONV_ITEM, 96),
-    "pnmn_wgrad_item": (WGRAD_ITEM, 48),
-    "pnmn_wgrad_job": (WGRAD_JOB, 24),
-    "pnmn_wtrans_item": (WTRANS_ITEM, 32),
-    "pnmn_dot1_item": (DOT1_ITEM, 64),
-    "pnmn_same_item": (SAME_ITEM, 80),
-    "pnmn_minmax_item": (MINMAX_ITEM, 64),
-    "pnmn_maskbwd_item": (MASKBWD_ITEM, 40),
-    "pnmn_axpy_item": (AXPY_ITEM, 24),
-    "pnmn_adam_item": (ADAM_ITEM, 48),
-    "pnmn_derive_job": (DERIVE_JOB, 40),
-    "pnmn_plan_in": (PLAN_IN, 216),
-    "pnmn_decoder_fwd_job": (DECODER_FWD_JOB, 184),
-    "pnmn_decoder_bwd_job": (DECODER_BWD_JOB, 136),
-    "pnmn_trunk_config": (TRUNK_CONFIG, 88),
-    "pnmn_trunk_io": (TRUNK_IO, 256),
-    "pnmn_gemm_desc": (GEMM_DESC, 120),
-    "pnmn_token_seg": (TOKEN_SEG, 32),
-    "pnmn_lstm_stack_job": (LSTM_STACK_JOB, 104),
-    "pnmn_lstm_dropout_desc": (LSTM_DROPOUT_DESC, 32),
-}
 
 
 def decoder_workspace_bytes(rows, backward: bool) -> int:

@@ -17,6 +17,8 @@ reference walks the token sequence right-to-left) over *values*:
 from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple
 
+from probnmn import _hip
+
 # token kinds
 SKIP, SCENE, AND, OR, CMP, ATT, QUERY, REL, SAME = range(9)
 KIND_NAMES = ["skip", "scene", "and", "or", "comparison", "attention", "query", "relate", "same"]
@@ -256,8 +258,8 @@ def register_step(kind: int, out_c: int, saved_c: Optional[int], D: int):
     return (D if kind == QUERY else 1), saved_c
 
 
-MAX_AUTOMATON_STATES = 32   # PNMN_BEAM_MAX_STATES / PNMN_BEAM_MAX_CLASSES of include/probnmn_hip.h
-MAX_AUTOMATON_CLASSES = 16
+MAX_AUTOMATON_STATES = _hip.BEAM_MAX_STATES   # PNMN_BEAM_MAX_STATES / PNMN_BEAM_MAX_CLASSES of include/probnmn_hip.h
+MAX_AUTOMATON_CLASSES = _hip.BEAM_MAX_CLASSES
 NO_COMPLETION = 255
 
 
