@@ -24,7 +24,9 @@ therefore builds, once per shape signature,
 Per iteration the host then replays ~100 prepared calls (a few microseconds each) and touches no torch op in the passes.
 Arithmetic is the eager path's kernel for kernel (same recurrent kernels, same losses); the GEMMs are this library's
 instead of hipBLASLt's, so results agree with ``Seq2SeqBase.forward`` to fp32 round-off (tests/test_seq_plan_gpu.py)."""
-from typing import Dict, List, Optional
+import os
+from dataclasses import dataclass
+from typing import Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -34,33 +36,18 @@ from probnmn import _hip
 
 #: workgroup slots of the chip for a launch of split-K products (256 CUs, the 64 KB workgroups of pnmn_gemm sit two to a CU)
 #: and the shortest chunk (k tiles) a product is cut into
-SPLIT_SLOTS = int(__import__("os").environ.get("PNMN_PLAN_SPLIT_SLOTS", "512"))
-SPLIT_MIN_KTILES = int(__import__("os").environ.get("PNMN_PLAN_SPLIT_MIN", "8"))
+SPLIT_SLOTS = int(os.environ.get("PNMN_PLAN_SPLIT_SLOTS", "512"))
+SPLIT_MIN_KTILES = int(os.environ.get("PNMN_PLAN_SPLIT_MIN", "8"))
 #: an encoder's two LSTM layers as a wavefront, independent encoder passes in one launch (pnmn_lstm_stack_*); False: a launch
 #: per layer with the input projection as a GEMM in between (A/B aid, and what batches too large for the chip fall back to)
 USE_STACK = True
-#: encoder passes per wavefront launch, forward / backward (0: a launch per layer), and decoder passes per backward launch --
-#: A/B aids (env PNMN_PLAN_FWD_ENC / PNMN_PLAN_BWD_ENC / PNMN_PLAN_DEC_GROUP); the defaults are what measured best beside
-#: the NMN trunk at 128 questions (DESIGN 5 "Round 6")
-import os as _os
-STACK_FWD_ENCODERS = int(_os.environ.get("PNMN_PLAN_FWD_ENC", "2"))
-STACK_PG_ENCODER = int(_os.environ.get("PNMN_PLAN_PG_ENC", "1"))
-STACK_BWD_ENCODERS = int(_os.environ.get("PNMN_PLAN_BWD_ENC", "0"))
-DECODER_BWD_GROUP = int(_os.environ.get("PNMN_PLAN_DEC_GROUP", "3"))
-#: workgroups a GEMM launch of the plan may occupy (0: one per tile)
-GEMM_WORKGROUPS = int(_os.environ.get("PNMN_PLAN_GEMM_WGS", "0"))
-#: parameter gradients of the passes on an auxiliary stream beside the backward chains (0: on the one stream, at the end)
-USE_AUX_STREAM = _os.environ.get("PNMN_PLAN_AUX", "0") != "0"
-_AUX_STREAMS: Dict = {}
-
-
-def _aux_stream(dev: torch.device) -> "torch.cuda.Stream":
-    """ONE auxiliary stream per device for every plan of the process (HIP multiplexes a process's streams onto four hardware
-    queues: every further stream shifts which of them share one -- see trainers.joint_training.shared_stream)."""
-    key = dev.index if dev.index is not None else torch.cuda.current_device()
-    if key not in _AUX_STREAMS:
-        _AUX_STREAMS[key] = torch.cuda.Stream(device=dev)
-    return _AUX_STREAMS[key]
+#: encoder passes per wavefront launch, forward / generator alone / backward (0: a launch per layer) -- A/B aids; the
+#: defaults are what measured best beside the NMN trunk at 128 questions (DESIGN 5 "Round 6")
+STACK_FWD_ENCODERS = int(os.environ.get("PNMN_PLAN_FWD_ENC", "2"))
+STACK_PG_ENCODER = int(os.environ.get("PNMN_PLAN_PG_ENC", "1"))
+STACK_BWD_ENCODERS = int(os.environ.get("PNMN_PLAN_BWD_ENC", "0"))
+#: the per-model decoder buffers, [flat sequence rows of all the model's passes][width]
+DECODER_BUFFERS = (("hs", 256), ("cs", 256), ("cx", 256), ("act", 1024), ("dhs", 256), ("dg", 1024), ("dctx", 256))
 
 
 class PlanUnsupported(Exception):
@@ -116,6 +103,7 @@ class _Model:
         self.grads = [self.gflat[o:o + p.numel()].view(p.shape) for o, p in zip(offs, self.params)]
         self.g = {id(p): g for p, g in zip(self.params, self.grads)}
         self.signature = tuple(p.data_ptr() for p in self.params)
+        self.derived = model._derived()  # (the same dict as long as the plan is valid: ``Seq2SeqPlan.still_valid``)
 
     def grad(self, p) -> torch.Tensor:
         return self.g[id(p)]
@@ -125,38 +113,117 @@ class _Model:
             p.grad = g
 
 
+class _TokenTable(NamedTuple):
+    """A per-token projection table, table[v] = bias + emb[v] @ w_ih[:, col0:col0 + 256].T (a first encoder layer's input
+    projection, or the embedding half of a decoder cell's): its forward launch and its gradient's come from here."""
+    tag: str
+    emb: torch.Tensor
+    w_ih: torch.Tensor
+    col0: int
+    b_ih: torch.Tensor
+    b_hh: torch.Tensor
+    bias: torch.Tensor  # their sum (a derived parameter)
+    pad_idx: int        # the embedding row that receives no gradient (-1: none)
+    table: torch.Tensor
+
+
+class _Loss(NamedTuple):
+    """A sequence loss over [rows][T] steps of a logits view.  ``pnmn_seq_nll_fwd`` and ``pnmn_seq_nll_bwd`` are both
+    generated from this record, so they cannot disagree."""
+    logits: torch.Tensor  # from the pass's first row on
+    ld: int               # logits elements from one sequence to the next
+    target: int           # pointer to the first target token / elements from row to row
+    target_stride: int
+    mask: int             # same for the tokens whose padding masks the steps
+    mask_stride: int
+    pad: int
+    loss: torch.Tensor
+    lse: torch.Tensor
+    rows: int
+    T: int
+    V: int
+    eps: float
+
+    def _head(self):
+        return (self.logits.data_ptr(), self.ld, self.target, self.target_stride, self.mask, self.mask_stride, self.pad)
+
+    def forward(self, calls: _Calls, stream: int) -> None:
+        calls.add("pnmn_seq_nll_fwd", *self._head(), self.loss.data_ptr(), self.lse.data_ptr(), self.rows, self.T, self.V,
+                  self.eps, stream)
+
+    def backward(self, calls: _Calls, dloss: torch.Tensor, dlogits: torch.Tensor, stream: int) -> None:
+        calls.add("pnmn_seq_nll_bwd", *self._head(), self.lse.data_ptr(), dloss.data_ptr(), dlogits.data_ptr(), self.ld,
+                  self.rows, self.T, self.V, self.eps, stream)
+
+
+@dataclass
+class _DecoderPass:
+    """One pass of a model's decoder: ``rows`` sequences of ``T`` steps attending to ``S`` source positions."""
+    tag: str
+    rows: int
+    T: int
+    S: int
+    row0: int             # first flat row in the model's decoder buffers
+    enc_row0: int         # first row in the model's encoder batch
+    tokens: torch.Tensor  # step tokens: a teacher-forced [@start@, ..., @end@] matrix, or the tokens the pass samples
+    shift: int            # step t reads tokens[t - shift] (1: its own sample of the step before, @start@ at t = 0)
+    trimmed: Optional[torch.Tensor]  # the sampling pass only: its samples cut at @end@ (what masks its loss)
+    v: Dict[str, torch.Tensor]       # [rows][T][.] views of DECODER_BUFFERS, and the pass's own probs / dscore / weights
+    loss: _Loss
+
+
+@dataclass
+class _DecoderSet:
+    """A model's decoder: its passes share the parameters, the token table and flat buffers over all their rows."""
+    tag: str
+    mm: _Model
+    enc: Dict
+    table: _TokenTable
+    flat: Dict[str, torch.Tensor]
+    logits: torch.Tensor
+    dlogits: torch.Tensor
+    passes: List[_DecoderPass]
+
+
+class _EncoderPass(NamedTuple):
+    """What ``_encoder_prepare`` builds an encoder pass from."""
+    tag: str
+    mm: Optional[_Model]         # None: the prior (no gradients)
+    embedding: torch.nn.Embedding
+    tokens: torch.Tensor
+    width: int
+    rows: int
+    drop_first: bool = True      # drop the first of [@start@, tokens, @end@]
+    want_last: bool = True       # masked outputs and last states (what a decoder attends to / starts from)
+    p: float = 0.0               # dropout between the layers
+
+
 class Seq2SeqPlan:
     """See the module docstring.  ``n`` unsupervised (sampled) rows, ``m`` supervised rows, both > 0; ``tq`` / ``tp``: the
     widths of the batch's question / program matrices."""
 
-    def __init__(self, pg, qr, prior, dev: torch.device, n: int, m: int, tq: int, tp: int, with_prior: bool = True):
+    def __init__(self, pg, qr, prior, dev: torch.device, n: int, m: int, tq: int, tp: int):
         if not (_supported(pg) and _supported(qr)) or n <= 0 or m <= 0:
             raise PlanUnsupported("model shapes")
-        if with_prior:
-            pl = prior._encoder._module
-            if pl.hidden_size != 256 or pl.num_layers != 2 or pl.input_size != 256:
-                raise PlanUnsupported("prior shapes")
-            if pl.training and _dropout_p(pl) > 0:  # (the trainers keep the prior in eval mode: its pass drops nothing)
-                raise PlanUnsupported("prior in training mode with dropout")
-        lib = _hip.lib()
+        pl = prior._encoder._module
+        if pl.hidden_size != 256 or pl.num_layers != 2 or pl.input_size != 256:
+            raise PlanUnsupported("prior shapes")
+        if pl.training and _dropout_p(pl) > 0:  # (the trainers keep the prior in eval mode: its pass drops nothing)
+            raise PlanUnsupported("prior in training mode with dropout")
         self.dev, self.n, self.m, self.tq, self.tp = dev, n, m, tq, tp
         self.stream = _hip.stream_ptr(dev)
         self.pg, self.qr, self.prior = _Model(pg, dev), _Model(qr, dev), prior
         # the masks between the encoders' layers (the plan serves training-mode passes only)
         self.drop_p = (_dropout_p(pg._encoder._module), _dropout_p(qr._encoder._module))
-        self.with_prior = with_prior
-        B = n + m
-        self.B = B
-        D = pg._max_decoding_steps
-        self.D = D
-        if _hip.decoder_workspace_bytes([n, m], False) <= 0 or _hip.decoder_workspace_bytes([B], False) <= 0 \
-                or int(lib.pnmn_lstm_seq_workspace_bytes(B, 0)) <= 0:
+        self.B, self.D = n + m, pg._max_decoding_steps
+        if _hip.decoder_workspace_bytes([n, m], False) <= 0 or _hip.decoder_workspace_bytes([self.B], False) <= 0 \
+                or int(_hip.lib().pnmn_lstm_seq_workspace_bytes(self.B, 0)) <= 0:
             raise PlanUnsupported("batch does not fit the multi-CU recurrent kernels in one launch")
         self._bufs: Dict[str, torch.Tensor] = {}
         self._keep: List = []  # numpy records the call tuples point into
         self.anchor = torch.zeros((), device=dev, requires_grad=True)
-        self.fwd_pg_enc, self.fwd_pg, self.fwd_qr, self.fwd_prior, self.bwd = _Calls(), _Calls(), _Calls(), _Calls(), _Calls()
-        self._derived_sig = None
+        self.fwd_pg_enc, self.fwd_pg, self.fwd_pg_finish, self.fwd_qr, self.fwd_prior = (_Calls() for _ in range(5))
+        self.bwd_a, self.bwd_b = _Calls(), _Calls()  # the decoders' backward / the encoders' and every parameter gradient
         self._build()
 
     # ---- workspace ---------------------------------------------------------------------------------------------------------
@@ -218,32 +285,47 @@ class Seq2SeqPlan:
                 r["shift_t"], r["shift_h0"], r["ld_h0"] = d.get("shift_t", 0), d.get("h0", 0), d.get("ld_h0", 0)
                 r["colsum"], r["colsum2"] = d.get("colsum", 0), d.get("colsum2", 0)
             self._keep.append(rec)
-            calls.add("pnmn_gemm_cus", rec.ctypes.data, len(rec), GEMM_WORKGROUPS, self.stream)
+            calls.add("pnmn_gemm_cus", rec.ctypes.data, len(rec), 0, self.stream)
 
-    def _encoder_prepare(self, calls: _Calls, tag: str, mm: Optional[_Model], derived, tokens: torch.Tensor, width: int, rows: int,
-                         drop_first: bool, emb: torch.Tensor, pad_idx, lstm, want_last: bool = True, p: float = 0.0) -> Dict:
+    def _table_forward(self, calls: _Calls, t: _TokenTable) -> None:
+        calls.add("pnmn_token_table_fwd", t.emb.data_ptr(), t.w_ih.data_ptr() + 4 * t.col0, t.w_ih.stride(0), t.bias.data_ptr(),
+                  t.emb.size(0), 256, 1024, t.table.data_ptr(), self.stream)
+
+    def _table_backward(self, calls: _Calls, t: _TokenTable, mm: _Model, start: int, uses) -> None:
+        """The gradients a token table passes on.  uses: (workspace name, dgates [rows][T][1024], tokens, shift) per pass that
+        read it -- step t of a row read table[tokens[t - shift]], table[start] before its first token."""
+        V, g = t.emb.size(0), mm.grad
+        dtable = self.buf(t.tag + ".dtable", V, 1024)
+        for k, (ws_name, dg, tokens, shift) in enumerate(uses):
+            rows, T = dg.shape[:2]
+            ews = self.bytes_buf(ws_name, _hip.lib().pnmn_embedding_grad_workspace_bytes(rows, T, V))
+            calls.add("pnmn_embedding_grad", dg.data_ptr(), tokens.data_ptr(), tokens.stride(0), rows, T, 1024, V, shift, start, -1,
+                      1 if k else 0, dtable.data_ptr(), ews.data_ptr(), self.stream)
+        ld = t.w_ih.stride(0)  # (the gradient's: 0 where its rows are just the table's 256 columns)
+        calls.add("pnmn_token_table_bwd", dtable.data_ptr(), t.emb.data_ptr(), t.w_ih.data_ptr() + 4 * t.col0, ld, V, 256, 1024, t.pad_idx,
+                  g(t.emb).data_ptr(), g(t.w_ih).data_ptr() + 4 * t.col0, ld if ld != 256 else 0, g(t.b_ih).data_ptr(),
+                  g(t.b_hh).data_ptr(), self.stream)
+
+    def _encoder_prepare(self, calls: _Calls, ep: _EncoderPass) -> Dict:
         """Buffers of one encoder pass + what precedes its recurrence: token_prep and the per-token table of layer 1.  ``p`` > 0:
         dropout between the layers -- "hsd" holds layer 1's output after the mask (layer 2's input), and every call that
         applies the mask finds this iteration's seed in "seed" / the records listed in "drop_recs" (``_set_dropout``)."""
-        st = self.stream
-        model = mm.model if mm is not None else self.prior
-        pad, bos, eos = model._pad_index, model._start_index, model._end_index
-        T = width + 2 - int(drop_first)
-        V = emb.size(0)
-        f = self.buf
-        e = dict(tag=tag, mm=mm, derived=derived, lstm=lstm, T=T, rows=rows, V=V, pad_idx=-1 if pad_idx is None else pad_idx, emb=emb,
-                 want_last=want_last,
+        model, derived = (ep.mm.model, ep.mm.derived) if ep.mm is not None else (self.prior, self.prior._derived())
+        tag, rows, lstm, emb, f = ep.tag, ep.rows, model._encoder._module, ep.embedding.weight, self.buf
+        T, V = ep.width + 2 - int(ep.drop_first), emb.size(0)
+        e = dict(tag=tag, mm=ep.mm, derived=derived, lstm=lstm, T=T, rows=rows, want_last=ep.want_last,
                  src=f(tag + ".src", rows, T, dtype=torch.long), fmask=f(tag + ".fmask", rows, T), last=f(tag + ".last", rows, dtype=torch.int32),
                  table=f(tag + ".table", V, 1024), hs1=f(tag + ".hs1", rows, T, 256), cs1=f(tag + ".cs1", rows, T, 256),
                  act1=f(tag + ".act1", rows, T, 1024), hs2=f(tag + ".hs2", rows, T, 256), cs2=f(tag + ".cs2", rows, T, 256),
-                 act2=f(tag + ".act2", rows, T, 1024), p=p, seed=0, row_offset=0, drop_recs=[])
-        if p > 0:
+                 act2=f(tag + ".act2", rows, T, 1024), p=ep.p, seed=0, row_offset=0, drop_recs=[])
+        e["tab"] = _TokenTable(tag, emb, lstm.weight_ih_l0, 0, lstm.bias_ih_l0, lstm.bias_hh_l0, derived["l0.b"],
+                               -1 if ep.embedding.padding_idx is None else ep.embedding.padding_idx, e["table"])
+        if ep.p > 0:
             e["hsd"] = f(tag + ".hsd", rows, T, 256)
-        calls.add("pnmn_token_prep", tokens.data_ptr(), tokens.stride(0), rows, width, pad, bos, eos, int(drop_first), e["src"].data_ptr(),
-                  e["fmask"].data_ptr(), e["last"].data_ptr(), st)
-        calls.add("pnmn_token_table_fwd", emb.data_ptr(), lstm.weight_ih_l0.data_ptr(), lstm.weight_ih_l0.stride(0),
-                  derived["l0.b"].data_ptr(), V, 256, 1024, e["table"].data_ptr(), st)
-        if want_last:
+        calls.add("pnmn_token_prep", ep.tokens.data_ptr(), ep.tokens.stride(0), rows, ep.width, model._pad_index, model._start_index,
+                  model._end_index, int(ep.drop_first), e["src"].data_ptr(), e["fmask"].data_ptr(), e["last"].data_ptr(), self.stream)
+        self._table_forward(calls, e["tab"])
+        if ep.want_last:
             e["enc"], e["h"] = f(tag + ".enc", rows, T, 256), f(tag + ".h", rows, 256)
         return e
 
@@ -251,14 +333,13 @@ class Seq2SeqPlan:
         jobs = np.zeros(2 * len(encs), _hip.LSTM_STACK_JOB)
         for k, e in enumerate(encs):
             d = e["derived"]
+            a, b = jobs[2 * k], jobs[2 * k + 1]
             if not backward:
-                a, b = jobs[2 * k], jobs[2 * k + 1]
                 a["xp"], a["tokens"], a["token_stride"], a["w_hh"] = e["table"].data_ptr(), e["src"].data_ptr(), e["src"].stride(0), d["l0.hh"].data_ptr()
                 a["hs"], a["cs"], a["act"], a["dep"] = e["hs1"].data_ptr(), e["cs1"].data_ptr(), e["act1"].data_ptr(), -1
                 b["w_hh"], b["w_ih"], b["bias"] = d["l1.hh"].data_ptr(), d["l1.ih"].data_ptr(), d["l1.b"].data_ptr()
                 b["hs"], b["cs"], b["act"], b["dep"] = e["hs2"].data_ptr(), e["cs2"].data_ptr(), e["act2"].data_ptr(), 2 * k
             else:  # layer 2 first (top), layer 1 below it
-                a, b = jobs[2 * k], jobs[2 * k + 1]
                 a["dhs"], a["act"], a["cs"], a["w_hh"], a["dgates"], a["dep"] = (e["dhs2"].data_ptr(), e["act2"].data_ptr(), e["cs2"].data_ptr(),
                                                                                  d["l1.hhT"].data_ptr(), e["dg2"].data_ptr(), -1)
                 b["act"], b["cs"], b["w_hh"], b["w_ih"], b["dgates"], b["dep"] = (e["act1"].data_ptr(), e["cs1"].data_ptr(), d["l0.hhT"].data_ptr(),
@@ -375,18 +456,10 @@ class Seq2SeqPlan:
     def _encoders_param_grads(self, calls: _Calls, deferred: List, encs: List[Dict]) -> None:
         """The encoders' parameter gradients from what the chain left behind (dgates of both layers): the table's rows and the
         bias sums as launches, everything GEMM-shaped appended to ``deferred``."""
-        lib, st = _hip.lib(), self.stream
-        f = self.buf
         for e in encs:
-            mm, lstm, tag, rows, T, V = e["mm"], e["lstm"], e["tag"], e["rows"], e["T"], e["V"]
-            dtable = f(tag + ".dtable", V, 1024)
-            ews = self.bytes_buf(tag + ".emb_ws", lib.pnmn_embedding_grad_workspace_bytes(rows, T, V))
+            mm, lstm, rows, T = e["mm"], e["lstm"], e["rows"], e["T"]
             dg1, dg2, g = e["dg1"], e["dg2"], mm.grad
-            calls.add("pnmn_embedding_grad", dg1.data_ptr(), e["src"].data_ptr(), e["src"].stride(0), rows, T, 1024, V, 0, 0, -1, 0,
-                      dtable.data_ptr(), ews.data_ptr(), st)
-            calls.add("pnmn_token_table_bwd", dtable.data_ptr(), e["emb"].data_ptr(), lstm.weight_ih_l0.data_ptr(), lstm.weight_ih_l0.stride(0),
-                      V, 256, 1024, e["pad_idx"], g(e["emb"]).data_ptr(), g(lstm.weight_ih_l0).data_ptr(), 0, g(lstm.bias_ih_l0).data_ptr(),
-                      g(lstm.bias_hh_l0).data_ptr(), st)
+            self._table_backward(calls, e["tab"], mm, 0, [(e["tag"] + ".emb_ws", dg1, e["src"], 0)])
             K = rows * T
             # (layer 2's bias gradients = the column sums of dgates2: the weight-gradient product that reads dgates2 as its
             # transposed operand adds them up on the way -- pnmn_gemm_desc.colsum)
@@ -399,262 +472,201 @@ class Seq2SeqPlan:
                      ldc=256, ta=1, split="auto", shift_t=T),
             ]
 
-    def _decoder_side(self, tag: str, rows: int, T: int, S: int, base: Dict[str, torch.Tensor], row0: int) -> Dict[str, torch.Tensor]:
-        """Views of a model's concatenated decoder buffers for one pass: rows*T sequence rows starting at flat row ``row0``."""
-        v = {}
-        R = rows * T
-        for k, w in (("hs", 256), ("cs", 256), ("cx", 256), ("act", 1024), ("dhs", 256), ("dg", 1024), ("dctx", 256)):
-            v[k] = base[k][row0:row0 + R].view(rows, T, w)
-        for k in ("probs", "dscore", "weights"):
-            v[k] = self.buf("%s.%s" % (tag, k), rows, T, S)
-        v.update(rows=rows, T=T, S=S, row0=row0, R=R)
-        return v
+    def _decoder_set(self, tag: str, mm: _Model, enc: Dict, passes) -> _DecoderSet:
+        """A model's decoder buffers and its passes.  passes: (tag, loss-name suffix, rows, T, tokens, trimmed) in the
+        order of their rows in the encoder's batch, which is their order in the flat buffers."""
+        f, S, V = self.buf, enc["T"], mm.proj.weight.size(0)
+        R = sum(rows * T for _, _, rows, T, _, _ in passes)
+        # (the table's weight: columns [256, 512) of W_ih, the embedding half of cat(attended, embedded))
+        table = _TokenTable(tag + ".d", mm.emb_tgt, mm.cell.weight_ih, 256, mm.cell.bias_ih, mm.cell.bias_hh, mm.derived["d.b"], -1,
+                            f(tag + ".d.table", V, 1024))
+        dec = _DecoderSet(tag, mm, enc, table, {k: f("%s.d.%s" % (tag, k), R, w) for k, w in DECODER_BUFFERS},
+                          f(tag + ".logits", R, V), f(tag + ".dlogits", R, V), [])
+        row0 = enc_row0 = 0
+        for ptag, suffix, rows, T, tokens, trimmed in passes:
+            v = {k: dec.flat[k][row0:row0 + rows * T].view(rows, T, w) for k, w in DECODER_BUFFERS}
+            for k in ("probs", "dscore", "weights"):
+                v[k] = f("%s.%s" % (ptag, k), rows, T, S)
+            # a sampling pass is scored on its own tokens, masked by their trimmed copy, a teacher-forced pass on its
+            # matrix from the token after @start@ on
+            target = tokens.data_ptr() + (0 if trimmed is not None else 8)
+            loss = _Loss(dec.logits[row0:], T * V, target, tokens.stride(0), target if trimmed is None else trimmed.data_ptr(),
+                         tokens.stride(0), mm.model._pad_index, f("%s.loss%s" % (tag, suffix), rows), f("%s.lse%s" % (tag, suffix), rows, T),
+                         rows, T, V, 1e-13 if trimmed is None else 1e-12)
+            dec.passes.append(_DecoderPass(ptag, rows, T, S, row0, enc_row0, tokens, int(trimmed is not None), trimmed, v, loss))
+            row0, enc_row0 = row0 + rows * T, enc_row0 + rows
+        return dec
 
-    @staticmethod
-    def _decoder_fwd_job(j, sd: Dict[str, torch.Tensor], table: torch.Tensor, e: Dict[str, torch.Tensor], r0: int, derived, start: int) -> None:
-        """What every pass's ``DECODER_FWD_JOB`` holds: the table, the encoder's rows from ``r0`` on, the weight packs, the pass's
-        saved tensors (``_decoder_side``) and its shape; the caller adds the step tokens or the sampler's fields."""
-        j["etable"], j["enc"], j["mask"], j["h0"] = table.data_ptr(), e["enc"][r0:].data_ptr(), e["fmask"][r0:].data_ptr(), e["h"][r0:].data_ptr()
-        j["w_c"], j["w_hh"] = derived["d.c"].data_ptr(), derived["d.hh"].data_ptr()
-        j["hs"], j["cs"], j["act"], j["ctx"], j["probs"] = (sd[k].data_ptr() for k in ("hs", "cs", "act", "cx", "probs"))
-        j["B"], j["T"], j["S"], j["start_index"] = sd["rows"], sd["T"], sd["S"], start
+    def _decoder_fwd_job(self, j, dec: _DecoderSet, p: _DecoderPass) -> None:
+        """A pass's ``DECODER_FWD_JOB``; its step tokens are read from the teacher-forced matrix, or drawn by the sampler and written."""
+        e, r0, mm = dec.enc, p.enc_row0, dec.mm
+        j["etable"], j["enc"], j["mask"], j["h0"] = dec.table.table.data_ptr(), e["enc"][r0:].data_ptr(), e["fmask"][r0:].data_ptr(), e["h"][r0:].data_ptr()
+        j["w_c"], j["w_hh"] = mm.derived["d.c"].data_ptr(), mm.derived["d.hh"].data_ptr()
+        j["hs"], j["cs"], j["act"], j["ctx"], j["probs"] = (p.v[k].data_ptr() for k in ("hs", "cs", "act", "cx", "probs"))
+        j["B"], j["T"], j["S"], j["start_index"] = p.rows, p.T, p.S, mm.model._start_index
+        if p.trimmed is None:
+            j["in_tokens"], j["in_token_stride"] = p.tokens.data_ptr(), p.tokens.stride(0)
+        else:
+            j["w_p"], j["b_p"], j["tokens"], j["V"], j["sample"] = mm.proj.weight.data_ptr(), mm.proj.bias.data_ptr(), p.tokens.data_ptr(), mm.proj.weight.size(0), 1
+            j["pad_index"], j["unk_index"] = mm.model._pad_index, mm.model._unk_index
+
+    def _decoder_forward(self, calls: _Calls, dec: _DecoderSet, source: torch.Tensor, tgt: torch.Tensor, ws_name: str) -> np.ndarray:
+        """[@start@, source row, @end@] as the teacher-forced matrix ``tgt``, the token table, and the set's passes in one launch;
+        returns the launch's job records, for the caller to keep."""
+        model, rows = dec.mm.model, [p.rows for p in dec.passes]
+        calls.add("pnmn_token_prep", source.data_ptr(), source.stride(0), source.size(0), source.size(1), model._pad_index, model._start_index,
+                  model._end_index, 0, tgt.data_ptr(), None, None, self.stream)
+        self._table_forward(calls, dec.table)
+        jobs = np.zeros(len(dec.passes), _hip.DECODER_FWD_JOB)
+        for j, p in zip(jobs, dec.passes):
+            self._decoder_fwd_job(j, dec, p)
+        ws = self.bytes_buf(ws_name, _hip.decoder_workspace_bytes(rows, False))
+        calls.add("pnmn_attn_lstm_fwd_group", jobs.ctypes.data, len(jobs), 256, ws.data_ptr(), self.stream)
+        return jobs
+
+    def _decoder_losses(self, calls: _Calls, dec: _DecoderSet) -> None:
+        """The output projection over all rows of the set's passes, and each pass's loss."""
+        proj, (R, V) = dec.mm.proj, dec.logits.shape
+        self._gemm(calls, dec.tag + ".logits_g", [dict(a=dec.flat["hs"].data_ptr(), b=proj.weight.data_ptr(), c=dec.logits.data_ptr(), M=R, N=V,
+                                                       K=256, lda=256, ldb=256, ldc=V, tb=1, bias=proj.bias.data_ptr())])
+        for p in dec.passes:
+            p.loss.forward(calls, self.stream)
 
     # ---- the plan ----------------------------------------------------------------------------------------------------------
     def _build(self) -> None:
-        lib, st = _hip.lib(), self.stream
-        n, m, B, D, tq, tp = self.n, self.m, self.B, self.D, self.tq, self.tp
-        pg, qr = self.pg, self.qr
-        dpg, dqr = pg.model._derived(), qr.model._derived()
-        if dpg is None or dqr is None:
+        if self.pg.derived is None or self.qr.derived is None or self.prior._derived() is None:
             raise PlanUnsupported("derived parameters")
-        f = self.buf
-        pad, bos, eos = pg.model._pad_index, pg.model._start_index, pg.model._end_index
-        # ---- generator: encoder over [unsupervised ; supervised] questions -------------------------------------------------
-        ques = f("ques", B, tq, dtype=torch.long)
-        prog_sup = f("prog_sup", m, tp, dtype=torch.long)
-        e_pg = self._encoder_prepare(self.fwd_pg_enc, "pg.e", pg, dpg, ques, tq, B, True, pg.emb_src,
-                                     pg.model._source_embedder.embedding.padding_idx, pg.lstm, p=self.drop_p[0])
-        self._encoders_fwd(self.fwd_pg_enc, "pg.e", [e_pg], most=STACK_PG_ENCODER)
-        #: workgroups of the generator's encoder launch (0: a launch per layer): a trainer that runs the NMN's stem beside it
-        #: cuts the stem's launches for the CUs this leaves (JointTrainingStep)
-        self.pg_encoder_workgroups = 16 * (-(-B // 16)) if any(n.startswith("pnmn_lstm_stack_fwd") for _, _, n in self.fwd_pg_enc) else 0
-        S = e_pg["T"]
-        if S > 64 or D > 64:
-            raise PlanUnsupported("more than 64 source positions / decoding steps")
-        # ---- generator: sampling decode of rows [0, n) and teacher-forced decode of rows [n, B) in one launch ----------------
-        Tt = tp + 1  # teacher-forced steps over [@start@, program, @end@]
-        Rs, Rt = n * D, m * Tt
-        Vp = pg.proj.weight.size(0)
-        tgt = f("pg.tgt", m, tp + 2, dtype=torch.long)
-        table_d = f("pg.d.table", Vp, 1024)
-        base = {k: f("pg.d." + k, Rs + Rt, w) for k, w in (("hs", 256), ("cs", 256), ("cx", 256), ("act", 1024), ("dhs", 256),
-                                                           ("dg", 1024), ("dctx", 256))}
-        side_s = self._decoder_side("pg.s", n, D, S, base, 0)
-        side_t = self._decoder_side("pg.t", m, Tt, S, base, Rs)
-        raw, z = f("pg.raw", n, D, dtype=torch.long), f("pg.z", n, D, dtype=torch.long)
-        logits, dlogits = f("pg.logits", Rs + Rt, Vp), f("pg.dlogits", Rs + Rt, Vp)
-        loss_s, loss_t = f("pg.loss_s", n), f("pg.loss_t", m)
-        lse_s, lse_t = f("pg.lse_s", n, D), f("pg.lse_t", m, Tt)
-        c = self.fwd_pg
-        c.add("pnmn_token_prep", prog_sup.data_ptr(), prog_sup.stride(0), m, tp, pad, bos, eos, 0, tgt.data_ptr(), None, None, st)
-        cell = pg.cell
-        w_e_ptr = cell.weight_ih.data_ptr() + 4 * 256  # columns [256, 512): the embedding half of cat(attended, embedded)
-        c.add("pnmn_token_table_fwd", pg.emb_tgt.data_ptr(), w_e_ptr, 512, dpg["d.b"].data_ptr(), Vp, 256, 1024, table_d.data_ptr(), st)
-        jobs = np.zeros(2, _hip.DECODER_FWD_JOB)
-        self._decoder_fwd_job(jobs[0], side_s, table_d, e_pg, 0, dpg, bos)
-        self._decoder_fwd_job(jobs[1], side_t, table_d, e_pg, n, dpg, bos)
-        js = jobs[0]
-        js["w_p"], js["b_p"], js["tokens"], js["V"], js["sample"] = pg.proj.weight.data_ptr(), pg.proj.bias.data_ptr(), raw.data_ptr(), Vp, 1
-        js["pad_index"], js["unk_index"] = pad, pg.model._unk_index
-        jobs[1]["in_tokens"], jobs[1]["in_token_stride"] = tgt.data_ptr(), tgt.stride(0)
-        self.pair_jobs = jobs
-        pws = self.bytes_buf("pg.pair_ws", _hip.decoder_workspace_bytes([n, m], False))
-        c.add("pnmn_attn_lstm_fwd_group", jobs.ctypes.data, 2, 256, pws.data_ptr(), st)
-        c.add("pnmn_trim_predictions", raw.data_ptr(), n, D, eos, z.data_ptr(), st)
-        # (the output projection and the losses follow in `fwd_pg_finish`: the samples are what the host waits for)
-        self.fwd_pg_finish = _Calls()
-        c = self.fwd_pg_finish
-        self._gemm(c, "pg.logits_g", [dict(a=base["hs"].data_ptr(), b=pg.proj.weight.data_ptr(), c=logits.data_ptr(), M=Rs + Rt, N=Vp,
-                                           K=256, lda=256, ldb=256, ldc=Vp, tb=1, bias=pg.proj.bias.data_ptr())])
-        c.add("pnmn_seq_nll_fwd", logits.data_ptr(), D * Vp, raw.data_ptr(), D, z.data_ptr(), D, pad, loss_s.data_ptr(), lse_s.data_ptr(),
-              n, D, Vp, 1e-12, st)
-        lt = logits[Rs:]
-        c.add("pnmn_seq_nll_fwd", lt.data_ptr(), Tt * Vp, tgt.data_ptr() + 8, tgt.stride(0), tgt.data_ptr() + 8, tgt.stride(0), pad,
-              loss_t.data_ptr(), lse_t.data_ptr(), m, Tt, Vp, 1e-13, st)
-        # ---- reconstructor: encoder over [sampled ; ground-truth] programs, teacher-forced decode over the questions ----------
-        Wq = max(D, tp)
-        source = f("qr.source", B, Wq, dtype=torch.long)
-        segs = np.zeros(2, _hip.TOKEN_SEG)
-        segs[0]["src"], segs[0]["row_stride"], segs[0]["rows"], segs[0]["width"] = z.data_ptr(), D, n, D
-        segs[1]["src"], segs[1]["row_stride"], segs[1]["rows"], segs[1]["width"] = prog_sup.data_ptr(), tp, m, tp
-        self._keep.append(segs)
-        c = self.fwd_qr
-        c.add("pnmn_token_rows", segs.ctypes.data, 2, source.data_ptr(), Wq, 0, st)
-        e_qr = self._encoder_prepare(c, "qr.e", qr, dqr, source, Wq, B, True, qr.emb_src, qr.model._source_embedder.embedding.padding_idx,
-                                     qr.lstm, p=self.drop_p[1])
-        self.e_pg, self.e_qr = e_pg, e_qr
-        # the prior reads the same samples: its two LSTM layers ride in the reconstructor encoder's launch (its projections
-        # and loss follow in `fwd_prior`, behind the trunk's launch)
-        e_pr = None
-        if self.with_prior:
-            pr = self.prior
-            dpr = pr._derived()
-            if dpr is None:
-                raise PlanUnsupported("prior derived parameters")
-            e_pr = self._encoder_prepare(c, "pr.e", None, dpr, z, D, n, False, pr._embedder.embedding.weight,
-                                         pr._embedder.embedding.padding_idx, pr._encoder._module, want_last=False)
-        self._encoders_fwd(c, "qr.e", [e_qr] + ([e_pr] if e_pr is not None else []))
-        Sq = e_qr["T"]
-        Tq = tq + 1
-        if Sq > 64 or Tq > 64:
-            raise PlanUnsupported("more than 64 positions in the reconstructor")
-        Vq = qr.proj.weight.size(0)
-        qtgt = f("qr.tgt", B, tq + 2, dtype=torch.long)
-        table_q = f("qr.d.table", Vq, 1024)
-        qbase = {k: f("qr.d." + k, B * Tq, w) for k, w in (("hs", 256), ("cs", 256), ("cx", 256), ("act", 1024), ("dhs", 256), ("dg", 1024),
-                                                            ("dctx", 256))}
-        side_q = self._decoder_side("qr.q", B, Tq, Sq, qbase, 0)
-        qlogits, qdlogits = f("qr.logits", B * Tq, Vq), f("qr.dlogits", B * Tq, Vq)
-        loss_q, lse_q = f("qr.loss", B), f("qr.lse", B, Tq)
-        c.add("pnmn_token_prep", ques.data_ptr(), ques.stride(0), B, tq, pad, bos, eos, 0, qtgt.data_ptr(), None, None, st)
-        qcell = qr.cell
-        c.add("pnmn_token_table_fwd", qr.emb_tgt.data_ptr(), qcell.weight_ih.data_ptr() + 4 * 256, 512, dqr["d.b"].data_ptr(), Vq, 256, 1024,
-              table_q.data_ptr(), st)
-        qjob = np.zeros(1, _hip.DECODER_FWD_JOB)
-        self._decoder_fwd_job(qjob[0], side_q, table_q, e_qr, 0, dqr, bos)
-        qjob[0]["in_tokens"], qjob[0]["in_token_stride"] = qtgt.data_ptr(), qtgt.stride(0)
-        self._keep.append(qjob)
-        qws = self.bytes_buf("qr.dec_ws", _hip.decoder_workspace_bytes([B], False))
-        c.add("pnmn_attn_lstm_fwd_group", qjob.ctypes.data, 1, 256, qws.data_ptr(), st)
-        self._gemm(c, "qr.logits_g", [dict(a=qbase["hs"].data_ptr(), b=qr.proj.weight.data_ptr(), c=qlogits.data_ptr(), M=B * Tq, N=Vq, K=256,
-                                           lda=256, ldb=256, ldc=Vq, tb=1, bias=qr.proj.bias.data_ptr())])
-        c.add("pnmn_seq_nll_fwd", qlogits.data_ptr(), Tq * Vq, qtgt.data_ptr() + 8, qtgt.stride(0), qtgt.data_ptr() + 8, qtgt.stride(0), pad,
-              loss_q.data_ptr(), lse_q.data_ptr(), B, Tq, Vq, 1e-13, st)
-        # ---- prior: LSTM language model over the samples (no gradient: its loss only enters the detached reward) ---------------
-        if self.with_prior:
-            c = self.fwd_prior
-            emb = pr._embedder.embedding.weight
-            Vz = emb.size(0)
-            Tz = e_pr["T"]
-            proj, plog = f("pr.proj", n * Tz, 256), f("pr.logits", n * Tz, Vz)
-            loss_p, lse_p = f("pr.loss", n), f("pr.lse", n, Tz - 1)
-            # (the padded steps are not zeroed as PytorchSeq2SeqWrapper does: they only meet padded targets, whose weight is zero)
-            self._gemm(c, "pr.proj_g", [dict(a=e_pr["hs2"].data_ptr(), b=pr._projection_layer.weight.data_ptr(), c=proj.data_ptr(), M=n * Tz,
-                                             N=256, K=256, lda=256, ldb=256, ldc=256, tb=1)])
-            self._gemm(c, "pr.out_g", [dict(a=proj.data_ptr(), b=emb.data_ptr(), c=plog.data_ptr(), M=n * Tz, N=Vz, K=256, lda=256, ldb=256,
-                                            ldc=Vz, tb=1)])
-            src = e_pr["src"]
-            c.add("pnmn_seq_nll_fwd", plog.data_ptr(), Tz * Vz, src.data_ptr() + 8, src.stride(0), src.data_ptr() + 8, src.stride(0),
-                  pr._pad_index, loss_p.data_ptr(), lse_p.data_ptr(), n, Tz - 1, Vz, 1e-13, st)
-            self.prior_sig = tuple(p.data_ptr() for p in pr.parameters())
-        # ---- backward ------------------------------------------------------------------------------------------------------------
-        c = self.bwd
-        self.d_rows = {"s": f("d.loss_s", n), "t": f("d.loss_t", m), "q": f("d.loss_q", B)}
-        c.add("pnmn_seq_nll_bwd", logits.data_ptr(), D * Vp, raw.data_ptr(), D, z.data_ptr(), D, pad, lse_s.data_ptr(),
-              self.d_rows["s"].data_ptr(), dlogits.data_ptr(), D * Vp, n, D, Vp, 1e-12, st)
-        c.add("pnmn_seq_nll_bwd", lt.data_ptr(), Tt * Vp, tgt.data_ptr() + 8, tgt.stride(0), tgt.data_ptr() + 8, tgt.stride(0), pad,
-              lse_t.data_ptr(), self.d_rows["t"].data_ptr(), dlogits[Rs:].data_ptr(), Tt * Vp, m, Tt, Vp, 1e-13, st)
-        c.add("pnmn_seq_nll_bwd", qlogits.data_ptr(), Tq * Vq, qtgt.data_ptr() + 8, qtgt.stride(0), qtgt.data_ptr() + 8, qtgt.stride(0), pad,
-              lse_q.data_ptr(), self.d_rows["q"].data_ptr(), qdlogits.data_ptr(), Tq * Vq, B, Tq, Vq, 1e-13, st)
-        self._gemm(c, "dhs_g", [
-            dict(a=dlogits.data_ptr(), b=pg.proj.weight.data_ptr(), c=base["dhs"].data_ptr(), M=Rs + Rt, N=256, K=Vp, lda=Vp, ldb=256, ldc=256),
-            dict(a=qdlogits.data_ptr(), b=qr.proj.weight.data_ptr(), c=qbase["dhs"].data_ptr(), M=B * Tq, N=256, K=Vq, lda=Vq, ldb=256, ldc=256)])
-        # the three decoders' backward in one launch
-        denc_pg, dh_pg = f("pg.denc", B, S, 256), f("pg.dh", B, 256)
-        denc_qr, dh_qr = f("qr.denc", B, Sq, 256), f("qr.dh", B, 256)
-        bj = np.zeros(3, _hip.DECODER_BWD_JOB)
-        for j, sd, mdl, der, e, r0, dh in ((bj[0], side_s, pg, dpg, e_pg, 0, dh_pg), (bj[1], side_t, pg, dpg, e_pg, n, dh_pg),
-                                           (bj[2], side_q, qr, dqr, e_qr, 0, dh_qr)):
-            j["dhs"], j["act"], j["cs"], j["hs"], j["probs"] = (sd[k].data_ptr() for k in ("dhs", "act", "cs", "hs", "probs"))
-            j["enc"], j["mask"], j["h0"] = e["enc"][r0:].data_ptr(), e["fmask"][r0:].data_ptr(), e["h"][r0:].data_ptr()
-            j["w_c_t"], j["w_hh_t"] = der["d.cT"].data_ptr(), der["d.hhT"].data_ptr()
-            j["dgates"], j["dctx"], j["dscore"], j["weights"] = (sd[k].data_ptr() for k in ("dg", "dctx", "dscore", "weights"))
-            j["dh0"] = dh[r0:].data_ptr()
-            j["B"], j["T"], j["S"] = sd["rows"], sd["T"], sd["S"]
-        self._keep.append(bj)
-        if DECODER_BWD_GROUP >= 3:
-            groups = [("group_ws", [0, 1, 2])]
-        elif DECODER_BWD_GROUP == 2:
-            groups = [("pair_bws", [0, 1]), ("single_bws2", [2])]
-        else:
-            groups = [("single_bws%d" % k, [k]) for k in range(3)]
-        for name, ks in groups:  # (each a run of consecutive jobs of `bj`)
-            gws = self.bytes_buf(name, _hip.decoder_workspace_bytes([int(bj[k]["B"]) for k in ks], True))
-            c.add("pnmn_attn_lstm_bwd_group", bj[ks[0]:ks[-1] + 1].ctypes.data, len(ks), 256, gws.data_ptr(), st)
-        for sd, e, r0, denc in ((side_s, e_pg, 0, denc_pg), (side_t, e_pg, n, denc_pg), (side_q, e_qr, 0, denc_qr)):
-            c.add("pnmn_attn_denc", sd["weights"].data_ptr(), sd["dscore"].data_ptr(), sd["dctx"].data_ptr(), sd["hs"].data_ptr(),
-                  e["h"][r0:].data_ptr(), denc[r0:].data_ptr(), sd["rows"], sd["T"], sd["S"], 256, st)
-        # Parameter gradients leave the chain: nothing in backward waits for them, so they go to an auxiliary stream behind
-        # events -- the decoders' right behind the decoder launch, the encoders' behind their layers -- and fill the CUs the
-        # latency-bound chains (this one and the NMN trunk's on its stream) leave idle; every kernel there is one of this
-        # library's that never waits for another workgroup (DESIGN 6).  PNMN_PLAN_AUX=0: all on the one stream, at the end.
-        main_stream = self.stream
-        self.bwd_a, self.bwd_b, self.aux_a, self.aux_b = c, _Calls(), _Calls(), _Calls()
-        self.aux_stream = _aux_stream(self.dev) if USE_AUX_STREAM else None
-        if self.aux_stream is not None:
-            self.stream = self.aux_stream.cuda_stream
-        ca = self.aux_a if self.aux_stream is not None else _Calls()
-        deferred: List[dict] = []
-        for mdl, der, tab, tag, sides in ((pg, dpg, table_d, "pg", ((side_s, raw, D, 1, 0), (side_t, tgt, tp + 2, 0, 0))),
-                                          (qr, dqr, table_q, "qr", ((side_q, qtgt, tq + 2, 0, 0),))):
-            V = tab.size(0)
-            dtab = f(tag + ".d.dtable", V, 1024)
-            g = mdl.grad
-            for k, (sd, toks, tstride, shift, _) in enumerate(sides):
-                ews = self.bytes_buf("%s.d.emb_ws%d" % (tag, k), lib.pnmn_embedding_grad_workspace_bytes(sd["rows"], sd["T"], V))
-                ca.add("pnmn_embedding_grad", sd["dg"].data_ptr(), toks.data_ptr(), tstride, sd["rows"], sd["T"], 1024, V, shift, bos, -1,
-                       1 if k else 0, dtab.data_ptr(), ews.data_ptr(), self.stream)
-            w_ih = mdl.cell.weight_ih
-            ca.add("pnmn_token_table_bwd", dtab.data_ptr(), mdl.emb_tgt.data_ptr(), w_ih.data_ptr() + 4 * 256, 512, V, 256, 1024, -1,
-                   g(mdl.emb_tgt).data_ptr(), g(w_ih).data_ptr() + 4 * 256, 512, g(mdl.cell.bias_ih).data_ptr(), g(mdl.cell.bias_hh).data_ptr(),
-                   self.stream)
-            bs = base if mdl is pg else qbase
-            R = bs["hs"].size(0)
-            lg, dlg = (logits, dlogits) if mdl is pg else (qlogits, qdlogits)
-            deferred.append(dict(a=dlg.data_ptr(), b=bs["hs"].data_ptr(), c=g(mdl.proj.weight).data_ptr(), M=V, N=256, K=R, lda=V, ldb=256,
-                                 ldc=256, ta=1, split="auto", colsum=g(mdl.proj.bias).data_ptr()))
-            deferred.append(dict(a=bs["dg"].data_ptr(), b=bs["cx"].data_ptr(), c=g(w_ih).data_ptr(), M=1024, N=256, K=R, lda=1024, ldb=256,
-                                 ldc=512, ta=1, split="auto"))
-            for k, (sd, _, _, _, _) in enumerate(sides):
-                e, r0 = (e_pg, (0 if sd is side_s else n)) if mdl is pg else (e_qr, 0)
-                deferred.append(dict(a=sd["dg"].data_ptr(), b=sd["hs"].data_ptr(), c=g(mdl.cell.weight_hh).data_ptr(), M=1024, N=256,
-                                     K=sd["R"], lda=1024, ldb=256, ldc=256, ta=1, split="auto", shift_t=sd["T"],
-                                     h0=e["h"][r0:].data_ptr(), ld_h0=256, acc=1 if k else 0))
-
-        def flush(calls, name):
-            # (an accumulating product must follow the product it adds to: keep them in different launches)
-            first = [d for d in deferred if not d.get("acc")]
-            second = [d for d in deferred if d.get("acc")]
-            if first:
-                self._gemm(calls, name, first)
-            if second:
-                self._gemm(calls, name + "2", second)
-            del deferred[:]
-
-        if self.aux_stream is not None:
-            flush(ca, "wgrad_dec")
-        # the encoders' chain on the main stream ...
-        self.stream = main_stream
-        e_pg["denc"], e_pg["dh"], e_qr["denc"], e_qr["dh"] = denc_pg, dh_pg, denc_qr, dh_qr
-        self._encoders_bwd(self.bwd_b, "enc", [e_pg, e_qr])
-        # ... their parameter gradients behind it
-        if self.aux_stream is not None:
-            self.stream = self.aux_stream.cuda_stream
-            self._encoders_param_grads(self.aux_b, deferred, [e_pg, e_qr])
-            flush(self.aux_b, "wgrad_enc")
-            self.stream = main_stream
-            self.events = [torch.cuda.Event() for _ in range(3)]
-        else:
-            self.bwd_b.extend(ca)
-            self._encoders_param_grads(self.bwd_b, deferred, [e_pg, e_qr])
-            flush(self.bwd_b, "wgrad")
-        self.out = dict(z=z, raw=raw, loss_s=loss_s, loss_t=loss_t, loss_q=loss_q, loss_p=self._bufs.get("pr.loss"), ques=ques,
-                        prog_sup=prog_sup)
+        self._generator_encoder()
+        dec_pg = self._generator_decoders()
+        self._decoder_losses(self.fwd_pg_finish, dec_pg)  # (apart from the decoders: the samples are what the host waits for)
+        e_pr = self._reconstructor_encoder()
+        dec_qr = self._reconstructor_decoder()
+        self._prior_loss(e_pr)
+        self._backward_chain([dec_pg, dec_qr])
+        self._parameter_gradients([dec_pg, dec_qr])
+        self.out.update(loss_s=dec_pg.passes[0].loss.loss, loss_t=dec_pg.passes[1].loss.loss, loss_q=dec_qr.passes[0].loss.loss)
         self._derived_sig = self._sig()
 
+    def _generator_encoder(self) -> None:
+        """The encoder over the [unsupervised ; supervised] questions."""
+        pg, f = self.pg, self.buf
+        self.out = dict(ques=f("ques", self.B, self.tq, dtype=torch.long), prog_sup=f("prog_sup", self.m, self.tp, dtype=torch.long))
+        self.e_pg = self._encoder_prepare(self.fwd_pg_enc, _EncoderPass(
+            "pg.e", pg, pg.model._source_embedder.embedding, self.out["ques"], self.tq, self.B, p=self.drop_p[0]))
+        self._encoders_fwd(self.fwd_pg_enc, "pg.e", [self.e_pg], most=STACK_PG_ENCODER)
+        #: workgroups of the generator's encoder launch (0: a launch per layer): a trainer that runs the NMN's stem beside it
+        #: cuts the stem's launches for the CUs this leaves (JointTrainingStep)
+        stacked = any(name.startswith("pnmn_lstm_stack_fwd") for _, _, name in self.fwd_pg_enc)
+        self.pg_encoder_workgroups = 16 * (-(-self.B // 16)) if stacked else 0
+        if self.e_pg["T"] > 64 or self.D > 64:
+            raise PlanUnsupported("more than 64 source positions / decoding steps")
+
+    def _generator_decoders(self) -> _DecoderSet:
+        """The sampling decode of rows [0, n) and the teacher-forced decode of rows [n, B) over [@start@, program, @end@] in one
+        launch, and the samples' trimmed copy."""
+        n, m, D, tp, f = self.n, self.m, self.D, self.tp, self.buf
+        tgt, raw, z = f("pg.tgt", m, tp + 2, dtype=torch.long), f("pg.raw", n, D, dtype=torch.long), f("pg.z", n, D, dtype=torch.long)
+        dec = self._decoder_set("pg", self.pg, self.e_pg, [("pg.s", "_s", n, D, raw, z), ("pg.t", "_t", m, tp + 1, tgt, None)])
+        self.pair_jobs = self._decoder_forward(self.fwd_pg, dec, self.out["prog_sup"], tgt, "pg.pair_ws")
+        self.fwd_pg.add("pnmn_trim_predictions", raw.data_ptr(), n, D, self.pg.model._end_index, z.data_ptr(), self.stream)
+        self.out.update(z=z, raw=raw)
+        return dec
+
+    def _reconstructor_encoder(self) -> Dict:
+        """The encoder over the [sampled ; ground-truth] programs.  The prior reads the same samples: its two LSTM layers ride
+        in this launch (its projections and loss follow in `fwd_prior`, behind the trunk's launch); returns its pass."""
+        n, m, D, tp, qr, pr, c = self.n, self.m, self.D, self.tp, self.qr, self.prior, self.fwd_qr
+        z, Wq = self.out["z"], max(D, tp)
+        source = self.buf("qr.source", self.B, Wq, dtype=torch.long)
+        segs = np.zeros(2, _hip.TOKEN_SEG)
+        segs[0]["src"], segs[0]["row_stride"], segs[0]["rows"], segs[0]["width"] = z.data_ptr(), D, n, D
+        segs[1]["src"], segs[1]["row_stride"], segs[1]["rows"], segs[1]["width"] = self.out["prog_sup"].data_ptr(), tp, m, tp
+        self._keep.append(segs)
+        c.add("pnmn_token_rows", segs.ctypes.data, 2, source.data_ptr(), Wq, 0, self.stream)
+        self.e_qr = self._encoder_prepare(c, _EncoderPass(
+            "qr.e", qr, qr.model._source_embedder.embedding, source, Wq, self.B, p=self.drop_p[1]))
+        e_pr = self._encoder_prepare(c, _EncoderPass("pr.e", None, pr._embedder.embedding, z, D, n, drop_first=False, want_last=False))
+        self._encoders_fwd(c, "qr.e", [self.e_qr, e_pr])
+        if self.e_qr["T"] > 64 or self.tq + 1 > 64:
+            raise PlanUnsupported("more than 64 positions in the reconstructor")
+        return e_pr
+
+    def _reconstructor_decoder(self) -> _DecoderSet:
+        """The teacher-forced decode of all rows over [@start@, question, @end@], and its loss."""
+        tgt = self.buf("qr.tgt", self.B, self.tq + 2, dtype=torch.long)
+        dec = self._decoder_set("qr", self.qr, self.e_qr, [("qr.q", "", self.B, self.tq + 1, tgt, None)])
+        self._keep.append(self._decoder_forward(self.fwd_qr, dec, self.out["ques"], tgt, "qr.dec_ws"))
+        self._decoder_losses(self.fwd_qr, dec)
+        return dec
+
+    def _prior_loss(self, e_pr: Dict) -> None:
+        """The prior's projections and loss over the samples (no gradient: its loss only enters the detached reward)."""
+        n, pr, c, f = self.n, self.prior, self.fwd_prior, self.buf
+        emb, src, Tz, Vz = pr._embedder.embedding.weight, e_pr["src"], e_pr["T"], pr._embedder.embedding.weight.size(0)
+        proj, plog = f("pr.proj", n * Tz, 256), f("pr.logits", n * Tz, Vz)
+        # (the padded steps are not zeroed as PytorchSeq2SeqWrapper does: they only meet padded targets, whose weight is zero)
+        self._gemm(c, "pr.proj_g", [dict(a=e_pr["hs2"].data_ptr(), b=pr._projection_layer.weight.data_ptr(), c=proj.data_ptr(), M=n * Tz,
+                                         N=256, K=256, lda=256, ldb=256, ldc=256, tb=1)])
+        self._gemm(c, "pr.out_g", [dict(a=proj.data_ptr(), b=emb.data_ptr(), c=plog.data_ptr(), M=n * Tz, N=Vz, K=256, lda=256, ldb=256,
+                                        ldc=Vz, tb=1)])
+        loss = _Loss(plog, Tz * Vz, src.data_ptr() + 8, src.stride(0), src.data_ptr() + 8, src.stride(0), pr._pad_index,
+                     f("pr.loss", n), f("pr.lse", n, Tz - 1), n, Tz - 1, Vz, 1e-13)
+        loss.forward(c, self.stream)
+        self.out["loss_p"] = loss.loss
+        self.prior_sig = tuple(p.data_ptr() for p in pr.parameters())
+
+    def _backward_chain(self, decs: List[_DecoderSet]) -> None:
+        """`bwd_a`: the losses' backward, the output projections' data gradient, every decoder pass's backward in one launch and
+        the encoder-output gradients; `bwd_b` begins with the encoders' layers."""
+        c, f, st = self.bwd_a, self.buf, self.stream
+        passes = [(dec, p) for dec in decs for p in dec.passes]
+        self.d_rows = {key: f("d.loss_" + key, p.rows) for key, (_, p) in zip("stq", passes)}
+        for dloss, (dec, p) in zip(self.d_rows.values(), passes):
+            p.loss.backward(c, dloss, dec.dlogits[p.row0:], st)
+        self._gemm(c, "dhs_g", [dict(a=dec.dlogits.data_ptr(), b=dec.mm.proj.weight.data_ptr(), c=dec.flat["dhs"].data_ptr(), M=dec.logits.size(0),
+                                     N=256, K=dec.logits.size(1), lda=dec.logits.size(1), ldb=256, ldc=256) for dec in decs])
+        for dec in decs:  # (gradients of what the decoders read of their encoder: its masked outputs and last states)
+            dec.enc["denc"], dec.enc["dh"] = f(dec.tag + ".denc", *dec.enc["enc"].shape), f(dec.tag + ".dh", *dec.enc["h"].shape)
+        bj = np.zeros(len(passes), _hip.DECODER_BWD_JOB)
+        for j, (dec, p) in zip(bj, passes):
+            e, r0 = dec.enc, p.enc_row0
+            j["dhs"], j["act"], j["cs"], j["hs"], j["probs"] = (p.v[k].data_ptr() for k in ("dhs", "act", "cs", "hs", "probs"))
+            j["enc"], j["mask"], j["h0"] = e["enc"][r0:].data_ptr(), e["fmask"][r0:].data_ptr(), e["h"][r0:].data_ptr()
+            j["w_c_t"], j["w_hh_t"] = dec.mm.derived["d.cT"].data_ptr(), dec.mm.derived["d.hhT"].data_ptr()
+            j["dgates"], j["dctx"], j["dscore"], j["weights"] = (p.v[k].data_ptr() for k in ("dg", "dctx", "dscore", "weights"))
+            j["dh0"] = e["dh"][r0:].data_ptr()
+            j["B"], j["T"], j["S"] = p.rows, p.T, p.S
+        self._keep.append(bj)
+        gws = self.bytes_buf("group_ws", _hip.decoder_workspace_bytes([p.rows for _, p in passes], True))
+        c.add("pnmn_attn_lstm_bwd_group", bj.ctypes.data, len(bj), 256, gws.data_ptr(), st)
+        for dec, p in passes:
+            c.add("pnmn_attn_denc", p.v["weights"].data_ptr(), p.v["dscore"].data_ptr(), p.v["dctx"].data_ptr(), p.v["hs"].data_ptr(),
+                  dec.enc["h"][p.enc_row0:].data_ptr(), dec.enc["denc"][p.enc_row0:].data_ptr(), p.rows, p.T, p.S, 256, st)
+        self._encoders_bwd(self.bwd_b, "enc", [dec.enc for dec in decs])
+
+    def _parameter_gradients(self, decs: List[_DecoderSet]) -> None:
+        """Nothing in backward waits for a parameter gradient, so they all follow the chain at the end of `bwd_b`: the token
+        tables' as launches, every product over all steps in one grouped GEMM launch."""
+        c, deferred = self.bwd_b, []
+        for dec in decs:
+            mm, flat, (R, V), g, cell = dec.mm, dec.flat, dec.logits.shape, dec.mm.grad, dec.mm.cell
+            self._table_backward(c, dec.table, mm, mm.model._start_index,
+                                 [("%s.d.emb_ws%d" % (dec.tag, k), p.v["dg"], p.tokens, p.shift) for k, p in enumerate(dec.passes)])
+            deferred.append(dict(a=dec.dlogits.data_ptr(), b=flat["hs"].data_ptr(), c=g(mm.proj.weight).data_ptr(), M=V, N=256, K=R, lda=V,
+                                 ldb=256, ldc=256, ta=1, split="auto", colsum=g(mm.proj.bias).data_ptr()))
+            deferred.append(dict(a=flat["dg"].data_ptr(), b=flat["cx"].data_ptr(), c=g(cell.weight_ih).data_ptr(), M=1024, N=256, K=R, lda=1024,
+                                 ldb=256, ldc=512, ta=1, split="auto"))
+            for k, p in enumerate(dec.passes):
+                deferred.append(dict(a=p.v["dg"].data_ptr(), b=p.v["hs"].data_ptr(), c=g(cell.weight_hh).data_ptr(), M=1024, N=256,
+                                     K=p.rows * p.T, lda=1024, ldb=256, ldc=256, ta=1, split="auto", shift_t=p.T,
+                                     h0=dec.enc["h"][p.enc_row0:].data_ptr(), ld_h0=256, acc=1 if k else 0))
+        self._encoders_param_grads(c, deferred, [dec.enc for dec in decs])
+        # (an accumulating product must follow the product it adds to: keep them in different launches)
+        self._gemm(c, "wgrad", [d for d in deferred if not d.get("acc")])
+        self._gemm(c, "wgrad2", [d for d in deferred if d.get("acc")])
+
     def _sig(self):
-        d = [self.pg.model._derived(), self.qr.model._derived()] + ([self.prior._derived()] if self.with_prior else [])
-        return tuple(t.data_ptr() for dd in d for t in dd.values())
+        return tuple(t.data_ptr() for model in (self.pg.model, self.qr.model, self.prior) for t in model._derived().values())
 
     def still_valid(self) -> bool:
         """Parameters, derived copies and the stream are where the plan's calls point (a ``.to()``, a re-pointed parameter
@@ -664,11 +676,11 @@ class Seq2SeqPlan:
         for mm in (self.pg, self.qr):
             if tuple(p.data_ptr() for p in mm.params) != mm.signature:
                 return False
-        if self.with_prior and tuple(p.data_ptr() for p in self.prior.parameters()) != self.prior_sig:
+        if tuple(p.data_ptr() for p in self.prior.parameters()) != self.prior_sig:
             return False
         if (_dropout_p(self.pg.lstm), _dropout_p(self.qr.lstm)) != self.drop_p:
             return False
-        if self.with_prior and self.prior.training and _dropout_p(self.prior._encoder._module) > 0:
+        if self.prior.training and _dropout_p(self.prior._encoder._module) > 0:
             return False
         return self._sig() == self._derived_sig
 
@@ -730,20 +742,7 @@ class Seq2SeqPlan:
             else:
                 self.d_rows[key].copy_(d)
         self.bwd_a.run()
-        if self.aux_stream is not None:
-            main = torch.cuda.current_stream(self.dev)
-            e1, e2, e3 = self.events
-            e1.record(main)
-            self.aux_stream.wait_event(e1)
-            self.aux_a.run()
-            self.bwd_b.run()
-            e2.record(main)
-            self.aux_stream.wait_event(e2)
-            self.aux_b.run()
-            e3.record(self.aux_stream)
-            main.wait_event(e3)  # (the optimiser and the gradient all-reduce read the gradients on this stream)
-        else:
-            self.bwd_b.run()
+        self.bwd_b.run()
         self.pg.attach()
         self.qr.attach()
 
