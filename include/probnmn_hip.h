@@ -818,6 +818,32 @@ int pnmn_conv2d_weight_floats(int Cout, int Cin, int kh, int kw);
 int pnmn_maxpool3x3s2_nhwc(const float* x, float* y, int N, int H, int W, int C, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Image front end of the feature extractor (csrc/image_prep.hip): decoded uint8 images -> the stem convolution's input.
+ * Replaces: Image.resize((224, 224), BILINEAR) + ToTensor + Normalize of the reference's transform
+ *           (scripts/preprocess/extract_features.py:60-73), which runs on the CPU in Pillow and torchvision.
+ * Pillow's 8-bit resampler is integer arithmetic, and this is that arithmetic: bit-identical results.  Per axis the host
+ * supplies Pillow's coefficient table (probnmn.data.feature_extractor.resize_coefficients): for output index i the taps
+ * k[i][0 .. ksize) in 22-bit fixed point and bounds[i] = (first input index, number of taps n <= ksize); one pass is
+ *   pass(in)[i] = clip(((1 << 21) + sum_{t < n} in[first + t] * k[i][t]) >> 22, 0, 255)          -> uint8
+ * The horizontal pass runs first, the vertical pass on its uint8 result, then
+ *   out[n][y][x][c] = lut[c][resized[n][y][x][c]]  for c < 3,   out[n][y][x][3] = 0
+ * with lut[c][v] = (v / 255 - mean[c]) / std[c] computed by the host in fp32.
+ *   images   [N][Hin][Win][3] uint8, image n at images + n * image_stride bytes (image_stride >= 3 * Hin * Win)
+ *   kx, ky   int32 [Wout][ksx], [Hout][ksy];   xbounds, ybounds   int32 [Wout][2], [Hout][2];   lut   fp32 [3][256]
+ *   out      fp32 [N][Hout][Wout][4], 16-byte aligned
+ * Limits (PNMN_EINVAL beyond them, as for a null pointer, a non-positive size or a short image_stride; nothing is
+ * launched): ksx, ksy <= PNMN_IMAGE_PREP_MAX_TAPS (33: a 16x downscale), Wout <= PNMN_IMAGE_PREP_MAX_WIDTH, Hin, Win,
+ * Hout <= PNMN_IMAGE_PREP_MAX_SIZE.  N == 0 returns 0 without a launch.  No byte outside [images, images + N *
+ * image_stride) is read whatever the tables hold: every index is clamped to the image.
+ * ------------------------------------------------------------------------------------------- */
+#define PNMN_IMAGE_PREP_MAX_TAPS  33
+#define PNMN_IMAGE_PREP_MAX_WIDTH 448
+#define PNMN_IMAGE_PREP_MAX_SIZE  16384
+int pnmn_image_prep(const uint8_t* images, int64_t image_stride, int N, int Hin, int Win, const int32_t* kx,
+                    const int32_t* xbounds, int ksx, const int32_t* ky, const int32_t* ybounds, int ksy,
+                    const float* lut, float* out, int Hout, int Wout, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Several LSTM-layer passes in ONE launch; the two layers of an encoder as a wavefront (csrc/lstm_stack.hip).
  * Replaces: the stacked nn.LSTM of the seq2seq encoders and of ProgramPrior under autograd
  *           (probnmn/modules/seq2seq_base.py:56-60 via allennlp PytorchSeq2SeqWrapper; probnmn/models/program_prior.py:50-56),

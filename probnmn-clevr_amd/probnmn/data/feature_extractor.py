@@ -11,6 +11,11 @@ result is a ``channels_last`` tensor, which is the layout ``NeuralModuleNetwork`
 (``probnmn.data.feature_store``) take without a layout pass -- on this part the features of all 70 000 CLEVR training
 images fit in HBM (56 GB of 288), so extraction can feed a ``DeviceFeatureStore`` directly instead of a file.
 
+Decoded images go in as they are: :func:`resize_normalize` (``pnmn_image_prep``, csrc/image_prep.hip) is the transform's
+``Resize((224, 224))`` -- Pillow's 8-bit bilinear resampler, integer arithmetic reproduced bit for bit -- fused with
+``ToTensor`` / ``Normalize`` and the 3 -> 4 channel padding of the stem convolution's input, and
+:meth:`ResNet101Stage3.forward_pixels` runs the network on its result.  Only the PNG decoding stays on the CPU.
+
 No CPU fallback: parameters and images must be on a ROCm device.
 """
 from typing import Dict, Iterable, List, Optional, Tuple
@@ -133,10 +138,30 @@ class ResNet101Stage3(nn.Module):
                                        "there is no CPU fallback" % (dev, images.device))
         if images.dim() != 4 or images.size(1) != 3 or images.size(2) % 32 or images.size(3) % 32:
             raise ValueError("expected images (N, 3, H, W) with H and W multiples of 32, got %s" % (tuple(images.shape),))
-        packed = self._pack()
         n, _, h, w = images.shape
         x = torch.zeros(n, h, w, 4, dtype=torch.float32, device=dev)
         x[..., :3] = images.float().permute(0, 2, 3, 1)
+        return self._trunk(x)
+
+    @torch.no_grad()
+    def forward_pixels(self, images_uint8: torch.Tensor, size: Tuple[int, int] = (IMAGE_SIZE, IMAGE_SIZE)) -> torch.Tensor:
+        """``images_uint8``: (N, H, W, 3) uint8 decoded RGB images of any size, on the parameters' device.  The reference's
+        whole transform (``Resize(size)`` as Pillow does it, ``ToTensor``, ``Normalize``) runs in one kernel
+        (:func:`resize_normalize`) whose output is the stem convolution's input; ``size`` multiples of 32.  Returns what
+        :meth:`forward` returns for ``preprocess`` of the Pillow-resized images, bit for bit."""
+        dev = self.conv1.weight.device
+        if dev.type != "cuda" or images_uint8.device != dev:
+            raise _hip.HipLibraryError("ResNet101Stage3 runs on a ROCm device only (parameters on %s, images on %s): "
+                                       "there is no CPU fallback" % (dev, images_uint8.device))
+        if len(size) != 2 or size[0] % 32 or size[1] % 32:
+            raise ValueError("expected size (H, W) with H and W multiples of 32, got %s" % (tuple(size),))
+        return self._trunk(resize_normalize(images_uint8, size))
+
+    def _trunk(self, x: torch.Tensor) -> torch.Tensor:
+        """The network on the stem convolution's input: (N, H, W, 4) fp32 NHWC, normalised, channel 3 zero."""
+        dev = x.device
+        packed = self._pack()
+        n = x.size(0)
         x = self._conv(packed["conv1"], x, relu=True)
         pooled = torch.empty(n, x.size(1) // 2, x.size(2) // 2, 64, dtype=torch.float32, device=dev)
         _hip.check(_hip.lib().pnmn_maxpool3x3s2_nhwc(x.data_ptr(), pooled.data_ptr(), n, x.size(1), x.size(2), 64,
@@ -171,7 +196,8 @@ class ResNet101Stage3(nn.Module):
 
 def preprocess(images_uint8: torch.Tensor) -> torch.Tensor:
     """``ToTensor`` + ``Normalize`` of the reference's transform (extract_features.py:70-73) on (N, 3, H, W) uint8 images,
-    on whatever device they are; ``Resize((224, 224))`` (PIL, bilinear) stays with the caller that decodes the PNGs."""
+    on whatever device they are.  The transform's ``Resize((224, 224))`` (PIL, bilinear) is not in here: the images are
+    already resized (:func:`resize_normalize` does all three steps on decoded images of any size)."""
     x = images_uint8.float() / 255.0
     mean = torch.tensor(MEAN, device=x.device).view(1, 3, 1, 1)
     std = torch.tensor(STD, device=x.device).view(1, 3, 1, 1)
@@ -188,6 +214,104 @@ def extract_features(model: ResNet101Stage3, image_batches: Iterable[torch.Tenso
     counter = 0
     for batch in image_batches:
         feats = model(batch.to(dev, non_blocking=True))
+        out[counter: counter + feats.size(0)].copy_(feats)
+        counter += feats.size(0)
+    return counter
+
+
+# ---- the transform on the device: Resize (Pillow, bilinear) + ToTensor + Normalize ------------------------------------
+PRECISION_BITS = 22  # Pillow's 8-bit resampler: coefficients in 32 - 8 - 2 bits of fixed point
+
+
+def resize_coefficients(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Pillow's coefficient table of one axis of ``Image.resize(..., BILINEAR)`` on an 8-bit image (its
+    ``precompute_coeffs`` and ``normalize_coeffs_8bpc``, in float64 as there): ``(k, bounds)`` with ``k`` int32
+    [out_size][ksize] -- the taps of every output index in 22-bit fixed point, zero beyond its count -- and ``bounds``
+    int32 [out_size][2] -- (first input index, number of taps).  A triangle filter whose support grows with the downscale
+    factor; ``ksize = 2 * ceil(max(in / out, 1)) + 1``."""
+    if in_size < 1 or out_size < 1:
+        raise ValueError("resize_coefficients: sizes must be positive, got %d -> %d" % (in_size, out_size))
+    scale = float(in_size) / float(out_size)
+    support = max(scale, 1.0)
+    ss = 1.0 / support
+    ksize = int(np.ceil(support)) * 2 + 1
+    center = (np.arange(out_size, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum(np.trunc(center - support + 0.5).astype(np.int64), 0)
+    xmax = np.minimum(np.trunc(center + support + 0.5).astype(np.int64), in_size)
+    n = xmax - xmin
+    taps = np.arange(ksize, dtype=np.int64)[None, :]
+    arg = ((taps + xmin[:, None]).astype(np.float64) - center[:, None] + 0.5) * ss
+    w = np.where((np.abs(arg) < 1.0) & (taps < n[:, None]), 1.0 - np.abs(arg), 0.0)
+    ww = np.zeros(out_size, dtype=np.float64)
+    for t in range(ksize):  # (summed in tap order, as the C loop does)
+        ww = ww + w[:, t]
+    w = np.where(ww[:, None] != 0.0, w / np.where(ww == 0.0, 1.0, ww)[:, None], w)
+    k = np.trunc(0.5 + w * float(1 << PRECISION_BITS)).astype(np.int32)
+    return k, np.stack([xmin, n], axis=1).astype(np.int32)
+
+
+def normalization_table() -> torch.Tensor:
+    """fp32 [3][256]: :func:`preprocess` of every byte value per channel, so a lookup equals ``preprocess`` bit for bit."""
+    values = torch.arange(256, dtype=torch.uint8).view(1, 1, 256, 1).expand(1, 3, 256, 1)
+    return preprocess(values).reshape(3, 256).contiguous()
+
+
+_PREP_TABLES: Dict[tuple, tuple] = {}
+
+
+def _prep_tables(h: int, w: int, size: Tuple[int, int], device: torch.device) -> tuple:
+    key = (h, w, int(size[0]), int(size[1]), device.type, device.index if device.index is not None else torch.cuda.current_device())
+    if key not in _PREP_TABLES:
+        (ky, yb), (kx, xb) = resize_coefficients(h, size[0]), resize_coefficients(w, size[1])
+        tensors = tuple(torch.from_numpy(np.ascontiguousarray(t)).to(device) for t in (kx, xb, ky, yb))
+        _PREP_TABLES[key] = tensors + (normalization_table().to(device), kx.shape[1], ky.shape[1])
+    return _PREP_TABLES[key]
+
+
+def resize_normalize(images_uint8: torch.Tensor, size: Tuple[int, int] = (IMAGE_SIZE, IMAGE_SIZE)) -> torch.Tensor:
+    """The reference's whole image transform (extract_features.py:60-73) on the device, in one kernel: (N, H, W, 3) uint8
+    RGB images -> (N, size[0], size[1], 4) fp32 NHWC, channels 0-2 ``preprocess`` of ``PIL.Image.resize(size[::-1],
+    BILINEAR)`` bit for bit, channel 3 zero -- the stem convolution's input.  The coefficient tables and the
+    normalisation table are built once per (H, W, size, device)."""
+    if images_uint8.dtype != torch.uint8 or images_uint8.dim() != 4 or images_uint8.size(3) != 3 or images_uint8.size(1) < 1 \
+            or images_uint8.size(2) < 1:
+        raise ValueError("expected uint8 images (N, H, W, 3), got %s %s" % (images_uint8.dtype, tuple(images_uint8.shape)))
+    if len(size) != 2 or size[0] < 1 or size[1] < 1:
+        raise ValueError("expected size (H, W), got %s" % (size,))
+    if images_uint8.device.type != "cuda":
+        raise _hip.HipLibraryError("resize_normalize runs on a ROCm device only (images on %s): there is no CPU fallback"
+                                   % images_uint8.device)
+    n, h, w, _ = images_uint8.shape
+    ksy, ksx = (int(np.ceil(max(i / o, 1.0))) * 2 + 1 for i, o in ((h, size[0]), (w, size[1])))
+    if max(ksx, ksy) > _hip.IMAGE_PREP_MAX_TAPS or size[1] > _hip.IMAGE_PREP_MAX_WIDTH \
+            or max(h, w, size[0]) > _hip.IMAGE_PREP_MAX_SIZE:
+        raise NotImplementedError(
+            "resize_normalize %dx%d -> %dx%d is beyond pnmn_image_prep's limits: at most %d taps per axis (a %dx downscale; "
+            "this one needs %d), output width <= %d, sizes <= %d"
+            % (h, w, size[0], size[1], _hip.IMAGE_PREP_MAX_TAPS, (_hip.IMAGE_PREP_MAX_TAPS - 1) // 2, max(ksx, ksy),
+               _hip.IMAGE_PREP_MAX_WIDTH, _hip.IMAGE_PREP_MAX_SIZE))
+    dev = images_uint8.device
+    images_uint8 = images_uint8.contiguous()
+    out = torch.empty(n, size[0], size[1], 4, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    kx, xb, ky, yb, lut, ksx, ksy = _prep_tables(h, w, size, dev)
+    _hip.check(_hip.lib().pnmn_image_prep(images_uint8.data_ptr(), 3 * h * w, n, h, w, kx.data_ptr(), xb.data_ptr(), ksx,
+                                          ky.data_ptr(), yb.data_ptr(), ksy, lut.data_ptr(), out.data_ptr(), size[0], size[1],
+                                          _hip.stream_ptr(dev)), "image_prep")
+    return out
+
+
+@torch.no_grad()
+def extract_features_from_pixels(model: ResNet101Stage3, pixel_batches: Iterable[torch.Tensor], out: torch.Tensor,
+                                 size: Tuple[int, int] = (IMAGE_SIZE, IMAGE_SIZE)) -> int:
+    """:func:`extract_features` for decoded images: ``pixel_batches`` yields (b, H, W, 3) uint8 batches in image order (of
+    any size; one size per batch), resized and normalised on the device (:meth:`ResNet101Stage3.forward_pixels`).
+    Returns the number of images written."""
+    dev = model.conv1.weight.device
+    counter = 0
+    for batch in pixel_batches:
+        feats = model.forward_pixels(batch.to(dev, non_blocking=True), size)
         out[counter: counter + feats.size(0)].copy_(feats)
         counter += feats.size(0)
     return counter

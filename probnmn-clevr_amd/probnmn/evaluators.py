@@ -123,7 +123,7 @@ def evaluate_answer_accuracy(program_generator, nmn, batches: Iterable[Dict[str,
 @torch.no_grad()
 def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary,
                     beam_size: Optional[int] = None, prefer_valid: bool = True,
-                    constrained: bool = False) -> List[Dict[str, Any]]:
+                    constrained: bool = False, extractor=None) -> List[Dict[str, Any]]:
     """scripts/inference.py:76-91: sampled programs -> NMN -> answer strings, one record per question
     (``question_index`` from the batch when present, else a running index).
 
@@ -135,7 +135,12 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
 
     ``constrained`` (needs ``beam_size``): the beam kernel searches under the program compiler's validity rule
     (``nmn.engine.compiler.decoding_automaton``), so every hypothesis it returns is a valid program: ``program_valid`` is
-    always true, and ``beam_rank`` is 0 under ``prefer_valid``.  The record layout is the same."""
+    always true, and ``beam_rank`` is 0 under ``prefer_valid``.  The record layout is the same.
+
+    ``extractor`` (a ``ResNet101Stage3`` on the device): a batch without ``"image"`` features but with ``"pixels"`` --
+    decoded uint8 images [B, H, W, 3] of any size, on the device -- gets its features from ``extractor.forward_pixels``
+    (resize, normalisation and the network, all on the device), queued with the generator pass; the NMN reads the
+    ``channels_last`` result in place.  A batch with neither key, or with pixels but no extractor, is a ``ValueError``."""
     if constrained and beam_size is None:
         raise ValueError("constrained=True constrains the beam search: give a beam_size")
     was_training = (program_generator.training, nmn.training)
@@ -151,22 +156,32 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
             exclude = [getattr(program_generator, name) for name in ("_pad_index", "_unk_index", "_start_index", "_end_index")]
             constraint = nmn.engine.compiler.decoding_automaton(exclude=exclude)
 
+        def features(batch):
+            if "image" in batch:
+                return batch["image"]
+            if "pixels" not in batch:
+                raise ValueError("a batch needs \"image\" features or \"pixels\" (uint8 [B, H, W, 3]); it has %s" % sorted(batch))
+            if extractor is None:
+                raise ValueError("a batch of \"pixels\" needs an extractor (predict_answers(..., extractor=ResNet101Stage3))")
+            return extractor.forward_pixels(batch["pixels"])
+
         def queue(batch, iteration):
+            image = features(batch)
             if beam_size is None:
                 programs = program_generator(batch["question"])["predictions"]
             else:
                 extra = {} if constraint is None else {"constraint": constraint}
                 programs = program_generator(batch["question"], decoding_strategy="beam", beam_size=beam_size,
                                              **extra)["beam_predictions"]
-            if not (programs.is_cuda and batch["image"].is_cuda):
-                return programs, None
+            if not (programs.is_cuda and image.is_cuda):
+                return programs, None, image
             key = (iteration & 1, tuple(programs.shape), programs.dtype)
             if key not in pinned:
                 pinned[key] = torch.empty(programs.shape, dtype=programs.dtype, pin_memory=True)
             pinned[key].copy_(programs, non_blocking=True)
             copied = torch.cuda.Event()
             copied.record()
-            return pinned[key], copied
+            return pinned[key], copied, image
 
         def choose(beams):
             """[B, K, T] host tokens -> (programs [B, T], rank per question, validity of the chosen program)."""
@@ -184,14 +199,14 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
             return beams[torch.arange(B), torch.tensor(ranks, dtype=torch.long)], ranks, valid
 
         def finish(batch, queued):
-            programs, copied = queued
+            programs, copied, image = queued
             if copied is not None:
                 copied.synchronize()
             extra = None
             if beam_size is not None:
                 programs, ranks, valid = choose(programs)
                 extra = (programs.tolist(), ranks, valid)
-            answers = nmn(batch["image"], programs)["predictions"].cpu().tolist()
+            answers = nmn(image, programs)["predictions"].cpu().tolist()
             index = batch["question_index"].cpu().tolist() if "question_index" in batch else range(len(records), len(records) + len(answers))
             for i, (qi, a) in enumerate(zip(index, answers)):
                 record = {"question_index": int(qi), "answer": vocabulary.get_token_from_index(int(a), namespace="answers")}
