@@ -294,6 +294,12 @@ int pnmn_answer_loss(const float* logits, const int64_t* answers, const int32_t*
  * pnmn_mask_last_fwd/bwd   PytorchSeq2SeqWrapper's zeroed padded steps + get_final_encoder_states:
  *     enc = hs * fmask[..., None],  hlast[b] = enc[b][last[b]]  (negative index: from the end)
  *     dhs = (denc + [t == last[b]] dhlast[b]) * fmask        (denc, dhlast may be null)
+ * pnmn_length_order        the rows of a pass grouped by length, for the recurrent layer kernels (pnmn_lstm_seq_*_ordered
+ *                          below; no reference counterpart other than PytorchSeq2SeqWrapper's sort-and-pack):
+ *     steps[b] = clamp(last[b] + 1, 1, T)            (last: what pnmn_token_prep writes)
+ *     order [B] = the rows sorted by steps, longest first, equal lengths in row order (a counting sort in one
+ *                 workgroup: deterministic, no host synchronisation; T <= 4096)
+ *     tile_steps [ceil(B/16)]: tile_steps[i] = max of steps over order[16 i .. 16 i + 15]
  * pnmn_embedding_grad      dw[v] = sum_{rows with token v} dy[row]   (V <= 128, C % 4 == 0; dw is written whole, or --
  *                          accumulate != 0 -- added to;
  *                          rows = (b, t) of tokens [B][T]; shift = 1: row (b, t) takes token (b, t-1) and
@@ -313,6 +319,7 @@ typedef struct {
 
 int pnmn_token_prep(const int64_t* tokens, int64_t token_row_stride, int B, int T, int pad, int bos, int eos,
                     int drop_first, int64_t* out, float* fmask, int* last, void* stream);
+int pnmn_length_order(const int32_t* last, int B, int T, int32_t* order, int32_t* tile_steps, void* stream);
 int pnmn_trim_predictions(const int64_t* raw, int B, int T, int end, int64_t* out, void* stream);
 int pnmn_mask_last_fwd(const float* hs, const float* fmask, const int* last, int B, int T, int H, float* enc,
                        float* hlast, void* stream);
@@ -471,6 +478,24 @@ int pnmn_lstm_seq_bwd(const float* dhs, const float* act, const float* cs, const
  * (hipMalloc on a stream's first launch; the kernels leave it zeroed); while the stream is being captured
  * into a graph they go to the head of `workspace` behind a zeroing kernel node instead. */
 int64_t pnmn_lstm_seq_workspace_bytes(int B, int backward);
+/* Rows grouped by length: the same kernels (with or without a workspace) given pnmn_length_order's `order` and
+ * `tile_steps`.  Slot s of the 16-row tiles holds batch row order[s] -- a device-side indirection: every tensor stays
+ * in batch order -- and tile i runs tile_steps[i] steps instead of T (forward from step 0, backward from step
+ * tile_steps[i] - 1 down), which is where a batch of ragged rows spends its time: the kernels are latency-bound per
+ * step.  A row's accumulation order does not depend on the lane or tile that holds it, so for t < steps[b] the
+ * outputs are bit for bit those of pnmn_lstm_seq_fwd / _bwd with the same workspace choice.
+ * The skipped steps, t in [tile_steps[tile of b], T): hs[b][t] (forward) and dgates[b][t] (backward) are written
+ * as zeros -- the mask multiply and the dX / dW / bias products read them; cs and act are left unwritten there (only
+ * the backward kernel reads them, and it skips the same steps).
+ * CONTRACT (backward): dhs[b][t] for t >= steps[b] is taken as zero, whatever the buffer holds at t >= tile_steps;
+ * pnmn_mask_last_bwd and the products of zero dgates rows give exactly that.  Between steps[b] and its tile's count
+ * a row is computed as by the unordered kernels (forward: states nobody uses; backward: zeros from zero dhs). */
+int pnmn_lstm_seq_fwd_ordered(const float* xp, const int64_t* tokens, int64_t token_stride, const float* w_hh,
+                              float* hs, float* cs, float* act, int B, int T, int hidden, const int32_t* order,
+                              const int32_t* tile_steps, void* workspace, void* stream);
+int pnmn_lstm_seq_bwd_ordered(const float* dhs, const float* act, const float* cs, const float* w_hh_t,
+                              float* dgates, int B, int T, int hidden, const int32_t* order,
+                              const int32_t* tile_steps, void* workspace, void* stream);
 /* Data parallel (replaces nothing in the reference, whose nn.DataParallel is one process:
  * trainers/_trainer.py:94-100): keep `cus` compute units out of the grids of the multi-CU recurrent kernels
  * (these and the decoder's), so that RCCL's workgroups -- resident for a whole collective, waiting for their

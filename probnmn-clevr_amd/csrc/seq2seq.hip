@@ -202,13 +202,46 @@ constexpr int LH = 256;        // hidden size the kernel is built for
 constexpr int LROWS = 16;      // batch rows per workgroup
 constexpr int LLD = LH + 4;    // LDS row stride (floats): 16-byte aligned, breaks the 1 KiB bank period
 
+// Rows grouped by length (pnmn_lstm_seq_fwd_ordered / _bwd_ordered).  `order` turns a tile's SLOT into the batch row
+// it holds -- every tensor stays in batch order, only which rows share a tile changes -- and `tile_steps[tile]` is
+// how many steps the tile runs: its longest row's.  Both null: slot = row, T steps (the unordered entry points).
+// A row's accumulation order over k does not depend on the lane or the tile that holds it, so what a row gets at
+// its valid steps is bit for bit what the unordered call of the same kernel gives it.
+__device__ __forceinline__ int batch_row(const int32_t* __restrict__ order, int slot) { return order ? order[slot] : slot; }
+
+__device__ __forceinline__ int steps_of_tile(const int32_t* __restrict__ tile_steps, int tile, int T) {
+    return tile_steps ? min(max(tile_steps[tile], 1), T) : T;
+}
+
+// The steps a tile skips, defined: zeros at [steps, T) x (`groups` column groups LH apart, each W wide from col0) of
+// the tile's real rows in a [B][T][ld] tensor (hs: what the mask multiplies by 0; dgates: what the dX / dW / bias
+// products read whole).  Called by all 512 threads.
+template <int W>
+__device__ __forceinline__ void zero_skipped_steps(float* __restrict__ out, int ld, int groups, int col0,
+                                                   const int32_t* __restrict__ order, int row0, int B, int T, int steps) {
+    constexpr int W4 = W / 4;
+    const int n = (T - steps) * groups * W4;
+    if (n <= 0) return;
+    const f32x4_ zero = f32x4_{0.f, 0.f, 0.f, 0.f};
+    for (int rl = 0; rl < LROWS && row0 + rl < B; ++rl) {
+        float* base = out + (size_t)batch_row(order, row0 + rl) * T * ld + col0;
+        for (int i = threadIdx.x; i < n; i += 512) {
+            const int c4 = i % W4, q = (i / W4) % groups, t = steps + i / (W4 * groups);
+            *reinterpret_cast<f32x4_*>(base + (size_t)t * ld + q * LH + 4 * c4) = zero;
+        }
+    }
+}
+
 __global__ __launch_bounds__(512) void lstm_seq_fwd_kernel(const float* __restrict__ xp, const int64_t* __restrict__ tokens,
                                                            long tstride, const float* __restrict__ w_hh,
                                                            float* __restrict__ hs, float* __restrict__ cs,
-                                                           float* __restrict__ act, int B, int T) {
+                                                           float* __restrict__ act, int B, int T,
+                                                           const int32_t* __restrict__ order,
+                                                           const int32_t* __restrict__ tile_steps) {
     __shared__ __attribute__((aligned(16))) float hl[2][LROWS][LLD];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int row0 = blockIdx.x * LROWS;
+    const int steps = steps_of_tile(tile_steps, blockIdx.x, T);
     float creg[2][4];
 #pragma unroll
     for (int ut = 0; ut < 2; ++ut)
@@ -218,13 +251,14 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_kernel(const float* __restri
     // this lane's four rows of xp (rows past the batch re-read the last one; never stored); with tokens the row of
     // step t + 1 is fetched during step t (see the multi-CU kernel below)
     int64_t xrow[4];
+    int brow[4];  // batch row of this lane's four slots
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int row = min(row0 + 4 * g + r, B - 1);
-        xrow[r] = tokens ? tokens[(size_t)row * tstride] : (int64_t)row * T;
+        brow[r] = batch_row(order, min(row0 + 4 * g + r, B - 1));
+        xrow[r] = tokens ? tokens[(size_t)brow[r] * tstride] : (int64_t)brow[r] * T;
     }
 
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < steps; ++t) {
         const int cur = t & 1, nxt = cur ^ 1;
         f32x4_ acc[4][2];
         // start from the input projection
@@ -236,10 +270,8 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_kernel(const float* __restri
                 for (int r = 0; r < 4; ++r)
                     acc[gate][ut][r] = xp[(size_t)xrow[r] * (4 * LH) + gate * LH + 32 * wave + 16 * ut + li];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int row = min(row0 + 4 * g + r, B - 1);
-            xrow[r] = tokens ? tokens[(size_t)row * tstride + min(t + 1, T - 1)] : xrow[r] + 1;
-        }
+        for (int r = 0; r < 4; ++r)
+            xrow[r] = tokens ? tokens[(size_t)brow[r] * tstride + min(t + 1, T - 1)] : xrow[r] + 1;
         if (t > 0) {
 #pragma unroll 4
             for (int kb = 0; kb < LH / 16; ++kb) {
@@ -263,7 +295,7 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_kernel(const float* __restri
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int rl = 4 * g + r;
-                const int row = row0 + rl;
+                const int row = brow[r];
                 const int u = 32 * wave + 16 * ut + li;
                 const float ig = sigm(acc[0][ut][r]);
                 const float fg = sigm(acc[1][ut][r]);
@@ -273,7 +305,7 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_kernel(const float* __restri
                 const float h = og * tanhf(c);
                 creg[ut][r] = c;
                 hl[nxt][rl][u] = h;
-                if (row < B) {
+                if (row0 + rl < B) {
                     const size_t o = ((size_t)row * T + t) * LH + u;
                     hs[o] = h;
                     cs[o] = c;
@@ -288,34 +320,41 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_kernel(const float* __restri
             }
         __syncthreads();  // h_t complete before anyone starts step t+1 (and everyone is done with h_{t-1})
     }
+    zero_skipped_steps<LH>(hs, LH, 1, 0, order, row0, B, T, steps);
 }
 
 // backward: dgates[b][t][4H] (gradient wrt the gate pre-activations = wrt xp), given dhs (gradient wrt
 // every output h_t), the saved activated gates and cell states, and W_hh^T ([H][4H], k contiguous).
 __global__ __launch_bounds__(512) void lstm_seq_bwd_kernel(const float* __restrict__ dhs, const float* __restrict__ act,
                                                            const float* __restrict__ cs, const float* __restrict__ w_hh_t,
-                                                           float* __restrict__ dgates, int B, int T) {
+                                                           float* __restrict__ dgates, int B, int T,
+                                                           const int32_t* __restrict__ order,
+                                                           const int32_t* __restrict__ tile_steps) {
     extern __shared__ __attribute__((aligned(16))) char lraw[];
     float (*dgl)[4 * LH + 4] = reinterpret_cast<float (*)[4 * LH + 4]>(lraw);  // [16][1028]
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int row0 = blockIdx.x * LROWS;
+    const int steps = steps_of_tile(tile_steps, blockIdx.x, T);
     float dh_rec[2][4], dc_rec[2][4];
 #pragma unroll
     for (int ut = 0; ut < 2; ++ut)
 #pragma unroll
         for (int r = 0; r < 4; ++r) dh_rec[ut][r] = dc_rec[ut][r] = 0.f;
+    int brow[4];  // batch row of this lane's four slots
+#pragma unroll
+    for (int r = 0; r < 4; ++r) brow[r] = batch_row(order, min(row0 + 4 * g + r, B - 1));
 
-    for (int t = T - 1; t >= 0; --t) {
+    for (int t = steps - 1; t >= 0; --t) {
         // cell backward, lane-local: this lane owns (rows 4g+r, units 32w+16ut+li)
 #pragma unroll
         for (int ut = 0; ut < 2; ++ut)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int rl = 4 * g + r;
-                const int row = row0 + rl;
+                const int row = brow[r];
                 const int u = 32 * wave + 16 * ut + li;
                 float di = 0.f, df = 0.f, dg = 0.f, dout = 0.f, dcp = 0.f;
-                if (row < B) {
+                if (row0 + rl < B) {
                     const size_t o = ((size_t)row * T + t) * LH + u;
                     const float* ar = act + ((size_t)row * T + t) * (4 * LH);
                     const float ig = ar[u], fg = ar[LH + u], gg = ar[2 * LH + u], og = ar[3 * LH + u];
@@ -367,6 +406,7 @@ __global__ __launch_bounds__(512) void lstm_seq_bwd_kernel(const float* __restri
             for (int r = 0; r < 4; ++r) dh_rec[ut][r] = acc[ut][r];
         __syncthreads();  // everyone done reading dgl before it is overwritten
     }
+    zero_skipped_steps<4 * LH>(dgates, 4 * LH, 1, 0, order, row0, B, T, steps);
 }
 
 
@@ -404,7 +444,8 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_cluster_kernel(const float* 
                                                                    const float* __restrict__ w_hh,
                                                                    float* hs, float* __restrict__ cs,
                                                                    float* __restrict__ act, int* sync, int B, int T,
-                                                                   int tiles) {
+                                                                   int tiles, const int32_t* __restrict__ order,
+                                                                   const int32_t* __restrict__ tile_steps) {
     constexpr int UW = LH / S;          // hidden units of this workgroup
     constexpr int UB = UW / 32;         // 16-unit blocks per wave: waves 2q and 2q+1 split gate q's UW columns
     constexpr int J = UW * 16 / 512;    // (row, unit) pairs per thread in the cell update
@@ -421,6 +462,9 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_cluster_kernel(const float* 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int row0 = tile * LROWS, u0 = part * UW;
     const int gate = wave >> 1, ub0 = (wave & 1) * UB;
+    // one word, the same for every member of the tile, written by an earlier kernel on the stream: every member
+    // runs the same number of hand-offs
+    const int steps = steps_of_tile(tile_steps, tile, T);
     pnmn::Cluster cl;
     cl.start(sync + tile * pnmn::CLUSTER_COUNTER_STRIDE, S);
 
@@ -446,12 +490,18 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_cluster_kernel(const float* 
     const int64_t* trow[4];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const int row = min(row0 + 4 * g + r, B - 1);
+        const int row = batch_row(order, min(row0 + 4 * g + r, B - 1));
         trow[r] = TOK ? tokens + (size_t)row * tstride : nullptr;
         xrow[r] = TOK ? trow[r][0] : (int64_t)row * T;
     }
+    // the batch rows this thread stages h_{t-1} of, and those of its (row, unit) pairs in the cell update
+    int hrow[2], crow[J];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) hrow[k] = batch_row(order, min(row0 + (tid + 512 * k) / (LH / 4), B - 1));
+#pragma unroll
+    for (int j = 0; j < J; ++j) crow[j] = batch_row(order, min(row0 + (tid + 512 * j) / UW, B - 1));
 
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < steps; ++t) {
         f32x4_ acc[UB];
 #pragma unroll
         for (int ub = 0; ub < UB; ++ub)
@@ -468,9 +518,8 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_cluster_kernel(const float* 
                 f32x4_ piece[2];
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
-                    const int i = tid + 512 * k, rl = i / (LH / 4), c4 = i % (LH / 4);
-                    const int row = min(row0 + rl, B - 1);
-                    piece[k] = *reinterpret_cast<const f32x4_*>(hs + ((size_t)row * T + (t - 1)) * LH + 4 * c4);
+                    const int c4 = (tid + 512 * k) % (LH / 4);
+                    piece[k] = *reinterpret_cast<const f32x4_*>(hs + ((size_t)hrow[k] * T + (t - 1)) * LH + 4 * c4);
                 }
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
@@ -502,7 +551,7 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_cluster_kernel(const float* 
         for (int j = 0; j < J; ++j) {
             const int idx = tid + 512 * j;
             const int rl = idx / UW, ul = idx % UW;
-            const int row = row0 + rl, u = u0 + ul;
+            const int row = crow[j], u = u0 + ul;
             const float ig = sigm(gl[0][rl][ul]);
             const float fg = sigm(gl[1][rl][ul]);
             const float gg = tanhf(gl[2][rl][ul]);
@@ -510,7 +559,7 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_cluster_kernel(const float* 
             const float c = fg * creg[j] + ig * gg;
             const float h = og * tanhf(c);
             creg[j] = c;
-            if (row < B) {
+            if (row0 + rl < B) {
                 const size_t o = ((size_t)row * T + t) * LH + u;
                 hs[o] = h;
                 cs[o] = c;
@@ -523,8 +572,9 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_cluster_kernel(const float* 
                 }
             }
         }
-        if (t + 1 < T) cl.signal();  // also the barrier that protects gl for the next step
+        if (t + 1 < steps) cl.signal();  // also the barrier that protects gl for the next step
     }
+    zero_skipped_steps<UW>(hs, LH, 1, u0, order, row0, B, T, steps);
     cl.finish();
 }
 
@@ -534,7 +584,9 @@ __global__ __launch_bounds__(512) void lstm_seq_bwd_cluster_kernel(const float* 
                                                                    const float* __restrict__ cs,
                                                                    const float* __restrict__ w_hh_t,
                                                                    float* __restrict__ dgates, float* px, int* sync,
-                                                                   int B, int T, int tiles) {
+                                                                   int B, int T, int tiles,
+                                                                   const int32_t* __restrict__ order,
+                                                                   const int32_t* __restrict__ tile_steps) {
     constexpr int UW = LH / S;
     constexpr int KB = 4 * UW / 16;     // k blocks of this workgroup's gate columns
     constexpr int J = UW * 16 / 512;
@@ -545,6 +597,7 @@ __global__ __launch_bounds__(512) void lstm_seq_bwd_cluster_kernel(const float* 
     if (tile >= tiles) return;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int row0 = tile * LROWS, u0 = part * UW;
+    const int steps = steps_of_tile(tile_steps, tile, T);  // (one word for the whole tile: see the forward kernel)
     pnmn::Cluster cl;
     cl.start(sync + tile * pnmn::CLUSTER_COUNTER_STRIDE, S);
     float* ptile = px + (size_t)tile * 2 * S * LROWS * LH;  // [parity][source part][16][H]
@@ -562,17 +615,20 @@ __global__ __launch_bounds__(512) void lstm_seq_bwd_cluster_kernel(const float* 
     float dh_rec[J], dc_rec[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) dh_rec[j] = dc_rec[j] = 0.f;
+    int crow[J];  // batch rows of this thread's (row, unit) pairs
+#pragma unroll
+    for (int j = 0; j < J; ++j) crow[j] = batch_row(order, min(row0 + (tid + 512 * j) / UW, B - 1));
 
-    for (int t = T - 1; t >= 0; --t) {
+    for (int t = steps - 1; t >= 0; --t) {
         // everything of step t that does not depend on the recurrence, before the wait
         float ig[J], fg[J], gg[J], og[J], cc[J], cp[J], dho[J];
 #pragma unroll
         for (int j = 0; j < J; ++j) {
             const int idx = tid + 512 * j;
             const int rl = idx / UW, ul = idx % UW;
-            const int row = row0 + rl, u = u0 + ul;
+            const int row = crow[j], u = u0 + ul;
             ig[j] = fg[j] = gg[j] = og[j] = cc[j] = cp[j] = dho[j] = 0.f;
-            if (row < B) {
+            if (row0 + rl < B) {
                 const size_t o = ((size_t)row * T + t) * LH + u;
                 const float* ar = act + ((size_t)row * T + t) * (4 * LH);
                 ig[j] = ar[u], fg[j] = ar[LH + u], gg[j] = ar[2 * LH + u], og[j] = ar[3 * LH + u];
@@ -581,7 +637,7 @@ __global__ __launch_bounds__(512) void lstm_seq_bwd_cluster_kernel(const float* 
                 dho[j] = dhs[o];
             }
         }
-        if (t < T - 1) {
+        if (t < steps - 1) {
             cl.wait();
             const float* pp = ptile + (size_t)((t + 1) & 1) * S * LROWS * LH;
 #pragma unroll
@@ -598,9 +654,9 @@ __global__ __launch_bounds__(512) void lstm_seq_bwd_cluster_kernel(const float* 
         for (int j = 0; j < J; ++j) {
             const int idx = tid + 512 * j;
             const int rl = idx / UW, ul = idx % UW;
-            const int row = row0 + rl, u = u0 + ul;
+            const int row = crow[j], u = u0 + ul;
             float di = 0.f, df = 0.f, dg = 0.f, dout = 0.f, dcp = 0.f;
-            if (row < B) {
+            if (row0 + rl < B) {
                 const float tc = tanhf(cc[j]);
                 const float dh = dho[j] + dh_rec[j];
                 const float dc = dc_rec[j] + dh * og[j] * (1.f - tc * tc);
@@ -645,6 +701,7 @@ __global__ __launch_bounds__(512) void lstm_seq_bwd_cluster_kernel(const float* 
             *reinterpret_cast<f32x4_*>(po + (size_t)li * LH + 16 * (2 * wave + nt) + 4 * g) = acc[nt];
         cl.signal();  // also: everyone is done reading dgl
     }
+    zero_skipped_steps<UW>(dgates, 4 * LH, 4, u0, order, row0, B, T, steps);
     cl.finish();
 }
 
@@ -677,10 +734,13 @@ int pnmn_cluster_reserve_cus(int cus) {
     return pnmn::device_cus();
 }
 
-int pnmn_lstm_seq_fwd(const float* xp, const int64_t* tokens, int64_t token_stride, const float* w_hh, float* hs,
-                      float* cs, float* act, int B, int T, int hidden, void* workspace, void* stream) {
+// `order` / `tile_steps`: both null (rows in batch order, all T steps) or both given (pnmn_length_order's).  With an
+// order a row-range launch moves only the two index arrays: the tensors are addressed by batch row through them.
+static int lstm_seq_fwd_launch(const float* xp, const int64_t* tokens, int64_t token_stride, const float* w_hh, float* hs,
+                               float* cs, float* act, int B, int T, int hidden, const int32_t* order,
+                               const int32_t* tile_steps, void* workspace, void* stream) {
     if (B <= 0 || T <= 0) return 0;
-    if (!xp || !w_hh || !hs || !cs) return PNMN_EINVAL;
+    if (!xp || !w_hh || !hs || !cs || !order != !tile_steps) return PNMN_EINVAL;
     const long tstride = (long)token_stride;
     if (hidden != LH) return PNMN_ESHAPE;
     const int tiles = (B + LROWS - 1) / LROWS;
@@ -697,24 +757,40 @@ int pnmn_lstm_seq_fwd(const float* xp, const int64_t* tokens, int64_t token_stri
             const size_t r0 = (size_t)t0 * LROWS;
             const int rows = (int)((size_t)B - r0 < (size_t)nt * LROWS ? (size_t)B - r0 : (size_t)nt * LROWS);
             const dim3 grid(8 * S * ((nt + 7) / 8));
+            const size_t b0 = order ? 0 : r0;  // first batch row the tensor bases point at
             auto kern = S == 8 ? (tokens ? lstm_seq_fwd_cluster_kernel<8, true> : lstm_seq_fwd_cluster_kernel<8, false>)
                                : (tokens ? lstm_seq_fwd_cluster_kernel<4, true> : lstm_seq_fwd_cluster_kernel<4, false>);
             // (with tokens, xp is the per-token table: only the token rows move with the range)
-            hipLaunchKernelGGL(kern, grid, dim3(512), 0, st, tokens ? xp : xp + r0 * T * (4 * LH),
-                               tokens ? tokens + r0 * tstride : nullptr, tstride, w_hh, hs + r0 * T * LH, cs + r0 * T * LH,
-                               act ? act + r0 * T * (4 * LH) : nullptr, sync, rows, T, nt);
+            hipLaunchKernelGGL(kern, grid, dim3(512), 0, st, tokens ? xp : xp + b0 * T * (4 * LH),
+                               tokens ? tokens + b0 * tstride : nullptr, tstride, w_hh, hs + b0 * T * LH, cs + b0 * T * LH,
+                               act ? act + b0 * T * (4 * LH) : nullptr, sync, rows, T, nt, order ? order + r0 : nullptr,
+                               tile_steps ? tile_steps + t0 : nullptr);
             if ((e = hipGetLastError()) != hipSuccess) return (int)e;
         }
         return 0;
     }
-    hipLaunchKernelGGL(lstm_seq_fwd_kernel, dim3(tiles), dim3(512), 0, st, xp, tokens, tstride, w_hh, hs, cs, act, B, T);
+    hipLaunchKernelGGL(lstm_seq_fwd_kernel, dim3(tiles), dim3(512), 0, st, xp, tokens, tstride, w_hh, hs, cs, act, B, T,
+                       order, tile_steps);
     return (int)hipGetLastError();
 }
 
-int pnmn_lstm_seq_bwd(const float* dhs, const float* act, const float* cs, const float* w_hh_t, float* dgates, int B,
-                      int T, int hidden, void* workspace, void* stream) {
+int pnmn_lstm_seq_fwd(const float* xp, const int64_t* tokens, int64_t token_stride, const float* w_hh, float* hs,
+                      float* cs, float* act, int B, int T, int hidden, void* workspace, void* stream) {
+    return lstm_seq_fwd_launch(xp, tokens, token_stride, w_hh, hs, cs, act, B, T, hidden, nullptr, nullptr, workspace, stream);
+}
+
+int pnmn_lstm_seq_fwd_ordered(const float* xp, const int64_t* tokens, int64_t token_stride, const float* w_hh, float* hs,
+                              float* cs, float* act, int B, int T, int hidden, const int32_t* order,
+                              const int32_t* tile_steps, void* workspace, void* stream) {
+    if (B > 0 && T > 0 && (!order || !tile_steps)) return PNMN_EINVAL;
+    return lstm_seq_fwd_launch(xp, tokens, token_stride, w_hh, hs, cs, act, B, T, hidden, order, tile_steps, workspace, stream);
+}
+
+static int lstm_seq_bwd_launch(const float* dhs, const float* act, const float* cs, const float* w_hh_t, float* dgates, int B,
+                               int T, int hidden, const int32_t* order, const int32_t* tile_steps, void* workspace,
+                               void* stream) {
     if (B <= 0 || T <= 0) return 0;
-    if (!dhs || !act || !cs || !w_hh_t || !dgates) return PNMN_EINVAL;
+    if (!dhs || !act || !cs || !w_hh_t || !dgates || !order != !tile_steps) return PNMN_EINVAL;
     if (hidden != LH) return PNMN_ESHAPE;
     const int tiles = (B + LROWS - 1) / LROWS;
     hipStream_t st = static_cast<hipStream_t>(stream);
@@ -731,14 +807,17 @@ int pnmn_lstm_seq_bwd(const float* dhs, const float* act, const float* cs, const
             const size_t r0 = (size_t)t0 * LROWS;
             const int rows = (int)((size_t)B - r0 < (size_t)nt * LROWS ? (size_t)B - r0 : (size_t)nt * LROWS);
             const dim3 grid(8 * S * ((nt + 7) / 8));
-            const float* d = dhs + r0 * T * LH;
-            const float* a = act + r0 * T * (4 * LH);
-            const float* c = cs + r0 * T * LH;
-            float* dg = dgates + r0 * T * (4 * LH);
+            const size_t b0 = order ? 0 : r0;  // (as in the forward)
+            const float* d = dhs + b0 * T * LH;
+            const float* a = act + b0 * T * (4 * LH);
+            const float* c = cs + b0 * T * LH;
+            float* dg = dgates + b0 * T * (4 * LH);
+            const int32_t* ord = order ? order + r0 : nullptr;
+            const int32_t* ts = tile_steps ? tile_steps + t0 : nullptr;
             if (S == 8)
-                hipLaunchKernelGGL(lstm_seq_bwd_cluster_kernel<8>, grid, dim3(512), 0, st, d, a, c, w_hh_t, dg, px, sync, rows, T, nt);
+                hipLaunchKernelGGL(lstm_seq_bwd_cluster_kernel<8>, grid, dim3(512), 0, st, d, a, c, w_hh_t, dg, px, sync, rows, T, nt, ord, ts);
             else
-                hipLaunchKernelGGL(lstm_seq_bwd_cluster_kernel<4>, grid, dim3(512), 0, st, d, a, c, w_hh_t, dg, px, sync, rows, T, nt);
+                hipLaunchKernelGGL(lstm_seq_bwd_cluster_kernel<4>, grid, dim3(512), 0, st, d, a, c, w_hh_t, dg, px, sync, rows, T, nt, ord, ts);
             if ((e = hipGetLastError()) != hipSuccess) return (int)e;
         }
         return 0;
@@ -746,8 +825,20 @@ int pnmn_lstm_seq_bwd(const float* dhs, const float* act, const float* cs, const
     constexpr size_t lds = (size_t)LROWS * (4 * LH + 4) * sizeof(float);
     static std::atomic<uint64_t> cfg{0};  // (per device: lds_optin.h)
     if (const int e = pnmn::opt_in_lds(reinterpret_cast<const void*>(lstm_seq_bwd_kernel), lds, cfg)) return e;
-    hipLaunchKernelGGL(lstm_seq_bwd_kernel, dim3(tiles), dim3(512), lds, st, dhs, act, cs, w_hh_t, dgates, B, T);
+    hipLaunchKernelGGL(lstm_seq_bwd_kernel, dim3(tiles), dim3(512), lds, st, dhs, act, cs, w_hh_t, dgates, B, T, order, tile_steps);
     return (int)hipGetLastError();
+}
+
+int pnmn_lstm_seq_bwd(const float* dhs, const float* act, const float* cs, const float* w_hh_t, float* dgates, int B,
+                      int T, int hidden, void* workspace, void* stream) {
+    return lstm_seq_bwd_launch(dhs, act, cs, w_hh_t, dgates, B, T, hidden, nullptr, nullptr, workspace, stream);
+}
+
+int pnmn_lstm_seq_bwd_ordered(const float* dhs, const float* act, const float* cs, const float* w_hh_t, float* dgates, int B,
+                              int T, int hidden, const int32_t* order, const int32_t* tile_steps, void* workspace,
+                              void* stream) {
+    if (B > 0 && T > 0 && (!order || !tile_steps)) return PNMN_EINVAL;
+    return lstm_seq_bwd_launch(dhs, act, cs, w_hh_t, dgates, B, T, hidden, order, tile_steps, workspace, stream);
 }
 
 }  // extern "C"

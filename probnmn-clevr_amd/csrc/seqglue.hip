@@ -108,6 +108,56 @@ __global__ __launch_bounds__(256) void mask_last_fwd_kernel(const float* __restr
     }
 }
 
+// ---- rows ordered by length ------------------------------------------------------------------------------
+// steps[b] = clamp(last[b] + 1, 1, T);  order = the rows sorted by steps, longest first, equal lengths in row order;
+// tile_steps[i] = steps of order[16 i], the longest row of the i-th 16-row tile of that order.  What the recurrent
+// layer kernels group their row tiles by (pnmn_lstm_seq_fwd_ordered), so that a tile stops at its rows' length.
+// A counting sort in ONE wave: the histogram's integer adds commute, and the placement walks the rows 64 at a time
+// in row order -- a row's slot is its bucket's next free one plus the rows of the same length on lower lanes, and
+// the last lane of a length moves the bucket on -- so the result does not depend on any timing.
+constexpr int LO_MAX_T = 4096;  // buckets (LDS words)
+__global__ __launch_bounds__(64) void length_order_kernel(const int32_t* __restrict__ last, int B, int T,
+                                                          int32_t* __restrict__ order, int32_t* __restrict__ tile_steps) {
+    extern __shared__ int first[];  // [T + 1]: rows of `s` steps, then the first free slot of their bucket
+    const int lane = threadIdx.x;
+    for (int s = lane; s <= T; s += 64) first[s] = 0;
+    __syncthreads();
+    for (int b = lane; b < B; b += 64) atomicAdd(&first[min(max(last[b] + 1, 1), T)], 1);
+    __syncthreads();
+    int carry = 0;  // exclusive prefix sums from the longest bucket down, 64 buckets a round
+    for (int top = T; top >= 1; top -= 64) {
+        const int s = top - lane;
+        const int n = s >= 1 ? first[s] : 0;
+        int incl = n;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(incl, o);
+            if (lane >= o) incl += v;
+        }
+        if (s >= 1) first[s] = carry + incl - n;
+        carry += __shfl(incl, 63);
+    }
+    __syncthreads();
+    for (int b0 = 0; b0 < B; b0 += 64) {
+        const int b = b0 + lane;
+        const int s = b < B ? min(max(last[b] + 1, 1), T) : 0;  // 0: no row on this lane
+        int before = 0, after = 0;
+        for (int j = 0; j < 64; ++j) {
+            const int sj = __shfl(s, j);
+            before += (sj == s && j < lane);
+            after += (sj == s && j > lane);
+        }
+        const int pos = s ? first[s] + before : 0;
+        __syncthreads();  // every lane has read its bucket's slot before any bucket moves on
+        if (s) {
+            order[pos] = b;
+            if ((pos & 15) == 0) tile_steps[pos >> 4] = s;
+            if (after == 0) first[s] = pos + 1;
+        }
+        __syncthreads();
+    }
+}
+
 //   dhs[b][t] = (denc[b][t] + [t == last[b]] dhlast[b]) * fmask[b][t]        (denc / dhlast may be null)
 __global__ __launch_bounds__(256) void mask_last_bwd_kernel(const float* __restrict__ denc, const float* __restrict__ dhlast,
                                                             const float* __restrict__ fmask, const int* __restrict__ last,
@@ -389,6 +439,15 @@ extern "C" int pnmn_token_prep(const int64_t* tokens, int64_t token_row_stride, 
     if (!tokens || !out || T < 0) return PNMN_EINVAL;
     hipLaunchKernelGGL(token_prep_kernel, dim3((B + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), tokens,
                        token_row_stride, B, T, pad, bos, eos, drop_first, out, fmask, last);
+    return (int)hipGetLastError();
+}
+
+extern "C" int pnmn_length_order(const int32_t* last, int B, int T, int32_t* order, int32_t* tile_steps, void* stream) {
+    if (B <= 0) return 0;
+    if (!last || !order || !tile_steps || T <= 0) return PNMN_EINVAL;
+    if (T > LO_MAX_T) return PNMN_ESHAPE;
+    hipLaunchKernelGGL(length_order_kernel, dim3(1), dim3(64), (size_t)(T + 1) * sizeof(int), static_cast<hipStream_t>(stream),
+                       last, B, T, order, tile_steps);
     return (int)hipGetLastError();
 }
 

@@ -430,16 +430,36 @@ def _decoder_workspace(rows, backward: bool, device) -> Optional[torch.Tensor]:
     return torch.empty(n, dtype=torch.uint8, device=device) if n > 0 else None
 
 
+def lstm_length_order_enabled() -> bool:
+    """PNMN_LSTM_LENGTH_ORDER=0: the layer kernels run every row over all T steps (the unordered entry points), for A/B
+    runs; by default rows with a known length are grouped by it and a tile stops at its longest row."""
+    return os.environ.get("PNMN_LSTM_LENGTH_ORDER", "1") != "0"
+
+
+def length_order(last: torch.Tensor, T: int):
+    """``pnmn_length_order``: (order [B], tile_steps [ceil(B/16)]), both int32, of the rows whose last valid step is
+    ``last`` ([B] int32, as ``pnmn_token_prep`` writes it) in a pass of ``T`` steps; no host synchronisation."""
+    B = last.size(0)
+    order = torch.empty(B, dtype=torch.int32, device=last.device)
+    tile_steps = torch.empty((B + 15) // 16, dtype=torch.int32, device=last.device)
+    _hip.check(_hip.lib().pnmn_length_order(last.data_ptr(), B, T, order.data_ptr(), tile_steps.data_ptr(),
+                                            _hip.stream_ptr(last.device)), "length_order")
+    return order, tile_steps
+
+
 class _LSTMLayerSeq(torch.autograd.Function):
     """The recurrent half of one LSTM layer over a whole padded sequence, as ONE persistent kernel
     launch (``pnmn_lstm_seq_fwd`` / ``_bwd``): (xp [B,T,4H] = input projection + biases, W_hh) -> all
     hidden states [B,T,H].  The weight gradient of W_hh is one GEMM over the saved states.
     With ``tokens`` ([B,T] int64): ``xp`` is the [V,4H] per-token table of ``_TokenTable`` and the kernel reads
     row ``tokens[b,t]`` of it -- ``F.embedding(tokens, table)`` is never written out; its gradient is the
-    per-token sum of ``pnmn_embedding_grad`` over the gate gradients."""
+    per-token sum of ``pnmn_embedding_grad`` over the gate gradients.
+    With ``order`` / ``tile_steps`` (``length_order``): the ``_ordered`` entry points -- row tiles grouped by length, each
+    run to its longest row; the output is zero from there on, and the caller's gradient must be zero past each row's
+    length (what ``_MaskAndLast`` gives)."""
 
     @staticmethod
-    def forward(ctx, xp, w_hh, wp=None, w_t=None, tokens=None):
+    def forward(ctx, xp, w_hh, wp=None, w_t=None, tokens=None, order=None, tile_steps=None):
         if xp.device.type != "cuda":
             raise _hip.HipLibraryError("LSTM layer on %s: the HIP path needs a ROCm device (no CPU fallback)" % xp.device)
         xp, w = xp.contiguous(), w_hh.detach()
@@ -457,12 +477,16 @@ class _LSTMLayerSeq(torch.autograd.Function):
             wp = pack_fragments(w)
         ctx.w_t = w_t  # (fragment order of W_hh^T from the model's DerivedParams, else packed in backward)
         ctx.tokens, ctx.vocab = tokens, xp.size(0)
+        ctx.order = (order, tile_steps) if order is not None else None
         ws = _lstm_workspace(B, False, xp.device)
-        _hip.check(_hip.lib().pnmn_lstm_seq_fwd(xp.data_ptr(), tokens.data_ptr() if tokens is not None else None,
-                                                tokens.stride(0) if tokens is not None else 0, wp.data_ptr(),
-                                                hs.data_ptr(), cs.data_ptr(), act.data_ptr(),
-                                                B, T, Hd, ws.data_ptr() if ws is not None else None,
-                                                _hip.stream_ptr(xp.device)), "lstm_seq_fwd")
+        args = (xp.data_ptr(), tokens.data_ptr() if tokens is not None else None, tokens.stride(0) if tokens is not None else 0,
+                wp.data_ptr(), hs.data_ptr(), cs.data_ptr(), act.data_ptr(), B, T, Hd)
+        tail = (ws.data_ptr() if ws is not None else None, _hip.stream_ptr(xp.device))
+        if order is not None:
+            _hip.check(_hip.lib().pnmn_lstm_seq_fwd_ordered(*args, order.data_ptr(), tile_steps.data_ptr(), *tail),
+                       "lstm_seq_fwd_ordered")
+        else:
+            _hip.check(_hip.lib().pnmn_lstm_seq_fwd(*args, *tail), "lstm_seq_fwd")
         ctx.save_for_backward(hs, cs, act, w)
         return hs
 
@@ -474,9 +498,13 @@ class _LSTMLayerSeq(torch.autograd.Function):
         w_t = ctx.w_t if ctx.w_t is not None else pack_fragments(w.t())  # W_hh^T [H][4H], fragment order
         dgates = torch.empty_like(act)
         ws = _lstm_workspace(B, True, hs.device)
-        _hip.check(_hip.lib().pnmn_lstm_seq_bwd(dhs.data_ptr(), act.data_ptr(), cs.data_ptr(), w_t.data_ptr(),
-                                                dgates.data_ptr(), B, T, Hd, ws.data_ptr() if ws is not None else None,
-                                                _hip.stream_ptr(hs.device)), "lstm_seq_bwd")
+        args = (dhs.data_ptr(), act.data_ptr(), cs.data_ptr(), w_t.data_ptr(), dgates.data_ptr(), B, T, Hd)
+        tail = (ws.data_ptr() if ws is not None else None, _hip.stream_ptr(hs.device))
+        if ctx.order is not None:
+            _hip.check(_hip.lib().pnmn_lstm_seq_bwd_ordered(*args, ctx.order[0].data_ptr(), ctx.order[1].data_ptr(), *tail),
+                       "lstm_seq_bwd_ordered")
+        else:
+            _hip.check(_hip.lib().pnmn_lstm_seq_bwd(*args, *tail), "lstm_seq_bwd")
         dw_hh = None
         if ctx.needs_input_grad[1]:
             hprev = torch.cat((hs.new_zeros(B, 1, Hd), hs[:, :-1]), 1).reshape(B * T, Hd)  # h_{t-1} per (row, step)
@@ -484,7 +512,7 @@ class _LSTMLayerSeq(torch.autograd.Function):
         dxp = dgates
         if ctx.tokens is not None:
             dxp = _table_grad(dgates, ctx.tokens, ctx.vocab) if ctx.needs_input_grad[0] else None
-        return dxp, dw_hh, None, None, None
+        return dxp, dw_hh, None, None, None, None, None
 
 
 class _LSTMDropout(torch.autograd.Function):
@@ -890,8 +918,10 @@ def masked_lstm(lstm: nn.LSTM, x: torch.Tensor, mask: torch.Tensor, first_projec
                 first_tokens: Optional[torch.Tensor] = None, dropout_seed: Optional[int] = None, row_offset: int = 0,
                 dropout: bool = True):
     """``PytorchSeq2SeqWrapper(nn.LSTM)(x, mask)``: zero initial state, outputs zero past each row's
-    length.  Rows are run over all T steps (a unidirectional state never sees later steps) with the
-    input GEMM batched over time and the recurrence in one persistent HIP kernel per layer.
+    length.  The input GEMM is batched over time and the recurrence is one persistent HIP kernel per layer.  Without
+    ``last`` rows are run over all T steps (a unidirectional state never sees later steps); with it (and hidden size 256)
+    the layers' row tiles are grouped by length and each runs to its longest row (``length_order``; one order for all
+    layers and both directions; PNMN_LSTM_LENGTH_ORDER=0: all T steps as before).
     ``first_projection``: the first layer's input projection when the caller already has it
     ; ``x`` is then unused -- with ``first_tokens`` it is the [V,4H] per-token TABLE and the
     layer kernel looks the rows up itself.  ``derived``: the model's ``DerivedParams`` output (packed
@@ -905,6 +935,9 @@ def masked_lstm(lstm: nn.LSTM, x: torch.Tensor, mask: torch.Tensor, first_projec
         dropout_seed = None
     elif dropout_seed is None:
         dropout_seed = lstm_dropout_seed(lstm)
+    order = tile_steps = None
+    if last is not None and lstm.hidden_size == 256 and lstm_length_order_enabled():
+        order, tile_steps = length_order(last, T)
     for layer in range(lstm.num_layers):
         w_ih = getattr(lstm, "weight_ih_l%d" % layer)
         w_hh = getattr(lstm, "weight_hh_l%d" % layer)
@@ -921,9 +954,9 @@ def masked_lstm(lstm: nn.LSTM, x: torch.Tensor, mask: torch.Tensor, first_projec
         if lstm.hidden_size == 256:
             # one persistent launch for all T steps
             if derived is not None:
-                inp = _LSTMLayerSeq.apply(xp, w_hh, derived["l%d.hh" % layer], derived["l%d.hhT" % layer], tokens)
+                inp = _LSTMLayerSeq.apply(xp, w_hh, derived["l%d.hh" % layer], derived["l%d.hhT" % layer], tokens, order, tile_steps)
             else:
-                inp = _LSTMLayerSeq.apply(xp, w_hh, None, None, tokens)
+                inp = _LSTMLayerSeq.apply(xp, w_hh, None, None, tokens, order, tile_steps)
         else:  # other widths: step by step (GEMM per step + the cell kernel)
             _note_slow_path("LSTM layer", "hidden size %d (the persistent layer kernel is built for 256)" % lstm.hidden_size)
             h = xp.new_zeros(B, lstm.hidden_size)

@@ -46,6 +46,11 @@ USE_STACK = True
 STACK_FWD_ENCODERS = int(os.environ.get("PNMN_PLAN_FWD_ENC", "2"))
 STACK_PG_ENCODER = int(os.environ.get("PNMN_PLAN_PG_ENC", "1"))
 STACK_BWD_ENCODERS = int(os.environ.get("PNMN_PLAN_BWD_ENC", "0"))
+#: rows of an encoder pass above which its per-layer launches group their row tiles by length (pnmn_length_order,
+#: pnmn_lstm_seq_*_ordered): the passes too large for the wavefront launches.  Up to 256 rows a pass runs as a wavefront,
+#: whose job record has no room for an order, and its per-layer form (USE_STACK = False) stays the A/B partner of that, call
+#: for call.  PNMN_LSTM_LENGTH_ORDER=0 (read when a plan is built) keeps every pass on the unordered calls.
+LENGTH_ORDER_ABOVE_ROWS = 256
 #: the per-model decoder buffers, [flat sequence rows of all the model's passes][width]
 DECODER_BUFFERS = (("hs", 256), ("cs", 256), ("cx", 256), ("act", 1024), ("dhs", 256), ("dg", 1024), ("dctx", 256))
 
@@ -324,6 +329,10 @@ class Seq2SeqPlan:
             e["hsd"] = f(tag + ".hsd", rows, T, 256)
         calls.add("pnmn_token_prep", ep.tokens.data_ptr(), ep.tokens.stride(0), rows, ep.width, model._pad_index, model._start_index,
                   model._end_index, int(ep.drop_first), e["src"].data_ptr(), e["fmask"].data_ptr(), e["last"].data_ptr(), self.stream)
+        if rows > LENGTH_ORDER_ABOVE_ROWS and os.environ.get("PNMN_LSTM_LENGTH_ORDER", "1") != "0":
+            # the pass's rows grouped by length: one order for both layers, forward and backward
+            e["order"], e["tile_steps"] = f(tag + ".order", rows, dtype=torch.int32), f(tag + ".tile_steps", (rows + 15) // 16, dtype=torch.int32)
+            calls.add("pnmn_length_order", e["last"].data_ptr(), rows, T, e["order"].data_ptr(), e["tile_steps"].data_ptr(), self.stream)
         self._table_forward(calls, e["tab"])
         if ep.want_last:
             e["enc"], e["h"] = f(tag + ".enc", rows, T, 256), f(tag + ".h", rows, 256)
@@ -415,16 +424,17 @@ class Seq2SeqPlan:
             d, lstm, rows, T = e["derived"], e["lstm"], e["rows"], e["T"]
             xp2 = self.buf(e["tag"] + ".xp2", rows, T, 1024)
             ws = self.bytes_buf(e["tag"] + ".lstm_ws", lib.pnmn_lstm_seq_workspace_bytes(rows, 0))
-            calls.add("pnmn_lstm_seq_fwd", e["table"].data_ptr(), e["src"].data_ptr(), e["src"].stride(0), d["l0.hh"].data_ptr(),
-                      e["hs1"].data_ptr(), e["cs1"].data_ptr(), e["act1"].data_ptr(), rows, T, 256, ws.data_ptr(), st)
+            fwd, ordered = ("pnmn_lstm_seq_fwd_ordered", (e["order"].data_ptr(), e["tile_steps"].data_ptr())) if "order" in e else ("pnmn_lstm_seq_fwd", ())
+            calls.add(fwd, e["table"].data_ptr(), e["src"].data_ptr(), e["src"].stride(0), d["l0.hh"].data_ptr(),
+                      e["hs1"].data_ptr(), e["cs1"].data_ptr(), e["act1"].data_ptr(), rows, T, 256, *ordered, ws.data_ptr(), st)
             x2 = e["hs1"]
             if e["p"] > 0:
                 self._dropout_call(calls, e, e["hs1"], e["hsd"])
                 x2 = e["hsd"]
             self._gemm(calls, e["tag"] + ".xp2g", [dict(a=x2.data_ptr(), b=lstm.weight_ih_l1.data_ptr(), c=xp2.data_ptr(), M=rows * T,
                                                         N=1024, K=256, lda=256, ldb=256, ldc=1024, tb=1, bias=d["l1.b"].data_ptr())])
-            calls.add("pnmn_lstm_seq_fwd", xp2.data_ptr(), None, 0, d["l1.hh"].data_ptr(), e["hs2"].data_ptr(), e["cs2"].data_ptr(),
-                      e["act2"].data_ptr(), rows, T, 256, ws.data_ptr(), st)
+            calls.add(fwd, xp2.data_ptr(), None, 0, d["l1.hh"].data_ptr(), e["hs2"].data_ptr(), e["cs2"].data_ptr(),
+                      e["act2"].data_ptr(), rows, T, 256, *ordered, ws.data_ptr(), st)
         for e in encs:
             if e["want_last"]:
                 calls.add("pnmn_mask_last_fwd", e["hs2"].data_ptr(), e["fmask"].data_ptr(), e["last"].data_ptr(), e["rows"], e["T"], 256,
@@ -444,14 +454,15 @@ class Seq2SeqPlan:
             d, lstm, tag, rows, T = e["derived"], e["lstm"], e["tag"], e["rows"], e["T"]
             dhs1 = f(tag + ".dhs1", rows, T, 256)
             ws = self.bytes_buf(tag + ".lstm_bws", lib.pnmn_lstm_seq_workspace_bytes(rows, 1))
-            calls.add("pnmn_lstm_seq_bwd", e["dhs2"].data_ptr(), e["act2"].data_ptr(), e["cs2"].data_ptr(), d["l1.hhT"].data_ptr(),
-                      e["dg2"].data_ptr(), rows, T, 256, ws.data_ptr(), st)
+            bwd, ordered = ("pnmn_lstm_seq_bwd_ordered", (e["order"].data_ptr(), e["tile_steps"].data_ptr())) if "order" in e else ("pnmn_lstm_seq_bwd", ())
+            calls.add(bwd, e["dhs2"].data_ptr(), e["act2"].data_ptr(), e["cs2"].data_ptr(), d["l1.hhT"].data_ptr(),
+                      e["dg2"].data_ptr(), rows, T, 256, *ordered, ws.data_ptr(), st)
             self._gemm(calls, tag + ".dx", [dict(a=e["dg2"].data_ptr(), b=lstm.weight_ih_l1.data_ptr(), c=dhs1.data_ptr(), M=rows * T, N=256,
                                                  K=1024, lda=1024, ldb=256, ldc=256, split="auto")])
             if e["p"] > 0:
                 self._dropout_call(calls, e, dhs1, dhs1)
-            calls.add("pnmn_lstm_seq_bwd", dhs1.data_ptr(), e["act1"].data_ptr(), e["cs1"].data_ptr(), d["l0.hhT"].data_ptr(),
-                      e["dg1"].data_ptr(), rows, T, 256, ws.data_ptr(), st)
+            calls.add(bwd, dhs1.data_ptr(), e["act1"].data_ptr(), e["cs1"].data_ptr(), d["l0.hhT"].data_ptr(),
+                      e["dg1"].data_ptr(), rows, T, 256, *ordered, ws.data_ptr(), st)
 
     def _encoders_param_grads(self, calls: _Calls, deferred: List, encs: List[Dict]) -> None:
         """The encoders' parameter gradients from what the chain left behind (dgates of both layers): the table's rows and the
