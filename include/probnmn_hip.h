@@ -23,6 +23,9 @@
  *   - a record is one `typedef struct [tag] { ... } pnmn_x;` of pointers, fixed-width scalars (int32_t, uint32_t,
  *     int64_t, uint64_t, float, double) and arrays of them -- no nested records, unions or bit fields
  *   - scalar parameters are int, int32_t, uint32_t, int64_t, uint64_t, float or double; anything with a `*` is a pointer
+ *   - a host argument block -- a few scalars the caller fills in HOST memory and an entry point reads before it returns,
+ *     never an element of a device work list -- is a plain `struct pnmn_x { ... };` of the same field kinds, named
+ *     `struct pnmn_x` in prototypes; the binding derives its dtype too, beside the records, not among them
  *   - a constant is `#define PNMN_NAME <integer>` or `(<negative integer>)`
  * A pnmn_ declaration written any other way makes the import fail with its text (tests/test_abi.py).
  */
@@ -650,6 +653,47 @@ int pnmn_attn_denc(const float* weights, const float* dscore, const float* dctx,
 int pnmn_sample_tokens(const float* logits, int64_t* tokens, float* logprobs, int B, int V,
                        int greedy, uint64_t seed, uint64_t row_offset, uint32_t step, int pad_index,
                        int unk_index, int start_index, void* stream);
+
+/* Sampling under a filter: temperature, top-k and nucleus (top-p) truncation of the distribution a token is drawn from.
+ * A filter is (temperature, top_k, top_p); (1, 0, 1) is the identity.  It applies to sampling only: a greedy choice and
+ * a teacher-forced pass ignore it.  For one row of logits z[0..V):
+ *   A      = every index but pad, unk and start (the allowed set, as above)
+ *   s_j    = z_j / temperature, w_j = exp(s_j - max_A s)                                  for j in A
+ *   rank   j ranks before i when w_j > w_i, or w_j == w_i and j < i                       (within A)
+ *   top_k > 0: keep the top_k first-ranked indices (top_k >= |A| keeps all of A)
+ *   top_p < 1: of those, keep i iff the summed weight of the kept indices ranked before i is < top_p * total, total = the
+ *              weight top-k kept; the first-ranked index is always kept
+ *   draw   inverse CDF in INDEX order over the kept weights, from the uniform pnmn_sample_tokens draws: Philox4x32-10,
+ *          counter (row_offset + row, step) -- a filtered and an unfiltered decode from one seed share their random numbers
+ *   logprobs (and any loss built from them) stay log_softmax(z)[token] of the UNMODIFIED distribution, as the reference
+ *          already scores a draw from which pad / unk / start were removed (seq2seq_base.py:204,220)
+ * A row that holds a NaN or +inf, or whose allowed weights sum to 0 in the unfiltered rule, follows that rule's fallback
+ * unchanged and ignores the filter; a token is always in [0, V).  With the identity filter each entry point below runs
+ * the kernel of its unfiltered counterpart: the same output, bit for bit.  Each returns PNMN_EINVAL and launches nothing
+ * for a null filter, a temperature that is not finite or <= 0, top_k < 0, or a top_p outside (0, 1] (NaN included).
+ * The filters are HOST memory, read before the call returns, and travel by value in the launch arguments: no device
+ * allocation, no copy, no synchronisation.  Otherwise: the arguments, limits and return codes of the counterpart.
+ * pnmn_attn_lstm_fwd_group_filtered: filters[i] belongs to jobs[i] and applies when that job's sample == 1; for any
+ * other job it is checked and ignored.  The fit and fall-back rule of pnmn_attn_lstm_fwd_group is unchanged. */
+struct pnmn_sampling_filter {
+    float temperature;
+    int32_t top_k;
+    float top_p;
+    int32_t reserved;
+};                         /* 16 bytes; a host argument block (see the declaration conventions), not a work-item record */
+int pnmn_sample_tokens_filtered(const float* logits, int64_t* tokens, float* logprobs, int B, int V,
+                                int greedy, uint64_t seed, uint64_t row_offset, uint32_t step, int pad_index,
+                                int unk_index, int start_index, const struct pnmn_sampling_filter* filter /* HOST */,
+                                void* stream);
+int pnmn_attn_lstm_fwd_filtered(const float* xe, const float* etable, const float* enc, const float* mask,
+                                const float* h0, const float* w_c, const float* w_hh, const float* w_p,
+                                const float* b_p, float* hs, float* cs, float* act, float* ctx, float* probs,
+                                int64_t* tokens, int B, int T, int S, int V, int hidden, int sample,
+                                int pad_index, int unk_index, int start_index, uint64_t seed,
+                                uint64_t row_offset, const int64_t* in_tokens, int64_t in_token_stride,
+                                const struct pnmn_sampling_filter* filter /* HOST */, void* stream);
+int pnmn_attn_lstm_fwd_group_filtered(const pnmn_decoder_fwd_job* jobs, const struct pnmn_sampling_filter* filters /* HOST, one per job */,
+                                      int n, int hidden, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Host-side launch sequencer (no device work of its own): `list` is a HOST array; entry i calls the entry

@@ -69,7 +69,10 @@ struct FwdArgs {
     uint64_t seed, row_offset;
 };
 
-__global__ __launch_bounds__(512) void attn_lstm_fwd_kernel(const FwdArgs a) {
+// FILT: the sampling mode draws under the filter `f` (sampling.h); its weights take the place of the row's logits in `logl`,
+// which nothing reads between the choice and the next step's logits tile.  Both instantiations take `f`; only FILT reads it.
+template <bool FILT>
+__global__ __launch_bounds__(512) void attn_lstm_fwd_kernel(const FwdArgs a, const pnmn::SamplingFilter f) {
     __shared__ __attribute__((aligned(16))) float hl[2][ROWS][LD];
     __shared__ __attribute__((aligned(16))) float cl[ROWS][LD];
     __shared__ float wl[ROWS][MAXS];
@@ -210,8 +213,8 @@ __global__ __launch_bounds__(512) void attn_lstm_fwd_kernel(const FwdArgs a) {
                 const int rl = 2 * wave + rr;
                 const int row = row0 + rl;
                 if (row >= a.B) continue;
-                const int choice = pnmn::choose_row_token(logl[rl], V, a.sample, a.pad, a.unk, a.start, a.seed,
-                                                          a.row_offset + (uint64_t)row, (uint32_t)t);
+                const int choice = pnmn::choose_row_token<FILT>(logl[rl], V, a.sample, a.pad, a.unk, a.start, a.seed,
+                                                                a.row_offset + (uint64_t)row, (uint32_t)t, logl[rl], f);
                 if (lane == 0) {
                     tokl[rl] = choice;
                     a.tokens[(size_t)row * T + t] = choice;
@@ -397,20 +400,50 @@ __global__ __launch_bounds__(512) void attn_lstm_bwd_kernel(const BwdArgs a) {
 
 extern "C" {
 
-int pnmn_attn_lstm_fwd(const float* xe, const float* etable, const float* enc, const float* mask, const float* h0,
-                       const float* w_c, const float* w_hh, const float* w_p, const float* b_p, float* hs, float* cs,
-                       float* act, float* ctx, float* probs, int64_t* tokens, int B, int T, int S, int V, int hidden,
-                       int sample, int pad_index, int unk_index, int start_index, uint64_t seed, uint64_t row_offset,
-                       const int64_t* in_tokens, int64_t in_token_stride, void* stream) {
+// `filter`: null (pnmn_attn_lstm_fwd) or a filter to check; it applies to a sampling pass unless it is the identity
+static int attn_lstm_fwd_launch(const float* xe, const float* etable, const float* enc, const float* mask, const float* h0,
+                                const float* w_c, const float* w_hh, const float* w_p, const float* b_p, float* hs, float* cs,
+                                float* act, float* ctx, float* probs, int64_t* tokens, int B, int T, int S, int V, int hidden,
+                                int sample, int pad_index, int unk_index, int start_index, uint64_t seed, uint64_t row_offset,
+                                const int64_t* in_tokens, int64_t in_token_stride, const pnmn_sampling_filter* filter,
+                                void* stream) {
+    if (filter && !pnmn::filter_valid(filter)) return PNMN_EINVAL;
     if (B <= 0 || T <= 0) return 0;
     if (!enc || !mask || !h0 || !w_c || !w_hh || !hs || !cs || !act || !ctx || !probs) return PNMN_EINVAL;
     if (sample ? (!etable || !w_p || !b_p || !tokens) : (!xe && !(etable && in_tokens))) return PNMN_EINVAL;
     if (hidden != H || S < 1 || S > MAXS || (sample && (V < 1 || V > MAXV))) return PNMN_ESHAPE;
     FwdArgs a{xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, hs, cs, act, ctx, probs, tokens, (!sample && !xe) ? in_tokens : nullptr,
               (long)in_token_stride, B, T, S, V, sample, pad_index, unk_index, start_index, seed, row_offset};
-    hipLaunchKernelGGL(attn_lstm_fwd_kernel, dim3((B + ROWS - 1) / ROWS), dim3(512), 0,
-                       static_cast<hipStream_t>(stream), a);
+    const dim3 grid((B + ROWS - 1) / ROWS);
+    if (filter && sample == 1 && !pnmn::filter_is_identity(*filter))
+        hipLaunchKernelGGL(attn_lstm_fwd_kernel<true>, grid, dim3(512), 0, static_cast<hipStream_t>(stream), a,
+                           pnmn::SamplingFilter{filter->temperature, filter->top_k, filter->top_p});
+    else
+        hipLaunchKernelGGL(attn_lstm_fwd_kernel<false>, grid, dim3(512), 0, static_cast<hipStream_t>(stream), a,
+                           pnmn::SamplingFilter{1.f, 0, 1.f});
     return (int)hipGetLastError();
+}
+
+int pnmn_attn_lstm_fwd(const float* xe, const float* etable, const float* enc, const float* mask, const float* h0,
+                       const float* w_c, const float* w_hh, const float* w_p, const float* b_p, float* hs, float* cs,
+                       float* act, float* ctx, float* probs, int64_t* tokens, int B, int T, int S, int V, int hidden,
+                       int sample, int pad_index, int unk_index, int start_index, uint64_t seed, uint64_t row_offset,
+                       const int64_t* in_tokens, int64_t in_token_stride, void* stream) {
+    return attn_lstm_fwd_launch(xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, hs, cs, act, ctx, probs, tokens, B, T, S, V, hidden,
+                                sample, pad_index, unk_index, start_index, seed, row_offset, in_tokens, in_token_stride, nullptr,
+                                stream);
+}
+
+int pnmn_attn_lstm_fwd_filtered(const float* xe, const float* etable, const float* enc, const float* mask, const float* h0,
+                                const float* w_c, const float* w_hh, const float* w_p, const float* b_p, float* hs, float* cs,
+                                float* act, float* ctx, float* probs, int64_t* tokens, int B, int T, int S, int V, int hidden,
+                                int sample, int pad_index, int unk_index, int start_index, uint64_t seed, uint64_t row_offset,
+                                const int64_t* in_tokens, int64_t in_token_stride, const pnmn_sampling_filter* filter,
+                                void* stream) {
+    if (!pnmn::filter_valid(filter)) return PNMN_EINVAL;
+    return attn_lstm_fwd_launch(xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, hs, cs, act, ctx, probs, tokens, B, T, S, V, hidden,
+                                sample, pad_index, unk_index, start_index, seed, row_offset, in_tokens, in_token_stride, filter,
+                                stream);
 }
 
 int pnmn_attn_lstm_bwd(const float* dhs, const float* act, const float* cs, const float* hs, const float* ctx,

@@ -88,8 +88,11 @@ constexpr size_t FWD_OVERLAP_LDS = sizeof(float) * (ROWS * H + 64);  // (OVERLAP
 // products behind the hand-off, their A operands double buffered in the 16 KB that `cpart` and `logl` leave idle there.
 // SAMPLE: the free-running modes (the kernel picks each step's token); a teacher-forced pass compiles without the token
 // phase -- its logits tile, Philox draw and the pointers they keep live are what the register allocator spills.
-template <bool OVERLAP, bool SAMPLE>
-__device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, const int tile, const int part) {
+// FILT (with SAMPLE): mode 1 draws under the filter `f` (sampling.h); the weights take the place of the row's logits in `logl`,
+// dead by then.  Every member repeats the choice and gets the same token: it is a pure function of the row and the filter.
+template <bool OVERLAP, bool SAMPLE, bool FILT = false>
+__device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, const int tile, const int part,
+                                                         const pnmn::SamplingFilter& f = pnmn::SamplingFilter{1.f, 0, 1.f}) {
     extern __shared__ __attribute__((aligned(16))) char raw[];
     const int T = a.T, S = a.S;
     float* encl = reinterpret_cast<float*>(raw);                                       // [RW][S][H]
@@ -441,8 +444,8 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
                 const int rl = 2 * wave + rr;
                 const int row = row0 + rl;
                 if (row >= a.B) continue;
-                const int choice = pnmn::choose_row_token(logl[rl], V, a.sample, a.pad, a.unk, a.start, a.seed,
-                                                          a.row_offset + (uint64_t)row, (uint32_t)t);
+                const int choice = pnmn::choose_row_token<FILT>(logl[rl], V, a.sample, a.pad, a.unk, a.start, a.seed,
+                                                                a.row_offset + (uint64_t)row, (uint32_t)t, logl[rl], f);
                 if (lane == 0) {
                     tokl[rl] = choice;
                     if (part == 0) a.tokens[(size_t)row * T + t] = choice;
@@ -482,6 +485,32 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         tile -= tiles0;
         if (tile >= a1.tiles) return;
         attn_lstm_fwd_multi_body<OVERLAP, SAMPLE1>(a1, tile, part);
+    }
+}
+
+// The same two kernels with a sampling filter per free-running pass.  M: 0 teacher forced, 1 free running, 2 sampling under
+// its filter.  Kernels of their own, so that the unfiltered ones keep their arguments and their code.
+template <bool OVERLAP>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_lstm_fwd_multi_filtered_kernel(
+    const MFwdArgs a, const pnmn::SamplingFilter f) {
+    int tile, part;
+    pnmn::cluster_coords<MEMBERS>(tile, part);
+    if (tile >= a.tiles) return;
+    attn_lstm_fwd_multi_body<OVERLAP, true, true>(a, tile, part, f);
+}
+
+template <bool OVERLAP, int M0, int M1>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_lstm_fwd_pair_filtered_kernel(
+    const MFwdArgs a0, const MFwdArgs a1, const int tiles0, const pnmn::SamplingFilter f0, const pnmn::SamplingFilter f1) {
+    int tile, part;
+    pnmn::cluster_coords<MEMBERS>(tile, part);
+    if (tile < tiles0) {
+        if (tile >= a0.tiles) return;
+        attn_lstm_fwd_multi_body<OVERLAP, M0 != 0, M0 == 2>(a0, tile, part, f0);
+    } else {
+        tile -= tiles0;
+        if (tile >= a1.tiles) return;
+        attn_lstm_fwd_multi_body<OVERLAP, M1 != 0, M1 == 2>(a1, tile, part, f1);
     }
 }
 
@@ -867,6 +896,23 @@ const void* fwd_pair_variant(bool overlap, bool s0, bool s1) {
     return overlap ? fwd_pair_variant_of<true>(s0, s1) : fwd_pair_variant_of<false>(s0, s1);
 }
 
+// the variants with a filter: m0 / m1 as the kernel's M0 / M1, at least one of them 2
+const void* fwd_multi_filtered_variant(bool overlap) {
+    return overlap ? reinterpret_cast<const void*>(attn_lstm_fwd_multi_filtered_kernel<true>)
+                   : reinterpret_cast<const void*>(attn_lstm_fwd_multi_filtered_kernel<false>);
+}
+template <bool OVERLAP>
+const void* fwd_pair_filtered_variant_of(int m0, int m1) {
+    if (m0 == 2) return m1 == 2 ? reinterpret_cast<const void*>(attn_lstm_fwd_pair_filtered_kernel<OVERLAP, 2, 2>)
+                       : m1 == 1 ? reinterpret_cast<const void*>(attn_lstm_fwd_pair_filtered_kernel<OVERLAP, 2, 1>)
+                                 : reinterpret_cast<const void*>(attn_lstm_fwd_pair_filtered_kernel<OVERLAP, 2, 0>);
+    return m0 == 1 ? reinterpret_cast<const void*>(attn_lstm_fwd_pair_filtered_kernel<OVERLAP, 1, 2>)
+                   : reinterpret_cast<const void*>(attn_lstm_fwd_pair_filtered_kernel<OVERLAP, 0, 2>);
+}
+const void* fwd_pair_filtered_variant(bool overlap, int m0, int m1) {
+    return overlap ? fwd_pair_filtered_variant_of<true>(m0, m1) : fwd_pair_filtered_variant_of<false>(m0, m1);
+}
+
 // rows one launch can take: all tiles x 8 members resident, one workgroup per CU
 int rows_per_launch() {
     const int cus = pnmn::device_cus();
@@ -973,10 +1019,12 @@ int plan_group(const Job* j, int n, int hidden, int& smax, int& chunk, int* rows
 
 // Passes that fit the chip together go out as ONE launch; otherwise the first n - 1 by the same rule and then the last
 // alone (identical results).  A lone pass beyond one launch runs in row chunks.
-int launch_fwd(const pnmn_decoder_fwd_job* j, int n, int hidden, void* workspace, hipStream_t st) {
+// `f`: one filter per job (checked by the caller), or null: none.  A job runs under its filter when it samples (mode 1) and
+// the filter is not the identity; every other job, and every launch without such a job, takes the unfiltered kernels.
+int launch_fwd(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, int n, int hidden, void* workspace, hipStream_t st) {
     if (n > 1 && !jobs_fit(j, n)) {
-        const int rc = launch_fwd(j, n - 1, hidden, workspace, st);
-        return rc != 0 ? rc : launch_fwd(j + n - 1, 1, hidden, workspace, st);
+        const int rc = launch_fwd(j, f, n - 1, hidden, workspace, st);
+        return rc != 0 ? rc : launch_fwd(j + n - 1, f ? f + n - 1 : nullptr, 1, hidden, workspace, st);
     }
     if (j[0].B <= 0 || j[0].T <= 0) return 0;  // (a lone pass only: passes side by side have rows and steps, see jobs_fit)
     int smax, chunk, rows[MAX_JOBS], tile0[MAX_JOBS + 1];
@@ -984,27 +1032,47 @@ int launch_fwd(const pnmn_decoder_fwd_job* j, int n, int hidden, void* workspace
     const bool overlap = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + FWD_OVERLAP_LDS <= LDS_LIMIT;
     const size_t lds = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + (overlap ? FWD_OVERLAP_LDS : 0);
     const bool s0 = j[0].sample != 0, s1 = n > 1 && j[1].sample != 0;
-    const void* kernel = n == 1 ? fwd_multi_variant(overlap, s0) : fwd_pair_variant(overlap, s0, s1);
+    int m[2] = {0, 0};  // the kernels' M per pass
+    pnmn::SamplingFilter ff[2] = {{1.f, 0, 1.f}, {1.f, 0, 1.f}};
+    for (int i = 0; i < n; ++i) {
+        m[i] = j[i].sample == 0 ? 0 : (f && j[i].sample == 1 && !pnmn::filter_is_identity(f[i])) ? 2 : 1;
+        if (m[i] == 2) ff[i] = pnmn::SamplingFilter{f[i].temperature, f[i].top_k, f[i].top_p};
+    }
+    const bool filtered = m[0] == 2 || m[1] == 2;
+    const void* kernel = filtered ? (n == 1 ? fwd_multi_filtered_variant(overlap) : fwd_pair_filtered_variant(overlap, m[0], m[1]))
+                                  : (n == 1 ? fwd_multi_variant(overlap, s0) : fwd_pair_variant(overlap, s0, s1));
     {   // (the opt-in is per device and per kernel: lds_optin.h; the limit itself, whatever this launch uses)
-        static std::atomic<uint64_t> cfg[2][8];
-        if (const int e = pnmn::opt_in_lds(kernel, LDS_LIMIT, cfg[n - 1][4 * overlap + 2 * s0 + s1])) return e;
+        static std::atomic<uint64_t> cfg[2][8], cfg_filtered[2][2][9];
+        std::atomic<uint64_t>& c = filtered ? cfg_filtered[n - 1][overlap][3 * m[0] + m[1]] : cfg[n - 1][4 * overlap + 2 * s0 + s1];
+        if (const int e = pnmn::opt_in_lds(kernel, LDS_LIMIT, c)) return e;
     }
     int* sync = nullptr;
     if (n > 1) {
         hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
         if (e != hipSuccess) return (int)e;
-        const auto pair = reinterpret_cast<void (*)(const MFwdArgs, const MFwdArgs, const int)>(const_cast<void*>(kernel));
         const MFwdArgs a0 = kernel_args(j[0], 0, rows[0], sync, 0), a1 = kernel_args(j[1], 0, rows[1], sync, tile0[1]);
-        hipLaunchKernelGGL(pair, dim3(MEMBERS * tile0[2]), dim3(512), lds, st, a0, a1, tile0[1]);
+        if (filtered) {
+            const auto pair = reinterpret_cast<void (*)(const MFwdArgs, const MFwdArgs, const int, const pnmn::SamplingFilter,
+                                                        const pnmn::SamplingFilter)>(const_cast<void*>(kernel));
+            hipLaunchKernelGGL(pair, dim3(MEMBERS * tile0[2]), dim3(512), lds, st, a0, a1, tile0[1], ff[0], ff[1]);
+        } else {
+            const auto pair = reinterpret_cast<void (*)(const MFwdArgs, const MFwdArgs, const int)>(const_cast<void*>(kernel));
+            hipLaunchKernelGGL(pair, dim3(MEMBERS * tile0[2]), dim3(512), lds, st, a0, a1, tile0[1]);
+        }
         return (int)hipGetLastError();
     }
-    const auto multi = reinterpret_cast<void (*)(const MFwdArgs)>(const_cast<void*>(kernel));
     for (int r0 = 0; r0 < rows[0]; r0 += chunk) {
         const int part = rows[0] - r0 < chunk ? rows[0] - r0 : chunk;
         hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
         if (e != hipSuccess) return (int)e;
         const MFwdArgs a = kernel_args(j[0], (size_t)r0, part, sync, 0);
-        hipLaunchKernelGGL(multi, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a);
+        if (filtered) {
+            const auto multi = reinterpret_cast<void (*)(const MFwdArgs, const pnmn::SamplingFilter)>(const_cast<void*>(kernel));
+            hipLaunchKernelGGL(multi, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a, ff[0]);
+        } else {
+            const auto multi = reinterpret_cast<void (*)(const MFwdArgs)>(const_cast<void*>(kernel));
+            hipLaunchKernelGGL(multi, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a);
+        }
         e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
@@ -1063,7 +1131,15 @@ int64_t pnmn_attn_lstm_group_workspace_bytes(const int32_t* rows, int n, int bac
 
 int pnmn_attn_lstm_fwd_group(const pnmn_decoder_fwd_job* jobs, int n, int hidden, void* workspace, void* stream) {
     if (!jobs || !workspace || n < 1 || n > 2) return PNMN_EINVAL;
-    return launch_fwd(jobs, n, hidden, workspace, static_cast<hipStream_t>(stream));
+    return launch_fwd(jobs, nullptr, n, hidden, workspace, static_cast<hipStream_t>(stream));
+}
+
+int pnmn_attn_lstm_fwd_group_filtered(const pnmn_decoder_fwd_job* jobs, const pnmn_sampling_filter* filters, int n, int hidden,
+                                      void* workspace, void* stream) {
+    if (!jobs || !filters || !workspace || n < 1 || n > 2) return PNMN_EINVAL;
+    for (int i = 0; i < n; ++i)
+        if (!pnmn::filter_valid(filters + i)) return PNMN_EINVAL;
+    return launch_fwd(jobs, filters, n, hidden, workspace, static_cast<hipStream_t>(stream));
 }
 
 int pnmn_attn_lstm_bwd_group(const pnmn_decoder_bwd_job* jobs, int n, int hidden, void* workspace, void* stream) {

@@ -5,6 +5,8 @@
 #include <math.h>
 #include <stdint.h>
 
+#include "../../include/probnmn_hip.h"
+
 namespace pnmn {
 
 __device__ __forceinline__ float sigm(float z) { return 1.f / (1.f + expf(-z)); }
@@ -138,12 +140,92 @@ __device__ inline int choose_token_fallback(const float (&v)[K], int V, bool gre
     return first_argmax(v, in_row);  // greedy, or no allowed token at all
 }
 
+// A sampling filter (temperature, top-k, top-p): the rule is stated beside pnmn_sample_tokens_filtered in
+// include/probnmn_hip.h.  It travels by value in the launch arguments of the filtered kernels only.
+struct SamplingFilter {
+    float temperature;
+    int top_k;
+    float top_p;
+};
+// what every filtered entry point checks before it launches anything, and which filters change nothing
+inline bool filter_valid(const pnmn_sampling_filter* f) {
+    return f && isfinite(f->temperature) && f->temperature > 0.f && f->top_k >= 0 && f->top_p > 0.f && f->top_p <= 1.f;
+}
+inline bool filter_is_identity(const pnmn_sampling_filter& f) { return f.temperature == 1.f && f.top_k == 0 && f.top_p == 1.f; }
+
+// The filtered draw of one row that is all finite and has a positive allowed total (the caller has checked both: every
+// other row keeps choose_token_fallback).  `v` holds the row (chunk k of a lane = index lane + 64k), `wl` 64 K floats of
+// LDS this wave owns -- in the decoders the logit row itself, dead once it is in `v`.
+//   w_j = exp(z_j / temperature - max over the allowed), -1 for an index that is not allowed: it ranks before nothing
+//   every lane walks j = 0 .. V-1 in ascending order (all lanes read wl[j]: a broadcast) and accumulates, per entry of
+//   its own, how many indices rank before it (w_j larger, or equal and j smaller) and their weight: its rank and the
+//   mass before it, in one fixed summation order -- no sort, no atomics
+//   top-k keeps rank < top_k, top-p of those the ones with mass before < top_p x (total kept by top-k) and rank 0;
+//   the draw is the index-order inverse CDF over what is left, from the row's usual uniform `u`.
+// A pure function of the row and the filter, wave-uniform: the eight members of a multi-CU tile agree.
+template <int K>
+__device__ inline int filtered_draw(const float (&v)[K], float* wl, int V, int pad, int unk, int start,
+                                    const SamplingFilter& f, float u) {
+    const int lane = threadIdx.x & 63;
+    float w[K], m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int j = lane + 64 * k;
+        w[k] = (j < V && j != pad && j != unk && j != start) ? v[k] / f.temperature : -INFINITY;
+        m = fmaxf(m, w[k]);
+    }
+    m = wmax(m);  // finite: some allowed weight of the unfiltered distribution is positive
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        const int j = lane + 64 * k;
+        w[k] = (j < V && j != pad && j != unk && j != start) ? expf(w[k] - m) : -1.f;
+        wl[j] = w[k];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // one wave: its LDS accesses complete in order
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    int rank[K];
+    float mass[K];
+#pragma unroll
+    for (int k = 0; k < K; ++k) rank[k] = 0, mass[k] = 0.f;
+    for (int j = 0; j < V; ++j) {
+        const float wj = wl[j];
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            const bool before = wj > w[k] || (wj == w[k] && j < lane + 64 * k);
+            rank[k] += before ? 1 : 0;
+            mass[k] += before ? wj : 0.f;
+        }
+    }
+    float kept[K], tot = 0.f;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        kept[k] = (w[k] >= 0.f && (f.top_k <= 0 || rank[k] < f.top_k)) ? w[k] : 0.f;
+        tot += kept[k];
+    }
+    tot = wsum(tot);  // (>= 1: the first-ranked index weighs exp(0))
+    if (f.top_p < 1.f) {
+        const float cut = f.top_p * tot;
+        float left = 0.f;
+#pragma unroll
+        for (int k = 0; k < K; ++k) {
+            if (!(mass[k] < cut) && rank[k] > 0) kept[k] = 0.f;
+            left += kept[k];
+        }
+        tot = wsum(left);
+    }
+    return inverse_cdf(kept, u * tot);
+}
+
 // One wave picks one row's token from `logits` (LDS, V <= 128 entries): mode 2 = first arg-max,
 // mode 1 = inverse-CDF draw from softmax(logits) with pad / unk / start removed (reference
 // seq2seq_base.py:203-220); rows that are not all finite follow choose_token_fallback.  The result is
-// wave-uniform and always in [0, V).
+// wave-uniform and always in [0, V).  FILT: mode 1 draws under the filter `f` instead (filtered_draw, which overwrites
+// the 128 floats at `wl`); the rows the fallback serves, and mode 2, ignore it.
+template <bool FILT = false>
 __device__ inline int choose_row_token(const float* logits, int V, int mode, int pad, int unk, int start, uint64_t seed,
-                                       uint64_t global_row, uint32_t t) {
+                                       uint64_t global_row, uint32_t t, float* wl = nullptr,
+                                       const SamplingFilter& f = SamplingFilter{1.f, 0, 1.f}) {
     const int lane = threadIdx.x & 63;
     float v[2];
     float mx = -INFINITY;
@@ -182,10 +264,12 @@ __device__ inline int choose_row_token(const float* logits, int V, int mode, int
         }
         tot = wsum(tot);
         const float u = philox_uniform(seed, global_row, t);
-        if (tot > 0.f)  // (a NaN or +inf anywhere in the row makes the total NaN)
-            choice = inverse_cdf(w, u * tot);
-        else
+        if (tot > 0.f) {  // (a NaN or +inf anywhere in the row makes the total NaN)
+            if constexpr (FILT) choice = filtered_draw(v, wl, V, pad, unk, start, f, u);
+            else choice = inverse_cdf(w, u * tot);
+        } else {
             choice = choose_token_fallback(v, V, false, pad, unk, start, u);
+        }
     }
     return min(max(choice, 0), V - 1);
 }

@@ -72,10 +72,13 @@ __device__ __forceinline__ float wave_sum(float v) { return pnmn::wsum(v); }  //
 
 // one wave per row; V up to 64*MAXV
 constexpr int MAXV = 8;
+// FILT: the sampling draw runs under the filter `f` (pnmn::filtered_draw), its weights in LDS: one row per wave, in this
+// instantiation only.  Both instantiations take `f`; only FILT reads it.
+template <bool FILT>
 __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restrict__ logits, int64_t* __restrict__ tokens,
                                                             float* __restrict__ logprobs, int B, int V, int greedy,
                                                             uint64_t seed, uint64_t row_offset, uint32_t step,
-                                                            int pad, int unk, int start) {
+                                                            int pad, int unk, int start, const pnmn::SamplingFilter f) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
     if (row >= B) return;
@@ -125,10 +128,16 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
         tot = wave_sum(tot);
         // token order = index order: chunk k holds indices [64k, 64k+64)
         const float u = pnmn::philox_uniform(seed, row_offset + (uint64_t)row, step);
-        if (tot > 0.f)  // (a NaN or +inf anywhere in the row makes the total NaN)
-            choice = pnmn::inverse_cdf(w, u * tot);
-        else
+        if (tot > 0.f) {  // (a NaN or +inf anywhere in the row makes the total NaN)
+            if constexpr (FILT) {
+                __shared__ float wl[4][64 * MAXV];
+                choice = pnmn::filtered_draw(v, wl[threadIdx.x >> 6], V, pad, unk, start, f, u);
+            } else {
+                choice = pnmn::inverse_cdf(w, u * tot);
+            }
+        } else {
             choice = pnmn::choose_token_fallback(v, V, false, pad, unk, start, u);
+        }
     }
     choice = min(max(choice, 0), V - 1);
     if (lane == 0) {
@@ -167,8 +176,25 @@ int pnmn_sample_tokens(const float* logits, int64_t* tokens, float* logprobs, in
     if (B <= 0) return 0;
     if (!logits || !tokens || !logprobs || V <= 0) return PNMN_EINVAL;
     if (V > 64 * MAXV) return PNMN_ESHAPE;
-    hipLaunchKernelGGL(sample_tokens_kernel, dim3((B + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
-                       tokens, logprobs, B, V, greedy, seed, row_offset, step, pad_index, unk_index, start_index);
+    hipLaunchKernelGGL(sample_tokens_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
+                       tokens, logprobs, B, V, greedy, seed, row_offset, step, pad_index, unk_index, start_index,
+                       pnmn::SamplingFilter{1.f, 0, 1.f});
+    return (int)hipGetLastError();
+}
+
+int pnmn_sample_tokens_filtered(const float* logits, int64_t* tokens, float* logprobs, int B, int V, int greedy,
+                                uint64_t seed, uint64_t row_offset, uint32_t step, int pad_index, int unk_index,
+                                int start_index, const pnmn_sampling_filter* filter, void* stream) {
+    if (!pnmn::filter_valid(filter)) return PNMN_EINVAL;
+    if (greedy || pnmn::filter_is_identity(*filter))
+        return pnmn_sample_tokens(logits, tokens, logprobs, B, V, greedy, seed, row_offset, step, pad_index, unk_index,
+                                  start_index, stream);
+    if (B <= 0) return 0;
+    if (!logits || !tokens || !logprobs || V <= 0) return PNMN_EINVAL;
+    if (V > 64 * MAXV) return PNMN_ESHAPE;
+    hipLaunchKernelGGL(sample_tokens_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
+                       tokens, logprobs, B, V, 0, seed, row_offset, step, pad_index, unk_index, start_index,
+                       pnmn::SamplingFilter{filter->temperature, filter->top_k, filter->top_p});
     return (int)hipGetLastError();
 }
 

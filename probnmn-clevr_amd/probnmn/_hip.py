@@ -2,7 +2,8 @@
 
 The header is the one statement of the ABI.  ``read_header`` parses it when this module is imported and everything the
 package binds comes out of that: ``SIGNATURES`` / ``RESTYPES`` (every ``pnmn_*`` prototype), one numpy record dtype per
-``typedef struct ... pnmn_x;`` (``pnmn_conv_item`` -> ``CONV_ITEM``) and one integer per ``#define PNMN_NAME``
+``typedef struct ... pnmn_x;`` (``pnmn_conv_item`` -> ``CONV_ITEM``), one per host argument block ``struct pnmn_x { ... };``
+(``HOST_BLOCKS``; ``pnmn_sampling_filter`` -> ``SAMPLING_FILTER``) and one integer per ``#define PNMN_NAME``
 (``PNMN_OP_CONV`` -> ``OP_CONV``).  A new entry point, record or constant is therefore added in the header and in its
 ``.hip`` file, nowhere else; tests/test_abi.py holds the result against the C++ compiler's own view of the header.
 
@@ -44,10 +45,14 @@ _C_SCALARS = {
 }
 
 
+HOST_BLOCKS: Dict[str, np.dtype] = {}  # `struct pnmn_x { ... };` of the header last read -> aligned numpy dtype
+
+
 def read_header(path: str = HEADER_PATH, text: Optional[str] = None):
     """(signatures, restypes, records, constants) of the C header at ``path`` (or of ``text``), following the declaration
     conventions stated at its top: prototype name -> argtypes tuple and -> return type, struct name -> aligned numpy
-    dtype (pointer fields as uint64), ``PNMN_*`` -> int.  A ``pnmn_`` declaration it cannot read raises, naming it."""
+    dtype (pointer fields as uint64), ``PNMN_*`` -> int.  A ``pnmn_`` declaration it cannot read raises, naming it.
+    Host argument blocks (``struct pnmn_x { ... };`` without a typedef) are not records: their dtypes go to ``HOST_BLOCKS``."""
     if text is None:
         try:
             with open(path) as f:
@@ -69,28 +74,33 @@ def read_header(path: str = HEADER_PATH, text: Optional[str] = None):
             raise HipLibraryError("probnmn_hip.h: `%s` is not an integer constant" % line.strip())
         constants[m[1]] = int(m[2] or m[3])
 
+    def record(body: str, name: str) -> np.dtype:
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            # `const float *a, *b` or `int32_t n, p[8]`: a type, then declarators; a `*` makes its declarator a pointer
+            words = re.sub(r"\bconst\b", " ", decl).replace("*", " * ").split(None, 1)
+            declarators = [re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[\s*(\w+)\s*\])?\s*", d) for d in words[-1].split(",")]
+            if len(words) != 2 or None in declarators:
+                raise HipLibraryError("probnmn_hip.h: cannot read the field `%s` of %s" % (decl, name))
+            for star, field, length in (d.groups() for d in declarators):
+                kind = np.uint64 if star else scalar(words[0], "%s; /* %s */" % (decl, name), 1)
+                if length is None:
+                    fields.append((field, kind))
+                elif length.isdigit() or length in constants:
+                    fields.append((field, kind, (int(length) if length.isdigit() else constants[length],)))
+                else:
+                    raise HipLibraryError("probnmn_hip.h: array length `%s` of `%s` in %s is neither a number nor a "
+                                          "#define above it" % (length, decl, name))
+        return np.dtype(fields, align=True)
+
     records: Dict[str, np.dtype] = {}
     for m in re.finditer(r"\btypedef\b(?:\s+struct\s*\w*\s*\{([^{}]*)\}\s*(pnmn_\w+)\s*;)?", text):
         if m[2] is None:
             raise HipLibraryError("probnmn_hip.h: cannot read the record at `%s`: a record is `typedef struct [tag] { ... } "
                                   "pnmn_x;`" % " ".join(text[m.start():m.start() + 60].split()))
-        fields = []
-        for decl in filter(None, (d.strip() for d in m[1].split(";"))):
-            # `const float *a, *b` or `int32_t n, p[8]`: a type, then declarators; a `*` makes its declarator a pointer
-            words = re.sub(r"\bconst\b", " ", decl).replace("*", " * ").split(None, 1)
-            declarators = [re.fullmatch(r"\s*(\*?)\s*(\w+)\s*(?:\[\s*(\w+)\s*\])?\s*", d) for d in words[-1].split(",")]
-            if len(words) != 2 or None in declarators:
-                raise HipLibraryError("probnmn_hip.h: cannot read the field `%s` of %s" % (decl, m[2]))
-            for star, name, length in (d.groups() for d in declarators):
-                kind = np.uint64 if star else scalar(words[0], "%s; /* %s */" % (decl, m[2]), 1)
-                if length is None:
-                    fields.append((name, kind))
-                elif length.isdigit() or length in constants:
-                    fields.append((name, kind, (int(length) if length.isdigit() else constants[length],)))
-                else:
-                    raise HipLibraryError("probnmn_hip.h: array length `%s` of `%s` in %s is neither a number nor a "
-                                          "#define above it" % (length, decl, m[2]))
-        records[m[2]] = np.dtype(fields, align=True)
+        records[m[2]] = record(m[1], m[2])
+    # host argument blocks, `struct pnmn_x { ... };` without a typedef: the same field kinds, kept beside the records
+    HOST_BLOCKS.update({m[1]: record(m[2], m[1]) for m in re.finditer(r"^[ \t]*struct\s+(pnmn_\w+)\s*\{([^{}]*)\}\s*;", text, flags=re.M)})
 
     signatures: Dict[str, tuple] = {}
     restypes = {}
@@ -98,7 +108,7 @@ def read_header(path: str = HEADER_PATH, text: Optional[str] = None):
         params = [p.strip() for p in m[3].split(",")]
         argtypes = []
         for p in [] if params in (["void"], [""]) else params:
-            words = re.sub(r"\bconst\b", " ", p).split()
+            words = re.sub(r"\b(const|struct)\b", " ", p).split()
             if "*" in p:
                 argtypes.append(ctypes.c_void_p)
             elif len(words) == 2:
@@ -117,6 +127,7 @@ def read_header(path: str = HEADER_PATH, text: Optional[str] = None):
 # name -> argtypes / restype of every entry point, C struct name -> record dtype, PNMN_* -> value
 SIGNATURES, RESTYPES, RECORDS, CONSTANTS = read_header()
 globals().update({name[len("pnmn_"):].upper(): dtype for name, dtype in RECORDS.items()})  # pnmn_conv_item -> CONV_ITEM
+globals().update({name[len("pnmn_"):].upper(): dtype for name, dtype in HOST_BLOCKS.items()})  # struct pnmn_sampling_filter -> SAMPLING_FILTER
 globals().update({name[len("PNMN_"):]: value for name, value in CONSTANTS.items()})        # PNMN_OP_CONV -> OP_CONV, ...
 GEMM_A_T, GEMM_B_T, GEMM_ACC = (CONSTANTS["PNMN_GEMM_" + n] for n in ("A_TRANSPOSED", "B_TRANSPOSED", "ACCUMULATE"))
 ABI_VERSION = CONSTANTS["PNMN_ABI_VERSION"]  # what pnmn_abi_version() of a library built from this header returns

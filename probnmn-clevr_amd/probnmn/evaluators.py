@@ -16,6 +16,8 @@ from typing import Any, Callable, Dict, Iterable, List, Optional
 
 import torch
 
+from probnmn.modules.seq2seq_base import sampling_filter
+
 
 class Evaluator:
     """``_Evaluator``: ``models`` name -> module (the trainer's dict, shared by reference), ``do_iteration(batch)``
@@ -123,7 +125,8 @@ def evaluate_answer_accuracy(program_generator, nmn, batches: Iterable[Dict[str,
 @torch.no_grad()
 def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary,
                     beam_size: Optional[int] = None, prefer_valid: bool = True,
-                    constrained: bool = False, extractor=None) -> List[Dict[str, Any]]:
+                    constrained: bool = False, extractor=None, temperature: float = 1.0, top_k: int = 0,
+                    top_p: float = 1.0) -> List[Dict[str, Any]]:
     """scripts/inference.py:76-91: sampled programs -> NMN -> answer strings, one record per question
     (``question_index`` from the batch when present, else a running index).
 
@@ -140,9 +143,17 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
     ``extractor`` (a ``ResNet101Stage3`` on the device): a batch without ``"image"`` features but with ``"pixels"`` --
     decoded uint8 images [B, H, W, 3] of any size, on the device -- gets its features from ``extractor.forward_pixels``
     (resize, normalisation and the network, all on the device), queued with the generator pass; the NMN reads the
-    ``channels_last`` result in place.  A batch with neither key, or with pixels but no extractor, is a ``ValueError``."""
+    ``channels_last`` result in place.  A batch with neither key, or with pixels but no extractor, is a ``ValueError``.
+
+    ``temperature``, ``top_k``, ``top_p``: the sampling filter of the generator's sampled programs (``Seq2SeqBase.decode``);
+    the record layout is unchanged.  Values out of range, or a filter other than (1, 0, 1) together with ``beam_size``
+    (a beam search draws nothing), are a ``ValueError``."""
     if constrained and beam_size is None:
         raise ValueError("constrained=True constrains the beam search: give a beam_size")
+    filt = sampling_filter(temperature, top_k, top_p)
+    if filt is not None and beam_size is not None:
+        raise ValueError("temperature / top_k / top_p filter sampled programs; with beam_size the programs are searched, not drawn")
+    sampling = {} if filt is None else dict(temperature=filt[0], top_k=filt[1], top_p=filt[2])
     was_training = (program_generator.training, nmn.training)
     program_generator.eval()
     nmn.eval()
@@ -168,7 +179,7 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
         def queue(batch, iteration):
             image = features(batch)
             if beam_size is None:
-                programs = program_generator(batch["question"])["predictions"]
+                programs = program_generator(batch["question"], **sampling)["predictions"]
             else:
                 extra = {} if constraint is None else {"constraint": constraint}
                 programs = program_generator(batch["question"], decoding_strategy="beam", beam_size=beam_size,

@@ -22,6 +22,7 @@ Not in the reference: ``decoding_strategy="beam"`` (``Seq2SeqBase.decode_beam``)
 of a persistent kernel that keeps the K hypotheses of a question in one workgroup (``pnmn_attn_lstm_beam``,
 csrc/decoder_beam.hip).
 """
+import math
 import os
 from typing import Dict, NamedTuple, Optional
 
@@ -632,12 +633,25 @@ def _decoder_forward(tensors, metas) -> _DecoderLaunch:
     dev, Hd = hs.device, hs.size(2)
     ws = _decoder_workspace([sd[0][0].size(0) for sd in sides], False, dev)
     lib = _hip.lib()
-    if ws is not None:
+    # ``meta["filter"]``: the pass's sampling filter (``sampling_filter``), honoured when it samples; with none anywhere the
+    # unfiltered entry points are called, as ever
+    filters = None
+    if any(m.get("filter") is not None for m in metas):
+        filters = np.zeros(n, _hip.SAMPLING_FILTER)
+        for k, m in enumerate(metas):
+            filters[k] = (*(m.get("filter") or IDENTITY_FILTER), 0)
+    if ws is not None and filters is not None:
+        _hip.check(lib.pnmn_attn_lstm_fwd_group_filtered(jobs.ctypes.data, filters.ctypes.data, n, Hd, ws.data_ptr(),
+                                                         _hip.stream_ptr(dev)), "attn_lstm_fwd_group_filtered")
+    elif ws is not None:
         _hip.check(lib.pnmn_attn_lstm_fwd_group(jobs.ctypes.data, n, Hd, ws.data_ptr(), _hip.stream_ptr(dev)), "attn_lstm_fwd_group")
     elif n == 1:
         j = jobs[0].item()  # (the record's fields in order: 16 pointers, stride, seed, row offset, 8 ints)
-        _hip.check(lib.pnmn_attn_lstm_fwd(*j[:15], *j[19:23], Hd, *j[23:27], j[17], j[18], j[15], j[16], _hip.stream_ptr(dev)),
-                   "attn_lstm_fwd")
+        args = (*j[:15], *j[19:23], Hd, *j[23:27], j[17], j[18], j[15], j[16])
+        if filters is not None:
+            _hip.check(lib.pnmn_attn_lstm_fwd_filtered(*args, filters.ctypes.data, _hip.stream_ptr(dev)), "attn_lstm_fwd_filtered")
+        else:
+            _hip.check(lib.pnmn_attn_lstm_fwd(*args, _hip.stream_ptr(dev)), "attn_lstm_fwd")
     else:
         raise _hip.HipLibraryError("decoder passes side by side need the multi-CU decoder kernels (none on this device)")
     return _DecoderLaunch(tuple(t for sd in sides for t in sd[0]), tuple(t for sd in sides for t in sd[1]),
@@ -730,9 +744,9 @@ class _AttnLSTMDecoder(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, mode, T, seed, row_offset, pad, unk, start,
-                packs=None, in_tokens=None):
+                packs=None, in_tokens=None, filter=None):
         m = dict(mode=mode, T=T, seed=seed, row_offset=row_offset, pad=pad, unk=unk, start=start, packs=packs, w_p=w_p, b_p=b_p,
-                 in_tokens=in_tokens if mode == 0 else None)
+                 in_tokens=in_tokens if mode == 0 else None, filter=filter)
         ctx.projected = mode == 0 and in_tokens is None
         got = _decoder_forward([(xe if ctx.projected else etable, enc, mask, h0, w_c, w_hh)], [m])
         ctx.save_for_backward(*got.saved)
@@ -744,7 +758,7 @@ class _AttnLSTMDecoder(torch.autograd.Function):
     def backward(ctx, dhs, _):
         need = ctx.needs_input_grad
         d = _decoder_sides_backward(ctx.saved_tensors, ctx.side_meta, (dhs,), (need[0 if ctx.projected else 1], *need[2:7]))
-        return ((d[0], None) if ctx.projected else (None, d[0])) + tuple(d[1:]) + (None,) * 11
+        return ((d[0], None) if ctx.projected else (None, d[0])) + tuple(d[1:]) + (None,) * 12
 
 
 class _AttnLSTMDecoderGroup(torch.autograd.Function):
@@ -785,16 +799,46 @@ class _AttnLSTMDecoderGroup(torch.autograd.Function):
         return (*_decoder_sides_backward(ctx.saved_tensors, ctx.side_meta, grads[0::2], ctx.needs_input_grad), None, None)
 
 
+IDENTITY_FILTER = (1.0, 0, 1.0)
+
+
+def sampling_filter(temperature=1.0, top_k=0, top_p=1.0):
+    """(temperature, top_k, top_p) as the kernels take them (the rule: include/probnmn_hip.h, beside
+    ``pnmn_sample_tokens_filtered``), or None for the identity filter (1, 0, 1).  ``ValueError`` for a temperature that is not
+    finite or not positive, a negative or non-integer ``top_k``, a ``top_p`` outside (0, 1]."""
+    try:
+        t, p = float(temperature), float(top_p)
+    except (TypeError, ValueError):
+        raise ValueError("temperature and top_p must be numbers, got %r and %r" % (temperature, top_p))
+    if not (math.isfinite(t) and t > 0.0):
+        raise ValueError("temperature must be finite and > 0, got %r" % (temperature,))
+    if isinstance(top_k, bool) or not isinstance(top_k, (int, np.integer)) or top_k < 0 or top_k > 2 ** 31 - 1:
+        raise ValueError("top_k must be an integer >= 0 (0: no truncation), got %r" % (top_k,))
+    if not (0.0 < p <= 1.0):
+        raise ValueError("top_p must lie in (0, 1], got %r" % (top_p,))
+    f = (t, int(top_k), p)
+    return None if f == IDENTITY_FILTER else f
+
+
 def choose_tokens(logits: torch.Tensor, greedy: bool, seed: int, row_offset: int, step: int,
-                  pad: int, unk: int, start: int):
-    """One decoding step's token choice on the device; returns (tokens int64 [B], logprob [B] no grad)."""
+                  pad: int, unk: int, start: int, temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0):
+    """One decoding step's token choice on the device; returns (tokens int64 [B], logprob [B] no grad).  ``temperature``,
+    ``top_k``, ``top_p``: the sampling filter (``sampling_filter``; a greedy choice ignores it); the log-probabilities stay
+    those of the unmodified distribution."""
+    filt = sampling_filter(temperature, top_k, top_p)
     logits = logits.detach().contiguous()
     B, V = logits.shape
     tokens = torch.empty(B, dtype=torch.long, device=logits.device)
     lp = torch.empty(B, dtype=torch.float32, device=logits.device)
-    _hip.check(_hip.lib().pnmn_sample_tokens(logits.data_ptr(), tokens.data_ptr(), lp.data_ptr(), B, V, int(greedy),
-                                             seed, row_offset, step, pad, unk, start,
-                                             _hip.stream_ptr(logits.device)), "sample_tokens")
+    if filt is None:
+        _hip.check(_hip.lib().pnmn_sample_tokens(logits.data_ptr(), tokens.data_ptr(), lp.data_ptr(), B, V, int(greedy),
+                                                 seed, row_offset, step, pad, unk, start,
+                                                 _hip.stream_ptr(logits.device)), "sample_tokens")
+    else:
+        rec = np.array([(*filt, 0)], _hip.SAMPLING_FILTER)
+        _hip.check(_hip.lib().pnmn_sample_tokens_filtered(logits.data_ptr(), tokens.data_ptr(), lp.data_ptr(), B, V, int(greedy),
+                                                          seed, row_offset, step, pad, unk, start, rec.ctypes.data,
+                                                          _hip.stream_ptr(logits.device)), "sample_tokens_filtered")
     return tokens, lp
 
 
@@ -1081,17 +1125,23 @@ class Seq2SeqBase(nn.Module):
         need_predictions: bool = True,
         beam_size: int = 4,
         constraint=None,
+        temperature: float = 1.0,
+        top_k: int = 0,
+        top_p: float = 1.0,
     ) -> Dict[str, torch.Tensor]:
         """``decoding_strategy``: "sampling" / "greedy" as the reference; "beam": beam search of width ``beam_size`` (free
         running only, no gradients -- see ``decode_beam``).  ``beam_size`` is ignored by the other strategies;
-        ``constraint`` (a token automaton, beam search only) is refused by them."""
+        ``constraint`` (a token automaton, beam search only) is refused by them.  ``temperature``, ``top_k``, ``top_p``:
+        the sampling filter, "sampling" only (see ``decode``)."""
+        self._check_filter(decoding_strategy, temperature, top_k, top_p)
         if decoding_strategy == "beam":
             self._check_beam_arguments(target_tokens, beam_size)
             with torch.no_grad():  # (the encoder without its dropout: the search is the same in train() and eval() mode)
                 return self.decode_beam(self.encode(source_tokens, dropout=False), beam_size, constraint=constraint)
         if constraint is not None:
             raise ValueError("constraint: only decoding_strategy='beam' decodes under a token automaton")
-        return self.decode(self.encode(source_tokens), target_tokens, decoding_strategy, need_predictions)
+        return self.decode(self.encode(source_tokens), target_tokens, decoding_strategy, need_predictions,
+                           temperature=temperature, top_k=top_k, top_p=top_p)
 
     def encode(self, source_tokens: torch.LongTensor, dropout: bool = True) -> Dict[str, torch.Tensor]:
         """Encoder half of ``forward`` (reference seq2seq_base.py ``_encode`` + ``_init_decoder_state``).
@@ -1135,12 +1185,22 @@ class Seq2SeqBase(nn.Module):
         seed: Optional[int] = None,
         beam_size: int = 4,
         constraint=None,
+        temperature: float = 1.0,
+        top_k: int = 0,
+        top_p: float = 1.0,
     ) -> Dict[str, torch.Tensor]:
         """``need_predictions=False`` (teacher forcing only): skip drawing the per-step predictions from the
         teacher-forced distributions (reference :196-220) -- training iterations never read them.  ``seed``: the sampler
         seed a ``decode_prepare`` of this pass already drew (its pairing fell through): one draw per pass either way, so
         paired and unpaired schedules sample the same programs from the same torch seed.  ``decoding_strategy="beam"``:
-        ``decode_beam`` with ``beam_size`` (which the other strategies ignore) and ``constraint`` (which they refuse)."""
+        ``decode_beam`` with ``beam_size`` (which the other strategies ignore) and ``constraint`` (which they refuse).
+        ``temperature``, ``top_k``, ``top_p`` (``decoding_strategy="sampling"`` only; anything but (1, 0, 1) with another
+        strategy is a ``ValueError``): the tokens -- the free-running decode's, and the predictions drawn from teacher-forced
+        distributions -- are drawn from the distribution sharpened by the temperature and cut to its ``top_k`` most likely
+        tokens and its ``top_p`` nucleus (the rule: include/probnmn_hip.h).  They use the uniforms an unfiltered decode from
+        the same seed uses, and ``loss`` still scores them under the unmodified distribution.  Shapes outside the persistent
+        kernels have no filtered path: ``NotImplementedError``."""
+        filt = self._check_filter(decoding_strategy, temperature, top_k, top_p)
         if decoding_strategy == "beam":
             self._check_beam_arguments(target_tokens, beam_size)
             return self.decode_beam(state, beam_size, constraint=constraint)
@@ -1163,16 +1223,22 @@ class Seq2SeqBase(nn.Module):
         fused = Hd == 256 and enc.size(1) <= 64 and self._output_projection_layer.weight.size(0) <= 128
         if fused:
             prep = self._fused_prep(state, tgt, greedy, seed, self._derived())
+            if filt is not None:
+                prep["meta"]["filter"] = filt
             hs, raw = _AttnLSTMDecoderGroup.apply(*_prep_tensors(prep), [prep["meta"]], None)
             output_dict, logits_all = self._finish(prep, hs, raw)
             if tgt is not None and (need_predictions or not self.training):
                 # predictions are drawn / arg-maxed from the teacher-forced distributions (reference :196-220)
                 raw, _ = choose_tokens(logits_all.reshape(B * steps, -1), greedy, seed, self.sample_row_offset * steps,
-                                       0, pad, self._unk_index, bos)
+                                       0, pad, self._unk_index, bos, *(filt or ()))
                 output_dict["predictions"] = self._trim_predictions(raw.view(B, steps))
             ce = output_dict["loss"]
             predictions = output_dict.get("predictions")
         else:
+            if filt is not None:
+                raise NotImplementedError("temperature / top_k / top_p: hidden size %d, %d source positions, %d target tokens -- the "
+                                          "filtered draw exists in the persistent decoder kernels only (256 / <= 64 / <= 128)"
+                                          % (Hd, enc.size(1), self._output_projection_layer.weight.size(0)))
             _note_slow_path("decoder", "hidden size %d, %d source positions, %d target tokens (the persistent decoder kernel is "
                             "built for 256 / <= 64 / <= 128)" % (Hd, enc.size(1), self._output_projection_layer.weight.size(0)))
             raw, logits_all, logprobs = self._decode_stepwise(enc, fmask, h, torch.zeros_like(h), tgt, steps, greedy, seed)
@@ -1189,6 +1255,16 @@ class Seq2SeqBase(nn.Module):
                 self._record_metrics(predictions, tgt[:, 1:], ce)
                 self._bleu(predictions, tgt)  # (reference :260: against the targets WITH their @start@, as allennlp)
         return output_dict
+
+    @staticmethod
+    def _check_filter(decoding_strategy, temperature, top_k, top_p):
+        """The sampling filter of a call (``sampling_filter``: None for the identity); ``ValueError`` for values out of range,
+        and for a filter on a strategy that does not sample."""
+        filt = sampling_filter(temperature, top_k, top_p)
+        if filt is not None and decoding_strategy != "sampling":
+            raise ValueError("temperature / top_k / top_p filter what decoding_strategy='sampling' draws; %r does not sample"
+                             % (decoding_strategy,))
+        return filt
 
     # ---- beam search (inference) ---------------------------------------------------------------------------------------
     BEAM_SIZES = (1, 2, 4, 8, 16)
