@@ -695,6 +695,50 @@ int pnmn_attn_lstm_fwd_filtered(const float* xe, const float* etable, const floa
 int pnmn_attn_lstm_fwd_group_filtered(const pnmn_decoder_fwd_job* jobs, const struct pnmn_sampling_filter* filters /* HOST, one per job */,
                                       int n, int hidden, void* workspace, void* stream);
 
+/* Sampling and greedy decoding under a token automaton: the free-running modes of pnmn_attn_lstm_fwd / _fwd_group emit only
+ * strings the automaton accepts.  INFERENCE ONLY: a constrained draw is not a draw from the model's distribution, and no
+ * trainer uses it.  The tables (token_class, next_state, min_left, n_states, n_classes, state 0 = start, 255 = no completion)
+ * and the test of a candidate are those of pnmn_attn_lstm_beam_constrained above: HOST pointers, every entry checked, passed
+ * by value in the launch arguments and staged into LDS once per workgroup -- no device allocation, no copy, no synchronisation.
+ * Every row carries an automaton state (0 at the start) and a finished flag (false at the start).  At step t (0-based) of T a
+ * row in state s that has not finished has the allowed set A_c(s, t):
+ *   token v, not pad / unk / start and v != end_index   iff  min_left[next_state[s][token_class[v]]] <= T - 1 - t
+ *   end_index                                           iff  min_left[s] == 0
+ * and its token is chosen as by pnmn_sample_tokens / pnmn_sample_tokens_filtered with A_c in the place of A:
+ *   sample == 1: inverse CDF in index order over softmax(z) restricted to A_c, the uniform from the same Philox counter
+ *                (row_offset + row, t) -- a constrained and an unconstrained decode from one seed share their random numbers;
+ *                under a filter other than the identity: rank, top-k and top-p WITHIN A_c, then the same draw
+ *   sample == 2: the first index of the largest logit WITHIN A_c (the unconstrained arg-max looks at all of [0, V))
+ *   a row that holds a NaN or +inf (greedy: a NaN), or whose A_c weights sum to 0, follows the fallback rule stated beside
+ *                pnmn_sample_tokens with A_c as the allowed set (greedy: the arg-max of that rule within A_c): still in A_c
+ *   a row that has emitted end_index is finished: every later step of it emits end_index, its state is frozen, and the token
+ *                is fed to the next step as usual
+ *   state:       unchanged on end_index, otherwise s <- next_state[s][token_class[token]]
+ * By induction min_left[s] <= T - t before every step, so A_c is never empty, and every row, cut at its first end_index, is
+ * accepted by the automaton.  With one state, one class and min_left = {0} a sampling pass emits what the unconstrained pass
+ * emits up to and including each row's first end_index.  logprobs, and any loss built from the tokens, stay
+ * log_softmax(z)[token] of the UNMODIFIED distribution, exactly as for the filtered draw.
+ * `filter` is required (the identity (1, 0, 1) is allowed and draws as the unfiltered rule does); it applies to sample == 1.
+ * pnmn_attn_lstm_fwd_group_constrained: filters[i] belongs to jobs[i]; the automaton applies to every job with sample != 0;
+ * for a job with sample == 0 both are checked and ignored.  The fit and fall-back rule of pnmn_attn_lstm_fwd_group is unchanged.
+ * Each returns PNMN_EINVAL and launches nothing for: a null table, a table entry out of range (token_class[v] >= n_classes for
+ * v < V, next_state >= n_states), n_states outside 1..PNMN_BEAM_MAX_STATES, n_classes outside 1..PNMN_BEAM_MAX_CLASSES, V outside
+ * 1..128, end_index outside [0, V), min_left[0] > T (no accepted string fits; group: any job's T), a null or invalid filter.
+ * Otherwise: the arguments, limits and return codes of the unconstrained counterpart. */
+int pnmn_attn_lstm_fwd_constrained(const float* xe, const float* etable, const float* enc, const float* mask,
+                                   const float* h0, const float* w_c, const float* w_hh, const float* w_p,
+                                   const float* b_p, float* hs, float* cs, float* act, float* ctx, float* probs,
+                                   int64_t* tokens, int B, int T, int S, int V, int hidden, int sample,
+                                   int pad_index, int unk_index, int start_index, uint64_t seed,
+                                   uint64_t row_offset, const int64_t* in_tokens, int64_t in_token_stride,
+                                   const struct pnmn_sampling_filter* filter /* HOST */, int end_index,
+                                   const uint8_t* token_class /* HOST */, const uint8_t* next_state /* HOST */,
+                                   const uint8_t* min_left /* HOST */, int n_states, int n_classes, void* stream);
+int pnmn_attn_lstm_fwd_group_constrained(const pnmn_decoder_fwd_job* jobs, const struct pnmn_sampling_filter* filters /* HOST, one per job */,
+                                         int end_index, const uint8_t* token_class /* HOST */, const uint8_t* next_state /* HOST */,
+                                         const uint8_t* min_left /* HOST */, int n_states, int n_classes,
+                                         int n, int hidden, void* workspace, void* stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Host-side launch sequencer (no device work of its own): `list` is a HOST array; entry i calls the entry
  * point named by `op` with (a, b, c, n, p[...]) in that entry point's argument order (pointers first, then

@@ -69,10 +69,26 @@ struct FwdArgs {
     uint64_t seed, row_offset;
 };
 
+// the constrained kernels' arguments: the token automaton behind the others, by value
+struct ConstrainedFwdArgs : FwdArgs {
+    pnmn::TokenAutomaton automaton;
+};
+template <bool CONSTR>
+struct fwd_args {
+    using type = FwdArgs;
+};
+template <>
+struct fwd_args<true> {
+    using type = ConstrainedFwdArgs;
+};
+
 // FILT: the sampling mode draws under the filter `f` (sampling.h); its weights take the place of the row's logits in `logl`,
 // which nothing reads between the choice and the next step's logits tile.  Both instantiations take `f`; only FILT reads it.
-template <bool FILT>
-__global__ __launch_bounds__(512) void attn_lstm_fwd_kernel(const FwdArgs a, const pnmn::SamplingFilter f) {
+// CONSTR (free-running passes only): every choice is made within the automaton's allowed set A_c (the rule: include/probnmn_hip.h).
+// The tables are staged into LDS once; a row's state and finished flag stay in scalar registers of the wave that owns rows
+// 2 wave, 2 wave + 1 for all steps -- a pure function of the row's own earlier tokens.
+template <bool FILT, bool CONSTR = false>
+__global__ __launch_bounds__(512) void attn_lstm_fwd_kernel(const typename fwd_args<CONSTR>::type a, const pnmn::SamplingFilter f) {
     __shared__ __attribute__((aligned(16))) float hl[2][ROWS][LD];
     __shared__ __attribute__((aligned(16))) float cl[ROWS][LD];
     __shared__ float wl[ROWS][MAXS];
@@ -87,6 +103,12 @@ __global__ __launch_bounds__(512) void attn_lstm_fwd_kernel(const FwdArgs a, con
         hl[0][r][k] = (row0 + r < a.B) ? a.h0[(size_t)(row0 + r) * H + k] : 0.f;
     }
     if (tid < ROWS) tokl[tid] = a.start;
+    pnmn::AutomatonLds au{};
+    int row_state[2] = {0, 0};  // (CONSTR) of rows 2 wave, 2 wave + 1: the start state, not finished
+    if constexpr (CONSTR) {
+        __shared__ unsigned char autl[pnmn::AUTOMATON_LDS_BYTES];
+        au = pnmn::stage_automaton(autl, a.automaton);
+    }
     float creg[2][4];
 #pragma unroll
     for (int ut = 0; ut < 2; ++ut)
@@ -213,8 +235,16 @@ __global__ __launch_bounds__(512) void attn_lstm_fwd_kernel(const FwdArgs a, con
                 const int rl = 2 * wave + rr;
                 const int row = row0 + rl;
                 if (row >= a.B) continue;
-                const int choice = pnmn::choose_row_token<FILT>(logl[rl], V, a.sample, a.pad, a.unk, a.start, a.seed,
-                                                                a.row_offset + (uint64_t)row, (uint32_t)t, logl[rl], f);
+                int choice;
+                if constexpr (CONSTR) {
+                    const auto set = pnmn::allowed_lanes(au, row_state[rr], T - 1 - t, V, a.pad, a.unk, a.start);
+                    choice = pnmn::choose_row_token<FILT>(logl[rl], V, a.sample, a.pad, a.unk, a.start, a.seed,
+                                                          a.row_offset + (uint64_t)row, (uint32_t)t, logl[rl], f, set);
+                    row_state[rr] = pnmn::advance_row_state(au, row_state[rr], choice);
+                } else {
+                    choice = pnmn::choose_row_token<FILT>(logl[rl], V, a.sample, a.pad, a.unk, a.start, a.seed,
+                                                          a.row_offset + (uint64_t)row, (uint32_t)t, logl[rl], f);
+                }
                 if (lane == 0) {
                     tokl[rl] = choice;
                     a.tokens[(size_t)row * T + t] = choice;
@@ -401,12 +431,13 @@ __global__ __launch_bounds__(512) void attn_lstm_bwd_kernel(const BwdArgs a) {
 extern "C" {
 
 // `filter`: null (pnmn_attn_lstm_fwd) or a filter to check; it applies to a sampling pass unless it is the identity
+// `automaton`: null, or the checked tables of a constrained call: a free-running pass then runs the constrained kernels
 static int attn_lstm_fwd_launch(const float* xe, const float* etable, const float* enc, const float* mask, const float* h0,
                                 const float* w_c, const float* w_hh, const float* w_p, const float* b_p, float* hs, float* cs,
                                 float* act, float* ctx, float* probs, int64_t* tokens, int B, int T, int S, int V, int hidden,
                                 int sample, int pad_index, int unk_index, int start_index, uint64_t seed, uint64_t row_offset,
                                 const int64_t* in_tokens, int64_t in_token_stride, const pnmn_sampling_filter* filter,
-                                void* stream) {
+                                const pnmn::TokenAutomaton* automaton, void* stream) {
     if (filter && !pnmn::filter_valid(filter)) return PNMN_EINVAL;
     if (B <= 0 || T <= 0) return 0;
     if (!enc || !mask || !h0 || !w_c || !w_hh || !hs || !cs || !act || !ctx || !probs) return PNMN_EINVAL;
@@ -415,6 +446,18 @@ static int attn_lstm_fwd_launch(const float* xe, const float* etable, const floa
     FwdArgs a{xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, hs, cs, act, ctx, probs, tokens, (!sample && !xe) ? in_tokens : nullptr,
               (long)in_token_stride, B, T, S, V, sample, pad_index, unk_index, start_index, seed, row_offset};
     const dim3 grid((B + ROWS - 1) / ROWS);
+    if (automaton && sample) {
+        ConstrainedFwdArgs c{};
+        static_cast<FwdArgs&>(c) = a;
+        c.automaton = *automaton;
+        if (sample == 1 && !pnmn::filter_is_identity(*filter))
+            hipLaunchKernelGGL((attn_lstm_fwd_kernel<true, true>), grid, dim3(512), 0, static_cast<hipStream_t>(stream), c,
+                               pnmn::SamplingFilter{filter->temperature, filter->top_k, filter->top_p});
+        else
+            hipLaunchKernelGGL((attn_lstm_fwd_kernel<false, true>), grid, dim3(512), 0, static_cast<hipStream_t>(stream), c,
+                               pnmn::SamplingFilter{1.f, 0, 1.f});
+        return (int)hipGetLastError();
+    }
     if (filter && sample == 1 && !pnmn::filter_is_identity(*filter))
         hipLaunchKernelGGL(attn_lstm_fwd_kernel<true>, grid, dim3(512), 0, static_cast<hipStream_t>(stream), a,
                            pnmn::SamplingFilter{filter->temperature, filter->top_k, filter->top_p});
@@ -431,7 +474,7 @@ int pnmn_attn_lstm_fwd(const float* xe, const float* etable, const float* enc, c
                        const int64_t* in_tokens, int64_t in_token_stride, void* stream) {
     return attn_lstm_fwd_launch(xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, hs, cs, act, ctx, probs, tokens, B, T, S, V, hidden,
                                 sample, pad_index, unk_index, start_index, seed, row_offset, in_tokens, in_token_stride, nullptr,
-                                stream);
+                                nullptr, stream);
 }
 
 int pnmn_attn_lstm_fwd_filtered(const float* xe, const float* etable, const float* enc, const float* mask, const float* h0,
@@ -443,7 +486,23 @@ int pnmn_attn_lstm_fwd_filtered(const float* xe, const float* etable, const floa
     if (!pnmn::filter_valid(filter)) return PNMN_EINVAL;
     return attn_lstm_fwd_launch(xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, hs, cs, act, ctx, probs, tokens, B, T, S, V, hidden,
                                 sample, pad_index, unk_index, start_index, seed, row_offset, in_tokens, in_token_stride, filter,
-                                stream);
+                                nullptr, stream);
+}
+
+int pnmn_attn_lstm_fwd_constrained(const float* xe, const float* etable, const float* enc, const float* mask, const float* h0,
+                                   const float* w_c, const float* w_hh, const float* w_p, const float* b_p, float* hs, float* cs,
+                                   float* act, float* ctx, float* probs, int64_t* tokens, int B, int T, int S, int V, int hidden,
+                                   int sample, int pad_index, int unk_index, int start_index, uint64_t seed, uint64_t row_offset,
+                                   const int64_t* in_tokens, int64_t in_token_stride, const pnmn_sampling_filter* filter,
+                                   int end_index, const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left,
+                                   int n_states, int n_classes, void* stream) {
+    if (!pnmn::filter_valid(filter)) return PNMN_EINVAL;
+    pnmn::TokenAutomaton automaton;
+    if (const int e = pnmn::fill_automaton(automaton, token_class, next_state, min_left, n_states, n_classes, sample ? V : 0, T, end_index))
+        return e;
+    return attn_lstm_fwd_launch(xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, hs, cs, act, ctx, probs, tokens, B, T, S, V, hidden,
+                                sample, pad_index, unk_index, start_index, seed, row_offset, in_tokens, in_token_stride, filter,
+                                &automaton, stream);
 }
 
 int pnmn_attn_lstm_bwd(const float* dhs, const float* act, const float* cs, const float* hs, const float* ctx,

@@ -23,6 +23,7 @@
 // (the one-workgroup kernel's per-step read-modify-write of denc is the largest part of its step).
 #include <hip/hip_runtime.h>
 #include <math.h>
+#include <limits.h>
 #include <stdint.h>
 
 #include "../../include/probnmn_hip.h"
@@ -90,9 +91,16 @@ constexpr size_t FWD_OVERLAP_LDS = sizeof(float) * (ROWS * H + 64);  // (OVERLAP
 // phase -- its logits tile, Philox draw and the pointers they keep live are what the register allocator spills.
 // FILT (with SAMPLE): mode 1 draws under the filter `f` (sampling.h); the weights take the place of the row's logits in `logl`,
 // dead by then.  Every member repeats the choice and gets the same token: it is a pure function of the row and the filter.
-template <bool OVERLAP, bool SAMPLE, bool FILT = false>
+// CONSTR (with SAMPLE): every choice is made within the automaton's allowed set A_c (the rule: include/probnmn_hip.h).  The
+// tables `aut` are staged once into AUTOMATON_LDS_BYTES of LDS behind everything else of the pass (the launch sizes its LDS,
+// and picks OVERLAP, with them counted).  A row's state and finished flag stay in scalar registers of the wave that chooses the
+// row's tokens -- wave w of EVERY member for rows 2w, 2w + 1, for all steps: a pure function of the row's own earlier tokens,
+// which the members already agree on, so the state needs no hand-off either.
+template <bool OVERLAP, bool SAMPLE, bool FILT = false, bool CONSTR = false>
 __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, const int tile, const int part,
-                                                         const pnmn::SamplingFilter& f = pnmn::SamplingFilter{1.f, 0, 1.f}) {
+                                                         const pnmn::SamplingFilter& f = pnmn::SamplingFilter{1.f, 0, 1.f},
+                                                         const pnmn::TokenAutomaton* aut = nullptr) {
+    static_assert(SAMPLE || !CONSTR, "the automaton constrains the free-running modes only");
     extern __shared__ __attribute__((aligned(16))) char raw[];
     const int T = a.T, S = a.S;
     float* encl = reinterpret_cast<float*>(raw);                                       // [RW][S][H]
@@ -173,6 +181,9 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
         *reinterpret_cast<f32x4*>(hst + s_off + 2 * PARTF) = h_hi;
     };
     if constexpr (OVERLAP) stage_h(a.h0, H);
+    pnmn::AutomatonLds au{};
+    int row_state[2] = {0, 0};  // (CONSTR) of rows 2 wave, 2 wave + 1: the start state, not finished
+    if constexpr (CONSTR) au = pnmn::stage_automaton(reinterpret_cast<unsigned char*>(OVERLAP ? sink + 64 : hst), *aut);
     __syncthreads();
 
     for (int t = 0; t < T; ++t) {
@@ -444,8 +455,16 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
                 const int rl = 2 * wave + rr;
                 const int row = row0 + rl;
                 if (row >= a.B) continue;
-                const int choice = pnmn::choose_row_token<FILT>(logl[rl], V, a.sample, a.pad, a.unk, a.start, a.seed,
-                                                                a.row_offset + (uint64_t)row, (uint32_t)t, logl[rl], f);
+                int choice;
+                if constexpr (CONSTR) {
+                    const auto set = pnmn::allowed_lanes(au, row_state[rr], T - 1 - t, V, a.pad, a.unk, a.start);
+                    choice = pnmn::choose_row_token<FILT>(logl[rl], V, a.sample, a.pad, a.unk, a.start, a.seed,
+                                                          a.row_offset + (uint64_t)row, (uint32_t)t, logl[rl], f, set);
+                    row_state[rr] = pnmn::advance_row_state(au, row_state[rr], choice);
+                } else {
+                    choice = pnmn::choose_row_token<FILT>(logl[rl], V, a.sample, a.pad, a.unk, a.start, a.seed,
+                                                          a.row_offset + (uint64_t)row, (uint32_t)t, logl[rl], f);
+                }
                 if (lane == 0) {
                     tokl[rl] = choice;
                     if (part == 0) a.tokens[(size_t)row * T + t] = choice;
@@ -511,6 +530,34 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         tile -= tiles0;
         if (tile >= a1.tiles) return;
         attn_lstm_fwd_multi_body<OVERLAP, M1 != 0, M1 == 2>(a1, tile, part, f1);
+    }
+}
+
+// ... and under a token automaton (pnmn_attn_lstm_fwd_group_constrained): every free-running pass of the launch is constrained
+// by the one automaton `au`.  M: 0 teacher forced, 1 constrained (sampling under the identity filter, or greedy), 2 constrained
+// sampling under its filter.  The pair is instantiated for M0 <= M1 only: the host puts the passes in that order.
+template <bool OVERLAP, bool FILT>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_lstm_fwd_multi_constrained_kernel(
+    const MFwdArgs a, const pnmn::SamplingFilter f, const pnmn::TokenAutomaton au) {
+    int tile, part;
+    pnmn::cluster_coords<MEMBERS>(tile, part);
+    if (tile >= a.tiles) return;
+    attn_lstm_fwd_multi_body<OVERLAP, true, FILT, true>(a, tile, part, f, &au);
+}
+
+template <bool OVERLAP, int M0, int M1>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_lstm_fwd_pair_constrained_kernel(
+    const MFwdArgs a0, const MFwdArgs a1, const int tiles0, const pnmn::SamplingFilter f0, const pnmn::SamplingFilter f1,
+    const pnmn::TokenAutomaton au) {
+    int tile, part;
+    pnmn::cluster_coords<MEMBERS>(tile, part);
+    if (tile < tiles0) {
+        if (tile >= a0.tiles) return;
+        attn_lstm_fwd_multi_body<OVERLAP, M0 != 0, M0 == 2, M0 != 0>(a0, tile, part, f0, &au);
+    } else {
+        tile -= tiles0;
+        if (tile >= a1.tiles) return;
+        attn_lstm_fwd_multi_body<OVERLAP, M1 != 0, M1 == 2, M1 != 0>(a1, tile, part, f1, &au);
     }
 }
 
@@ -913,6 +960,25 @@ const void* fwd_pair_filtered_variant(bool overlap, int m0, int m1) {
     return overlap ? fwd_pair_filtered_variant_of<true>(m0, m1) : fwd_pair_filtered_variant_of<false>(m0, m1);
 }
 
+// the constrained variants: m / m0 <= m1 as the kernels' M, at least one of them not 0
+const void* fwd_multi_constrained_variant(bool overlap, int m) {
+    if (overlap) return m == 2 ? reinterpret_cast<const void*>(attn_lstm_fwd_multi_constrained_kernel<true, true>)
+                               : reinterpret_cast<const void*>(attn_lstm_fwd_multi_constrained_kernel<true, false>);
+    return m == 2 ? reinterpret_cast<const void*>(attn_lstm_fwd_multi_constrained_kernel<false, true>)
+                  : reinterpret_cast<const void*>(attn_lstm_fwd_multi_constrained_kernel<false, false>);
+}
+template <bool OVERLAP>
+const void* fwd_pair_constrained_variant_of(int m0, int m1) {
+    if (m0 == 0) return m1 == 2 ? reinterpret_cast<const void*>(attn_lstm_fwd_pair_constrained_kernel<OVERLAP, 0, 2>)
+                                : reinterpret_cast<const void*>(attn_lstm_fwd_pair_constrained_kernel<OVERLAP, 0, 1>);
+    if (m0 == 1) return m1 == 2 ? reinterpret_cast<const void*>(attn_lstm_fwd_pair_constrained_kernel<OVERLAP, 1, 2>)
+                                : reinterpret_cast<const void*>(attn_lstm_fwd_pair_constrained_kernel<OVERLAP, 1, 1>);
+    return reinterpret_cast<const void*>(attn_lstm_fwd_pair_constrained_kernel<OVERLAP, 2, 2>);
+}
+const void* fwd_pair_constrained_variant(bool overlap, int m0, int m1) {
+    return overlap ? fwd_pair_constrained_variant_of<true>(m0, m1) : fwd_pair_constrained_variant_of<false>(m0, m1);
+}
+
 // rows one launch can take: all tiles x 8 members resident, one workgroup per CU
 int rows_per_launch() {
     const int cus = pnmn::device_cus();
@@ -1021,11 +1087,17 @@ int plan_group(const Job* j, int n, int hidden, int& smax, int& chunk, int* rows
 // alone (identical results).  A lone pass beyond one launch runs in row chunks.
 // `f`: one filter per job (checked by the caller), or null: none.  A job runs under its filter when it samples (mode 1) and
 // the filter is not the identity; every other job, and every launch without such a job, takes the unfiltered kernels.
-int launch_fwd(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, int n, int hidden, void* workspace, hipStream_t st) {
+// `au`: the checked automaton of a constrained call, or null.  It applies to every free-running job; a launch with such a job
+// takes the constrained kernels (launch_fwd_constrained), every other launch the kernels it always took.
+int launch_fwd_constrained(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, const pnmn::TokenAutomaton& au, int n,
+                           int hidden, void* workspace, hipStream_t st);
+int launch_fwd(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, int n, int hidden, void* workspace, hipStream_t st,
+               const pnmn::TokenAutomaton* au = nullptr) {
     if (n > 1 && !jobs_fit(j, n)) {
-        const int rc = launch_fwd(j, f, n - 1, hidden, workspace, st);
-        return rc != 0 ? rc : launch_fwd(j + n - 1, f ? f + n - 1 : nullptr, 1, hidden, workspace, st);
+        const int rc = launch_fwd(j, f, n - 1, hidden, workspace, st, au);
+        return rc != 0 ? rc : launch_fwd(j + n - 1, f ? f + n - 1 : nullptr, 1, hidden, workspace, st, au);
     }
+    if (au && (j[0].sample != 0 || (n > 1 && j[1].sample != 0))) return launch_fwd_constrained(j, f, *au, n, hidden, workspace, st);
     if (j[0].B <= 0 || j[0].T <= 0) return 0;  // (a lone pass only: passes side by side have rows and steps, see jobs_fit)
     int smax, chunk, rows[MAX_JOBS], tile0[MAX_JOBS + 1];
     if (const int e = plan_group(j, n, hidden, smax, chunk, rows, tile0)) return e;
@@ -1073,6 +1145,55 @@ int launch_fwd(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, int
             const auto multi = reinterpret_cast<void (*)(const MFwdArgs)>(const_cast<void*>(kernel));
             hipLaunchKernelGGL(multi, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a);
         }
+        e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
+// One launch of one or two passes that fit together (launch_fwd has seen to that), at least one of them free running: the
+// constrained kernels.  The pair kernels exist for M0 <= M1, so the passes go out in that order (a pass's result does not
+// depend on where its tiles sit in the grid).  The tables take AUTOMATON_LDS_BYTES behind the passes' own LDS, so OVERLAP is
+// picked with them counted: one source position earlier (S <= 58) than without the automaton, bit-identical either way.
+int launch_fwd_constrained(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, const pnmn::TokenAutomaton& au, int n,
+                           int hidden, void* workspace, hipStream_t st) {
+    if (j[0].B <= 0 || j[0].T <= 0) return 0;
+    int smax, chunk, rows[MAX_JOBS], tile0[MAX_JOBS + 1];
+    if (const int e = plan_group(j, n, hidden, smax, chunk, rows, tile0)) return e;
+    constexpr size_t TABLES = pnmn::AUTOMATON_LDS_BYTES;
+    const bool overlap = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + FWD_OVERLAP_LDS + TABLES <= LDS_LIMIT;
+    const size_t lds = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + (overlap ? FWD_OVERLAP_LDS : 0) + TABLES;
+    int m[2] = {0, 0};
+    pnmn::SamplingFilter ff[2] = {{1.f, 0, 1.f}, {1.f, 0, 1.f}};
+    for (int i = 0; i < n; ++i) {
+        m[i] = j[i].sample == 0 ? 0 : (j[i].sample == 1 && !pnmn::filter_is_identity(f[i])) ? 2 : 1;
+        if (m[i] == 2) ff[i] = pnmn::SamplingFilter{f[i].temperature, f[i].top_k, f[i].top_p};
+    }
+    int* sync = nullptr;
+    static std::atomic<uint64_t> cfg[2][2][9];  // (the opt-in is per device and per kernel: lds_optin.h)
+    if (n > 1) {
+        const int lo = m[0] <= m[1] ? 0 : 1, hi = 1 - lo;  // the order the passes go out in
+        const void* kernel = fwd_pair_constrained_variant(overlap, m[lo], m[hi]);
+        if (const int e = pnmn::opt_in_lds(kernel, LDS_LIMIT, cfg[1][overlap][3 * m[lo] + m[hi]])) return e;
+        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
+        if (e != hipSuccess) return (int)e;
+        const int tiles_lo = padded_tiles(rows[lo]);
+        const MFwdArgs a0 = kernel_args(j[lo], 0, rows[lo], sync, 0), a1 = kernel_args(j[hi], 0, rows[hi], sync, tiles_lo);
+        const auto pair = reinterpret_cast<void (*)(const MFwdArgs, const MFwdArgs, const int, const pnmn::SamplingFilter,
+                                                    const pnmn::SamplingFilter, const pnmn::TokenAutomaton)>(const_cast<void*>(kernel));
+        hipLaunchKernelGGL(pair, dim3(MEMBERS * tile0[2]), dim3(512), lds, st, a0, a1, tiles_lo, ff[lo], ff[hi], au);
+        return (int)hipGetLastError();
+    }
+    const void* kernel = fwd_multi_constrained_variant(overlap, m[0]);
+    if (const int e = pnmn::opt_in_lds(kernel, LDS_LIMIT, cfg[0][overlap][m[0]])) return e;
+    const auto multi = reinterpret_cast<void (*)(const MFwdArgs, const pnmn::SamplingFilter, const pnmn::TokenAutomaton)>(
+        const_cast<void*>(kernel));
+    for (int r0 = 0; r0 < rows[0]; r0 += chunk) {
+        const int part = rows[0] - r0 < chunk ? rows[0] - r0 : chunk;
+        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
+        if (e != hipSuccess) return (int)e;
+        const MFwdArgs a = kernel_args(j[0], (size_t)r0, part, sync, 0);
+        hipLaunchKernelGGL(multi, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a, ff[0], au);
         e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
@@ -1140,6 +1261,23 @@ int pnmn_attn_lstm_fwd_group_filtered(const pnmn_decoder_fwd_job* jobs, const pn
     for (int i = 0; i < n; ++i)
         if (!pnmn::filter_valid(filters + i)) return PNMN_EINVAL;
     return launch_fwd(jobs, filters, n, hidden, workspace, static_cast<hipStream_t>(stream));
+}
+
+int pnmn_attn_lstm_fwd_group_constrained(const pnmn_decoder_fwd_job* jobs, const pnmn_sampling_filter* filters, int end_index,
+                                         const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left,
+                                         int n_states, int n_classes, int n, int hidden, void* workspace, void* stream) {
+    if (!jobs || !filters || !workspace || n < 1 || n > 2) return PNMN_EINVAL;
+    int V = 0, T = INT_MAX;  // of the free-running jobs: one automaton, one vocabulary; the fewest steps
+    for (int i = 0; i < n; ++i) {
+        if (!pnmn::filter_valid(filters + i)) return PNMN_EINVAL;
+        if (jobs[i].sample == 0) continue;
+        if (V != 0 && jobs[i].V != V) return PNMN_EINVAL;
+        V = jobs[i].V;
+        T = jobs[i].T < T ? jobs[i].T : T;
+    }
+    pnmn::TokenAutomaton au;
+    if (const int e = pnmn::fill_automaton(au, token_class, next_state, min_left, n_states, n_classes, V, T, end_index)) return e;
+    return launch_fwd(jobs, filters, n, hidden, workspace, static_cast<hipStream_t>(stream), &au);
 }
 
 int pnmn_attn_lstm_bwd_group(const pnmn_decoder_bwd_job* jobs, int n, int hidden, void* workspace, void* stream) {

@@ -82,6 +82,19 @@ __device__ __forceinline__ int inverse_cdf(const float (&w)[K], float target) {
     return choice < 0 ? last_ok : choice;
 }
 
+// The allowed set of a token choice, beyond the rule's fixed "every index but pad / unk / start": WholeSet adds nothing (and,
+// being empty, changes neither the code nor the arguments of the functions below); LaneSet is a set the caller worked out per
+// lane -- each lane answers for its own indices lane and lane + 64 (rows of V <= 128), so a set costs no reduction.  It
+// replaces the fixed set and also bounds the arg-max of mode 2: the constrained decoders' A_c (allowed_lanes below).
+struct WholeSet {
+    static constexpr bool whole = true;
+};
+struct LaneSet {
+    static constexpr bool whole = false;
+    bool lo, hi;
+    __device__ __forceinline__ bool has(int j) const { return j < 64 ? lo : hi; }
+};
+
 // First index j < V with ok(j) of the largest v, a NaN counting as larger than any number (torch.argmax); -1 when no
 // index is ok.  Wave-uniform.
 template <int K, typename Ok>
@@ -108,12 +121,23 @@ __device__ inline int first_argmax(const float (&v)[K], Ok ok) {
 // The token of a row the common path cannot serve (the rule is documented beside pnmn_sample_tokens in
 // include/probnmn_hip.h): greedy over a row with a NaN; sampling over a row with a NaN or +inf, or whose allowed weights
 // sum to 0.  `v` holds the row (entries j >= V are -inf), `u` the row's uniform.  Reached only through a wave-uniform
-// branch that a finite row with positive allowed mass never takes.
-template <int K>
-__device__ inline int choose_token_fallback(const float (&v)[K], int V, bool greedy, int pad, int unk, int start, float u) {
+// branch that a finite row with positive allowed mass never takes.  `set` (a LaneSet): the allowed set in the place of the
+// fixed one; it then also holds the greedy choice of a row with a NaN, which is the arg-max of this rule inside the set.
+template <int K, class Set = WholeSet>
+__device__ inline int choose_token_fallback(const float (&v)[K], int V, bool greedy, int pad, int unk, int start, float u,
+                                            const Set set = Set{}) {
     const int lane = threadIdx.x & 63;
     const auto in_row = [V](int j) { return j < V; };
-    const auto allowed = [=](int j) { return j < V && j != pad && j != unk && j != start; };
+    const auto allowed = [=](int j) {
+        if constexpr (Set::whole) return j < V && j != pad && j != unk && j != start;
+        else return set.has(j);
+    };
+    if constexpr (!Set::whole) {
+        if (greedy) {
+            const int c = first_argmax(v, allowed);
+            if (c >= 0) return c;
+        }
+    }
     if (!greedy) {
         bool bad = false;  // a NaN or +inf in the row
         float m = -INFINITY;  // largest allowed logit
@@ -163,22 +187,25 @@ inline bool filter_is_identity(const pnmn_sampling_filter& f) { return f.tempera
 //   top-k keeps rank < top_k, top-p of those the ones with mass before < top_p x (total kept by top-k) and rank 0;
 //   the draw is the index-order inverse CDF over what is left, from the row's usual uniform `u`.
 // A pure function of the row and the filter, wave-uniform: the eight members of a multi-CU tile agree.
-template <int K>
+// `set` (a LaneSet): the rule's A replaced by that set.
+template <int K, class Set = WholeSet>
 __device__ inline int filtered_draw(const float (&v)[K], float* wl, int V, int pad, int unk, int start,
-                                    const SamplingFilter& f, float u) {
+                                    const SamplingFilter& f, float u, const Set set = Set{}) {
     const int lane = threadIdx.x & 63;
     float w[K], m = -INFINITY;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int j = lane + 64 * k;
-        w[k] = (j < V && j != pad && j != unk && j != start) ? v[k] / f.temperature : -INFINITY;
+        if constexpr (Set::whole) w[k] = (j < V && j != pad && j != unk && j != start) ? v[k] / f.temperature : -INFINITY;
+        else w[k] = set.has(j) ? v[k] / f.temperature : -INFINITY;
         m = fmaxf(m, w[k]);
     }
     m = wmax(m);  // finite: some allowed weight of the unfiltered distribution is positive
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const int j = lane + 64 * k;
-        w[k] = (j < V && j != pad && j != unk && j != start) ? expf(w[k] - m) : -1.f;
+        if constexpr (Set::whole) w[k] = (j < V && j != pad && j != unk && j != start) ? expf(w[k] - m) : -1.f;
+        else w[k] = set.has(j) ? expf(w[k] - m) : -1.f;
         wl[j] = w[k];
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // one wave: its LDS accesses complete in order
@@ -222,10 +249,12 @@ __device__ inline int filtered_draw(const float (&v)[K], float* wl, int V, int p
 // seq2seq_base.py:203-220); rows that are not all finite follow choose_token_fallback.  The result is
 // wave-uniform and always in [0, V).  FILT: mode 1 draws under the filter `f` instead (filtered_draw, which overwrites
 // the 128 floats at `wl`); the rows the fallback serves, and mode 2, ignore it.
-template <bool FILT = false>
+// `set` (a LaneSet): the draw, filtered or not, and the fallback are restricted to that set instead of "all but pad / unk /
+// start", and so is the arg-max of mode 2; the softmax itself is always that of the whole row.
+template <bool FILT = false, class Set = WholeSet>
 __device__ inline int choose_row_token(const float* logits, int V, int mode, int pad, int unk, int start, uint64_t seed,
                                        uint64_t global_row, uint32_t t, float* wl = nullptr,
-                                       const SamplingFilter& f = SamplingFilter{1.f, 0, 1.f}) {
+                                       const SamplingFilter& f = SamplingFilter{1.f, 0, 1.f}, const Set set = Set{}) {
     const int lane = threadIdx.x & 63;
     float v[2];
     float mx = -INFINITY;
@@ -239,16 +268,27 @@ __device__ inline int choose_row_token(const float* logits, int V, int mode, int
     int choice;
     if (mode == 2) {
         int best = 0x7fffffff;
+        if constexpr (Set::whole) {
 #pragma unroll
-        for (int k = 0; k < 2; ++k)
-            if (lane + 64 * k < V && v[k] == mx && lane + 64 * k < best) best = lane + 64 * k;
+            for (int k = 0; k < 2; ++k)
+                if (lane + 64 * k < V && v[k] == mx && lane + 64 * k < best) best = lane + 64 * k;
+        } else {
+            float ms = -INFINITY;  // the largest logit inside the set
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+                if (set.has(lane + 64 * k)) ms = fmaxf(ms, v[k]);
+            ms = wmax(ms);
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+                if (set.has(lane + 64 * k) && v[k] == ms && lane + 64 * k < best) best = lane + 64 * k;
+        }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) {
             const int other = __shfl_xor(best, o);
             best = other < best ? other : best;
         }
         choice = best;
-        if (__ballot(v[0] != v[0] || v[1] != v[1])) choice = choose_token_fallback(v, V, true, pad, unk, start, 0.f);
+        if (__ballot(v[0] != v[0] || v[1] != v[1])) choice = choose_token_fallback(v, V, true, pad, unk, start, 0.f, set);
     } else {
         float se = 0.f;
 #pragma unroll
@@ -258,20 +298,99 @@ __device__ inline int choose_row_token(const float* logits, int V, int mode, int
 #pragma unroll
         for (int k = 0; k < 2; ++k) {
             const int j = lane + 64 * k;
-            const bool ok = j < V && j != pad && j != unk && j != start;
+            bool ok;
+            if constexpr (Set::whole) ok = j < V && j != pad && j != unk && j != start;
+            else ok = set.has(j);
             w[k] = ok ? expf(v[k] - lse) : 0.f;
             tot += w[k];
         }
         tot = wsum(tot);
         const float u = philox_uniform(seed, global_row, t);
         if (tot > 0.f) {  // (a NaN or +inf anywhere in the row makes the total NaN)
-            if constexpr (FILT) choice = filtered_draw(v, wl, V, pad, unk, start, f, u);
+            if constexpr (FILT) choice = filtered_draw(v, wl, V, pad, unk, start, f, u, set);
             else choice = inverse_cdf(w, u * tot);
         } else {
-            choice = choose_token_fallback(v, V, false, pad, unk, start, u);
+            choice = choose_token_fallback(v, V, false, pad, unk, start, u, set);
         }
     }
     return min(max(choice, 0), V - 1);
+}
+
+// ---- the token automaton of the constrained decoders (the rule: include/probnmn_hip.h, beside pnmn_attn_lstm_fwd_constrained) ----
+// The tables as the entry points check them and as they travel BY VALUE in the launch arguments; a workgroup stages them
+// into LDS once (stage_automaton).  Unused entries are 0.
+constexpr int AUTOMATON_STATES = PNMN_BEAM_MAX_STATES, AUTOMATON_CLASSES = PNMN_BEAM_MAX_CLASSES, AUTOMATON_TOKENS = 128;
+struct TokenAutomaton {
+    unsigned char token_class[AUTOMATON_TOKENS];                     // [V], < n_classes
+    unsigned char next_state[AUTOMATON_STATES * AUTOMATON_CLASSES];  // [n_states][n_classes] packed, < n_states
+    unsigned char min_left[AUTOMATON_STATES];                        // [n_states]; 255: no completion exists
+    int n_classes, end;
+};
+constexpr int AUTOMATON_LDS_BYTES = AUTOMATON_TOKENS + AUTOMATON_STATES * AUTOMATON_CLASSES + AUTOMATON_STATES;  // 672
+static_assert(AUTOMATON_STATES * AUTOMATON_CLASSES == 512 && AUTOMATON_TOKENS <= 512, "staged by 512 threads, one entry each");
+
+// What the constrained entry points check before they launch anything: 0 and `out` filled, or PNMN_EINVAL.  V, T: of the
+// free-running passes the automaton applies to; V = 0 when there is none (a teacher-forced call: the tables are checked as far
+// as they can be without a vocabulary, and ignored).
+inline int fill_automaton(TokenAutomaton& out, const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left,
+                          int n_states, int n_classes, int V, int T, int end_index) {
+    out = TokenAutomaton{};
+    if (!token_class || !next_state || !min_left) return PNMN_EINVAL;
+    if (n_states < 1 || n_states > AUTOMATON_STATES || n_classes < 1 || n_classes > AUTOMATON_CLASSES) return PNMN_EINVAL;
+    if (V != 0 && (V < 1 || V > AUTOMATON_TOKENS || end_index < 0 || end_index >= V)) return PNMN_EINVAL;
+    for (int v = 0; v < V; ++v) {
+        if (token_class[v] >= n_classes) return PNMN_EINVAL;
+        out.token_class[v] = token_class[v];
+    }
+    for (int i = 0; i < n_states * n_classes; ++i) {
+        if (next_state[i] >= n_states) return PNMN_EINVAL;
+        out.next_state[i] = next_state[i];
+    }
+    for (int s = 0; s < n_states; ++s) out.min_left[s] = min_left[s];
+    if (V != 0 && (int)min_left[0] > T) return PNMN_EINVAL;  // no accepted string fits the steps: A_c would run empty
+    out.n_classes = n_classes;
+    out.end = end_index;
+    return 0;
+}
+
+// the staged tables: three byte arrays in `AUTOMATON_LDS_BYTES` of LDS
+struct AutomatonLds {
+    const unsigned char *cls, *next, *left;
+    int ncls, end;
+};
+// all 512 threads of a workgroup, before a barrier of the caller's
+__device__ __forceinline__ AutomatonLds stage_automaton(unsigned char* lds, const TokenAutomaton& au) {
+    const int tid = threadIdx.x;
+    unsigned char *cls = lds, *next = cls + AUTOMATON_TOKENS, *left = next + AUTOMATON_STATES * AUTOMATON_CLASSES;
+    next[tid] = au.next_state[tid];
+    if (tid < AUTOMATON_TOKENS) cls[tid] = au.token_class[tid];
+    if (tid < AUTOMATON_STATES) left[tid] = au.min_left[tid];
+    return AutomatonLds{cls, next, left, au.n_classes, au.end};
+}
+// A row's automaton state as the wave that chooses its tokens carries it: bits 0-7 the state, bit 8 = the row has finished.
+constexpr int ROW_FINISHED = 256;
+// A_c(s, t) of a row, each lane answering for its indices lane, lane + 64: `left` = T - 1 - t.  A finished row: end_index alone.
+// All lanes of a wave read the same two state bytes (LDS broadcasts); the class and next-state bytes are per lane.
+__device__ __forceinline__ LaneSet allowed_lanes(const AutomatonLds& au, int row_state, int left, int V, int pad, int unk, int start) {
+    const int lane = threadIdx.x & 63;
+    const bool finished = (row_state & ROW_FINISHED) != 0;
+    const int s = row_state & 255;
+    const int room = left < 254 ? left : 254;  // (255 marks a state without completion, however many steps remain)
+    const bool may_end = finished || au.left[s] == 0;
+    bool in[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const int j = lane + 64 * k;
+        const bool token = !finished && j != pad && j != unk && j != start && (int)au.left[au.next[s * au.ncls + au.cls[j]]] <= room;
+        in[k] = j < V && (j == au.end ? may_end : token);
+    }
+    return LaneSet{in[0], in[1]};
+}
+// the row's state behind its token (wave-uniform in, wave-uniform out)
+__device__ __forceinline__ int advance_row_state(const AutomatonLds& au, int row_state, int token) {
+    if (row_state & ROW_FINISHED) return row_state;
+    if (token == au.end) return row_state | ROW_FINISHED;
+    return __builtin_amdgcn_readfirstlane((int)au.next[row_state * au.ncls + au.cls[token]]);
 }
 
 }  // namespace pnmn

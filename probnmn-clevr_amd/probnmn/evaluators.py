@@ -126,7 +126,7 @@ def evaluate_answer_accuracy(program_generator, nmn, batches: Iterable[Dict[str,
 def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary,
                     beam_size: Optional[int] = None, prefer_valid: bool = True,
                     constrained: bool = False, extractor=None, temperature: float = 1.0, top_k: int = 0,
-                    top_p: float = 1.0) -> List[Dict[str, Any]]:
+                    top_p: float = 1.0, constrained_sampling: bool = False) -> List[Dict[str, Any]]:
     """scripts/inference.py:76-91: sampled programs -> NMN -> answer strings, one record per question
     (``question_index`` from the batch when present, else a running index).
 
@@ -147,9 +147,18 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
 
     ``temperature``, ``top_k``, ``top_p``: the sampling filter of the generator's sampled programs (``Seq2SeqBase.decode``);
     the record layout is unchanged.  Values out of range, or a filter other than (1, 0, 1) together with ``beam_size``
-    (a beam search draws nothing), are a ``ValueError``."""
+    (a beam search draws nothing), are a ``ValueError``.
+
+    ``constrained_sampling``: the programs are SAMPLED under the program compiler's validity rule
+    (``decoding_strategy="constrained_sampling"`` with ``nmn.engine.compiler.decoding_automaton``; ``temperature``, ``top_k``
+    and ``top_p`` apply), on the multi-CU decoder kernels the plain sampled decode runs on, so no question is answered
+    ``@@UNKNOWN@@`` for want of a valid program.  Each record also names its ``"program"`` and whether it is a
+    ``"program_valid"`` one (decided on the host, as for the beams: always true).  Together with ``beam_size`` it is a
+    ``ValueError``."""
     if constrained and beam_size is None:
         raise ValueError("constrained=True constrains the beam search: give a beam_size")
+    if constrained_sampling and beam_size is not None:
+        raise ValueError("constrained_sampling=True samples the programs; with beam_size they are searched (constrained=True)")
     filt = sampling_filter(temperature, top_k, top_p)
     if filt is not None and beam_size is not None:
         raise ValueError("temperature / top_k / top_p filter sampled programs; with beam_size the programs are searched, not drawn")
@@ -163,7 +172,7 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
         pinned: Dict[Any, torch.Tensor] = {}
         pad = getattr(program_generator, "_pad_index", 0)
         constraint = None
-        if constrained:  # built once (and cached on the compiler): the tokens the decoder never emits do not count
+        if constrained or constrained_sampling:  # built once (and cached on the compiler): the tokens the decoder never emits do not count
             exclude = [getattr(program_generator, name) for name in ("_pad_index", "_unk_index", "_start_index", "_end_index")]
             constraint = nmn.engine.compiler.decoding_automaton(exclude=exclude)
 
@@ -178,7 +187,10 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
 
         def queue(batch, iteration):
             image = features(batch)
-            if beam_size is None:
+            if constrained_sampling:
+                programs = program_generator(batch["question"], decoding_strategy="constrained_sampling", constraint=constraint,
+                                             **sampling)["predictions"]
+            elif beam_size is None:
                 programs = program_generator(batch["question"], **sampling)["predictions"]
             else:
                 extra = {} if constraint is None else {"constraint": constraint}
@@ -217,13 +229,17 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
             if beam_size is not None:
                 programs, ranks, valid = choose(programs)
                 extra = (programs.tolist(), ranks, valid)
+            elif constrained_sampling:
+                host = programs.cpu()
+                extra = (host.tolist(), None, [c.valid for c in nmn.engine.compiler.compile_batch(host.numpy())])
             answers = nmn(image, programs)["predictions"].cpu().tolist()
             index = batch["question_index"].cpu().tolist() if "question_index" in batch else range(len(records), len(records) + len(answers))
             for i, (qi, a) in enumerate(zip(index, answers)):
                 record = {"question_index": int(qi), "answer": vocabulary.get_token_from_index(int(a), namespace="answers")}
                 if extra is not None:
                     record["program"] = [vocabulary.get_token_from_index(int(t), namespace="programs") for t in extra[0][i] if t != pad]
-                    record["beam_rank"] = int(extra[1][i])
+                    if extra[1] is not None:
+                        record["beam_rank"] = int(extra[1][i])
                     record["program_valid"] = bool(extra[2][i])
                 records.append(record)
 

@@ -640,7 +640,36 @@ def _decoder_forward(tensors, metas) -> _DecoderLaunch:
         filters = np.zeros(n, _hip.SAMPLING_FILTER)
         for k, m in enumerate(metas):
             filters[k] = (*(m.get("filter") or IDENTITY_FILTER), 0)
-    if ws is not None and filters is not None:
+    # ``meta["constraint"]``: (token_class, next_state, min_left, end index) of a free-running pass that decodes under a token
+    # automaton (``constraint_tables``).  The constrained entry points apply ONE automaton to every free-running pass of the
+    # launch, so passes side by side name the same one, or none
+    constraint = None
+    for m in metas:
+        c = m.get("constraint")
+        if c is not None and m["mode"] == 0:
+            raise ValueError("a teacher-forced decoder pass takes no constraint")
+        if c is not None and constraint is not None and c is not constraint:
+            raise ValueError("decoder passes side by side decode under one token automaton")
+        constraint = c if c is not None else constraint
+    if constraint is not None:
+        if any(m["mode"] != 0 and m.get("constraint") is None for m in metas):
+            raise ValueError("a constrained and an unconstrained free-running pass cannot share a launch")
+        if filters is None:
+            filters = np.zeros(n, _hip.SAMPLING_FILTER)
+            filters[:] = (*IDENTITY_FILTER, 0)
+        tc, ns, ml, end = constraint  # (host arrays: the library checks every entry and passes them by value)
+        automaton = (end, tc.ctypes.data, ns.ctypes.data, ml.ctypes.data, ns.shape[0], ns.shape[1])
+        if ws is not None:
+            _hip.check(lib.pnmn_attn_lstm_fwd_group_constrained(jobs.ctypes.data, filters.ctypes.data, *automaton, n, Hd, ws.data_ptr(),
+                                                                _hip.stream_ptr(dev)), "attn_lstm_fwd_group_constrained")
+        elif n == 1:
+            j = jobs[0].item()
+            _hip.check(lib.pnmn_attn_lstm_fwd_constrained(*j[:15], *j[19:23], Hd, *j[23:27], j[17], j[18], j[15], j[16],
+                                                          filters.ctypes.data, *automaton, _hip.stream_ptr(dev)),
+                       "attn_lstm_fwd_constrained")
+        else:
+            raise _hip.HipLibraryError("decoder passes side by side need the multi-CU decoder kernels (none on this device)")
+    elif ws is not None and filters is not None:
         _hip.check(lib.pnmn_attn_lstm_fwd_group_filtered(jobs.ctypes.data, filters.ctypes.data, n, Hd, ws.data_ptr(),
                                                          _hip.stream_ptr(dev)), "attn_lstm_fwd_group_filtered")
     elif ws is not None:
@@ -744,9 +773,9 @@ class _AttnLSTMDecoder(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, mode, T, seed, row_offset, pad, unk, start,
-                packs=None, in_tokens=None, filter=None):
+                packs=None, in_tokens=None, filter=None, constraint=None):
         m = dict(mode=mode, T=T, seed=seed, row_offset=row_offset, pad=pad, unk=unk, start=start, packs=packs, w_p=w_p, b_p=b_p,
-                 in_tokens=in_tokens if mode == 0 else None, filter=filter)
+                 in_tokens=in_tokens if mode == 0 else None, filter=filter, constraint=constraint)
         ctx.projected = mode == 0 and in_tokens is None
         got = _decoder_forward([(xe if ctx.projected else etable, enc, mask, h0, w_c, w_hh)], [m])
         ctx.save_for_backward(*got.saved)
@@ -758,7 +787,7 @@ class _AttnLSTMDecoder(torch.autograd.Function):
     def backward(ctx, dhs, _):
         need = ctx.needs_input_grad
         d = _decoder_sides_backward(ctx.saved_tensors, ctx.side_meta, (dhs,), (need[0 if ctx.projected else 1], *need[2:7]))
-        return ((d[0], None) if ctx.projected else (None, d[0])) + tuple(d[1:]) + (None,) * 12
+        return ((d[0], None) if ctx.projected else (None, d[0])) + tuple(d[1:]) + (None,) * 13
 
 
 class _AttnLSTMDecoderGroup(torch.autograd.Function):
@@ -818,6 +847,18 @@ def sampling_filter(temperature=1.0, top_k=0, top_p=1.0):
         raise ValueError("top_p must lie in (0, 1], got %r" % (top_p,))
     f = (t, int(top_k), p)
     return None if f == IDENTITY_FILTER else f
+
+
+def constraint_tables(constraint, n_vocab: int, end_index: int):
+    """``meta["constraint"]`` of a decoder pass, and what ``decode_beam`` hands its kernel: (token_class [V], next_state
+    [n_states, n_classes], min_left [n_states], end index) from a token automaton (``ProgramCompiler.decoding_automaton``) as
+    contiguous uint8 numpy arrays.  ``ValueError`` for tables of another shape or another vocabulary size."""
+    tables = [np.ascontiguousarray(getattr(constraint, name), dtype=np.uint8) for name in ("token_class", "next_state", "min_left")]
+    if tables[0].ndim != 1 or tables[0].shape[0] != n_vocab:
+        raise ValueError("constraint: token_class covers %s tokens, the target vocabulary has %d" % (tables[0].shape, n_vocab))
+    if tables[1].ndim != 2 or tables[2].shape != (tables[1].shape[0],):
+        raise ValueError("constraint: next_state must be [n_states, n_classes] and min_left [n_states]")
+    return (*tables, int(end_index))
 
 
 def choose_tokens(logits: torch.Tensor, greedy: bool, seed: int, row_offset: int, step: int,
@@ -1130,10 +1171,18 @@ class Seq2SeqBase(nn.Module):
         top_p: float = 1.0,
     ) -> Dict[str, torch.Tensor]:
         """``decoding_strategy``: "sampling" / "greedy" as the reference; "beam": beam search of width ``beam_size`` (free
-        running only, no gradients -- see ``decode_beam``).  ``beam_size`` is ignored by the other strategies;
-        ``constraint`` (a token automaton, beam search only) is refused by them.  ``temperature``, ``top_k``, ``top_p``:
-        the sampling filter, "sampling" only (see ``decode``)."""
+        running only, no gradients -- see ``decode_beam``); "constrained_sampling" / "constrained_greedy": a sampled / arg-max
+        decode under the token automaton ``constraint`` (free running, inference only -- see ``decode_constrained``).
+        ``beam_size`` is ignored by the other strategies; ``constraint`` (a token automaton) is required by the constrained
+        strategies, optional for "beam" and refused by "sampling" / "greedy".  ``temperature``, ``top_k``, ``top_p``: the
+        sampling filter, "sampling" and "constrained_sampling" only (see ``decode``)."""
         self._check_filter(decoding_strategy, temperature, top_k, top_p)
+        if decoding_strategy in self.CONSTRAINED_STRATEGIES:
+            self._check_constrained_arguments(target_tokens, constraint)
+            with torch.no_grad():  # (the encoder without its dropout, as for "beam": the same in train() and eval() mode)
+                return self.decode_constrained(self.encode(source_tokens, dropout=False), constraint,
+                                               greedy=decoding_strategy == "constrained_greedy", temperature=temperature,
+                                               top_k=top_k, top_p=top_p)
         if decoding_strategy == "beam":
             self._check_beam_arguments(target_tokens, beam_size)
             with torch.no_grad():  # (the encoder without its dropout: the search is the same in train() and eval() mode)
@@ -1193,21 +1242,28 @@ class Seq2SeqBase(nn.Module):
         teacher-forced distributions (reference :196-220) -- training iterations never read them.  ``seed``: the sampler
         seed a ``decode_prepare`` of this pass already drew (its pairing fell through): one draw per pass either way, so
         paired and unpaired schedules sample the same programs from the same torch seed.  ``decoding_strategy="beam"``:
-        ``decode_beam`` with ``beam_size`` (which the other strategies ignore) and ``constraint`` (which they refuse).
-        ``temperature``, ``top_k``, ``top_p`` (``decoding_strategy="sampling"`` only; anything but (1, 0, 1) with another
-        strategy is a ``ValueError``): the tokens -- the free-running decode's, and the predictions drawn from teacher-forced
+        ``decode_beam`` with ``beam_size`` (which the other strategies ignore) and ``constraint``.
+        ``decoding_strategy="constrained_sampling"`` / ``"constrained_greedy"``: ``decode_constrained`` under ``constraint``
+        (required; "sampling" / "greedy" refuse one).
+        ``temperature``, ``top_k``, ``top_p`` (``decoding_strategy="sampling"`` / ``"constrained_sampling"`` only; anything but
+        (1, 0, 1) with another strategy is a ``ValueError``): the tokens -- the free-running decode's, and the predictions drawn from teacher-forced
         distributions -- are drawn from the distribution sharpened by the temperature and cut to its ``top_k`` most likely
         tokens and its ``top_p`` nucleus (the rule: include/probnmn_hip.h).  They use the uniforms an unfiltered decode from
         the same seed uses, and ``loss`` still scores them under the unmodified distribution.  Shapes outside the persistent
         kernels have no filtered path: ``NotImplementedError``."""
         filt = self._check_filter(decoding_strategy, temperature, top_k, top_p)
+        if decoding_strategy in self.CONSTRAINED_STRATEGIES:
+            self._check_constrained_arguments(target_tokens, constraint)
+            return self.decode_constrained(state, constraint, greedy=decoding_strategy == "constrained_greedy", seed=seed,
+                                           temperature=temperature, top_k=top_k, top_p=top_p)
         if decoding_strategy == "beam":
             self._check_beam_arguments(target_tokens, beam_size)
             return self.decode_beam(state, beam_size, constraint=constraint)
         if constraint is not None:
-            raise ValueError("constraint: only decoding_strategy='beam' decodes under a token automaton")
+            raise ValueError("constraint: decoding_strategy='beam', 'constrained_sampling' and 'constrained_greedy' decode under a "
+                             "token automaton; %r does not" % (decoding_strategy,))
         if decoding_strategy not in ("sampling", "greedy"):
-            raise ValueError("decoding_strategy must be 'sampling', 'greedy' or 'beam'")
+            raise ValueError("decoding_strategy must be 'sampling', 'greedy', 'beam', 'constrained_sampling' or 'constrained_greedy'")
         pad, bos, eos = self._pad_index, self._start_index, self._end_index
         enc, h, fmask = state["enc"], state["h"], state["fmask"]
         tgt = None
@@ -1261,10 +1317,66 @@ class Seq2SeqBase(nn.Module):
         """The sampling filter of a call (``sampling_filter``: None for the identity); ``ValueError`` for values out of range,
         and for a filter on a strategy that does not sample."""
         filt = sampling_filter(temperature, top_k, top_p)
-        if filt is not None and decoding_strategy != "sampling":
+        if filt is not None and decoding_strategy not in ("sampling", "constrained_sampling"):
             raise ValueError("temperature / top_k / top_p filter what decoding_strategy='sampling' draws; %r does not sample"
                              % (decoding_strategy,))
         return filt
+
+    # ---- sampling and greedy decoding under a token automaton (inference) ----------------------------------------------
+    CONSTRAINED_STRATEGIES = ("constrained_sampling", "constrained_greedy")
+
+    @staticmethod
+    def _check_constrained_arguments(target_tokens, constraint) -> None:
+        if constraint is None:
+            raise ValueError("decoding_strategy='constrained_sampling' / 'constrained_greedy' needs constraint= (a token automaton)")
+        if target_tokens is not None:
+            raise ValueError("a constrained decode is free running: it takes no target_tokens")
+
+    @torch.no_grad()
+    def decode_constrained(self, state: Dict[str, torch.Tensor], constraint, greedy: bool = False, seed: Optional[int] = None,
+                           temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> Dict[str, torch.Tensor]:
+        """A sampled (or, ``greedy``, arg-max) free-running decode over ``max_decoding_steps`` steps in which every row is a
+        string the token automaton ``constraint`` accepts (``ProgramCompiler.decoding_automaton``: a valid program), on the
+        persistent decoder kernels the unconstrained decode runs on (``pnmn_attn_lstm_fwd_group_constrained`` /
+        ``pnmn_attn_lstm_fwd_constrained``; the rule is stated in include/probnmn_hip.h).  At every step a row may take only
+        the tokens from which an accepted string can still be completed in the steps that remain, and @end@ only where the
+        string so far is accepted; the draw is the usual one restricted to that set (with ``temperature`` / ``top_k`` /
+        ``top_p``: rank, top-k and nucleus within the set), the greedy choice the first largest logit within it.  The
+        uniforms are those of an unconstrained sampling decode from the same seed.
+
+        INFERENCE ONLY, no graph, the same in ``train()`` and ``eval()`` mode: a constrained draw is not a draw from the
+        generator's distribution, so no trainer calls this.  Returns ``predictions`` [B, T] (trimmed: padding after a row's
+        first @end@) and ``loss`` [B], the length-normalised negative log-probability of the trimmed row as the sampling
+        decode reports it -- ``log_softmax(z)[token]`` of the UNMODIFIED distribution, not of the restricted one.
+        ``seed``: None draws ONE seed from the torch CPU generator, exactly as the sampling decode does; a greedy call
+        draws none.  ``ValueError``: no constraint, tables of another vocabulary size, an automaton whose shortest accepted
+        string is longer than ``max_decoding_steps``, a filter together with ``greedy``.  There is no step-by-step path:
+        shapes outside the persistent kernels raise ``NotImplementedError``."""
+        if constraint is None:
+            raise ValueError("decode_constrained needs a token automaton")
+        filt = sampling_filter(temperature, top_k, top_p)
+        if greedy and filt is not None:
+            raise ValueError("temperature / top_k / top_p filter a draw; a greedy constrained decode draws nothing")
+        enc, h = state["enc"], state["h"]
+        n_vocab, T = self._output_projection_layer.weight.size(0), self._max_decoding_steps
+        tables = constraint_tables(constraint, n_vocab, self._end_index)
+        if int(tables[2][0]) > T:
+            raise ValueError("constraint: the shortest accepted string takes %d tokens, max_decoding_steps is %d" % (int(tables[2][0]), T))
+        Hd = h.size(1)
+        if not (Hd == 256 and enc.size(1) <= 64 and n_vocab <= 128):
+            raise NotImplementedError("constrained decoding: hidden size %d, %d source positions, %d target tokens -- it exists in the "
+                                      "persistent decoder kernels only (256 / <= 64 / <= 128)" % (Hd, enc.size(1), n_vocab))
+        if greedy:
+            seed = 0
+        elif seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # CPU generator: no device sync
+        state = {k: v.detach() for k, v in state.items()}
+        prep = self._fused_prep(state, None, greedy, seed, self._derived())
+        prep["meta"]["constraint"] = tables
+        if filt is not None:
+            prep["meta"]["filter"] = filt
+        hs, raw = _AttnLSTMDecoderGroup.apply(*_prep_tensors(prep), [prep["meta"]], None)
+        return self._finish(prep, hs, raw)[0]
 
     # ---- beam search (inference) ---------------------------------------------------------------------------------------
     BEAM_SIZES = (1, 2, 4, 8, 16)
@@ -1297,14 +1409,7 @@ class Seq2SeqBase(nn.Module):
         self._check_beam_arguments(None, beam_size)
         tables = None
         if constraint is not None:
-            tables = [np.ascontiguousarray(getattr(constraint, name), dtype=np.uint8)
-                      for name in ("token_class", "next_state", "min_left")]
-            n_vocab = self._output_projection_layer.weight.size(0)
-            if tables[0].ndim != 1 or tables[0].shape[0] != n_vocab:
-                raise ValueError("constraint: token_class covers %s tokens, the target vocabulary has %d"
-                                 % (tables[0].shape, n_vocab))
-            if tables[1].ndim != 2 or tables[2].shape != (tables[1].shape[0],):
-                raise ValueError("constraint: next_state must be [n_states, n_classes] and min_left [n_states]")
+            tables = constraint_tables(constraint, self._output_projection_layer.weight.size(0), self._end_index)[:3]
         enc, h, fmask = state["enc"].detach(), state["h"].detach(), state["fmask"].detach()
         dev = enc.device
         if dev.type != "cuda":
