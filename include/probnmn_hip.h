@@ -323,6 +323,22 @@ typedef struct {
 int pnmn_token_prep(const int64_t* tokens, int64_t token_row_stride, int B, int T, int pad, int bos, int eos,
                     int drop_first, int64_t* out, float* fmask, int* last, void* stream);
 int pnmn_length_order(const int32_t* last, int B, int T, int32_t* order, int32_t* tile_steps, void* stream);
+/* The valid (row, step) pairs of padded [rows][T][.] passes as lists of storage rows, for pnmn_gemm_rows.  n <= 8 segments
+ * (HOST arrays of n entries each); segment i is a pass of rows[i] sequences of T[i] steps whose sequence b has
+ *   steps_b = clamp(last[i][b] + 1, 1, T[i])                                  where last[i] != NULL (an encoder pass:
+ *             what pnmn_length_order takes), else
+ *   steps_b = 1 + the last t with mask_tokens[i][b * mask_stride[i] + t] != pad[i], 0 when there is none  (a decoder
+ *             pass: the last step pnmn_seq_nll_fwd weights, given the same mask tokens -- a pad inside a sampled
+ *             program drops no later step).
+ * Consecutive segments with the same list[i] are passes stored one behind the other (a decoder's flat buffers): their
+ * entries are appended, storage rows counted on from the segments before.  Per list: entries (row, prev) of two int32,
+ * row = b T + t for t < steps_b in ascending order, prev = row - 1, or ~b (b counted over the list's segments) at t = 0;
+ * *count[i] = their number.  list[i] must hold sum rows x T entries of 8 bytes.  One workgroup per list scans its rows in
+ * order: deterministic, no atomics, no host synchronisation. */
+int pnmn_valid_rows(const int32_t* const* last /* HOST array */, const int64_t* const* mask_tokens /* HOST array */,
+                    const int64_t* mask_stride /* HOST array */, const int32_t* pad /* HOST array */,
+                    const int32_t* rows /* HOST array */, const int32_t* T /* HOST array */, int32_t* const* list /* HOST array */,
+                    int32_t* const* count /* HOST array */, int n, void* stream);
 int pnmn_trim_predictions(const int64_t* raw, int B, int T, int end, int64_t* out, void* stream);
 int pnmn_mask_last_fwd(const float* hs, const float* fmask, const int* last, int B, int T, int H, float* enc,
                        float* hlast, void* stream);
@@ -1060,6 +1076,17 @@ int pnmn_gemm(const pnmn_gemm_desc* descs /* HOST array */, int n, void* stream)
 int pnmn_gemm_cus(const pnmn_gemm_desc* descs /* HOST array */, int n, int max_workgroups, void* stream);
 int64_t pnmn_gemm_workspace_bytes(int M, int N, int split_k);
 int pnmn_gemm_split_k(int M, int N, int K, int cus);
+/* ... over a LIST of k rows: rows[i] / count[i] (HOST arrays of n DEVICE addresses) give problem i a list of *count[i]
+ * entries (row, prev) as pnmn_valid_rows builds it, and the product contracts the listed storage rows only -- a weight
+ * gradient dy^T x of a padded [B][T][.] pass, whose dy is zero at the padded pairs, skips them.  The list serves both
+ * operands, so they must both be stored with k as the slow index: PNMN_GEMM_A_TRANSPOSED without PNMN_GEMM_B_TRANSPOSED,
+ * anything else with a list returns PNMN_ESHAPE.  rows[i] == NULL (or rows == NULL): problem i runs as in pnmn_gemm_cus.
+ * The shifted operand of a listed row reads storage row `prev`, or -- prev = ~b < 0 -- row b of shift_h0 (zeros when NULL);
+ * shift_t is then only a flag.  colsum / colsum2 sum the listed rows.  Nothing is read back: K, split_k and the workspace
+ * are those of the full product, the kernel reads *count (clamped to [0, K]) and every chunk takes its equal share of the
+ * listed k tiles; a chunk left without any writes a zero partial, count == 0 gives C = [C +] 0 [+ bias]. */
+int pnmn_gemm_rows(const pnmn_gemm_desc* descs /* HOST array */, int n, const int32_t* const* rows /* HOST array */,
+                   const int32_t* const* count /* HOST array */, int max_workgroups, void* stream);
 
 /* out[c] = [out[c] +] sum_r x[r*ld + c], c < C; also stored to out2 when not NULL (an LSTM layer's b_ih and b_hh receive
  * the same gradient: torch autograd's sum over rows of the gate gradients).  workspace: pnmn_colsum_workspace_bytes,
@@ -1067,7 +1094,7 @@ int pnmn_gemm_split_k(int M, int N, int K, int cus);
 int pnmn_colsum(const float* x, int64_t ld, int R, int C, float* out, float* out2, int accumulate, void* workspace, void* stream);
 int64_t pnmn_colsum_workspace_bytes(int R, int C);
 
-/* Library self-description (no GPU needed).  12: pnmn_gemm_desc gains colsum / colsum2 (120 bytes), pnmn_gemm_workspace_bytes includes the column-sum partials.  11 = round 6: pnmn_gemm / pnmn_colsum / pnmn_token_rows, an accumulate flag on pnmn_embedding_grad, row stride + second bias output on pnmn_token_table_bwd.  10 = round 5.  8 = round 4: the trunk executor of version 7 removed again (pnmn_trunk_exec, pnmn_plan_batch_owners, the EXEC launch op; pnmn_trunk_io shrinks to 224 bytes), streamed convolution kernel behind the same pnmn_conv_nhwc entry points (split 16 gone).  7: the trunk executor (pnmn_trunk_exec, EXEC launch op, pnmn_trunk_io grows to 232 bytes), conv segments in one launch; 6 = round 3: pnmn_conv_nhwc_cus, paired decoder launches, pnmn_attn_denc, pnmn_joint_objective, ingest by copy engine; 5: the trunk planner (pnmn_trunk_*), pnmn_set_rows, SET_ROWS / ACCUMULATE / ZERO launch ops; 4: pnmn_cluster_reserve_cus.  3 = round 2: 28x28 maps in the conv / weight-gradient / layout /
+/* Library self-description (no GPU needed).  13 also carries pnmn_valid_rows / pnmn_gemm_rows (new functions only: no record changes).  12: pnmn_gemm_desc gains colsum / colsum2 (120 bytes), pnmn_gemm_workspace_bytes includes the column-sum partials.  11 = round 6: pnmn_gemm / pnmn_colsum / pnmn_token_rows, an accumulate flag on pnmn_embedding_grad, row stride + second bias output on pnmn_token_table_bwd.  10 = round 5.  8 = round 4: the trunk executor of version 7 removed again (pnmn_trunk_exec, pnmn_plan_batch_owners, the EXEC launch op; pnmn_trunk_io shrinks to 224 bytes), streamed convolution kernel behind the same pnmn_conv_nhwc entry points (split 16 gone).  7: the trunk executor (pnmn_trunk_exec, EXEC launch op, pnmn_trunk_io grows to 232 bytes), conv segments in one launch; 6 = round 3: pnmn_conv_nhwc_cus, paired decoder launches, pnmn_attn_denc, pnmn_joint_objective, ingest by copy engine; 5: the trunk planner (pnmn_trunk_*), pnmn_set_rows, SET_ROWS / ACCUMULATE / ZERO launch ops; 4: pnmn_cluster_reserve_cus.  3 = round 2: 28x28 maps in the conv / weight-gradient / layout /
  * pool entry points, pnmn_conv_nhwc_launches takes H and W, sequence-loss / ELBO / feature-ingest entry points
  * added, the persistent dataflow executor (pnmn_dataflow) removed. */
 #define PNMN_ABI_VERSION 13   /* what pnmn_abi_version() returns; the binding refuses a library built from another */

@@ -21,6 +21,8 @@
 // Split-K: blockIdx walks (problem, tile, chunk); chunks write partial tiles to the problem's workspace and a second
 // small launch (gemm_reduce_kernel) adds them in chunk order -- deterministic, no atomics on the output; the kernel
 // boundary makes the partials visible (a fence + "last chunk reduces" in-kernel cost an L2 write-back per workgroup).
+// Over a list (pnmn_gemm_rows): a weight gradient of a padded pass contracts only the k rows a device-built list names;
+// see contract_rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -196,10 +198,36 @@ struct Direct {
     }
 };
 
+// One k tile from its LDS image into the wave's four accumulators.
 // `cs` (A stored [K][M] only; waves of the first wave column): this lane's share of the COLUMN SUMS of A over the chunk's k
 // range -- the A fragments a wave feeds its MFMAs with hold A[k][row] for all 32 k of a tile and the wave's 64 rows, lane
 // (i, h) those of k = 8 q + 4 h + s: adding them up as they pass costs eight additions per k group and no memory access
 // (sum_k A[k][m] = the bias gradient that goes with a weight gradient dy^T x).
+template <bool AKC, bool BKC>
+__device__ __forceinline__ void mac_tile(const float* ca, const float* cb, int wm, int wn, int i, int h, f32x16 (&acc)[2][2], bool want_cs,
+                                         float (&cs)[2]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        f32x4 a[2], b[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            a[t] = frag<AKC>(ca, 64 * wm + 32 * t + i, q, h);
+            b[t] = frag<BKC>(cb, 64 * wn + 32 * t + i, q, h);
+        }
+        if (!AKC && want_cs) {
+#pragma unroll
+            for (int t = 0; t < 2; ++t) cs[t] += (a[t][0] + a[t][1]) + (a[t][2] + a[t][3]);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt)
+                    acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mt][s], b[nt][s], acc[mt][nt], 0, 0, 0);
+    }
+}
+
 template <bool AKC, bool BKC>
 __device__ __forceinline__ void contract(const pnmn_gemm_desc& d, int m0, int n0, int kbeg, int kend, float* lds, f32x16 (&acc)[2][2],
                                          bool want_cs, float (&cs)[2]) {
@@ -257,26 +285,7 @@ __device__ __forceinline__ void contract(const pnmn_gemm_desc& d, int m0, int n0
             if (more) fetch(k0 + TK, cur ^ 1);  // (stage cur ^ 1 was read last in the previous iteration: free behind its barrier)
             const float* ca = la + cur * OP_FLOATS;
             const float* cb = lb + cur * OP_FLOATS;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 a[2], b[2];
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    a[t] = frag<AKC>(ca, 64 * wm + 32 * t + i, q, h);
-                    b[t] = frag<BKC>(cb, 64 * wn + 32 * t + i, q, h);
-                }
-                if (!AKC && want_cs) {
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) cs[t] += (a[t][0] + a[t][1]) + (a[t][2] + a[t][3]);
-                }
-#pragma unroll
-                for (int s = 0; s < 4; ++s)
-#pragma unroll
-                    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                        for (int nt = 0; nt < 2; ++nt)
-                            acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[mt][s], b[nt][s], acc[mt][nt], 0, 0, 0);
-            }
+            mac_tile<AKC, BKC>(ca, cb, wm, wn, i, h, acc, want_cs, cs);
             if (more) commit(cur ^ 1);
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
@@ -299,9 +308,155 @@ __device__ __forceinline__ void contract(const pnmn_gemm_desc& d, int m0, int n0
     }
 }
 
+// ---- a weight gradient over a LIST of k rows ------------------------------------------------------------------------------
+// dW = dy^T x of a padded [B][T][.] pass: at the padded (row, step) pairs dy is zero, so only the listed storage rows are
+// contracted (pnmn_valid_rows builds the list on the device; pnmn_gemm_rows).  Both operands are stored with k as the slow
+// index, so a k row is one 512-byte row of the LDS image whatever storage row it comes from: the loaders below differ from
+// those above only in where a row's source address comes from.  A list entry is (row, prev): the storage row, and what the
+// shifted operand reads in its place -- row - 1, or ~b at the first step of sequence b (-> h0[b], zeros when h0 is null) --
+// so that no loader divides.  Thread `tid` stages k rows tid / 32 + 8 j (j = 0..3) of a tile, through registers or straight
+// to LDS alike, and holds their four entries one tile ahead of the data loads that need them.
+using gint2 = __attribute__((address_space(1))) int2;
+
+__device__ __forceinline__ void load_rows(const gint2* list, int k0, int kend, int tid, int2 (&e)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = k0 + (tid >> 5) + 8 * j;
+        const gint2* q = list + (k < kend ? k : kend - 1);  // (kend >= 1; entries past the end are never used for an address)
+        e[j].x = q->x, e[j].y = q->y;
+    }
+}
+
+// One operand tile (32 listed k rows x 128 columns) into registers; `cols` / `kend`: bounds (pieces outside are zeros).
+__device__ __forceinline__ void load_tile_rows(const gfloat* base, int64_t ld, int col0, int k0, int cols, int kend, bool vec, int tid,
+                                               const int2 (&e)[4], f32x4 (&r)[4], bool shifted, const gfloat* h0, int64_t ld_h0) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int k = k0 + (tid >> 5) + 8 * j, col = col0 + 4 * (tid & 31);
+        f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (k < kend && col < cols) {
+            const int row = shifted ? e[j].y : e[j].x;
+            const bool first = row < 0;
+            const gfloat* src = first ? (h0 ? h0 + (int64_t)(~row) * ld_h0 + col : base + col) : base + (int64_t)row * ld + col;
+            if (vec && col + 3 < cols) {
+                v = pnmn::load4(src);
+            } else {
+#pragma unroll
+                for (int c = 0; c < 4; ++c)
+                    if (col + c < cols) v[c] = src[c];
+            }
+            if (first && !h0) v = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        r[j] = v;
+    }
+}
+
+// Interior tiles straight into the LDS image: load j of wave w fills k rows 2 w + 8 j, 2 w + 8 j + 1 (1 KiB lane-linear), each
+// lane with the address of its own listed row.
+struct DirectRows {
+    const gchar* origin;  // the operand at the tile's first column (uniform)
+    int64_t ld;           // bytes from row to row
+    uint32_t lane, off;   // this lane's byte offset inside a row; the wave's first load inside the operand tile (uniform)
+
+    __device__ __forceinline__ void start(const gfloat* base, int64_t ld_floats, int col0, int tid) {
+        origin = (const gchar*)(base + col0), ld = 4 * ld_floats;
+        lane = 16u * (tid & 31), off = (uint32_t)__builtin_amdgcn_readfirstlane(tid >> 6) * 1024u;
+    }
+    // (inline assembly for the reason given at Direct::issue; M0 is written in the statement that reads it)
+    __device__ __forceinline__ void issue(float* tile, const int2 (&e)[4]) {
+        const uint32_t dst = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)((lchar*)tile)) + off;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const gchar* src = origin + (int64_t)e[j].x * ld + lane;
+            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" : : "v"(src), "s"(dst + 4096u * j) : "memory");
+        }
+    }
+};
+
+// contract() for A stored [K][M], B stored [K][N] and the k range [kbeg, kend) of `list`
+__device__ __forceinline__ void contract_rows(const pnmn_gemm_desc& d, const gint2* list, int m0, int n0, int kbeg, int kend, float* lds,
+                                              f32x16 (&acc)[2][2], bool want_cs, float (&cs)[2]) {
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, i = lane & 31, h = lane >> 5;
+    const int wm = wave >> 1, wn = wave & 1;
+    const gfloat* A = as_global(d.a);
+    const gfloat* Bm = as_global(d.b);
+    const gfloat* h0 = as_global(d.shift_h0);
+    const bool shifted = d.shift_t > 0;
+    const bool avec = (d.lda & 3) == 0 && ((uintptr_t)d.a & 15) == 0;
+    const bool bvec = (d.ldb & 3) == 0 && ((uintptr_t)d.b & 15) == 0 &&
+                      (!shifted || d.shift_h0 == nullptr || ((d.ld_h0 & 3) == 0 && ((uintptr_t)d.shift_h0 & 15) == 0));
+    float* la = lds;
+    float* lb = lds + 2 * OP_FLOATS;
+    const bool adir = avec && m0 + TM <= d.M, bdir = bvec && n0 + TN <= d.N && !shifted;
+    const int kfull = kbeg + (kend - kbeg) / TK * TK;
+    DirectRows da, db;
+    da.start(A, d.lda, m0, tid);
+    db.start(Bm, d.ldb, n0, tid);
+    // (one loop per loader combination, as in contract(); the shifted operand goes through the registers)
+    auto loop = [&](auto ad_tag, auto bd_tag, int lo, int hi) {
+        constexpr bool AD = decltype(ad_tag)::value, BD = decltype(bd_tag)::value;
+        f32x4 ra[4], rb[4];
+        int2 e[4];
+        auto fetch = [&](int k0, int st) {
+            if constexpr (AD)
+                da.issue(la + st * OP_FLOATS, e);
+            else
+                load_tile_rows(A, d.lda, m0, k0, d.M, kend, avec, tid, e, ra, false, nullptr, 0);
+            if constexpr (BD)
+                db.issue(lb + st * OP_FLOATS, e);
+            else
+                load_tile_rows(Bm, d.ldb, n0, k0, d.N, kend, bvec, tid, e, rb, shifted, h0, d.ld_h0);
+        };
+        auto commit = [&](int st) {
+            if constexpr (!AD) store_tile<false>(la + st * OP_FLOATS, tid, ra);
+            if constexpr (!BD) store_tile<false>(lb + st * OP_FLOATS, tid, rb);
+        };
+        if (lo >= hi) return;
+        load_rows(list, lo, kend, tid, e);
+        fetch(lo, 0);
+        load_rows(list, lo + TK, kend, tid, e);
+        commit(0);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        int cur = 0;
+        for (int k0 = lo; k0 < hi; k0 += TK) {
+            const bool more = k0 + TK < hi;
+            if (more) {
+                fetch(k0 + TK, cur ^ 1);
+                load_rows(list, k0 + 2 * TK, kend, tid, e);  // (here by the end of this tile: a tile ahead of its use)
+            }
+            mac_tile<false, false>(la + cur * OP_FLOATS, lb + cur * OP_FLOATS, wm, wn, i, h, acc, want_cs, cs);
+            if (more) commit(cur ^ 1);
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+            cur ^= 1;
+        }
+    };
+    using yes = std::true_type;
+    using no = std::false_type;
+    if (adir && bdir) {
+        loop(yes{}, yes{}, kbeg, kfull);
+        loop(no{}, no{}, kfull, kend);
+    } else if (adir) {
+        loop(yes{}, no{}, kbeg, kfull);
+        loop(no{}, no{}, kfull, kend);
+    } else {
+        loop(no{}, no{}, kbeg, kend);
+    }
+}
+
+// the device lists of a launch's problems (pnmn_gemm_rows; null: the problem contracts every k row)
+struct Lists {
+    const int2* rows[PNMN_GEMM_MAX];
+    const int32_t* count[PNMN_GEMM_MAX];
+};
+
 // (waves_per_eu 2: the register allocator must stay within 256 registers per wave, accumulators included -- at 260 the second
 // workgroup of a CU is gone and every product of the plan ran 20 % slower)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_kernel(const Batch batch) {
+// LIST: problems may come with a list of k rows (pnmn_gemm_rows).  An instantiation of its own, so that the products
+// without one keep the kernel they had (175 VGPRs; with the lists 181 -- both leave room for two workgroups per CU).
+template <bool LIST>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void gemm_kernel(const Batch batch, const Lists lists) {
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [2 stages][A, B][OP_FLOATS] = 64 KB: two workgroups per CU
     // (a launch cut for fewer workgroups than it has units -- pnmn_gemm_cus: products that share the chip with another
     // stream's latency chain -- walks them; the LDS buffers are free again behind the last barrier of contract())
@@ -317,11 +472,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const int tm = tile / tiles_n, tn = tile % tiles_n;
     const int m0 = tm * TM, n0 = tn * TN;
     // k range of this chunk: whole k-tiles, the first chunks one longer
-    const int ktiles = (d.K + TK - 1) / TK;
+    // (a listed problem: K = the list's length, read here -- the host sized the grid for d.K and every chunk takes its equal
+    // share of the listed k tiles; a chunk left without any still writes its zero partial)
+    int K = d.K;
+    const gint2* list = nullptr;
+    if constexpr (LIST) {
+        list = (const gint2*)lists.rows[pi];
+        if (list) {
+            const int count = __builtin_amdgcn_readfirstlane(*(const __attribute__((address_space(1))) int32_t*)lists.count[pi]);
+            K = count < 0 ? 0 : (count < d.K ? count : d.K);
+        }
+    }
+    const int ktiles = (K + TK - 1) / TK;
     const int per = ktiles / split, extra = ktiles % split;
     const int kt0 = chunk * per + (chunk < extra ? chunk : extra);
     const int kt1 = kt0 + per + (chunk < extra ? 1 : 0);
-    const int kbeg = kt0 * TK, kend = kt1 * TK < d.K ? kt1 * TK : d.K;
+    const int kbeg = kt0 * TK, kend = kt1 * TK < K ? kt1 * TK : K;
 
     f32x16 acc[2][2];
 #pragma unroll
@@ -335,7 +501,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const bool want_cs = d.colsum != nullptr && !akc && tn == 0 && ((threadIdx.x >> 6) & 1) == 0;
     const bool tile_cs = d.colsum != nullptr && !akc && tn == 0;
     float cs[2] = {0.f, 0.f};
-    if (kbeg < kend) {
+    if (LIST && list) {
+        if (kbeg < kend) contract_rows(d, list, m0, n0, kbeg, kend, lds, acc, want_cs, cs);
+    } else if (kbeg < kend) {
         if (akc && bkc)
             contract<true, true>(d, m0, n0, kbeg, kend, lds, acc, false, cs);
         else if (akc)
@@ -547,12 +715,14 @@ extern "C" int pnmn_gemm_split_k(int M, int N, int K, int cus) {
     return want < 1 ? 1 : (int)want;
 }
 
-extern "C" int pnmn_gemm(const pnmn_gemm_desc* descs, int n, void* stream) { return pnmn_gemm_cus(descs, n, 0, stream); }
-
-extern "C" int pnmn_gemm_cus(const pnmn_gemm_desc* descs, int n, int max_workgroups, void* stream) {
+namespace {
+int launch(const pnmn_gemm_desc* descs, int n, const int32_t* const* rows, const int32_t* const* count, int max_workgroups,
+           void* stream) {
     if (n <= 0) return 0;
     if (!descs || n > PNMN_GEMM_MAX) return PNMN_EINVAL;
     Batch b;
+    Lists l = {};
+    bool listed = false;
     int blocks = 0, live = 0;
     for (int k = 0; k < n; ++k) {
         const pnmn_gemm_desc& d = descs[k];
@@ -561,6 +731,14 @@ extern "C" int pnmn_gemm_cus(const pnmn_gemm_desc* descs, int n, int max_workgro
         if (d.split_k > 1 && !d.workspace) return PNMN_EINVAL;
         if (d.shift_t > 0 && (d.flags & PNMN_GEMM_B_TRANSPOSED)) return PNMN_ESHAPE;  // (the shifted operand is B as [K][N])
         if (d.colsum && !(d.flags & PNMN_GEMM_A_TRANSPOSED)) return PNMN_ESHAPE;      // (column sums: of A stored [K][M])
+        l.rows[live] = nullptr, l.count[live] = nullptr;
+        if (rows && rows[k]) {
+            // (a list picks k rows: both operands must be stored with k as the slow index)
+            if ((d.flags & (PNMN_GEMM_A_TRANSPOSED | PNMN_GEMM_B_TRANSPOSED)) != PNMN_GEMM_A_TRANSPOSED) return PNMN_ESHAPE;
+            if (!count || !count[k]) return PNMN_EINVAL;
+            l.rows[live] = reinterpret_cast<const int2*>(rows[k]), l.count[live] = count[k];
+            listed = true;
+        }
         b.d[live] = d;
         b.first[live] = blocks;
         const int tiles = ((d.M + TM - 1) / TM) * ((d.N + TN - 1) / TN);
@@ -571,10 +749,15 @@ extern "C" int pnmn_gemm_cus(const pnmn_gemm_desc* descs, int n, int max_workgro
     b.first[live] = blocks;
     b.n = live;
     constexpr size_t lds = (size_t)4 * OP_FLOATS * sizeof(float);
-    static std::atomic<uint64_t> cfg{0};  // (per device: lds_optin.h)
-    if (const int e = pnmn::opt_in_lds(reinterpret_cast<const void*>(gemm_kernel), lds, cfg)) return e;
+    static std::atomic<uint64_t> cfg{0}, cfg_rows{0};  // (per device: lds_optin.h)
     const int grid = (max_workgroups > 0 && max_workgroups < blocks) ? max_workgroups : blocks;
-    hipLaunchKernelGGL(gemm_kernel, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), b);
+    if (listed) {
+        if (const int e = pnmn::opt_in_lds(reinterpret_cast<const void*>(gemm_kernel<true>), lds, cfg_rows)) return e;
+        hipLaunchKernelGGL(gemm_kernel<true>, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), b, l);
+    } else {
+        if (const int e = pnmn::opt_in_lds(reinterpret_cast<const void*>(gemm_kernel<false>), lds, cfg)) return e;
+        hipLaunchKernelGGL(gemm_kernel<false>, dim3(grid), dim3(256), lds, static_cast<hipStream_t>(stream), b, l);
+    }
     // the split problems' reduction: four blocks per output tile
     Batch r;
     int rblocks = 0, rlive = 0;
@@ -591,6 +774,18 @@ extern "C" int pnmn_gemm_cus(const pnmn_gemm_desc* descs, int n, int max_workgro
         hipLaunchKernelGGL(gemm_reduce_kernel, dim3(rblocks), dim3(256), 0, static_cast<hipStream_t>(stream), r);
     }
     return (int)hipGetLastError();
+}
+}  // namespace
+
+extern "C" int pnmn_gemm(const pnmn_gemm_desc* descs, int n, void* stream) { return launch(descs, n, nullptr, nullptr, 0, stream); }
+
+extern "C" int pnmn_gemm_cus(const pnmn_gemm_desc* descs, int n, int max_workgroups, void* stream) {
+    return launch(descs, n, nullptr, nullptr, max_workgroups, stream);
+}
+
+extern "C" int pnmn_gemm_rows(const pnmn_gemm_desc* descs, int n, const int32_t* const* rows, const int32_t* const* count,
+                              int max_workgroups, void* stream) {
+    return launch(descs, n, rows, count, max_workgroups, stream);
 }
 
 extern "C" int64_t pnmn_colsum_workspace_bytes(int R, int C) {

@@ -158,6 +158,75 @@ __global__ __launch_bounds__(64) void length_order_kernel(const int32_t* __restr
     }
 }
 
+// ---- the valid (row, step) pairs of padded passes, as lists of storage rows ------------------------------------------------
+// What pnmn_gemm_rows contracts a weight gradient over (include/probnmn_hip.h: pnmn_valid_rows).  One workgroup per list:
+// 1024 sequences a round -- a thread finds its sequence's steps, a scan over the workgroup gives every sequence its first
+// entry, and the waves write the sequences' entries (coalesced, a sequence per wave and turn).  Nothing depends on timing.
+constexpr int VR_SEGS = 8;
+struct ValidSegs {
+    const int32_t* last[VR_SEGS];
+    const int64_t* mask[VR_SEGS];
+    int64_t mask_stride[VR_SEGS];
+    int2* list[VR_SEGS];
+    int32_t* count[VR_SEGS];
+    int32_t pad[VR_SEGS], rows[VR_SEGS], T[VR_SEGS];
+    int32_t first[VR_SEGS + 1];  // first segment of each list
+};
+__global__ __launch_bounds__(1024) void valid_rows_kernel(const ValidSegs s) {
+    __shared__ int wsum[16], steps_of[1024], first_of[1024];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int seg0 = s.first[blockIdx.x], seg1 = s.first[blockIdx.x + 1];
+    int2* list = s.list[seg0];
+    int entries = 0, row_base = 0, seq_base = 0;  // so far: entries written, storage rows and sequences of the segments before
+    for (int g = seg0; g < seg1; ++g) {
+        const int rows = s.rows[g], T = s.T[g], pad = s.pad[g];
+        const int32_t* last = s.last[g];
+        for (int b0 = 0; b0 < rows; b0 += 1024) {
+            const int b = b0 + tid;
+            int steps = 0;
+            if (b < rows) {
+                if (last) {
+                    steps = min(max(last[b] + 1, 1), T);
+                } else {
+                    const int64_t* m = s.mask[g] + (int64_t)b * s.mask_stride[g];
+                    for (int t0 = 0; t0 < T; t0 += 8) {  // (eight loads in flight)
+                        int64_t v[8];
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) v[u] = m[min(t0 + u, T - 1)];
+#pragma unroll
+                        for (int u = 0; u < 8; ++u)
+                            if (t0 + u < T && v[u] != pad) steps = t0 + u + 1;
+                    }
+                }
+            }
+            int incl = steps;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int v = __shfl_up(incl, o);
+                if (lane >= o) incl += v;
+            }
+            if (lane == 63) wsum[wave] = incl;
+            __syncthreads();
+            int before = 0, total = 0;
+            for (int w = 0; w < 16; ++w) {
+                before += w < wave ? wsum[w] : 0;
+                total += wsum[w];
+            }
+            steps_of[tid] = steps, first_of[tid] = entries + before + incl - steps;
+            __syncthreads();
+            const int nb = min(1024, rows - b0);
+            for (int r = wave; r < nb; r += 16) {
+                const int n = steps_of[r], o = first_of[r], row0 = row_base + (b0 + r) * T;
+                for (int t = lane; t < n; t += 64) list[o + t] = int2{row0 + t, t ? row0 + t - 1 : ~(seq_base + b0 + r)};
+            }
+            entries += total;
+            __syncthreads();  // (the next round writes wsum / steps_of / first_of)
+        }
+        row_base += rows * T, seq_base += rows;
+    }
+    if (tid == 0) *s.count[seg0] = entries;
+}
+
 //   dhs[b][t] = (denc[b][t] + [t == last[b]] dhlast[b]) * fmask[b][t]        (denc / dhlast may be null)
 __global__ __launch_bounds__(256) void mask_last_bwd_kernel(const float* __restrict__ denc, const float* __restrict__ dhlast,
                                                             const float* __restrict__ fmask, const int* __restrict__ last,
@@ -448,6 +517,32 @@ extern "C" int pnmn_length_order(const int32_t* last, int B, int T, int32_t* ord
     if (T > LO_MAX_T) return PNMN_ESHAPE;
     hipLaunchKernelGGL(length_order_kernel, dim3(1), dim3(64), (size_t)(T + 1) * sizeof(int), static_cast<hipStream_t>(stream),
                        last, B, T, order, tile_steps);
+    return (int)hipGetLastError();
+}
+
+extern "C" int pnmn_valid_rows(const int32_t* const* last, const int64_t* const* mask_tokens, const int64_t* mask_stride,
+                               const int32_t* pad, const int32_t* rows, const int32_t* T, int32_t* const* list, int32_t* const* count,
+                               int n, void* stream) {
+    if (n <= 0) return 0;
+    if (n > VR_SEGS || !last || !mask_tokens || !mask_stride || !pad || !rows || !T || !list || !count) return PNMN_EINVAL;
+    ValidSegs s;
+    int lists = 0;
+    int64_t total = 0;
+    for (int k = 0; k < n; ++k) {
+        if (rows[k] < 0 || T[k] <= 0 || !list[k] || (rows[k] > 0 && !last[k] && !mask_tokens[k])) return PNMN_EINVAL;
+        const bool appended = k > 0 && list[k] == list[k - 1];
+        if (!appended) {
+            if (!count[k]) return PNMN_EINVAL;
+            s.first[lists++] = k, total = 0;
+        }
+        total += (int64_t)rows[k] * T[k];
+        if (total >= (1LL << 31)) return PNMN_ESHAPE;
+        s.last[k] = last[k], s.mask[k] = mask_tokens[k], s.mask_stride[k] = mask_stride[k];
+        s.list[k] = reinterpret_cast<int2*>(list[k]), s.count[k] = count[k];
+        s.pad[k] = pad[k], s.rows[k] = rows[k], s.T[k] = T[k];
+    }
+    s.first[lists] = n;
+    hipLaunchKernelGGL(valid_rows_kernel, dim3(lists), dim3(1024), 0, static_cast<hipStream_t>(stream), s);
     return (int)hipGetLastError();
 }
 

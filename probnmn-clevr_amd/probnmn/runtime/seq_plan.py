@@ -51,6 +51,12 @@ STACK_BWD_ENCODERS = int(os.environ.get("PNMN_PLAN_BWD_ENC", "0"))
 #: whose job record has no room for an order, and its per-layer form (USE_STACK = False) stays the A/B partner of that, call
 #: for call.  PNMN_LSTM_LENGTH_ORDER=0 (read when a plan is built) keeps every pass on the unordered calls.
 LENGTH_ORDER_ABOVE_ROWS = 256
+#: rows of a pass (a decoder's passes: of their model's batch) above which its weight gradients sum over the valid (row, step)
+#: pairs only (pnmn_valid_rows,
+#: pnmn_gemm_rows): dy is zero at the padded pairs -- the recurrent kernels write zeros there, and past a row's last weighted
+#: step the decoders' gradients are 0 x finite -- so about half of the k rows of a 1024-question pass add nothing.  Below it
+#: the plan is call for call what it was.  PNMN_GEMM_VALID_PAIRS=0 (read when a plan is built) keeps every product whole.
+VALID_PAIRS_ABOVE_ROWS = LENGTH_ORDER_ABOVE_ROWS
 #: the per-model decoder buffers, [flat sequence rows of all the model's passes][width]
 DECODER_BUFFERS = (("hs", 256), ("cs", 256), ("cx", 256), ("act", 1024), ("dhs", 256), ("dg", 1024), ("dctx", 256))
 
@@ -226,6 +232,9 @@ class Seq2SeqPlan:
             raise PlanUnsupported("batch does not fit the multi-CU recurrent kernels in one launch")
         self._bufs: Dict[str, torch.Tensor] = {}
         self._keep: List = []  # numpy records the call tuples point into
+        self._keep_args: List[np.ndarray] = []  # plain host arrays the call tuples point into (per-problem / per-segment arguments)
+        self._valid_lists: List = []  # segments of the (row, step) lists the weight gradients sum over (``_valid_list``)
+        self.valid_pairs = os.environ.get("PNMN_GEMM_VALID_PAIRS", "1") != "0"
         self.anchor = torch.zeros((), device=dev, requires_grad=True)
         self.fwd_pg_enc, self.fwd_pg, self.fwd_pg_finish, self.fwd_qr, self.fwd_prior = (_Calls() for _ in range(5))
         self.bwd_a, self.bwd_b = _Calls(), _Calls()  # the decoders' backward / the encoders' and every parameter gradient
@@ -247,7 +256,8 @@ class Seq2SeqPlan:
 
     # ---- pieces ------------------------------------------------------------------------------------------------------------
     def _gemm(self, calls: _Calls, name: str, descs) -> None:
-        """descs: list of dicts(a, b, c, M, N, K, lda, ldb, ldc, ta, tb, acc, bias, split, shift_t, h0, ld_h0, colsum, colsum2)."""
+        """descs: list of dicts(a, b, c, M, N, K, lda, ldb, ldc, ta, tb, acc, bias, split, shift_t, h0, ld_h0, colsum, colsum2,
+        valid); valid = (list, count) of ``_valid_list``: the k rows the product sums over (ta = 1 products only)."""
         lib = _hip.lib()
         for lo in range(0, len(descs), _hip.GEMM_MAX):
             part = descs[lo:lo + _hip.GEMM_MAX]
@@ -290,7 +300,42 @@ class Seq2SeqPlan:
                 r["shift_t"], r["shift_h0"], r["ld_h0"] = d.get("shift_t", 0), d.get("h0", 0), d.get("ld_h0", 0)
                 r["colsum"], r["colsum2"] = d.get("colsum", 0), d.get("colsum2", 0)
             self._keep.append(rec)
-            calls.add("pnmn_gemm_cus", rec.ctypes.data, len(rec), 0, self.stream)
+            if any(d.get("valid") for d in part):
+                # (the chunk counts above are those of the full K: the list's length is known to the device alone)
+                lists = np.array([d.get("valid", (0, 0)) for d in part], np.uint64).T.copy()
+                self._keep_args.append(lists)
+                calls.add("pnmn_gemm_rows", rec.ctypes.data, len(rec), lists[0].ctypes.data, lists[1].ctypes.data, 0, self.stream)
+            else:
+                calls.add("pnmn_gemm_cus", rec.ctypes.data, len(rec), 0, self.stream)
+
+    def _valid_list(self, name: str, segments) -> tuple:
+        """The list of valid (row, step) pairs of passes stored one behind the other, for the weight gradients that contract
+        them.  segments: (last, mask tokens, mask row stride, pad, rows, T) per pass -- `last` (an encoder's) or the tokens that
+        mask the pass's loss (a decoder's), the other 0.  Returns (list, count) for a ``_gemm`` description; the lists of a
+        backward are built by ``_valid_list_calls``."""
+        rows = self.buf(name + ".rows", sum(r * T for _, _, _, _, r, T in segments), 2, dtype=torch.int32)
+        count = self.buf(name + ".count", 1, dtype=torch.int32, zero=True)
+        self._valid_lists.append((rows.data_ptr(), count.data_ptr(), segments))
+        return rows.data_ptr(), count.data_ptr()
+
+    def _valid_list_calls(self, calls: _Calls) -> None:
+        """One launch for up to eight segments of the lists asked for so far (a workgroup per list)."""
+        group: List = []
+
+        def flush():
+            if group:
+                arg = np.array(group, np.int64).T.copy()  # rows: last, mask, stride, pad, rows, T, list, count
+                pad, rows, T = (arg[k].astype(np.int32) for k in (3, 4, 5))
+                self._keep_args += [arg, pad, rows, T]
+                calls.add("pnmn_valid_rows", arg[0].ctypes.data, arg[1].ctypes.data, arg[2].ctypes.data, pad.ctypes.data, rows.ctypes.data,
+                          T.ctypes.data, arg[6].ctypes.data, arg[7].ctypes.data, len(group), self.stream)
+                del group[:]
+        for lst, count, segments in self._valid_lists:
+            if len(group) + len(segments) > 8:
+                flush()
+            group += [seg + (lst, count) for seg in segments]
+        flush()
+        self._valid_lists = []
 
     def _table_forward(self, calls: _Calls, t: _TokenTable) -> None:
         calls.add("pnmn_token_table_fwd", t.emb.data_ptr(), t.w_ih.data_ptr() + 4 * t.col0, t.w_ih.stride(0), t.bias.data_ptr(),
@@ -472,15 +517,18 @@ class Seq2SeqPlan:
             dg1, dg2, g = e["dg1"], e["dg2"], mm.grad
             self._table_backward(calls, e["tab"], mm, 0, [(e["tag"] + ".emb_ws", dg1, e["src"], 0)])
             K = rows * T
+            # (one list for the pass's three products: both layers' dgates are zero from the row's length on)
+            valid = dict(valid=self._valid_list(e["tag"] + ".valid", [(e["last"].data_ptr(), 0, 0, 0, rows, T)])) \
+                if self.valid_pairs and rows > VALID_PAIRS_ABOVE_ROWS else {}
             # (layer 2's bias gradients = the column sums of dgates2: the weight-gradient product that reads dgates2 as its
             # transposed operand adds them up on the way -- pnmn_gemm_desc.colsum)
             deferred += [
                 dict(a=dg2.data_ptr(), b=e["hs2"].data_ptr(), c=g(lstm.weight_hh_l1).data_ptr(), M=1024, N=256, K=K, lda=1024, ldb=256,
-                     ldc=256, ta=1, split="auto", shift_t=T, colsum=g(lstm.bias_ih_l1).data_ptr(), colsum2=g(lstm.bias_hh_l1).data_ptr()),
+                     ldc=256, ta=1, split="auto", shift_t=T, colsum=g(lstm.bias_ih_l1).data_ptr(), colsum2=g(lstm.bias_hh_l1).data_ptr(), **valid),
                 dict(a=dg2.data_ptr(), b=(e["hsd"] if e["p"] > 0 else e["hs1"]).data_ptr(), c=g(lstm.weight_ih_l1).data_ptr(), M=1024,
-                     N=256, K=K, lda=1024, ldb=256, ldc=256, ta=1, split="auto"),  # (layer 2's input: after the mask)
+                     N=256, K=K, lda=1024, ldb=256, ldc=256, ta=1, split="auto", **valid),  # (layer 2's input: after the mask)
                 dict(a=dg1.data_ptr(), b=e["hs1"].data_ptr(), c=g(lstm.weight_hh_l0).data_ptr(), M=1024, N=256, K=K, lda=1024, ldb=256,
-                     ldc=256, ta=1, split="auto", shift_t=T),
+                     ldc=256, ta=1, split="auto", shift_t=T, **valid),
             ]
 
     def _decoder_set(self, tag: str, mm: _Model, enc: Dict, passes) -> _DecoderSet:
@@ -663,15 +711,24 @@ class Seq2SeqPlan:
             mm, flat, (R, V), g, cell = dec.mm, dec.flat, dec.logits.shape, dec.mm.grad, dec.mm.cell
             self._table_backward(c, dec.table, mm, mm.model._start_index,
                                  [("%s.d.emb_ws%d" % (dec.tag, k), p.v["dg"], p.tokens, p.shift) for k, p in enumerate(dec.passes)])
+            # (a pass's valid steps end at the last one its loss weights: dlogits and dgates are zero behind it.  The products over
+            # the flat buffers take the passes' list, the recurrent weights' each pass's own: a list's first steps point at
+            # ITS h0 rows.  A model with one pass has one list.)
+            segs = [(0, p.loss.mask, p.loss.mask_stride, p.loss.pad, p.rows, p.T) for p in dec.passes]
+            listed = self.valid_pairs and sum(p.rows for p in dec.passes) > VALID_PAIRS_ABOVE_ROWS
+            whole = dict(valid=self._valid_list(dec.tag + ".d.valid", segs)) if listed else {}
+            own = [whole if len(segs) == 1 else dict(valid=self._valid_list(p.tag + ".valid", [seg])) if listed else {}
+                   for p, seg in zip(dec.passes, segs)]
             deferred.append(dict(a=dec.dlogits.data_ptr(), b=flat["hs"].data_ptr(), c=g(mm.proj.weight).data_ptr(), M=V, N=256, K=R, lda=V,
-                                 ldb=256, ldc=256, ta=1, split="auto", colsum=g(mm.proj.bias).data_ptr()))
+                                 ldb=256, ldc=256, ta=1, split="auto", colsum=g(mm.proj.bias).data_ptr(), **whole))
             deferred.append(dict(a=flat["dg"].data_ptr(), b=flat["cx"].data_ptr(), c=g(cell.weight_ih).data_ptr(), M=1024, N=256, K=R, lda=1024,
-                                 ldb=256, ldc=512, ta=1, split="auto"))
+                                 ldb=256, ldc=512, ta=1, split="auto", **whole))
             for k, p in enumerate(dec.passes):
                 deferred.append(dict(a=p.v["dg"].data_ptr(), b=p.v["hs"].data_ptr(), c=g(cell.weight_hh).data_ptr(), M=1024, N=256,
                                      K=p.rows * p.T, lda=1024, ldb=256, ldc=256, ta=1, split="auto", shift_t=p.T,
-                                     h0=dec.enc["h"][p.enc_row0:].data_ptr(), ld_h0=256, acc=1 if k else 0))
+                                     h0=dec.enc["h"][p.enc_row0:].data_ptr(), ld_h0=256, acc=1 if k else 0, **own[k]))
         self._encoders_param_grads(c, deferred, [dec.enc for dec in decs])
+        self._valid_list_calls(c)
         # (an accumulating product must follow the product it adds to: keep them in different launches)
         self._gemm(c, "wgrad", [d for d in deferred if not d.get("acc")])
         self._gemm(c, "wgrad2", [d for d in deferred if d.get("acc")])
