@@ -756,6 +756,43 @@ int pnmn_attn_lstm_fwd_group_constrained(const pnmn_decoder_fwd_job* jobs, const
                                          int n, int hidden, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Free-running samples from the program prior p(z), all T steps in one launch       program_prior.py:174-301
+ * Per row, with (h0, c0, h1, c1) = 0 and last = start_index, step t = 0 .. T-1 is
+ *   g0 = table0[last] + h0 W_hh0^T, then the LSTM cell (gate order i, f, g, o)  -> h0', c0'
+ *        table0 [V][4H] = Emb W_ih0^T + b_ih0 + b_hh0: the per-token table of pnmn_token_table_fwd
+ *   g1 = b1 + h0' W_ih1^T + h1 W_hh1^T, then the cell                           -> h1', c1'      (b1 = b_ih1 + b_hh1)
+ *   p  = h1' W_proj^T  (256 wide),   z = p W_out^T  (W_out [V][256] row major: the tied embedding, no bias)
+ *   tokens[b][t]:  mode 1  the draw of pnmn_sample_tokens from z, Philox counter (row_offset + b, t)
+ *                  mode 2  its first arg-max
+ *                  mode 0  in_tokens[b * in_token_stride + t] in the place of the choice (clamped into [0, V))
+ *   logprob_vocab[b][t] = log_softmax(z)[token]      (the UNMODIFIED distribution, whatever filter or automaton chose)
+ *   logprob_proj[b][t]  = log_softmax(p)[token]      (over all 256 entries of p: the reference's own quirk, :243-244)
+ *   proj[b][t][0..256) = p  when `proj` is not null;   last = token
+ * A row keeps running after end_index, as the reference's loop does; the caller trims.
+ * w_hh0, w_ih1, w_hh1 ([1024][256]) and w_proj ([256][256]) are in MFMA fragment order (see pnmn_lstm_seq_fwd).
+ * `filter` (HOST, may be null = the identity) applies to mode 1 only, by the rule beside pnmn_sample_tokens_filtered.  The
+ * automaton tables (HOST; all three null = unconstrained) apply to modes 1 and 2 by the rule beside
+ * pnmn_attn_lstm_fwd_constrained: A_c in the place of the allowed set, a finished row emits end_index, its state frozen; mode 0
+ * checks them as far as it can without a vocabulary and ignores them.  The non-finite fallbacks of pnmn_sample_tokens apply,
+ * so a token is always in [0, V).  With the identity filter and no automaton the plain kernel runs: the same output, bit for
+ * bit, as with filter = null.
+ * One workgroup owns 16 rows for all T steps; rows are independent, so a batch of any size is a plain grid of ceil(B / 16)
+ * workgroups: no workspace, no counters, no co-residency.
+ * Returns PNMN_EINVAL and launches nothing for: hidden != 256, V outside 1..128, T < 1, B < 0, mode outside 0..2, start_index
+ * outside [0, V), mode 0 without in_tokens, a null required pointer (everything but proj, in_tokens, filter and the tables), an
+ * invalid filter, some but not all of the tables, and whatever pnmn_attn_lstm_fwd_constrained refuses in its tables (min_left[0] > T
+ * included).  B == 0 returns 0 without a launch.
+ * ------------------------------------------------------------------------------------------- */
+int pnmn_prior_sample(const float* table0, const float* w_hh0, const float* w_ih1, const float* w_hh1, const float* b1,
+                      const float* w_proj, const float* w_out,
+                      int64_t* tokens, float* logprob_vocab, float* logprob_proj, float* proj /* optional */,
+                      int B, int T, int V, int hidden, int mode, int pad_index, int unk_index, int start_index,
+                      uint64_t seed, uint64_t row_offset, const int64_t* in_tokens, int64_t in_token_stride,
+                      const struct pnmn_sampling_filter* filter /* HOST, may be NULL = identity */, int end_index,
+                      const uint8_t* token_class /* HOST */, const uint8_t* next_state /* HOST */,
+                      const uint8_t* min_left /* HOST */, int n_states, int n_classes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Host-side launch sequencer (no device work of its own): `list` is a HOST array; entry i calls the entry
  * point named by `op` with (a, b, c, n, p[...]) in that entry point's argument order (pointers first, then
  * the item count, then the integer arguments), all on `stream`; stops at the first non-zero return code.

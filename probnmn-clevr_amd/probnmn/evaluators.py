@@ -255,3 +255,37 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
     finally:
         program_generator.train(was_training[0])
         nmn.train(was_training[1])
+
+
+@torch.no_grad()
+def sample_programs(program_prior, vocabulary, num_samples: int, max_sequence_length: int = 28, seed: Optional[int] = None,
+                    temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, greedy: bool = False,
+                    constrained: bool = False, compiler=None) -> List[Dict[str, Any]]:
+    """Programs drawn from the prior p(z) with no question (``ProgramPrior.sample``: one persistent HIP launch), one record
+    per sample, most likely first: ``"program"`` (token strings without padding, the closing @end@ included),
+    ``"log_probability"`` (log p(z) of the kept tokens as ``ProgramPrior.forward`` scores them) and, with ``compiler`` (a
+    ``ProgramCompiler``), whether it is a ``"program_valid"`` one.  ``seed`` makes the draw reproducible; ``temperature``,
+    ``top_k``, ``top_p`` and ``greedy`` are those of ``sample``.  ``constrained`` (needs ``compiler``): the samples are
+    drawn under the compiler's validity rule (``compiler.decoding_automaton``, built as ``predict_answers`` builds it), so
+    every record is valid."""
+    if constrained and compiler is None:
+        raise ValueError("constrained=True draws under the program compiler's validity rule: give a compiler")
+    sampling_filter(temperature, top_k, top_p)
+    constraint = None
+    if constrained:
+        exclude = [getattr(program_prior, name) for name in ("_pad_index", "_unk_index", "_start_index", "_end_index")]
+        constraint = compiler.decoding_automaton(exclude=exclude)
+    out = program_prior.sample(num_samples, max_sequence_length, seed=seed, temperature=temperature, top_k=top_k, top_p=top_p,
+                               constraint=constraint, greedy=greedy)
+    programs = out["predictions"].cpu()
+    log_probability = out["log_probability"].cpu().tolist()
+    valid = None if compiler is None else [c.valid for c in compiler.compile_batch(programs.numpy())]
+    pad = program_prior._pad_index
+    records: List[Dict[str, Any]] = []
+    for i, row in enumerate(programs.tolist()):
+        record = {"program": [vocabulary.get_token_from_index(int(t), namespace="programs") for t in row if t != pad],
+                  "log_probability": float(log_probability[i])}
+        if valid is not None:
+            record["program_valid"] = bool(valid[i])
+        records.append(record)
+    return records
