@@ -9,6 +9,11 @@
 // channel's pixels), transposes 64 channels x <= 392 pixels through LDS and writes full 256-byte NHWC
 // pixel rows.  It replaces the gather, the cast, the H2D copy AND the NCHW -> NHWC pass of the stem's
 // prologue.  Bound by PCIe Gen5 x16 (63 GB/s spec): 0.8 MB per question -> ~78 k questions/s per GPU.
+//
+// The store may also keep its rows as fp16 or bf16 (pnmn_gather_features_typed): half the bytes over the link per
+// question, widened -- exactly -- on the way into the same fp32 NHWC batch (gather_half_kernel); and a store that lives in
+// HBM at two bytes per element is filled by the fp32 kernel rounding in its write-out and read back, widened, by
+// pnmn_expand_rows.  The networks compute in fp32 either way.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -16,6 +21,23 @@
 #include "../../include/probnmn_hip.h"
 
 namespace {
+
+// Element conversions of the half-precision stores (PNMN_ELEM_F16 / PNMN_ELEM_BF16).  Widening is exact; narrowing is
+// round to nearest even with overflow to infinity and subnormals kept, what torch's Tensor.to(dtype) gives on the host
+// (fp16: the hardware conversion, whose fp16 denormals are always on; bf16: the integer form of the same rounding).
+struct F16 { uint16_t bits; };
+struct BF16 { uint16_t bits; };
+template <class T> __device__ __forceinline__ float widen(uint16_t h);
+template <> __device__ __forceinline__ float widen<F16>(uint16_t h) { return (float)__builtin_bit_cast(_Float16, h); }
+template <> __device__ __forceinline__ float widen<BF16>(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
+template <class T> __device__ __forceinline__ T narrow(float x);
+template <> __device__ __forceinline__ float narrow<float>(float x) { return x; }
+template <> __device__ __forceinline__ F16 narrow<F16>(float x) { return F16{__builtin_bit_cast(uint16_t, (_Float16)x)}; }
+template <> __device__ __forceinline__ BF16 narrow<BF16>(float x) {
+    const uint32_t u = __builtin_bit_cast(uint32_t, x);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return BF16{(uint16_t)0x7fc0};  // (NaN: torch's quiet NaN)
+    return BF16{(uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16)};
+}
 
 // A FIXED, small number of workgroups walks the (example, 64-channel block, pixel range) work items: the kernel is
 // bound by PCIe, not by the chip -- a few hundred KB in flight saturate the link -- and it runs on the loader's
@@ -28,9 +50,12 @@ namespace {
 // 40.8 / 39.5 / 39.8 / 44.7 / 49.3 / 52.8 ms per step against 32.4 ms with resident features -- below ~12 the link is
 // not filled (the ingest becomes the critical path), above it the step slows with the number of PCIe reads in flight
 // (they hold memory-system queue entries for microseconds each), and ~7 ms of the step's 32 stay unhidden at best.
+// `Out`: float, or F16 / BF16 when the fp32 staging buffer fills a half-precision device store -- the same kernel, the
+// rounding in the store of the write-out.
+template <class Out>
 __global__ __launch_bounds__(256) void gather_features_kernel(const float* __restrict__ store,
                                                               const int64_t* __restrict__ indices,
-                                                              float* __restrict__ dst, int64_t n_store, int Cn,
+                                                              Out* __restrict__ dst, int64_t n_store, int Cn,
                                                               int HW, int PT, int n, int parts) {
     extern __shared__ float tile[];  // [64][PT+1]
     const int cblocks = (Cn + 63) / 64;
@@ -88,33 +113,220 @@ __global__ __launch_bounds__(256) void gather_features_kernel(const float* __res
             }
         }
         __syncthreads();
-        float* out = dst + ((size_t)e * HW + p0) * Cn + c0;
+        Out* out = dst + ((size_t)e * HW + p0) * Cn + c0;
         for (int i = threadIdx.x; i < total; i += 256) {
             const int p = i / cw, c = i - p * cw;
-            out[(size_t)p * Cn + c] = tile[c * ld + p];
+            out[(size_t)p * Cn + c] = narrow<Out>(tile[c * ld + p]);
         }
         __syncthreads();  // the tile is refilled by the next item
     }
 }
 
+// One stage of the half-precision gather: `nruns` runs of `run_len` 2-byte elements, run r at src + r * stride, into the
+// tile at r * ld -- V elements (16, 8 or 2 bytes) per load, eight non-temporal loads in flight per thread.  The caller
+// has checked that every run start, `ld` and `run_len` are multiples of V elements.
+template <int V>
+__device__ __forceinline__ void load_runs(const uint16_t* __restrict__ src, uint16_t* __restrict__ tile, int nruns,
+                                          int run_len, int stride, int ld) {
+    typedef uint16_t vec __attribute__((ext_vector_type(V)));
+    constexpr int NB = 8;
+    const int nq = run_len / V, units = nruns * nq;
+    for (int i0 = threadIdx.x; i0 < units; i0 += 256 * NB) {
+        vec v[NB];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const int i = i0 + k * 256;
+            const int r = i / nq;
+            if (i < units) v[k] = __builtin_nontemporal_load(reinterpret_cast<const vec*>(src + (size_t)r * stride + V * (i - r * nq)));
+        }
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const int i = i0 + k * 256;
+            const int r = i / nq;
+            if (i < units) *reinterpret_cast<vec*>(tile + r * ld + V * (i - r * nq)) = v[k];
+        }
+    }
+}
+template <>
+__device__ __forceinline__ void load_runs<1>(const uint16_t* __restrict__ src, uint16_t* __restrict__ tile, int nruns,
+                                             int run_len, int stride, int ld) {
+    constexpr int NB = 8;
+    const int units = nruns * run_len;
+    for (int i0 = threadIdx.x; i0 < units; i0 += 256 * NB) {
+        uint16_t v[NB];
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const int i = i0 + k * 256;
+            const int r = i / run_len;
+            v[k] = i < units ? __builtin_nontemporal_load(src + (size_t)r * stride + (i - r * run_len)) : (uint16_t)0;
+        }
+#pragma unroll
+        for (int k = 0; k < NB; ++k) {
+            const int i = i0 + k * 256;
+            const int r = i / run_len;
+            if (i < units) tile[r * ld + (i - r * run_len)] = v[k];
+        }
+    }
+}
+
+// The gather from a half-precision store (F16 / BF16 -> fp32): the same fixed grid and the same work items, at half
+// the bytes over the link.  The tile holds the 2-byte elements as they are stored, [64][PT] without padding, and the
+// write-out widens.  With 2-byte elements a channel's 196 pixels are 392 bytes -- every second channel's run starts 8
+// bytes off a 16-byte boundary -- so where the whole map fits the tile (parts == 1: HW <= 200, 25 088 bytes at 14x14)
+// the item's 64 channels are read as the ONE contiguous run they are in the store, which starts 16-byte aligned
+// whenever the store does (64 channels x HW x 2 bytes = 128 HW).  Larger maps (28x28) are cut into ranges of 200 pixels
+// (400 bytes: 16-byte aligned when HW is a multiple of 8) and read channel by channel.  Whatever does not divide -- HW
+// not a multiple of 4, a channel tail below 64 whose run is no multiple of 8 elements -- falls to 8-byte and then
+// 2-byte loads.  (The unpadded tile costs the write-out a 2- to 4-way bank conflict, stride 2 HW bytes between the
+// channels of a pixel; the kernel waits for PCIe, not for LDS.)
+template <class In>
+__global__ __launch_bounds__(256) void gather_half_kernel(const uint16_t* __restrict__ store,
+                                                          const int64_t* __restrict__ indices, float* __restrict__ dst,
+                                                          int64_t n_store, int Cn, int HW, int PT, int n, int parts) {
+    extern __shared__ __attribute__((aligned(16))) uint16_t htile[];  // [64][PT]
+    const int cblocks = (Cn + 63) / 64;
+    const int total_items = n * cblocks * parts;
+    for (int item = blockIdx.x; item < total_items; item += gridDim.x) {
+        const int part = item % parts, cb = (item / parts) % cblocks, e = item / (parts * cblocks);
+        const int c0 = cb * 64;
+        const int p0 = part * PT;
+        const int np = (HW - p0) < PT ? (HW - p0) : PT;
+        const int cw = (Cn - c0) < 64 ? (Cn - c0) : 64;
+        int64_t row = indices[e];
+        if (row < 0 || row >= n_store) row = 0;  // (validated on the host; never index outside the store)
+        const uint16_t* src = store + ((size_t)row * Cn + c0) * HW + p0;
+        // parts == 1: PT == HW, the channels' runs follow each other without a gap, in the store and in the tile
+        const int nruns = parts == 1 ? 1 : cw, run_len = parts == 1 ? cw * HW : np;
+        const int every = nruns == 1 ? run_len : (run_len | HW | PT);  // what every run start and length is a multiple of
+        const unsigned at = (unsigned)(uintptr_t)src;
+        if ((every & 7) == 0 && (at & 15) == 0) load_runs<8>(src, htile, nruns, run_len, HW, PT);
+        else if ((every & 3) == 0 && (at & 7) == 0) load_runs<4>(src, htile, nruns, run_len, HW, PT);
+        else load_runs<1>(src, htile, nruns, run_len, HW, PT);
+        __syncthreads();
+        const int total = cw * np;
+        float* out = dst + ((size_t)e * HW + p0) * Cn + c0;
+        for (int i = threadIdx.x; i < total; i += 256) {
+            const int p = i / cw, c = i - p * cw;
+            out[(size_t)p * Cn + c] = widen<In>(htile[c * PT + p]);
+        }
+        __syncthreads();  // the tile is refilled by the next item
+    }
+}
+
+// Rows of a half-precision device store widened into an fp32 batch (pnmn_expand_rows): a work item is 8192 elements
+// of one row -- 256 threads x 4 loads of 16 bytes in flight, 2 x 16 bytes stored per load -- and the grid walks the
+// (row, chunk) pairs.  HBM to HBM on the step's own stream: it may fill the chip.
+template <class In>
+__global__ __launch_bounds__(256) void expand_rows_kernel(const uint16_t* __restrict__ rows, const int64_t* __restrict__ indices,
+                                                          float* __restrict__ dst, int64_t n_store, int64_t row_elems,
+                                                          int64_t chunks_per_row, int64_t items, int vectors) {
+    typedef uint16_t h8 __attribute__((ext_vector_type(8)));
+    typedef float f4 __attribute__((ext_vector_type(4)));
+    for (int64_t item = blockIdx.x; item < items; item += gridDim.x) {
+        const int64_t e = item / chunks_per_row, chunk = item - e * chunks_per_row;
+        int64_t row = indices[e];
+        if (row < 0 || row >= n_store) row = 0;
+        const uint16_t* src = rows + (size_t)row * row_elems;
+        float* out = dst + (size_t)e * row_elems;
+        if (vectors) {
+            const int64_t nv = row_elems >> 3;
+            h8 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t j = chunk * 1024 + k * 256 + threadIdx.x;
+                if (j < nv) v[k] = *reinterpret_cast<const h8*>(src + 8 * j);
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int64_t j = chunk * 1024 + k * 256 + threadIdx.x;
+                if (j < nv) {
+                    *reinterpret_cast<f4*>(out + 8 * j) = f4{widen<In>(v[k][0]), widen<In>(v[k][1]), widen<In>(v[k][2]), widen<In>(v[k][3])};
+                    *reinterpret_cast<f4*>(out + 8 * j + 4) = f4{widen<In>(v[k][4]), widen<In>(v[k][5]), widen<In>(v[k][6]), widen<In>(v[k][7])};
+                }
+            }
+        } else {
+            const int64_t lo = chunk * 8192, hi = lo + 8192 < row_elems ? lo + 8192 : row_elems;
+            for (int64_t j = lo + threadIdx.x; j < hi; j += 256) out[j] = widen<In>(src[j]);
+        }
+    }
+}
 }  // namespace
 
-extern "C" int pnmn_gather_features(const float* store, const int64_t* indices, float* dst, int n, int64_t n_store,
-                                    int Cn, int HW, void* stream) {
-    if (n <= 0) return 0;
-    if (!store || !indices || !dst || Cn <= 0 || HW <= 0 || n_store <= 0) return PNMN_EINVAL;
-    // pixel ranges of 100 pixels (a multiple of four: 16-byte loads): a 26 KB tile (see the kernel's header)
-    const int PT = HW < 100 ? HW : 100;
-    const int parts = (HW + PT - 1) / PT;
-    const size_t lds = (size_t)64 * (PT + 1) * sizeof(float);
-    static const int max_wgs = [] {  // (tuning hook)
+static int ingest_wgs() {  // (tuning hook)
+    static const int max_wgs = [] {
         const char* e = getenv("PNMN_INGEST_WGS");
         const int v = e ? atoi(e) : 12;
         return v > 0 ? v : 12;
     }();
+    return max_wgs;
+}
+
+template <class Out>
+static int launch_gather_f32(const void* store, const int64_t* indices, void* dst, int n, int64_t n_store, int Cn, int HW,
+                             void* stream) {
+    // pixel ranges of 100 pixels (a multiple of four: 16-byte loads): a 26 KB tile (see the kernel's header)
+    const int PT = HW < 100 ? HW : 100;
+    const int parts = (HW + PT - 1) / PT;
+    const size_t lds = (size_t)64 * (PT + 1) * sizeof(float);
+    const int max_wgs = ingest_wgs();
     const long items = (long)n * ((Cn + 63) / 64) * parts;
-    hipLaunchKernelGGL(gather_features_kernel, dim3((unsigned)(items < max_wgs ? items : max_wgs)), dim3(256), lds,
-                       static_cast<hipStream_t>(stream), store, indices, dst, n_store, Cn, HW, PT, n, parts);
+    hipLaunchKernelGGL(gather_features_kernel<Out>, dim3((unsigned)(items < max_wgs ? items : max_wgs)), dim3(256), lds,
+                       static_cast<hipStream_t>(stream), static_cast<const float*>(store), indices, static_cast<Out*>(dst),
+                       n_store, Cn, HW, PT, n, parts);
+    return (int)hipGetLastError();
+}
+
+template <class In>
+static int launch_gather_half(const void* store, const int64_t* indices, void* dst, int n, int64_t n_store, int Cn, int HW,
+                              void* stream) {
+    // the whole map where 64 channels of it fit the tile (HW <= 200: 25 600 bytes), else ranges of 200 pixels
+    const int PT = HW < 200 ? HW : 200;
+    const int parts = (HW + PT - 1) / PT;
+    const size_t lds = (size_t)64 * PT * sizeof(uint16_t);
+    const int max_wgs = ingest_wgs();
+    const long items = (long)n * ((Cn + 63) / 64) * parts;
+    hipLaunchKernelGGL(gather_half_kernel<In>, dim3((unsigned)(items < max_wgs ? items : max_wgs)), dim3(256), lds,
+                       static_cast<hipStream_t>(stream), static_cast<const uint16_t*>(store), indices, static_cast<float*>(dst),
+                       n_store, Cn, HW, PT, n, parts);
+    return (int)hipGetLastError();
+}
+
+extern "C" int pnmn_gather_features_typed(const void* store, int src_elem, const int64_t* indices, void* dst, int dst_elem,
+                                          int n, int64_t n_store, int Cn, int HW, void* stream) {
+    const bool pair_ok = (src_elem == PNMN_ELEM_F32 && (dst_elem == PNMN_ELEM_F32 || dst_elem == PNMN_ELEM_F16 || dst_elem == PNMN_ELEM_BF16)) ||
+                         ((src_elem == PNMN_ELEM_F16 || src_elem == PNMN_ELEM_BF16) && dst_elem == PNMN_ELEM_F32);
+    if (!pair_ok) return PNMN_EINVAL;
+    if (n <= 0) return 0;
+    if (!store || !indices || !dst || Cn <= 0 || HW <= 0 || n_store <= 0) return PNMN_EINVAL;
+    if ((long)n * ((Cn + 63) / 64) * ((HW + 99) / 100) > 0x7fffffffL) return PNMN_EINVAL;  // (the kernels count items in an int)
+    if (src_elem == PNMN_ELEM_F16) return launch_gather_half<F16>(store, indices, dst, n, n_store, Cn, HW, stream);
+    if (src_elem == PNMN_ELEM_BF16) return launch_gather_half<BF16>(store, indices, dst, n, n_store, Cn, HW, stream);
+    if (dst_elem == PNMN_ELEM_F16) return launch_gather_f32<F16>(store, indices, dst, n, n_store, Cn, HW, stream);
+    if (dst_elem == PNMN_ELEM_BF16) return launch_gather_f32<BF16>(store, indices, dst, n, n_store, Cn, HW, stream);
+    return launch_gather_f32<float>(store, indices, dst, n, n_store, Cn, HW, stream);
+}
+
+extern "C" int pnmn_gather_features(const float* store, const int64_t* indices, float* dst, int n, int64_t n_store,
+                                    int Cn, int HW, void* stream) {
+    return pnmn_gather_features_typed(store, PNMN_ELEM_F32, indices, dst, PNMN_ELEM_F32, n, n_store, Cn, HW, stream);
+}
+
+extern "C" int pnmn_expand_rows(const void* rows, int src_elem, const int64_t* indices, void* dst, int n, int64_t n_store,
+                                int64_t row_elems, void* stream) {
+    if (src_elem != PNMN_ELEM_F16 && src_elem != PNMN_ELEM_BF16) return PNMN_EINVAL;
+    if (n <= 0) return 0;
+    if (!rows || !indices || !dst || n_store <= 0 || row_elems <= 0) return PNMN_EINVAL;
+    const int vectors = (row_elems & 7) == 0 && (((uintptr_t)rows | (uintptr_t)dst) & 15) == 0;
+    const int64_t chunks_per_row = (row_elems + 8191) / 8192, items = (int64_t)n * chunks_per_row;
+    const unsigned grid = (unsigned)(items < 4096 ? items : 4096);  // 16 workgroups per CU: the rest of the items by stride
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const uint16_t* src = static_cast<const uint16_t*>(rows);
+    if (src_elem == PNMN_ELEM_F16)
+        hipLaunchKernelGGL(expand_rows_kernel<F16>, dim3(grid), dim3(256), 0, st, src, indices, static_cast<float*>(dst), n_store,
+                           row_elems, chunks_per_row, items, vectors);
+    else
+        hipLaunchKernelGGL(expand_rows_kernel<BF16>, dim3(grid), dim3(256), 0, st, src, indices, static_cast<float*>(dst), n_store,
+                           row_elems, chunks_per_row, items, vectors);
     return (int)hipGetLastError();
 }
 

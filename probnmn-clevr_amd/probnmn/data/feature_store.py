@@ -1,5 +1,5 @@
-"""Image-feature ingest: a page-locked fp32 feature store on the host and a prefetching batch loader
-(SURVEY 8f-1).
+"""Image-feature ingest: a page-locked feature store on the host (fp32, or fp16 / bf16 at half the bytes), a
+resident one in HBM, and a prefetching batch loader.
 
 The reference reads one float64 row per example from HDF5 on the host, casts it, lets the DataLoader
 collate a batch and moves it to the GPU inside ``_Trainer.step`` (reference: probnmn/data/readers.py:63-108,
@@ -16,6 +16,12 @@ datasets.py:137-142,222-228, trainers/_trainer.py:272-287) -- at ~10 questions/s
     tensor in place);
   * :class:`PrefetchingLoader` issues the gather of batch k+1 on its own stream while the trainer runs
     batch k, and hands batches over with the stream dependency already in place.
+
+Both stores take ``dtype=torch.float16`` or ``torch.bfloat16``: the rows are kept in two bytes per element -- half the
+bytes over PCIe per gathered question, half the HBM or page-locked memory per image -- and widened to fp32 by the
+kernels that read them (``pnmn_gather_features_typed``, ``pnmn_expand_rows``).  The networks compute in fp32 either
+way: they see exactly ``features.to(dtype).float()`` of the fp32 features (a float64 source is cast to fp32 first,
+as for an fp32 store).
 """
 from typing import Dict, Iterable, Iterator, Optional
 
@@ -26,19 +32,61 @@ import torch
 
 from probnmn import _hip
 
+# store dtype -> element code of the kernels (include/probnmn_hip.h: PNMN_ELEM_*)
+_ELEM = {torch.float32: _hip.ELEM_F32, torch.float16: _hip.ELEM_F16, torch.bfloat16: _hip.ELEM_BF16}
+# the smallest magnitude that rounds (to nearest even) to infinity: the largest finite value plus half a unit of its last place
+_OVERFLOWS_AT = {torch.float16: 65520.0, torch.bfloat16: float(np.uint32(0x7F7F8000).view(np.float32))}
+
+
+def _elem(dtype) -> int:
+    if dtype not in _ELEM:
+        raise ValueError("a feature store keeps torch.float32, torch.float16 or torch.bfloat16, not %s" % (dtype,))
+    return _ELEM[dtype]
+
+
+def _require_fp32_for_dma(dtype) -> None:
+    if dtype != torch.float32:
+        raise ValueError("the copy engines cannot widen %s rows to fp32: a half-precision store is read by the gather "
+                         "kernel (gather / method=\"kernel\")" % (dtype,))
+
+
+def _check_overflow(chunk: torch.Tensor, dtype, lo: int) -> None:
+    """``chunk`` (host, fp32 or fp64; row 0 is row ``lo`` of the store) holds no finite value that ``dtype`` turns into
+    an infinity -- a feature clipped to inf would poison every activation behind it."""
+    limit = _OVERFLOWS_AT.get(dtype)
+    if limit is None or chunk.numel() == 0:
+        return
+    mag = chunk.abs()
+    bad = ((mag >= limit) & (mag != float("inf"))).flatten(1).any(1)
+    if bool(bad.any()):
+        row = int(bad.nonzero()[0])
+        worst = float(chunk[row].abs().nan_to_num(nan=0.0, posinf=0.0).max())
+        raise OverflowError("feature row %d holds %g, which is not finite as %s (|x| >= %g rounds to infinity): keep this "
+                            "store in torch.float32%s" % (lo + row, worst, dtype, limit,
+                                                           " or torch.bfloat16" if dtype == torch.float16 else ""))
+
 
 class PinnedFeatureStore:
-    def __init__(self, features, chunk_rows: int = 256):
-        """``features``: array-like of shape (N, C, H, W), float32 or float64."""
+    def __init__(self, features, chunk_rows: int = 256, dtype: torch.dtype = torch.float32):
+        """``features``: array-like of shape (N, C, H, W), float32 or float64.  ``dtype``: what the pinned rows are kept
+        as -- ``torch.float32``, or ``torch.float16`` / ``torch.bfloat16`` (converted once, here, chunk by chunk with
+        torch's ``.to(dtype)`` of the fp32 values -- a float64 source is rounded to fp32 first, in both stores; a finite value that the half type turns into an infinity is an ``OverflowError``)."""
         shape = tuple(int(d) for d in features.shape)
         if len(shape) != 4:
             raise ValueError("features must be (N, C, H, W), got %s" % (shape,))
+        _elem(dtype)
         self.shape = shape
-        self.store = torch.empty(shape, dtype=torch.float32).pin_memory()
-        view = self.store.numpy()
+        self.store = torch.empty(shape, dtype=dtype).pin_memory()
+        view = self.store.numpy() if dtype == torch.float32 else None
         for lo in range(0, shape[0], chunk_rows):  # bounded temporaries for out-of-core sources
             hi = min(shape[0], lo + chunk_rows)
-            view[lo:hi] = np.asarray(features[lo:hi], dtype=np.float32)
+            if view is not None:
+                view[lo:hi] = np.asarray(features[lo:hi], dtype=np.float32)
+                continue
+            # (through fp32, as the resident store's staging buffer: both stores hold the same bits of an fp64 source)
+            chunk = torch.from_numpy(np.ascontiguousarray(features[lo:hi], dtype=np.float32))
+            _check_overflow(chunk, dtype, lo)
+            self.store[lo:hi] = chunk.to(dtype)
 
     def __len__(self) -> int:
         return self.shape[0]
@@ -62,8 +110,10 @@ class PinnedFeatureStore:
             out = torch.empty((n, C, H, W), dtype=torch.float32, device=device, memory_format=torch.channels_last)
         elif tuple(out.shape) != (n, C, H, W) or not out.is_contiguous(memory_format=torch.channels_last):
             raise ValueError("`out` must be a channels_last (n, C, H, W) tensor")
-        _hip.check(_hip.lib().pnmn_gather_features(self.store.data_ptr(), indices.data_ptr(), out.data_ptr(), n, N, C,
-                                                   H * W, _hip.stream_ptr(device)), "gather_features")
+        # (the element type is the pinned tensor's: a store put together around `shape` and `store` alone works too)
+        _hip.check(_hip.lib().pnmn_gather_features_typed(self.store.data_ptr(), _elem(self.store.dtype), indices.data_ptr(),
+                                                         out.data_ptr(), _hip.ELEM_F32, n, N, C, H * W,
+                                                         _hip.stream_ptr(device)), "gather_features")
         return out
 
 
@@ -75,6 +125,7 @@ class PinnedFeatureStore:
             raise _hip.HipLibraryError("the feature store feeds a ROCm device, got %s" % device)
         if indices.device.type != "cpu":
             raise ValueError("copy_rows takes host indices (the copies are queued by the host)")
+        _require_fp32_for_dma(self.store.dtype)
         idx = np.ascontiguousarray(indices.to(torch.long).numpy())
         n, (N, C, H, W) = int(idx.size), self.shape
         if out is None:
@@ -109,6 +160,11 @@ class ResidentRows:
         return self.store.device
 
     @property
+    def is_cuda(self) -> bool:
+        """What a tensor in its place answers (probnmn.evaluators asks before it pipelines a batch)."""
+        return self.store.device.type == "cuda"
+
+    @property
     def shape(self):
         return (int(self.index.size),) + tuple(self.store.image_feature_size)
 
@@ -120,18 +176,32 @@ class ResidentRows:
         return ResidentRows(self.store, self.index[rows])
 
     def pointers(self) -> np.ndarray:
-        """Device address of every row's [H*W][C] map (int64, host)."""
+        """Device address of every row's [H*W][C] fp32 map (int64, host)."""
+        if self.store.dtype != torch.float32:
+            raise TypeError("the stem reads fp32 through these pointers and the store keeps %s: materialize() the rows"
+                            % (self.store.dtype,))
         return self.store.data_ptr() + self.index * np.int64(self.store.row_bytes)
 
     def materialize(self) -> torch.Tensor:
-        """The rows as an ordinary (n, C, H, W) ``channels_last`` tensor (a gathered copy: tests, evaluation code that
-        wants a tensor)."""
-        idx = torch.from_numpy(self.index).to(self.store.device)
-        return self.store.rows[idx].permute(0, 3, 1, 2)
+        """The rows as an ordinary (n, C, H, W) fp32 ``channels_last`` tensor.  Of an fp32 store: a gathered copy (tests,
+        evaluation code that wants a tensor).  Of a half-precision store: ONE launch of ``pnmn_expand_rows`` on the
+        current stream, which reads the selected rows and writes them widened -- what the engine runs in front of the
+        stem for such a batch."""
+        dev = self.store.device
+        if self.store.dtype == torch.float32:
+            idx = torch.from_numpy(self.index).to(dev)
+            return self.store.rows[idx].permute(0, 3, 1, 2)
+        n, (C, H, W) = int(self.index.size), self.store.image_feature_size
+        out = torch.empty((n, C, H, W), dtype=torch.float32, device=dev, memory_format=torch.channels_last)
+        if n:
+            idx = _hip.to_device(self.index, dev)  # (through the pinned ring: no wait for the stream's queued work)
+            _hip.check(_hip.lib().pnmn_expand_rows(self.store.data_ptr(), _elem(self.store.dtype), idx.data_ptr(), out.data_ptr(),
+                                                   n, len(self.store), C * H * W, _hip.stream_ptr(dev)), "expand_rows")
+        return out
 
 
 class DeviceFeatureStore:
-    """ALL features once in HBM, in the layout the stem reads (NHWC: ``rows[N][H][W][C]`` fp32).  70 000 CLEVR train
+    """ALL features once in HBM, in the layout the stem reads (NHWC: ``rows[N][H][W][C]``, fp32 by default).  70 000 CLEVR train
     images x 0.8 MB = 56.2 GB at 14x14 (15 000 val images: 12 GB) of the 288 GB of an MI355X; 28x28 maps: 225 GB -- the
     train set alone still fits.  A step then moves NO feature bytes over PCIe and runs no gather or layout pass: the
     first stem convolution and its weight gradient take per-example pointers (``pnmn_conv_item.in`` /
@@ -140,24 +210,36 @@ class DeviceFeatureStore:
     from HDF5 per item (probnmn/data/readers.py:63-108, datasets.py:137-142).
 
     Filled in chunks from any array-like (float32 / float64, (N, C, H, W)): a chunk goes through a page-locked staging
-    buffer and the ingest kernel, which writes the NHWC rows."""
+    buffer and the ingest kernel, which writes the NHWC rows.
 
-    def __init__(self, features, device: torch.device, chunk_rows: int = 512):
-        shape = tuple(int(d) for d in features.shape)
-        if len(shape) != 4:
-            raise ValueError("features must be (N, C, H, W), got %s" % (shape,))
+    ``dtype=torch.float16`` / ``torch.bfloat16``: the rows take two bytes per element (28 GB / 112 GB for the train set
+    at 14x14 / 28x28).  The fill stages fp32 chunks all the same and the ingest kernel rounds them (to nearest even, as
+    ``Tensor.to(dtype)``); a batch of such a store is widened by one ``pnmn_expand_rows`` launch in front of the stem
+    (``ResidentRows.materialize``), since the stem reads fp32.  ``empty`` + ``write_rows`` fill a store chunk by chunk
+    from device tensors, so that an extracted set never has to exist in fp32 as a whole."""
+
+    def _allocate(self, shape, device, dtype) -> None:
+        _elem(dtype)
         device = torch.device(device)
         if device.type != "cuda":
             raise _hip.HipLibraryError("the resident feature store lives on a ROCm device, got %s" % device)
         N, C, H, W = shape
         self.shape, self.device = shape, device
-        self.row_bytes = C * H * W * 4
+        self.row_bytes = C * H * W * torch.empty((), dtype=dtype).element_size()
         free, _ = torch.cuda.mem_get_info(device)
         if N * self.row_bytes > free:
             raise MemoryError("%d rows x %.1f MB = %.1f GB do not fit the %.1f GB free on %s: use PinnedFeatureStore"
                               % (N, self.row_bytes / 1e6, N * self.row_bytes / 1e9, free / 1e9, device))
-        self.rows = torch.empty((N, H, W, C), dtype=torch.float32, device=device)
-        self.device = device = self.rows.device  # ('cuda' resolved to 'cuda:<current>': compared with parameter devices)
+        self.rows = torch.empty((N, H, W, C), dtype=dtype, device=device)
+        self.device = self.rows.device  # ('cuda' resolved to 'cuda:<current>': compared with parameter devices)
+
+    def __init__(self, features, device: torch.device, chunk_rows: int = 512, dtype: torch.dtype = torch.float32):
+        shape = tuple(int(d) for d in features.shape)
+        if len(shape) != 4:
+            raise ValueError("features must be (N, C, H, W), got %s" % (shape,))
+        self._allocate(shape, device, dtype)
+        N, C, H, W = shape
+        device = self.device
         chunk_rows = max(1, min(chunk_rows, N))
         stage = torch.empty((chunk_rows, C, H, W), dtype=torch.float32).pin_memory()
         view = stage.numpy()
@@ -166,29 +248,59 @@ class DeviceFeatureStore:
             hi = min(N, lo + chunk_rows)
             torch.cuda.current_stream(device).synchronize()  # (the staging buffer is reused)
             view[: hi - lo] = np.asarray(features[lo:hi], dtype=np.float32)
+            _check_overflow(stage[: hi - lo], dtype, lo)
             idx = _hip.small_to_device(list(range(hi - lo)), torch.long, device) if hi - lo <= 4096 else \
                 torch.arange(hi - lo, device=device)
-            _hip.check(_hip.lib().pnmn_gather_features(stage.data_ptr(), idx.data_ptr(), self.rows[lo:hi].data_ptr(), hi - lo,
-                                                       chunk_rows, C, H * W, st), "gather_features")
+            _hip.check(_hip.lib().pnmn_gather_features_typed(stage.data_ptr(), _hip.ELEM_F32, idx.data_ptr(),
+                                                             self.rows[lo:hi].data_ptr(), _elem(dtype), hi - lo, chunk_rows, C,
+                                                             H * W, st), "gather_features")
         torch.cuda.current_stream(device).synchronize()
 
     @classmethod
+    def empty(cls, n: int, image_feature_size, device: torch.device, dtype: torch.dtype = torch.float32) -> "DeviceFeatureStore":
+        """A store of ``n`` rows of (C, H, W) features with nothing in them yet: ``write_rows`` fills it."""
+        C, H, W = (int(d) for d in image_feature_size)
+        self = cls.__new__(cls)
+        self._allocate((int(n), C, H, W), device, dtype)
+        return self
+
+    def write_rows(self, lo: int, chunk: torch.Tensor) -> None:
+        """Rows ``lo .. lo + len(chunk)`` from ``chunk``: a (k, C, H, W) ``channels_last`` tensor on the store's device,
+        fp32 (what ``probnmn.data.feature_extractor`` produces; rounded to the store's dtype by torch's ``copy_``) or
+        already of the store's dtype.  On the current stream, without a host synchronisation -- so, unlike the
+        constructors, it cannot refuse a value that overflows the store's dtype."""
+        if chunk.dim() != 4 or tuple(chunk.shape[1:]) != tuple(self.shape[1:]):
+            raise ValueError("expected a (k, %d, %d, %d) chunk, got %s" % (self.shape[1:] + (tuple(chunk.shape),)))
+        if chunk.device != self.device:
+            raise _hip.HipLibraryError("the chunk is on %s, the store on %s" % (chunk.device, self.device))
+        if chunk.dtype not in (torch.float32, self.dtype):
+            raise ValueError("a chunk is torch.float32 or the store's %s, got %s" % (self.dtype, chunk.dtype))
+        lo, k = int(lo), int(chunk.size(0))
+        if lo < 0 or lo + k > self.shape[0]:
+            raise IndexError("rows %d .. %d outside the store's [0, %d)" % (lo, lo + k, self.shape[0]))
+        self.rows[lo:lo + k].copy_(chunk.permute(0, 2, 3, 1))
+
+    @classmethod
     def from_device(cls, features: torch.Tensor) -> "DeviceFeatureStore":
-        """Adopt features that are already in HBM in the stem's layout -- an (N, C, H, W) fp32 ``channels_last`` tensor,
-        which is what ``probnmn.data.feature_extractor`` writes -- without a copy."""
-        if features.dim() != 4 or features.dtype != torch.float32 or features.device.type != "cuda":
-            raise ValueError("expected an (N, C, H, W) fp32 tensor on a ROCm device")
+        """Adopt features that are already in HBM in the stem's layout -- an (N, C, H, W) ``channels_last`` tensor, fp32
+        (which is what ``probnmn.data.feature_extractor`` writes), fp16 or bf16 -- without a copy."""
+        if features.dim() != 4 or features.dtype not in _ELEM or features.device.type != "cuda":
+            raise ValueError("expected an (N, C, H, W) fp32, fp16 or bf16 tensor on a ROCm device")
         rows = features.permute(0, 2, 3, 1)
         if not rows.is_contiguous():
             raise ValueError("features must be in channels_last memory format (NHWC storage)")
         self = cls.__new__(cls)
         self.shape, self.device = tuple(int(d) for d in features.shape), features.device
-        self.row_bytes = self.shape[1] * self.shape[2] * self.shape[3] * 4
+        self.row_bytes = self.shape[1] * self.shape[2] * self.shape[3] * features.element_size()
         self.rows = rows
         return self
 
     def __len__(self) -> int:
         return self.shape[0]
+
+    @property
+    def dtype(self) -> torch.dtype:
+        return self.rows.dtype
 
     @property
     def image_feature_size(self):
@@ -218,6 +330,8 @@ class PrefetchingLoader:
             method = "resident"  # (no feature bytes move: a batch's "image" is a ResidentRows)
         if method not in ("dma", "kernel", "resident"):
             raise ValueError("method must be 'dma', 'kernel' or 'resident'")
+        if method == "dma":
+            _require_fp32_for_dma(store.store.dtype)
         self.method = method
         device = torch.device(device)
         if device.type == "cuda" and device.index is None:

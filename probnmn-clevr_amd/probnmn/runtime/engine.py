@@ -417,6 +417,11 @@ class NMNEngine:
         resident = isinstance(features, ResidentRows)
         if resident and rows is not None:
             raise ValueError("rows of a resident batch: pass features.subset(rows) instead")
+        if resident and features.store.dtype != torch.float32:
+            # rows of a half-precision store: the stem reads fp32, so they are widened first (one pnmn_expand_rows launch
+            # on this stream, of the rows this pass uses -- a joint step has taken its subset already) and go on as any
+            # NHWC tensor, used in place
+            features, resident = features.materialize(), False
         B = features.size(0) if rows is None else int(rows.numel())
         if rows is not None and (rows.dtype != torch.long or rows.device != dev or not rows.is_contiguous()):
             raise ValueError("rows must be a contiguous int64 tensor on the network's device")
