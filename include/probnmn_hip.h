@@ -256,25 +256,34 @@ int pnmn_nhwc_to_nchw(const float* src, float* dst, int n, int C, int HW, void* 
  * device.  The kernel reads the selected rows over PCIe.  (= pnmn_gather_features_typed with F32, F32.) */
 int pnmn_gather_features(const float* store, const int64_t* indices, float* dst, int n, int64_t n_store,
                          int C, int HW, void* stream);
-/* Element types of a feature store.  The networks compute in fp32; a store may keep its rows in half the bytes. */
+/* Element types of a feature store.  The networks compute in fp32; a store may keep its rows in half or a quarter of
+ * the bytes.  (3 is no element type.) */
 #define PNMN_ELEM_F32  0
 #define PNMN_ELEM_F16  1   /* IEEE binary16 */
 #define PNMN_ELEM_BF16 2   /* bfloat16: the upper half of a binary32 */
+#define PNMN_ELEM_F8E4M3 4 /* OCP e4m3fn (torch.float8_e4m3fn): no infinities, 0x7f / 0xff are NaN, largest finite 448 */
+#define PNMN_ELEM_F8E5M2 5 /* e5m2 (torch.float8_e5m2): IEEE-like, infinities exist, largest finite 57344 */
 /* pnmn_gather_features with the element types as parameters: `store` [n_store][C][HW] of `src_elem` (page-locked host
- * memory or device memory), dst [n][HW][C] of `dst_elem`.  Supported: F16 | BF16 -> F32 (a half store feeding a batch;
- * widening is exact), F32 -> F16 | BF16 (filling a half device store from the fp32 staging buffer: round to nearest
- * even, overflow to infinity, subnormals kept -- what torch's Tensor.to(dtype) does on the host) and F32 -> F32 (what
- * pnmn_gather_features runs).  Any other pair returns PNMN_EINVAL.  The same fixed grid of at most 12 workgroups and
- * the same 26 KB LDS bound for every pair; an index outside [0, n_store) reads row 0. */
+ * memory or device memory), dst [n][HW][C] of `dst_elem`.  Supported: F16 | BF16 | F8E4M3 | F8E5M2 -> F32 (a narrow
+ * store feeding a batch; widening is exact for every code, NaN to NaN), F32 -> F16 | BF16 | F8E4M3 | F8E5M2 (filling a
+ * narrow device store from the fp32 staging buffer: round to nearest even, subnormals kept, overflow to infinity --
+ * to NaN for F8E4M3, which has no infinity: |x| > 464 -- what torch's Tensor.to(dtype) does on the host) and F32 ->
+ * F32 (what pnmn_gather_features runs).  Any other pair returns PNMN_EINVAL.  The same fixed grid of at most 12
+ * workgroups and the same 26 KB LDS bound for every pair; an index outside [0, n_store) reads row 0. */
 int pnmn_gather_features_typed(const void* store, int src_elem, const int64_t* indices, void* dst, int dst_elem, int n,
                                int64_t n_store, int C, int HW, void* stream);
-/* Rows of a half-precision store that lives in device memory, widened: rows [n_store][row_elems] F16 or BF16 (already
- * NHWC), indices [n] int64 on the device, dst [n][row_elems] fp32; dst row i = rows[indices[i]] (an index outside
- * [0, n_store) reads row 0).  No transpose.  16-byte loads when row_elems is a multiple of 8 and both bases are 16-byte
- * aligned (every row then starts aligned), element by element otherwise.  Runs in front of the stem on the step's own
- * stream and uses the whole chip.  src_elem other than F16 / BF16 returns PNMN_EINVAL. */
+/* Rows of a narrow store that lives in device memory, widened: rows [n_store][row_elems] F16, BF16, F8E4M3 or F8E5M2
+ * (already NHWC), indices [n] int64 on the device, dst [n][row_elems] fp32; dst row i = rows[indices[i]] (an index
+ * outside [0, n_store) reads row 0).  No transpose.  16-byte loads when row_elems is a multiple of the 8 or 16 elements
+ * in them and both bases are 16-byte aligned (every row then starts aligned), element by element otherwise.  Runs in
+ * front of the stem on the step's own stream and uses the whole chip.  Any other src_elem returns PNMN_EINVAL. */
 int pnmn_expand_rows(const void* rows, int src_elem, const int64_t* indices, void* dst, int n, int64_t n_store,
                      int64_t row_elems, void* stream);
+/* An fp32 chunk that is already in device memory, in the store's own order, rounded into an 8-bit store: src [n_elems]
+ * fp32, dst [n_elems] of `dst_elem` (F8E4M3 or F8E5M2; anything else returns PNMN_EINVAL), the rounding of
+ * pnmn_gather_features_typed.  `overflowed` (device) is incremented by the number of elements that were finite in fp32
+ * and are not after narrowing: the caller's running count, which a stream-ordered fill cannot turn into an error. */
+int pnmn_narrow_rows(const float* src, void* dst, int dst_elem, int64_t n_elems, uint64_t* overflowed, void* stream);
 /* The same rows through the copy engines instead of a kernel: n hipMemcpyAsync of `row_bytes` each from the
  * page-locked store into a contiguous (NCHW, as stored) device batch.  `indices` is a HOST array; an index outside
  * [0, n_store) returns PNMN_EINVAL with the copies before it queued.  The stem's layout pass then reads the batch

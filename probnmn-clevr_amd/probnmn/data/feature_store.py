@@ -1,5 +1,5 @@
-"""Image-feature ingest: a page-locked feature store on the host (fp32, or fp16 / bf16 at half the bytes), a
-resident one in HBM, and a prefetching batch loader.
+"""Image-feature ingest: a page-locked feature store on the host (fp32, fp16 / bf16 at half the bytes, or 8-bit floats at
+a quarter), a resident one in HBM, and a prefetching batch loader.
 
 The reference reads one float64 row per example from HDF5 on the host, casts it, lets the DataLoader
 collate a batch and moves it to the GPU inside ``_Trainer.step`` (reference: probnmn/data/readers.py:63-108,
@@ -22,6 +22,10 @@ bytes over PCIe per gathered question, half the HBM or page-locked memory per im
 kernels that read them (``pnmn_gather_features_typed``, ``pnmn_expand_rows``).  The networks compute in fp32 either
 way: they see exactly ``features.to(dtype).float()`` of the fp32 features (a float64 source is cast to fp32 first,
 as for an fp32 store).
+
+``dtype=torch.float8_e4m3fn`` / ``torch.float8_e5m2`` is the same contract at one byte per element (3 or 2 mantissa
+bits; largest finite value 448 or 57344): the same kernels read the rows, and a resident 8-bit store counts on the
+device what ``write_rows`` could not keep finite (``DeviceFeatureStore.overflowed``).
 """
 from typing import Dict, Iterable, Iterator, Optional
 
@@ -33,44 +37,57 @@ import torch
 from probnmn import _hip
 
 # store dtype -> element code of the kernels (include/probnmn_hip.h: PNMN_ELEM_*)
-_ELEM = {torch.float32: _hip.ELEM_F32, torch.float16: _hip.ELEM_F16, torch.bfloat16: _hip.ELEM_BF16}
+_ELEM = {torch.float32: _hip.ELEM_F32, torch.float16: _hip.ELEM_F16, torch.bfloat16: _hip.ELEM_BF16,
+         torch.float8_e4m3fn: _hip.ELEM_F8E4M3, torch.float8_e5m2: _hip.ELEM_F8E5M2}
+_EIGHT_BIT = (torch.float8_e4m3fn, torch.float8_e5m2)
 # the smallest magnitude that rounds (to nearest even) to infinity: the largest finite value plus half a unit of its last place
-_OVERFLOWS_AT = {torch.float16: 65520.0, torch.bfloat16: float(np.uint32(0x7F7F8000).view(np.float32))}
+_OVERFLOWS_AT = {torch.float16: 65520.0, torch.bfloat16: float(np.uint32(0x7F7F8000).view(np.float32)),
+                 torch.float8_e5m2: 61440.0}
+# e4m3fn has no infinity: beyond its largest value, 448, there is one more code of the top binade, and it is NaN.  The
+# tie at 448 + 16 = 464 goes to even, which is 448; whatever is LARGER than 464 becomes NaN.
+_BECOMES_NAN_ABOVE = {torch.float8_e4m3fn: 464.0}
 
 
 def _elem(dtype) -> int:
     if dtype not in _ELEM:
-        raise ValueError("a feature store keeps torch.float32, torch.float16 or torch.bfloat16, not %s" % (dtype,))
+        raise ValueError("a feature store keeps torch.float32, torch.float16, torch.bfloat16, torch.float8_e4m3fn or "
+                         "torch.float8_e5m2, not %s" % (dtype,))
     return _ELEM[dtype]
 
 
 def _require_fp32_for_dma(dtype) -> None:
     if dtype != torch.float32:
-        raise ValueError("the copy engines cannot widen %s rows to fp32: a half-precision store is read by the gather "
+        raise ValueError("the copy engines cannot widen %s rows to fp32: a narrower store is read by the gather "
                          "kernel (gather / method=\"kernel\")" % (dtype,))
 
 
 def _check_overflow(chunk: torch.Tensor, dtype, lo: int) -> None:
     """``chunk`` (host, fp32 or fp64; row 0 is row ``lo`` of the store) holds no finite value that ``dtype`` turns into
-    an infinity -- a feature clipped to inf would poison every activation behind it."""
-    limit = _OVERFLOWS_AT.get(dtype)
-    if limit is None or chunk.numel() == 0:
+    an infinity -- or, as torch.float8_e4m3fn, into a NaN -- a feature clipped to inf or NaN would poison every
+    activation behind it."""
+    limit, above = _OVERFLOWS_AT.get(dtype), _BECOMES_NAN_ABOVE.get(dtype)
+    if (limit is None and above is None) or chunk.numel() == 0:
         return
     mag = chunk.abs()
-    bad = ((mag >= limit) & (mag != float("inf"))).flatten(1).any(1)
+    bad = (((mag >= limit) if above is None else (mag > above)) & (mag != float("inf"))).flatten(1).any(1)
     if bool(bad.any()):
         row = int(bad.nonzero()[0])
         worst = float(chunk[row].abs().nan_to_num(nan=0.0, posinf=0.0).max())
-        raise OverflowError("feature row %d holds %g, which is not finite as %s (|x| >= %g rounds to infinity): keep this "
-                            "store in torch.float32%s" % (lo + row, worst, dtype, limit,
-                                                           " or torch.bfloat16" if dtype == torch.float16 else ""))
+        why = "|x| >= %g rounds to infinity" % limit if above is None else \
+            "the type has no infinity: |x| > %g becomes NaN" % above
+        wider = {torch.float16: " or torch.bfloat16", torch.float8_e4m3fn: ", a half type or torch.float8_e5m2",
+                 torch.float8_e5m2: " or a half type"}.get(dtype, "")
+        raise OverflowError("feature row %d holds %g, which is not finite as %s (%s): keep this store in torch.float32%s"
+                            % (lo + row, worst, dtype, why, wider))
 
 
 class PinnedFeatureStore:
     def __init__(self, features, chunk_rows: int = 256, dtype: torch.dtype = torch.float32):
         """``features``: array-like of shape (N, C, H, W), float32 or float64.  ``dtype``: what the pinned rows are kept
-        as -- ``torch.float32``, or ``torch.float16`` / ``torch.bfloat16`` (converted once, here, chunk by chunk with
-        torch's ``.to(dtype)`` of the fp32 values -- a float64 source is rounded to fp32 first, in both stores; a finite value that the half type turns into an infinity is an ``OverflowError``)."""
+        as -- ``torch.float32``, or ``torch.float16`` / ``torch.bfloat16`` / ``torch.float8_e4m3fn`` / ``torch.float8_e5m2``
+        (converted once, here, chunk by chunk with torch's ``.to(dtype)`` of the fp32 values -- a float64 source is rounded
+        to fp32 first, in both stores; a finite value that the narrower type turns into an infinity or a NaN is an
+        ``OverflowError``)."""
         shape = tuple(int(d) for d in features.shape)
         if len(shape) != 4:
             raise ValueError("features must be (N, C, H, W), got %s" % (shape,))
@@ -184,7 +201,7 @@ class ResidentRows:
 
     def materialize(self) -> torch.Tensor:
         """The rows as an ordinary (n, C, H, W) fp32 ``channels_last`` tensor.  Of an fp32 store: a gathered copy (tests,
-        evaluation code that wants a tensor).  Of a half-precision store: ONE launch of ``pnmn_expand_rows`` on the
+        evaluation code that wants a tensor).  Of a half-precision or 8-bit store: ONE launch of ``pnmn_expand_rows`` on the
         current stream, which reads the selected rows and writes them widened -- what the engine runs in front of the
         stem for such a batch."""
         dev = self.store.device
@@ -216,7 +233,16 @@ class DeviceFeatureStore:
     at 14x14 / 28x28).  The fill stages fp32 chunks all the same and the ingest kernel rounds them (to nearest even, as
     ``Tensor.to(dtype)``); a batch of such a store is widened by one ``pnmn_expand_rows`` launch in front of the stem
     (``ResidentRows.materialize``), since the stem reads fp32.  ``empty`` + ``write_rows`` fill a store chunk by chunk
-    from device tensors, so that an extracted set never has to exist in fp32 as a whole."""
+    from device tensors, so that an extracted set never has to exist in fp32 as a whole.
+
+    ``dtype=torch.float8_e4m3fn`` / ``torch.float8_e5m2``: one byte per element (14 GB / 56 GB), filled and widened by the
+    same kernels.  ``write_rows`` rounds an fp32 chunk with ``pnmn_narrow_rows`` (torch's host rounding, bit for bit) and
+    cannot raise without a host synchronisation, so such a store owns a counter in device memory of the elements that
+    were finite in fp32 and are not as stored: ``overflowed()`` reads it."""
+
+    def _count_overflows(self) -> None:
+        # (one uint64 the narrowing kernel adds to; int64 is what torch has for it)
+        self._overflowed = torch.zeros(1, dtype=torch.int64, device=self.device) if self.dtype in _EIGHT_BIT else None
 
     def _allocate(self, shape, device, dtype) -> None:
         _elem(dtype)
@@ -232,6 +258,7 @@ class DeviceFeatureStore:
                               % (N, self.row_bytes / 1e6, N * self.row_bytes / 1e9, free / 1e9, device))
         self.rows = torch.empty((N, H, W, C), dtype=dtype, device=device)
         self.device = self.rows.device  # ('cuda' resolved to 'cuda:<current>': compared with parameter devices)
+        self._count_overflows()
 
     def __init__(self, features, device: torch.device, chunk_rows: int = 512, dtype: torch.dtype = torch.float32):
         shape = tuple(int(d) for d in features.shape)
@@ -266,9 +293,10 @@ class DeviceFeatureStore:
 
     def write_rows(self, lo: int, chunk: torch.Tensor) -> None:
         """Rows ``lo .. lo + len(chunk)`` from ``chunk``: a (k, C, H, W) ``channels_last`` tensor on the store's device,
-        fp32 (what ``probnmn.data.feature_extractor`` produces; rounded to the store's dtype by torch's ``copy_``) or
-        already of the store's dtype.  On the current stream, without a host synchronisation -- so, unlike the
-        constructors, it cannot refuse a value that overflows the store's dtype."""
+        fp32 (what ``probnmn.data.feature_extractor`` produces; rounded to the store's dtype by torch's ``copy_``, to an
+        8-bit dtype by ``pnmn_narrow_rows``) or already of the store's dtype.  On the current stream, without a host
+        synchronisation -- so, unlike the constructors, it cannot refuse a value that overflows the store's dtype; an
+        8-bit store counts them (``overflowed``)."""
         if chunk.dim() != 4 or tuple(chunk.shape[1:]) != tuple(self.shape[1:]):
             raise ValueError("expected a (k, %d, %d, %d) chunk, got %s" % (self.shape[1:] + (tuple(chunk.shape),)))
         if chunk.device != self.device:
@@ -278,14 +306,28 @@ class DeviceFeatureStore:
         lo, k = int(lo), int(chunk.size(0))
         if lo < 0 or lo + k > self.shape[0]:
             raise IndexError("rows %d .. %d outside the store's [0, %d)" % (lo, lo + k, self.shape[0]))
-        self.rows[lo:lo + k].copy_(chunk.permute(0, 2, 3, 1))
+        if self.dtype not in _EIGHT_BIT:
+            self.rows[lo:lo + k].copy_(chunk.permute(0, 2, 3, 1))
+        elif chunk.dtype == self.dtype:
+            self.rows[lo:lo + k].view(torch.uint8).copy_(chunk.permute(0, 2, 3, 1).view(torch.uint8))  # (the bytes as they are)
+        elif k:
+            src = chunk.permute(0, 2, 3, 1).contiguous()  # (a channels_last chunk is that already)
+            _hip.check(_hip.lib().pnmn_narrow_rows(src.data_ptr(), self.rows[lo:lo + k].data_ptr(), _elem(self.dtype), src.numel(),
+                                                   self._overflowed.data_ptr(), _hip.stream_ptr(self.device)), "narrow_rows")
+
+    def overflowed(self) -> int:
+        """How many elements ``write_rows`` has met so far that were finite in fp32 and are not finite as stored (NaN in
+        ``torch.float8_e4m3fn``, an infinity in ``torch.float8_e5m2``).  Of an 8-bit store only; waits for the device."""
+        if self._overflowed is None:
+            raise TypeError("only an 8-bit store counts what write_rows could not keep finite; this one keeps %s" % (self.dtype,))
+        return int(self._overflowed.item())
 
     @classmethod
     def from_device(cls, features: torch.Tensor) -> "DeviceFeatureStore":
         """Adopt features that are already in HBM in the stem's layout -- an (N, C, H, W) ``channels_last`` tensor, fp32
-        (which is what ``probnmn.data.feature_extractor`` writes), fp16 or bf16 -- without a copy."""
+        (which is what ``probnmn.data.feature_extractor`` writes), fp16, bf16 or an 8-bit float -- without a copy."""
         if features.dim() != 4 or features.dtype not in _ELEM or features.device.type != "cuda":
-            raise ValueError("expected an (N, C, H, W) fp32, fp16 or bf16 tensor on a ROCm device")
+            raise ValueError("expected an (N, C, H, W) fp32, fp16, bf16, float8_e4m3fn or float8_e5m2 tensor on a ROCm device")
         rows = features.permute(0, 2, 3, 1)
         if not rows.is_contiguous():
             raise ValueError("features must be in channels_last memory format (NHWC storage)")
@@ -293,6 +335,7 @@ class DeviceFeatureStore:
         self.shape, self.device = tuple(int(d) for d in features.shape), features.device
         self.row_bytes = self.shape[1] * self.shape[2] * self.shape[3] * features.element_size()
         self.rows = rows
+        self._count_overflows()
         return self
 
     def __len__(self) -> int:

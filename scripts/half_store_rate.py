@@ -1,15 +1,16 @@
-"""Half-precision feature stores against the fp32 ones, in ONE process, warmed, the variants alternating:
+"""Half-precision and 8-bit feature stores against the fp32 ones, in ONE process, warmed, the variants alternating:
 
   * the gather kernel alone (PinnedFeatureStore.gather): GB/s over PCIe and questions/s at 128 and 1024 questions, for
-    fp32 / fp16 / bf16 pinned stores;
-  * pnmn_expand_rows alone (ResidentRows.materialize of an fp16 store) at 519 and 1024 rows against its HBM floor
-    (bytes read + written over the peak bandwidth);
-  * the 1024-question joint step fed through PrefetchingLoader from pinned fp32, pinned fp16, resident fp32 and
-    resident fp16 stores, fresh random rows every step (what bench.py: ingest_side does for the fp32 pair);
+    a pinned store of every dtype of --dtypes;
+  * pnmn_expand_rows alone (ResidentRows.materialize of every narrow store of --resident) at 519 and 1024 rows against
+    its HBM floor (bytes read + written over the peak bandwidth);
+  * the 1024-question joint step fed through PrefetchingLoader from every pinned and every resident store, fresh
+    random rows every step (what bench.py: ingest_side does for the fp32 pair);
   * what it takes to fill each store.
 
 The comparison that counts is between the variants of one run; every timed region ends in a device synchronise.
-Usage: python scripts/half_store_rate.py [--rows 4096] [--batch 1024] [--steps 10] [--rounds 3] [--out result.json]"""
+Usage: python scripts/half_store_rate.py [--dtypes fp32,fp16,bf16,fp8e4m3] [--resident fp32,fp16,fp8e4m3] [--rows 4096]
+                                         [--batch 1024] [--steps 10] [--rounds 3] [--out result.json]"""
 import argparse
 import json
 import os
@@ -25,7 +26,17 @@ from probnmn.data.feature_store import DeviceFeatureStore, PinnedFeatureStore, P
 
 HBM_PEAK = 8.0e12  # bytes/s, MI355X
 C, H, W = 1024, 14, 14
-NAMES = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16"}
+NAMES = {torch.float32: "fp32", torch.float16: "fp16", torch.bfloat16: "bf16", torch.float8_e4m3fn: "fp8e4m3",
+         torch.float8_e5m2: "fp8e5m2"}
+DTYPES = {name: dtype for dtype, name in NAMES.items()}
+
+
+def dtype_list(text):
+    names = [n for n in text.split(",") if n]
+    unknown = [n for n in names if n not in DTYPES]
+    if unknown or not names:
+        raise argparse.ArgumentTypeError("dtypes are a comma-separated list of %s, got %r" % (", ".join(DTYPES), text))
+    return [DTYPES[n] for n in names]
 
 
 def median(xs):
@@ -45,6 +56,8 @@ def event_ms(fn, reps):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--dtypes", type=dtype_list, default=dtype_list("fp32,fp16,bf16,fp8e4m3"), help="pinned stores to compare")
+    ap.add_argument("--resident", type=dtype_list, default=dtype_list("fp32,fp16,fp8e4m3"), help="resident stores to compare")
     ap.add_argument("--rows", type=int, default=4096, help="rows of every store (0.8 MB each in fp32)")
     ap.add_argument("--batch", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=10, help="timed joint steps per variant and round")
@@ -63,11 +76,11 @@ def main():
 
     # ---- fills ---------------------------------------------------------------------------------------------------
     pinned, resident, fills = {}, {}, {}
-    for dtype in (torch.float32, torch.float16, torch.bfloat16):
+    for dtype in args.dtypes:
         t0 = time.perf_counter()
         pinned[dtype] = PinnedFeatureStore(feats, dtype=dtype)
         fills["pinned_" + NAMES[dtype]] = round(time.perf_counter() - t0, 2)
-    for dtype in (torch.float32, torch.float16):
+    for dtype in args.resident:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         resident[dtype] = DeviceFeatureStore(feats, dev, dtype=dtype)
@@ -100,14 +113,24 @@ def main():
 
     # ---- the widening of resident rows alone ---------------------------------------------------------------------
     result["expand_rows"] = {}
+    narrow = [dtype for dtype in resident if dtype != torch.float32]
     for B in (519, 1024):
-        batch_rows = resident[torch.float16].batch(torch.randint(0, rows, (B,), generator=g))
-        batch_rows.materialize()
+        index = torch.randint(0, rows, (B,), generator=g)
+        batch_rows = {dtype: resident[dtype].batch(index) for dtype in narrow}
+        for b in batch_rows.values():
+            b.materialize()
         torch.cuda.synchronize()
-        t = median([event_ms(batch_rows.materialize, 10) for _ in range(args.rounds)])
-        floor = B * C * H * W * (2 + 4) / HBM_PEAK * 1e3
-        result["expand_rows"][str(B)] = {"ms": round(t, 4), "hbm_floor_ms": round(floor, 4), "of_floor": round(t / floor, 2)}
-        print("expand_rows %4d rows of fp16: %.4f ms, HBM floor %.4f ms (x%.2f; the index upload is in it)" % (B, t, floor, t / floor), flush=True)
+        ms = {dtype: [] for dtype in narrow}
+        for _ in range(args.rounds):
+            for dtype in narrow:
+                ms[dtype].append(event_ms(batch_rows[dtype].materialize, 10))
+        for dtype in narrow:
+            t = median(ms[dtype])
+            floor = B * C * H * W * (resident[dtype].rows.element_size() + 4) / HBM_PEAK * 1e3
+            result["expand_rows"]["%s_%d" % (NAMES[dtype], B)] = {"ms": round(t, 4), "hbm_floor_ms": round(floor, 4),
+                                                                  "of_floor": round(t / floor, 2)}
+            print("expand_rows %4d rows of %s: %.4f ms, HBM floor %.4f ms (x%.2f; the index upload is in it)"
+                  % (B, NAMES[dtype], t, floor, t / floor), flush=True)
 
     # ---- the joint step fed from each store ----------------------------------------------------------------------
     if not args.no_step:
@@ -152,8 +175,8 @@ def main():
             it.close()
             return elapsed / k * 1e3
 
-        variants = [("pinned_fp32", pinned[torch.float32]), ("pinned_fp16", pinned[torch.float16]),
-                    ("resident_fp32", resident[torch.float32]), ("resident_fp16", resident[torch.float16])]
+        variants = [("pinned_" + NAMES[dtype], store) for dtype, store in pinned.items()] + \
+                   [("resident_" + NAMES[dtype], store) for dtype, store in resident.items()]
         ms = {name: [] for name, _ in variants}
         for _ in range(args.rounds):
             for name, store in variants:
@@ -162,8 +185,10 @@ def main():
         for name, v in ms.items():
             print("joint step of %d questions fed from %-13s: %.2f ms per step (rounds: %s)"
                   % (n, name, median(v), ", ".join("%.2f" % x for x in v)), flush=True)
-        a, b = median(ms["pinned_fp32"]), median(ms["pinned_fp16"])
-        print("pinned fp16 against pinned fp32 of this run: %.2f ms against %.2f ms (x%.3f)" % (b, a, b / a), flush=True)
+        for name in ms:
+            if name != "pinned_fp32" and name.startswith("pinned_") and "pinned_fp32" in ms:
+                a, b = median(ms["pinned_fp32"]), median(ms[name])
+                print("%s against pinned fp32 of this run: %.2f ms against %.2f ms (x%.3f)" % (name.replace("_", " "), b, a, b / a), flush=True)
 
     torch.cuda.synchronize()
     print(json.dumps(result), flush=True)
