@@ -933,6 +933,14 @@ int pnmn_trunk_last_forward(void* planner, pnmn_launch* out, int capacity);
 /* test hook: the record words of the last launch == 0 call (the list entries then point into a buffer that would start
  * at device address 0x10000); returns their size in bytes */
 int64_t pnmn_trunk_last_records_bytes(void* planner, uint64_t* out, int64_t capacity_words);
+/* For the last pnmn_trunk_plan_and_launch call: offsets[i][p] = float offset into `act` of the one-channel map written by
+ * the module call of token position p of program i, or -1.  Returns n_programs * length, PNMN_EINVAL on a null
+ * planner / short capacity.  Works after launch == 0 calls too (no device).
+ * -1: the program is invalid; the token is skipped or `scene`; the call's output has `channels` channels (query,
+ * comparison, and / or with a wide operand); the call is not executed because the result does not depend on it.  Every
+ * executed call has a slot of its own in the arena, so the maps stay intact until the planner's next call.  A call that
+ * failed (PNMN_EAGAIN included) leaves nothing to ask about: 0. */
+int64_t pnmn_trunk_last_attention(void* planner, int64_t* offsets /* HOST [n_programs][length] */, int64_t capacity);
 
 /* ---------------------------------------------------------------------------------------------
  * Host-side batch planner (no device work)                    replaces the per-example interpreter loop of
@@ -1036,6 +1044,38 @@ int pnmn_maxpool3x3s2_nhwc(const float* x, float* y, int N, int H, int W, int C,
 int pnmn_image_prep(const uint8_t* images, int64_t image_stride, int N, int Hin, int Win, const int32_t* kx,
                     const int32_t* xbounds, int ksx, const int32_t* ky, const int32_t* ybounds, int ksy,
                     const float* lut, float* out, int Hout, int Wout, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Attention maps of the module programs (csrc/attention_maps.hip): where a program looked.
+ * Not in the reference (its interpreter drops every intermediate output: probnmn/models/nmn.py:197-238).
+ *
+ * pnmn_attention_gather: row j of out = the HW floats at act + offsets[j] (pnmn_trunk_last_attention's offsets, on the
+ *   device), or zeros where offsets[j] < 0.  n == 0 returns 0 without a launch; null pointers or HW <= 0: PNMN_EINVAL.
+ *
+ * pnmn_attention_overlay: map j, resized to the image with bilinear interpolation (half-pixel centres, as
+ *   F.interpolate(..., align_corners=False)), coloured through `lut` and blended over image image_of[j].  Integer
+ *   arithmetic throughout (tests/helpers/overlay_reference.py restates it in numpy, bit for bit):
+ *     quantise     q = (int)fmaf(fminf(fmaxf(a, 0), 1), 255.0f, 0.5f)                               (NaN -> 0)
+ *     per axis     (output size n_out, map size n_in, output index X)  num = (2X + 1) * n_in - n_out, den = 2 * n_out;
+ *                  num < 0: i0 = 0, f = 0; else i0 = num / den, f = ((num - i0 * den) * 256) / den;
+ *                  then i0 = min(i0, n_in - 1), i1 = min(i0 + 1, n_in - 1)
+ *     interpolate  v = ((q[y0][x0] * (256 - fx) + q[y0][x1] * fx) * (256 - fy)
+ *                       + (q[y1][x0] * (256 - fx) + q[y1][x1] * fx) * fy + 32768) >> 16               (0 .. 255)
+ *     blend        w = (v * strength + 127) / 255;
+ *                  out[j][Y][X][c] = (img[Y][X][c] * (255 - w) + lut[v][c] * w + 127) / 255         for c < 3
+ *   maps     fp32 [n][H][W];   image_of   int32 [n], clamped into [0, n_images): no byte outside the images is read
+ *   images   uint8 [n_images][Hi][Wi][3], image i at images + i * image_stride bytes (image_stride >= 3 * Hi * Wi)
+ *   lut      uint8 [256][3];   out   uint8 [n][Hi][Wi][3], any alignment
+ *   Limits (PNMN_EINVAL beyond them or with a null pointer; nothing is launched): 1 <= H, W <= PNMN_ATTENTION_MAX_MAP,
+ *   1 <= Hi, Wi <= PNMN_ATTENTION_MAX_IMAGE, 0 <= strength <= 255, n_images >= 1, n >= 0.  n == 0 returns 0 without a launch.
+ *   Items that share an image are best handed over next to each other: the image is then read from HBM once.
+ * ------------------------------------------------------------------------------------------- */
+#define PNMN_ATTENTION_MAX_MAP   64
+#define PNMN_ATTENTION_MAX_IMAGE 16384
+int pnmn_attention_gather(const float* act, const int64_t* offsets /* DEVICE [n] */, float* out /* [n][HW] */, int n, int HW, void* stream);
+int pnmn_attention_overlay(const float* maps /* [n][H][W] */, const int32_t* image_of /* DEVICE [n] */, const uint8_t* images,
+                           int64_t image_stride, int n_images, int Hi, int Wi, const uint8_t* lut /* DEVICE [256][3] */,
+                           int strength /* 0..255 */, uint8_t* out /* [n][Hi][Wi][3] */, int n, int H, int W, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Several LSTM-layer passes in ONE launch; the two layers of an encoder as a wavefront (csrc/lstm_stack.hip).

@@ -50,12 +50,14 @@ struct Template {
     int n_prims = 0, depth = 0;
     int64_t size = 0;            // arena floats per example (values + backward scratch)
     bool result_is_feat = false;
+    std::vector<int64_t> map_off;  // per call: block offset of its one-channel output map, -1 when wide or not executed
 };
 
 struct Program {
     bool valid = false;
     int tid = -1;
     std::vector<int64_t> tokens;  // token of every call
+    std::vector<int32_t> positions;  // position in the token row of every call (calls run right to left over the row)
     uint64_t reach[4] = {0, 0, 0, 0};  // tokens of the calls the result depends on (the template's primitives)
 };
 
@@ -94,6 +96,7 @@ Template build_template(const std::vector<Call>& calls, int result, int hw, int 
     loc[FEAT] = Loc{L_FEAT, 0};
     loc[ONES] = Loc{L_ONES, 0};
     Template t;
+    t.map_off.assign(n, -1);
     auto prim = [&](int kind, int level, int call, int widx, int dil, Loc a, Loc b, Loc out, int a_ch, int b_ch, int is_max,
                     int masked, int pa, int pb) {
         const int64_t row[NCOLS] = {kind, level, call, widx, dil, a.kind, a.off, b.kind, b.off, out.kind, out.off,
@@ -110,8 +113,10 @@ Template build_template(const std::vector<Call>& calls, int result, int hw, int 
         Loc out;
         if (c.out_ch == channels)
             out = is_result ? Loc{L_FINAL, 0} : Loc{L_SLOT, alloc(big)};
-        else
+        else {
             out = Loc{L_SLOT, alloc(small)};
+            t.map_off[ci] = out.off;
+        }
         int level, last;
         if (c.kind == AND || c.kind == OR) {
             level = std::max(lvl[c.a], lvl[c.b]) + 1;
@@ -191,6 +196,8 @@ struct Planner {
     std::vector<pnmn_launch> fwd;
     // per-call scratch kept between calls
     std::vector<int64_t> tids, examples, base, tokens;
+    std::vector<int> ids;  // program of every row of the last batch; last_length < 0: no planned batch to ask about
+    int last_length = -1;
     std::vector<int32_t> cuts;
     std::vector<int32_t> n_calls, result, calls;
     std::vector<uint8_t> cvalid;
@@ -245,6 +252,10 @@ int compile_new(Planner& P, const int64_t* rows, int length, const std::vector<i
                 const int32_t s[6] = {c[k * 7 + 0], c[k * 7 + 2], c[k * 7 + 3], c[k * 7 + 4], c[k * 7 + 5], c[k * 7 + 6]};
                 skey.append(reinterpret_cast<const char*>(s), sizeof(s));
             }
+            // the k-th token from the right that is a module (neither skipped nor `scene`) is call k (host_compile.hip)
+            const int64_t* row = rows + (size_t)which[j] * length;
+            for (int t = length - 1; t >= 0; --t)
+                if (P.kinds[row[t]] != SKIP && P.kinds[row[t]] != SCENE) prog.positions.push_back(t);
             const int32_t res = P.result[j];
             skey.append(reinterpret_cast<const char*>(&res), sizeof(res));
             auto th = P.template_ids.find(skey);
@@ -380,6 +391,24 @@ int64_t pnmn_trunk_last_records_bytes(void* planner, uint64_t* out, int64_t capa
     return n * 8;
 }
 
+int64_t pnmn_trunk_last_attention(void* planner, int64_t* offsets, int64_t capacity) {
+    Planner* P = static_cast<Planner*>(planner);
+    if (!P) return PNMN_EINVAL;
+    const int64_t length = std::max(P->last_length, 0), B = P->last_length < 0 ? 0 : (int64_t)P->ids.size();
+    const int64_t n = B * length;
+    if (capacity < n || (n > 0 && !offsets)) return PNMN_EINVAL;
+    if (n == 0) return 0;
+    std::fill(offsets, offsets + n, (int64_t)-1);
+    for (size_t v = 0; v < P->examples.size(); ++v) {  // the valid rows: those with an arena block
+        const int64_t i = P->examples[v];
+        const Program& pr = P->programs[P->ids[i]];
+        const Template& t = P->templates[pr.tid];
+        for (size_t k = 0; k < pr.positions.size(); ++k)
+            if (t.map_off[k] >= 0) offsets[i * length + pr.positions[k]] = P->base[v] + t.map_off[k];
+    }
+    return n;
+}
+
 int pnmn_trunk_plan_and_launch(void* planner, pnmn_trunk_io* io, void* stream_) {
     Planner* Pp = static_cast<Planner*>(planner);
     if (!Pp || !io || io->n_programs < 0 || io->length < 0 || (io->n_programs > 0 && (!io->programs || !io->valid)))
@@ -393,7 +422,9 @@ int pnmn_trunk_plan_and_launch(void* planner, pnmn_trunk_io* io, void* stream_) 
     const int64_t map_bytes = (int64_t)HW * C * 4;
 
     // ---- compile (cache by token row) ---------------------------------------------------------------------------
-    std::vector<int> ids(B, -1);
+    std::vector<int>& ids = P.ids;
+    ids.assign(B, -1);
+    P.last_length = -1;
     P.miss.clear();
     for (int i = 0; i < B; ++i) {
         const std::string key(reinterpret_cast<const char*>(io->programs + (size_t)i * length), sizeof(int64_t) * length);
@@ -588,6 +619,7 @@ int pnmn_trunk_plan_and_launch(void* planner, pnmn_trunk_io* io, void* stream_) 
         if (io->n_bwd > io->bwd_capacity || (io->n_bwd > 0 && !io->bwd)) return PNMN_EINVAL;
         std::copy(bwd.begin(), bwd.end(), io->bwd);
     }
+    P.last_length = length;
     if (on_device && !P.fwd.empty()) return pnmn_run_launches(P.fwd.data(), (int)P.fwd.size(), stream_);
     return 0;
 }

@@ -10,12 +10,15 @@ Stand-alone layout only (when the models are grafted onto the reference's packag
     answers on those; accuracy = #(prediction == answer) / N (an invalid program predicts @@UNKNOWN@@);
   * inference samples programs (``program_generator(question)`` with the default strategy, in eval mode)
     and lets the NMN answer without gold answers; with ``beam_size`` it beam-searches them instead (not in the
-    reference) and can prefer the best-ranked hypothesis that is a valid program.
+    reference) and can prefer the best-ranked hypothesis that is a valid program;
+  * ``explain`` (not in the reference either) adds to each answer where its program looked: the attention map of every
+    step, and that map painted over the question's image (``attention_overlay``).
 Batches are dicts of DEVICE tensors with the reference's keys (a ``PrefetchingLoader`` yields them)."""
 from typing import Any, Callable, Dict, Iterable, List, Optional
 
 import torch
 
+from probnmn import _hip
 from probnmn.modules.seq2seq_base import sampling_filter
 
 
@@ -122,11 +125,70 @@ def evaluate_answer_accuracy(program_generator, nmn, batches: Iterable[Dict[str,
     return answering_evaluator(program_generator, nmn).evaluate(batches, num_batches)
 
 
+def default_colormap() -> torch.Tensor:
+    """uint8 [256, 3], the ramp ``attention_overlay`` colours a map through when none is given -- black, red, yellow, white,
+    one channel after the other: entry v is (min(3v, 255), min(max(3v - 255, 0), 255), min(max(3v - 510, 0), 255))."""
+    v = 3 * torch.arange(256)
+    return torch.stack([(v - 255 * c).clamp(0, 255) for c in range(3)], dim=1).to(torch.uint8)
+
+
+_COLORMAPS: Dict[Any, torch.Tensor] = {}  # the default ramp, once per device
+
+
+@torch.no_grad()
+def attention_overlay(attention: torch.Tensor, attention_mask: torch.Tensor, pixels: torch.Tensor, strength: int = 160,
+                      colormap: Optional[torch.Tensor] = None):
+    """The attention maps of ``NeuralModuleNetwork.forward(..., return_attention=True)`` painted over the images the
+    questions were asked about, on the device (``pnmn_attention_overlay``, one launch): returns (overlays uint8
+    [M, Hi, Wi, 3], index int64 [M, 2]) for the M true entries of ``attention_mask`` in row-major order, ``index[m]`` =
+    (question, token position) of overlay m.
+
+    ``attention`` fp32 [B, T, H, W], ``attention_mask`` bool [B, T], ``pixels`` uint8 [B, Hi, Wi, 3], all on the device.
+    Each map is clamped to [0, 1], resized to the image (bilinear, half-pixel centres, 8-bit weights), coloured through
+    ``colormap`` (uint8 [256, 3]; default ``default_colormap()``) and blended over the image with weight
+    value * ``strength`` / 255**2 (``strength`` 0 .. 255: 0 leaves the image, 255 shows the pure colour where a map is 1).
+    The arithmetic is integer and stated in include/probnmn_hip.h.  Reading M costs one device -> host synchronisation."""
+    if attention.dim() != 4 or attention.dtype != torch.float32 or attention_mask.shape != attention.shape[:2] \
+            or attention_mask.dtype != torch.bool:
+        raise ValueError("attention fp32 [B, T, H, W] and attention_mask bool [B, T]; got %s %s and %s %s"
+                         % (attention.dtype, tuple(attention.shape), attention_mask.dtype, tuple(attention_mask.shape)))
+    if pixels.dim() != 4 or pixels.dtype != torch.uint8 or pixels.size(0) != attention.size(0) or pixels.size(3) != 3:
+        raise ValueError("pixels uint8 [%d, Hi, Wi, 3]; got %s %s" % (attention.size(0), pixels.dtype, tuple(pixels.shape)))
+    if not 0 <= int(strength) <= 255:
+        raise ValueError("strength %r is not in 0 .. 255" % (strength,))
+    dev = attention.device
+    if dev.type != "cuda" or attention_mask.device != dev or pixels.device != dev:
+        raise _hip.HipLibraryError("attention_overlay runs on the ROCm device the maps are on (got %s, %s, %s); there is no "
+                                   "CPU path" % (dev, attention_mask.device, pixels.device))
+    if colormap is None:
+        colormap = _COLORMAPS.get(dev)
+        if colormap is None:
+            colormap = _COLORMAPS[dev] = default_colormap().to(dev)
+    elif tuple(colormap.shape) != (256, 3) or colormap.dtype != torch.uint8:
+        raise ValueError("colormap uint8 [256, 3]; got %s %s" % (colormap.dtype, tuple(colormap.shape)))
+    colormap = colormap.to(dev).contiguous()
+    B, T, H, W = attention.shape
+    Hi, Wi = pixels.shape[1:3]
+    if pixels.stride()[1:] != (Wi * 3, 3, 1) or (B > 1 and pixels.stride(0) < Hi * Wi * 3):
+        pixels = pixels.contiguous()
+    index = attention_mask.nonzero()  # row-major: the maps of a question are neighbours, so its image is read from HBM once
+    M = index.size(0)
+    out = torch.empty(M, Hi, Wi, 3, dtype=torch.uint8, device=dev)
+    if M:
+        maps = attention[attention_mask].contiguous()
+        image_of = index[:, 0].to(torch.int32).contiguous()
+        _hip.check(_hip.lib().pnmn_attention_overlay(
+            maps.data_ptr(), image_of.data_ptr(), pixels.data_ptr(), pixels.stride(0) if B > 1 else Hi * Wi * 3, B, Hi, Wi,
+            colormap.data_ptr(), int(strength), out.data_ptr(), M, H, W, _hip.stream_ptr(dev)), "attention_overlay")
+    return out, index
+
+
 @torch.no_grad()
 def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary,
                     beam_size: Optional[int] = None, prefer_valid: bool = True,
                     constrained: bool = False, extractor=None, temperature: float = 1.0, top_k: int = 0,
-                    top_p: float = 1.0, constrained_sampling: bool = False) -> List[Dict[str, Any]]:
+                    top_p: float = 1.0, constrained_sampling: bool = False, explain: bool = False,
+                    overlay_strength: int = 160, colormap: Optional[torch.Tensor] = None) -> List[Dict[str, Any]]:
     """scripts/inference.py:76-91: sampled programs -> NMN -> answer strings, one record per question
     (``question_index`` from the batch when present, else a running index).
 
@@ -154,7 +216,15 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
     and ``top_p`` apply), on the multi-CU decoder kernels the plain sampled decode runs on, so no question is answered
     ``@@UNKNOWN@@`` for want of a valid program.  Each record also names its ``"program"`` and whether it is a
     ``"program_valid"`` one (decided on the host, as for the beams: always true).  Together with ``beam_size`` it is a
-    ``ValueError``."""
+    ``ValueError``.
+
+    ``explain``: each record also names its ``"program"`` (with every decoding option) and its ``"steps"``: one entry per
+    module call of the program the NMN ran that wrote a one-channel attention map (``NMNEngine.attention_maps``), in
+    execution order -- right to left over the program -- as ``{"position": token position, "token": its string,
+    "attention": float32 numpy [H, W]}``.  When the batch has ``"pixels"`` an entry also has ``"overlay"``: uint8 numpy
+    [Hi, Wi, 3], the map painted over the question's image (``attention_overlay`` with ``overlay_strength`` and
+    ``colormap``).  An invalid program has no steps.  The answers are those of ``explain=False``: the maps are copied out
+    of the activations the pass leaves behind."""
     if constrained and beam_size is None:
         raise ValueError("constrained=True constrains the beam search: give a beam_size")
     if constrained_sampling and beam_size is not None:
@@ -232,7 +302,17 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
             elif constrained_sampling:
                 host = programs.cpu()
                 extra = (host.tolist(), None, [c.valid for c in nmn.engine.compiler.compile_batch(host.numpy())])
-            answers = nmn(image, programs)["predictions"].cpu().tolist()
+            out = nmn(image, programs, return_attention=True) if explain else nmn(image, programs)
+            answers = out["predictions"].cpu().tolist()
+            if explain:
+                rows = extra[0] if extra is not None else programs.cpu().tolist()
+                mask = out["attention_mask"].cpu().numpy()
+                maps = out["attention"].cpu().numpy()
+                overlays, where = None, {}
+                if "pixels" in batch:
+                    overlays, at = attention_overlay(out["attention"], out["attention_mask"], batch["pixels"], overlay_strength, colormap)
+                    overlays = overlays.cpu().numpy()
+                    where = {(int(i), int(p)): m for m, (i, p) in enumerate(at.cpu().tolist())}
             index = batch["question_index"].cpu().tolist() if "question_index" in batch else range(len(records), len(records) + len(answers))
             for i, (qi, a) in enumerate(zip(index, answers)):
                 record = {"question_index": int(qi), "answer": vocabulary.get_token_from_index(int(a), namespace="answers")}
@@ -241,6 +321,15 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
                     if extra[1] is not None:
                         record["beam_rank"] = int(extra[1][i])
                     record["program_valid"] = bool(extra[2][i])
+                if explain:
+                    tokens = [vocabulary.get_token_from_index(int(t), namespace="programs") for t in rows[i]]
+                    record.setdefault("program", [tok for tok, t in zip(tokens, rows[i]) if t != pad])
+                    record["steps"] = []
+                    for p in reversed(mask[i].nonzero()[0].tolist()):  # execution order: right to left
+                        step = {"position": p, "token": tokens[p], "attention": maps[i, p]}
+                        if overlays is not None:
+                            step["overlay"] = overlays[where[(i, p)]]
+                        record["steps"].append(step)
                 records.append(record)
 
         pending = None

@@ -34,10 +34,11 @@ class _Tokens:
     """A batch of programs as the host token matrix, on its way through the library's trunk planner
     (``NMNEngine.run_forward_tokens``); ``valid`` is filled in by the forward pass."""
 
-    __slots__ = ("tokens", "valid")
+    __slots__ = ("tokens", "valid", "attention")
 
     def __init__(self, tokens):
         self.tokens, self.valid = tokens, None
+        self.attention = None  # (maps, mask) when the caller asked for them (``return_attention``)
 
 
 class _Trunk(torch.autograd.Function):
@@ -319,17 +320,19 @@ class NeuralModuleNetwork(nn.Module):
         return self._engine
 
     def forward(self, features: torch.Tensor, programs: torch.Tensor, answers: Optional[torch.Tensor] = None,
-                started=None, trunk_stream=None, rows: Optional[torch.Tensor] = None):
+                started=None, trunk_stream=None, rows: Optional[torch.Tensor] = None, return_attention: bool = False):
         # ``started``: token of ``begin(features)`` when the caller already launched the stem (optional)
         # ``rows``: run on ``features[rows]`` (programs / answers belong to those examples) without the gathered copy
         # ``trunk_stream``: run the trunk (stem, module programs, classifier conv + pool -- this build's own
         # kernels, none of which waits for another workgroup) on that stream, forward and backward, beside
         # whatever the caller queues on the current stream; the fully connected layers and the loss stay on
         # the current stream (see DESIGN 6 for why the library GEMMs must not leave it)
-        return self.forward_head(self.forward_trunk(features, programs, started, trunk_stream, rows), answers)
+        # ``return_attention``: the output dict gains "attention" [B, T, H, W] -- the one-channel map each program token's
+        # module wrote, zeros where there is none -- and "attention_mask" [B, T] (``NMNEngine.attention_maps``); detached
+        return self.forward_head(self.forward_trunk(features, programs, started, trunk_stream, rows, return_attention), answers)
 
     def forward_trunk(self, features: torch.Tensor, programs: torch.Tensor, started=None, trunk_stream=None,
-                      rows: Optional[torch.Tensor] = None):
+                      rows: Optional[torch.Tensor] = None, return_attention: bool = False):
         """First half of ``forward``: compile and schedule the programs, launch the trunk (on ``trunk_stream`` when
         given).  Nothing is queued on the current stream, so a caller that runs the trunk on its own stream can
         keep feeding the current one before ``forward_head`` makes it wait for the trunk."""
@@ -353,8 +356,12 @@ class NeuralModuleNetwork(nn.Module):
         if trunk_stream is not None:
             with torch.cuda.stream(trunk_stream):
                 pooled = _Trunk.apply(features, engine, compiled, started, *params)
+                if return_attention:  # (queued right behind the trunk, on its stream)
+                    compiled.attention = engine.attention_maps(tokens.shape[1])
         else:
             pooled = _Trunk.apply(features, engine, compiled, started, *params)
+            if return_attention:
+                compiled.attention = engine.attention_maps(tokens.shape[1])
         return pooled, compiled, trunk_stream
 
     def forward_head(self, trunk, answers: Optional[torch.Tensor] = None):
@@ -371,6 +378,8 @@ class NeuralModuleNetwork(nn.Module):
             current = torch.cuda.current_stream(pooled.device)
             current.wait_stream(trunk_stream)
             pooled.record_stream(current)
+            for t in compiled.attention or ():
+                t.record_stream(current)
         hidden = F.relu(_first_fc(self.classifier[4], pooled))
         answer_logits = self.classifier[6](hidden)
         _hip.mark("classifier FC forward done")
@@ -388,6 +397,8 @@ class NeuralModuleNetwork(nn.Module):
             self._average_invalid_programs(sum(1 for v in valid_host if not v))
 
         output_dict = {"predictions": answer_predictions, "loss": loss}
+        if compiled.attention is not None:
+            output_dict["attention"], output_dict["attention_mask"] = compiled.attention
         if self.training and self.report_batch_metrics:
             output_dict["metrics"] = self.get_metrics(reset=True)
         return output_dict

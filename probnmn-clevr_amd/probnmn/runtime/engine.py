@@ -123,6 +123,7 @@ class NMNEngine:
         self.wgrad_cus = 0  # the same for the weight-gradient launches: at most that many (persistent) workgroups
         self._planner = None
         self._native_fixed: Dict[tuple, dict] = {}
+        self._trunk_pass = None  # (generation, stream, B, length) of the last module-program launch: attention_maps
 
     def _conv(self, ptr, n, cin_chunks, ntaps, in_stride, out_stride, cout_blocks, relu):
         self._list.add(_hip.OP_CONV, n, ptr, c=self.conv_cus,
@@ -599,6 +600,7 @@ class NMNEngine:
         valid = self._planner_valid[:B].copy()
         self.last_plan = _NativePlan(int(out["n_prims"]), int(out["arena_floats"]), int(out["n_fwd"]), int(out["n_bwd"]))
         self.last_counts = (int(out["n_conv"]), int(out["n_proj"]))
+        self._trunk_pass = (self.generation, st, B, programs.shape[1])
         state = None
         if need_backward:
             state = _State()
@@ -610,6 +612,42 @@ class NMNEngine:
             n = int(out["n_bwd"])
             state.backward_rows = (self._planner_bwd[:n].copy(), int(out["bwd_piece_cut"]), rows["dpooled_row"])
         return pooled, state, valid
+
+    def attention_maps(self, length: int) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Where the programs of the last ``run_forward_tokens`` looked: (maps fp32 [B, length, H, W], mask bool [B, length]),
+        on the device.  ``maps[i, p]`` is the one-channel output of the module call of token position ``p`` of program ``i``
+        (``filter_*``, ``relate``, ``same_*``, and ``intersect`` / ``union`` of two such maps), as the next module read it;
+        ``mask`` is false -- and the map all zeros -- where there is none: an invalid program, a skipped token or ``scene``,
+        a call with a ``module_channels`` wide output (``query_*``, comparisons), a call the result does not depend on.
+
+        Every executed call has its own slot in the activation arena, so the maps are there until this engine's next
+        forward pass; asked later (or before any pass) this raises ``RuntimeError``.  The planner names the slots
+        (``pnmn_trunk_last_attention``), one small upload carries them and ``pnmn_attention_gather`` copies the maps out, on
+        the stream the trunk ran on: a caller on another stream waits for that stream before reading, as for ``pooled``."""
+        if self._trunk_pass is None or self._trunk_pass[0] != self.generation or not self._planner:
+            raise RuntimeError("attention_maps: no forward pass of this engine to read (the maps of a pass are kept until "
+                               "the next begin_forward)")
+        _, st, B, planned_length = self._trunk_pass
+        if length != planned_length:
+            raise ValueError("attention_maps: the programs of the last pass have %d tokens, not %d" % (planned_length, length))
+        dev = self.arena.device
+        if st != _hip.stream_ptr(dev):
+            with torch.cuda.stream(torch.cuda.ExternalStream(st, device=dev) if st else torch.cuda.default_stream(dev)):
+                return self.attention_maps(length)
+        offsets = np.empty(B * length, np.int64)
+        n = int(_hip.lib().pnmn_trunk_last_attention(self._planner, offsets.ctypes.data, offsets.size))
+        if n != offsets.size:
+            raise _hip.HipLibraryError("pnmn_trunk_last_attention returned %d for %d x %d programs" % (n, B, length))
+        maps = torch.empty(B, length, self.H, self.W, dtype=torch.float32, device=dev)
+        if n == 0:
+            return maps, torch.zeros(B, length, dtype=torch.bool, device=dev)
+        act = self._ws["act"]
+        if int(offsets.max()) + self.HW > act.numel():
+            raise _hip.HipLibraryError("pnmn_trunk_last_attention: a map lies beyond the activation arena")
+        offsets_dev = _hip.to_device(offsets, dev).view(torch.int64)
+        _hip.check(_hip.lib().pnmn_attention_gather(act.data_ptr(), offsets_dev.data_ptr(), maps.data_ptr(), n, self.HW, st),
+                   "attention_gather")
+        return maps, (offsets_dev >= 0).view(B, length)
 
     def _touched_from_tokens(self, words, any_valid: bool) -> np.ndarray:
         """``_touched_by`` from what the library's planner reports of the batch it just compiled (pnmn_trunk_io.touched_tokens:
