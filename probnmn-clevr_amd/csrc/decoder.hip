@@ -30,7 +30,7 @@
 #include "lds_optin.h"
 #include "sampling.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using pnmn::f32x4;
 
 namespace {
 
@@ -338,14 +338,8 @@ __global__ __launch_bounds__(512) void attn_lstm_bwd_kernel(const BwdArgs a) {
                 const size_t fo = ((size_t)((2 * wave + ut) * (G4 / 16) + kb) * 64 + lane) * 4;
                 const f32x4 bc = *reinterpret_cast<const f32x4*>(a.w_c_t + fo);
                 const f32x4 bh = *reinterpret_cast<const f32x4*>(a.w_hh_t + fo);
-                accc[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, bc.x, accc[ut], 0, 0, 0);
-                accc[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, bc.y, accc[ut], 0, 0, 0);
-                accc[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, bc.z, accc[ut], 0, 0, 0);
-                accc[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, bc.w, accc[ut], 0, 0, 0);
-                acch[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.x, bh.x, acch[ut], 0, 0, 0);
-                acch[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.y, bh.y, acch[ut], 0, 0, 0);
-                acch[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.z, bh.z, acch[ut], 0, 0, 0);
-                acch[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(av.w, bh.w, acch[ut], 0, 0, 0);
+                accc[ut] = pnmn::mfma4(av, bc, accc[ut]);
+                acch[ut] = pnmn::mfma4(av, bh, acch[ut]);
             }
         }
 #pragma unroll

@@ -34,7 +34,7 @@
 #include "decoder_stages.h"
 #include "sampling.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using pnmn::f32x4;
 
 namespace {
 

@@ -29,9 +29,10 @@
 #include "../../include/probnmn_hip.h"
 #include "cluster.h"
 #include "lds_optin.h"
+#include "recurrent_tile.h"
 #include "sampling.h"
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using pnmn::f32x4;
 
 namespace {
 
@@ -662,12 +663,7 @@ __device__ __forceinline__ void attn_lstm_bwd_multi_body(const MBwdArgs& a, cons
         for (int kl = kl0; kl < kl0 + 2; ++kl) {
             const f32x4 av = dg_frag(kl);
 #pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[nt][kl].x, av.x, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[nt][kl].y, av.y, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[nt][kl].z, av.z, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[nt][kl].w, av.w, acc[nt], 0, 0, 0);
-            }
+            for (int nt = 0; nt < 2; ++nt) acc[nt] = pnmn::mfma4(w[nt][kl], av, acc[nt]);
         }
     };
 

@@ -11,17 +11,17 @@
 
 namespace {
 
-__device__ __forceinline__ float wave_max(float v) { return pnmn::wmax(v); }  // (DPP reductions, sampling.h)
-__device__ __forceinline__ float wave_sum(float v) { return pnmn::wsum(v); }
+using pnmn::wmax;  // (DPP reductions, sampling.h)
+using pnmn::wsum;
 
 // log-sum-exp of one row of V logits, computed by one wave (every lane gets the result)
 __device__ __forceinline__ float row_lse(const float* __restrict__ z, int V, int lane) {
     float m = -INFINITY;
     for (int k = lane; k < V; k += 64) m = fmaxf(m, z[k]);
-    m = wave_max(m);
+    m = wmax(m);
     float s = 0.f;
     for (int k = lane; k < V; k += 64) s += expf(z[k] - m);
-    return m + logf(wave_sum(s));
+    return m + logf(wsum(s));
 }
 
 // one workgroup (4 waves) per sequence; wave w takes steps w, w+4, ...
@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void seq_nll_bwd_kernel(const float* __restric
     if (wave == 0) {
         float d = 0.f;
         for (int t = lane; t < T; t += 64) d += mask_tokens[(size_t)b * mask_bstride + t] != pad ? 1.f : 0.f;
-        d = wave_sum(d);
+        d = wsum(d);
         if (lane == 0) den_s = d;
     }
     __syncthreads();
@@ -113,7 +113,7 @@ __global__ __launch_bounds__(256) void elbo_rows_kernel(const float* __restrict_
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
-        const float s = wave_sum(acc[k]);
+        const float s = wsum(acc[k]);
         if (lane == 0) red[k][wave] = s;
     }
     __syncthreads();
@@ -164,7 +164,7 @@ __global__ __launch_bounds__(256) void joint_objective_kernel(
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-        const float s = wave_sum(acc[k]);
+        const float s = wsum(acc[k]);
         if (lane == 0) red[k][wave] = s;
     }
     __syncthreads();

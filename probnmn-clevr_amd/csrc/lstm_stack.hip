@@ -29,14 +29,16 @@
 #include "cluster.h"
 #include "dropout.h"
 #include "lds_optin.h"
+#include "recurrent_tile.h"
 
 namespace {
 
-typedef float f32x4_ __attribute__((ext_vector_type(4)));
-constexpr int LH = 256, LROWS = 16, S = 8, UW = LH / S;  // eight members per tile, 32 hidden units each
+using pnmn::f32x4;
+using pnmn::mfma4;
+using pnmn::sigm;
+constexpr int LH = pnmn::TILE_H, LROWS = pnmn::TILE_ROWS, S = 8, UW = LH / S;  // eight members per tile, 32 hidden units each
+constexpr int HLD = pnmn::TILE_LD;
 constexpr int MAXJ = PNMN_LSTM_STACK_JOBS;
-
-__device__ __forceinline__ float sigm(float z) { return 1.f / (1.f + expf(-z)); }
 
 struct Jobs {
     pnmn_lstm_stack_job j[MAXJ];
@@ -59,9 +61,10 @@ struct Drop {
 };
 
 // ---- hand-offs ----------------------------------------------------------------------------------------------------------
-// line of a virtual tile (64 ints): [0] own arrivals  [1] started << 16 | XCC bits (unlinked jobs)  [2] finished
-//                                   [3] cross arrivals: the producer's members count here (consumer's line)
-//                                   [4] started << 16 | XCC bits of a LINKED pair (consumer's line, 2 S members)
+// What a virtual tile adds to the hand-off of cluster.h (the line's five words are laid out there): a producer's members
+// also count in their consumer's cross word [3], and a LINKED pair votes as one group of 2 S members in the consumer's
+// word [4] (zeroed by the consumer's last member: it outlives the producer by the dependency); an unlinked job votes in
+// its own word [1] like a Cluster.
 struct Sync {
     int* line;        // this tile's line
     int* cross_out;   // consumer tile's word [3] (producer side) or nullptr
@@ -74,96 +77,26 @@ struct Sync {
         cross_out = consumer_line ? consumer_line + 3 : nullptr;
         cross_in = has_dep ? mine + 3 : nullptr;
         own = cross = 0;
-        __shared__ int decided;
-        if (threadIdx.x == 0) {
-            // a linked pair publishes into the consumer's word [4] (zeroed by the consumer's last member: it outlives
-            // the producer by the dependency), an unlinked job into its own word [1]
-            int* word = consumer_line ? consumer_line + 4 : (has_dep ? mine + 4 : mine + 1);
-            const int expect = (consumer_line || has_dep) ? 2 * S : S;
-            const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 15u;  // HW_REG_XCC_ID[3:0]
-            __hip_atomic_fetch_or(word, 1 << xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_add(word, 1 << 16, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            int spins = 0, w;
-            while (((w = __hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) >> 16) < expect) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1 << 26)) __builtin_trap();
-            }
-            decided = __builtin_popcount(w & 0xFFFF) == 1;  // (the value that showed the full count carries every bit)
-        }
-        __syncthreads();
-        fast = decided != 0;
-    }
-
-    __device__ __forceinline__ void publish(int* word) {
-        if (fast)
-            __hip_atomic_fetch_add(word, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (consumer_line || has_dep)
+            fast = pnmn::handoff::vote((consumer_line ? consumer_line : mine) + 4, 2 * S);
         else
-            __hip_atomic_fetch_add(word, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            fast = pnmn::handoff::vote(mine + 1, S);
     }
 
     // this step's stores are out: tell the partners (`to_own`) and / or the consumer job
     __device__ __forceinline__ void signal(bool to_own) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
+        pnmn::handoff::stores_out();
         if (threadIdx.x == 0) {
-            if (to_own) publish(line);
-            if (cross_out) publish(cross_out);
+            if (to_own) pnmn::handoff::publish(line, fast);
+            if (cross_out) pnmn::handoff::publish(cross_out, fast);
         }
     }
 
-    __device__ __forceinline__ void spin(int* word, int target) {
-        if (threadIdx.x == 0) {
-            int spins = 0;
-            while (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                __builtin_amdgcn_s_sleep(1);
-                if (++spins > (1 << 26)) __builtin_trap();
-            }
-            if (fast)
-                asm volatile("buffer_inv sc0\n\ts_waitcnt vmcnt(0)" ::: "memory");
-            else
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        }
-        __syncthreads();
-    }
-    __device__ __forceinline__ void wait_own() { spin(line, S * ++own); }
-    __device__ __forceinline__ void wait_cross() { spin(cross_in, S * ++cross); }
+    __device__ __forceinline__ void wait_own() { pnmn::handoff::await(line, S * ++own, fast); }
+    __device__ __forceinline__ void wait_cross() { pnmn::handoff::await(cross_in, S * ++cross, fast); }
 
-    __device__ __forceinline__ void finish() {
-        if (threadIdx.x == 0) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            const int before = __hip_atomic_fetch_add(line + 2, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (before == S - 1)
-                for (int k = 0; k < 5; ++k) __hip_atomic_store(line + k, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    __device__ __forceinline__ void finish() { pnmn::handoff::finish(line, S, 5); }
 };
-
-__device__ __forceinline__ f32x4_ mfma4(const f32x4_ a, const f32x4_ b, f32x4_ acc) {
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc, 0, 0, 0);
-    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc, 0, 0, 0);
-    return acc;
-}
-
-// the tile's 16 x 256 vector of step `t` of a [B][T][256] tensor into LDS (two 16-byte pieces per thread, both requested
-// before the first store: see lstm_seq_fwd_cluster_kernel)
-constexpr int HLD = LH + 4;
-__device__ __forceinline__ void stage_rows(const float* src, int row0, int B, int T, int t, float (*hl)[HLD]) {
-    const int tid = threadIdx.x;
-    f32x4_ piece[2];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int i = tid + 512 * k, rl = i / (LH / 4), c4 = i % (LH / 4);
-        const int row = min(row0 + rl, B - 1);
-        piece[k] = *reinterpret_cast<const f32x4_*>(src + ((size_t)row * T + t) * LH + 4 * c4);
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) {
-        const int i = tid + 512 * k, rl = i / (LH / 4), c4 = i % (LH / 4);
-        *reinterpret_cast<f32x4_*>(&hl[rl][4 * c4]) = piece[k];
-    }
-}
 
 // =========================================================================================================================
 // forward
@@ -174,8 +107,8 @@ __global__ __launch_bounds__(512) void lstm_stack_fwd_kernel(const Jobs jobs, in
     __shared__ float gl[4][LROWS][GLD];
     __shared__ __attribute__((aligned(16))) float hl[LROWS][HLD];   // h_{t-1} of this layer
     __shared__ __attribute__((aligned(16))) float xl[LROWS][HLD];   // SECOND: h_t of the layer below
-    const int slot = blockIdx.x >> 3;
-    const int vtile = (blockIdx.x & 7) + 8 * (slot / S), part = slot % S;
+    int vtile, part;
+    pnmn::cluster_coords<S>(vtile, part);
     int ji = 0;
     while (ji + 1 < jobs.n && vtile >= jobs.base[ji + 1]) ++ji;
     const pnmn_lstm_stack_job jb = jobs.j[ji];
@@ -192,12 +125,13 @@ __global__ __launch_bounds__(512) void lstm_stack_fwd_kernel(const Jobs jobs, in
              cons >= 0 ? sync + (jobs.base[cons] + tile) * pnmn::CLUSTER_COUNTER_STRIDE : nullptr, second);
 
     const int ntile = gate * (LH / 16) + u0 / 16 + ub;
-    f32x4_ whh[LH / 16], wih[LH / 16];
+    f32x4 whh[LH / 16], wih[LH / 16];
+    pnmn::load_wslice<LH / 16>(whh, jb.w_hh, ntile, LH / 16, 0, lane);
+    if (second) {
+        pnmn::load_wslice<LH / 16>(wih, jb.w_ih, ntile, LH / 16, 0, lane);
+    } else {
 #pragma unroll
-    for (int kb = 0; kb < LH / 16; ++kb) {
-        whh[kb] = *reinterpret_cast<const f32x4_*>(jb.w_hh + ((size_t)(ntile * (LH / 16) + kb) * 64 + lane) * 4);
-        wih[kb] = second ? *reinterpret_cast<const f32x4_*>(jb.w_ih + ((size_t)(ntile * (LH / 16) + kb) * 64 + lane) * 4)
-                         : f32x4_{0.f, 0.f, 0.f, 0.f};
+        for (int kb = 0; kb < LH / 16; ++kb) wih[kb] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     float creg = 0.f;  // J = UW * 16 / 512 = 1 (row, unit) pair per thread
     const float* below = second ? ((DROP && drop.on[jb.dep]) ? drop.hsd[jb.dep] : jobs.j[jb.dep].hs) : nullptr;
@@ -206,7 +140,9 @@ __global__ __launch_bounds__(512) void lstm_stack_fwd_kernel(const Jobs jobs, in
     float* const hsd = dp ? drop.hsd[ji] : nullptr;
     const float bias = second ? jb.bias[gate * LH + u0 + 16 * ub + li] : 0.f;
 
-    // FIRST: this lane's four rows of the step inputs (see lstm_seq_fwd_cluster_kernel for the token look-ahead)
+    int srow[2];  // the rows this thread stages of h_{t-1} (and, SECOND, of the layer below)
+    pnmn::stage_rows(srow, nullptr, row0, B);
+    // FIRST: this lane's four rows of the step inputs (the token look-ahead: seq2seq.hip, lstm_seq_fwd_cluster_kernel)
     const bool tok = jb.tokens != nullptr;
     int64_t xrow[4];
     const int64_t* trow[4];
@@ -218,20 +154,20 @@ __global__ __launch_bounds__(512) void lstm_stack_fwd_kernel(const Jobs jobs, in
     }
 
     // SECOND: the input product of step t, from the layer below (ahead of us by construction)
-    auto xpart = [&](int t) -> f32x4_ {
+    auto xpart = [&](int t) -> f32x4 {
         sy.wait_cross();
-        stage_rows(below, row0, B, T, t, xl);
+        pnmn::stage_step(below, srow, T, t, xl);
         __syncthreads();
-        f32x4_ acc = f32x4_{bias, bias, bias, bias};
+        f32x4 acc = f32x4{bias, bias, bias, bias};
 #pragma unroll
-        for (int kb = 0; kb < LH / 16; ++kb) acc = mfma4(*reinterpret_cast<const f32x4_*>(&xl[li][kb * 16 + 4 * g]), wih[kb], acc);
+        for (int kb = 0; kb < LH / 16; ++kb) acc = mfma4(*reinterpret_cast<const f32x4*>(&xl[li][kb * 16 + 4 * g]), wih[kb], acc);
         return acc;
     };
 
-    f32x4_ xacc = f32x4_{0.f, 0.f, 0.f, 0.f};
+    f32x4 xacc = f32x4{0.f, 0.f, 0.f, 0.f};
     if (second) xacc = xpart(0);
     for (int t = 0; t < T; ++t) {
-        f32x4_ acc;
+        f32x4 acc;
         if (second) {
             acc = xacc;
         } else {
@@ -242,11 +178,11 @@ __global__ __launch_bounds__(512) void lstm_stack_fwd_kernel(const Jobs jobs, in
         }
         if (t > 0) {
             sy.wait_own();
-            stage_rows(jb.hs, row0, B, T, t - 1, hl);
+            pnmn::stage_step(jb.hs, srow, T, t - 1, hl);
             __syncthreads();
-            f32x4_ a[LH / 16];
+            f32x4 a[LH / 16];
 #pragma unroll
-            for (int kb = 0; kb < LH / 16; ++kb) a[kb] = *reinterpret_cast<const f32x4_*>(&hl[li][kb * 16 + 4 * g]);
+            for (int kb = 0; kb < LH / 16; ++kb) a[kb] = *reinterpret_cast<const f32x4*>(&hl[li][kb * 16 + 4 * g]);
 #pragma unroll
             for (int kb = 0; kb < LH / 16; ++kb) acc = mfma4(a[kb], whh[kb], acc);
         }
@@ -299,8 +235,8 @@ __global__ __launch_bounds__(512) void lstm_stack_bwd_kernel(const Jobs jobs, in
     extern __shared__ __attribute__((aligned(16))) float dyn[];
     float (*dgx)[XLD] = reinterpret_cast<float (*)[XLD]>(dyn);                    // BELOW: dgates of the layer above, [16][1028]
     float (*red)[LROWS][UW + 1] = reinterpret_cast<float (*)[LROWS][UW + 1]>(dyn + LROWS * XLD);  // [8 waves][16][33]
-    const int slot = blockIdx.x >> 3;
-    const int vtile = (blockIdx.x & 7) + 8 * (slot / S), part = slot % S;
+    int vtile, part;
+    pnmn::cluster_coords<S>(vtile, part);
     int ji = 0;
     while (ji + 1 < jobs.n && vtile >= jobs.base[ji + 1]) ++ji;
     const pnmn_lstm_stack_job jb = jobs.j[ji];
@@ -317,23 +253,23 @@ __global__ __launch_bounds__(512) void lstm_stack_bwd_kernel(const Jobs jobs, in
     float* ptile = jobs.px[ji] + (size_t)tile * 2 * S * LROWS * LH;  // [parity][source part][16][H]
 
     // recurrence: this wave's two 16-unit output tiles x this workgroup's gate columns
-    f32x4_ wreg[2][KB];
+    f32x4 wreg[2][KB];
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-        for (int kl = 0; kl < KB; ++kl) {
-            const int q = kl / (UW / 16), jj = kl % (UW / 16);
-            const int kb = (q * LH + u0) / 16 + jj;
-            wreg[nt][kl] = *reinterpret_cast<const f32x4_*>(jb.w_hh + ((size_t)((2 * wave + nt) * (4 * LH / 16) + kb) * 64 + lane) * 4);
-        }
+        for (int q = 0; q < 4; ++q)  // gate q's columns of this member: UW / 16 k blocks from column q LH + u0
+            pnmn::load_wslice<UW / 16>(wreg[nt] + q * (UW / 16), jb.w_hh, 2 * wave + nt, 4 * LH / 16, (q * LH + u0) / 16, lane);
     // BELOW: W_ih of the layer above ([1024 gate columns] x [my 32 units]): this wave's K slice of 128 columns
-    f32x4_ wx[2][8];
+    f32x4 wx[2][8];
 #pragma unroll
-    for (int nt = 0; nt < 2; ++nt)
+    for (int nt = 0; nt < 2; ++nt) {
+        if (below) {
+            pnmn::load_wslice<8>(wx[nt], jb.w_ih, u0 / 16 + nt, 4 * LH / 16, 8 * wave, lane);
+        } else {
 #pragma unroll
-        for (int kl = 0; kl < 8; ++kl)
-            wx[nt][kl] = below ? *reinterpret_cast<const f32x4_*>(jb.w_ih + ((size_t)((u0 / 16 + nt) * (4 * LH / 16) + 8 * wave + kl) * 64 + lane) * 4)
-                               : f32x4_{0.f, 0.f, 0.f, 0.f};
+            for (int kl = 0; kl < 8; ++kl) wx[nt][kl] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    }
     const float* above = below ? jobs.j[jb.dep].dgates : nullptr;
     const int rl = tid / UW, ul = tid % UW;   // this thread's (row, unit) pair of the cell backward
     const int row = row0 + rl, u = u0 + ul;
@@ -343,24 +279,24 @@ __global__ __launch_bounds__(512) void lstm_stack_bwd_kernel(const Jobs jobs, in
     auto xpart = [&](int t) -> float {
         sy.wait_cross();
         {   // 16 x 1024 floats: eight 16-byte pieces per thread, all in flight before the first LDS store
-            f32x4_ piece[8];
+            f32x4 piece[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int i = tid + 512 * k, r = i / LH, c4 = i % LH;
                 const int rr = min(row0 + r, B - 1);
-                piece[k] = *reinterpret_cast<const f32x4_*>(above + ((size_t)rr * T + t) * (4 * LH) + 4 * c4);
+                piece[k] = *reinterpret_cast<const f32x4*>(above + ((size_t)rr * T + t) * (4 * LH) + 4 * c4);
             }
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const int i = tid + 512 * k, r = i / LH, c4 = i % LH;
-                *reinterpret_cast<f32x4_*>(&dgx[r][4 * c4]) = piece[k];
+                *reinterpret_cast<f32x4*>(&dgx[r][4 * c4]) = piece[k];
             }
         }
         __syncthreads();
-        f32x4_ acc[2] = {f32x4_{0.f, 0.f, 0.f, 0.f}, f32x4_{0.f, 0.f, 0.f, 0.f}};
+        f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int kl = 0; kl < 8; ++kl) {
-            const f32x4_ a = *reinterpret_cast<const f32x4_*>(&dgx[li][(8 * wave + kl) * 16 + 4 * g]);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(&dgx[li][(8 * wave + kl) * 16 + 4 * g]);
             acc[0] = mfma4(a, wx[0][kl], acc[0]);
             acc[1] = mfma4(a, wx[1][kl], acc[1]);
         }
@@ -425,16 +361,16 @@ __global__ __launch_bounds__(512) void lstm_stack_bwd_kernel(const Jobs jobs, in
             break;
         }
         __syncthreads();
-        f32x4_ acc[2] = {f32x4_{0.f, 0.f, 0.f, 0.f}, f32x4_{0.f, 0.f, 0.f, 0.f}};
+        f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
 #pragma unroll
         for (int kl = 0; kl < KB; ++kl) {
-            const f32x4_ a = *reinterpret_cast<const f32x4_*>(&dgl[li][kl * 16 + 4 * g]);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(&dgl[li][kl * 16 + 4 * g]);
 #pragma unroll
-            for (int nt = 0; nt < 2; ++nt) acc[nt] = mfma4(wreg[nt][kl], a, acc[nt]);  // (weights as A: see lstm_seq_bwd_cluster_kernel)
+            for (int nt = 0; nt < 2; ++nt) acc[nt] = mfma4(wreg[nt][kl], a, acc[nt]);  // (weights as A: the product comes out transposed, seq2seq.hip)
         }
         float* po = ptile + ((size_t)(t & 1) * S + part) * LROWS * LH;
 #pragma unroll
-        for (int nt = 0; nt < 2; ++nt) *reinterpret_cast<f32x4_*>(po + (size_t)li * LH + 16 * (2 * wave + nt) + 4 * g) = acc[nt];
+        for (int nt = 0; nt < 2; ++nt) *reinterpret_cast<f32x4*>(po + (size_t)li * LH + 16 * (2 * wave + nt) + 4 * g) = acc[nt];
         sy.signal(true);
         if (below) dho_next = xpart(t - 1);
     }
@@ -514,63 +450,57 @@ int drop_block(const Layout& L, const pnmn_lstm_stack_job* jobs, const pnmn_lstm
     return 0;
 }
 
-int stack_fwd(const pnmn_lstm_stack_job* jobs, const pnmn_lstm_dropout_desc* drops, int n, void* workspace, void* stream) {
-    if (n <= 0) return 0;
-    if (!jobs || !workspace) return PNMN_EINVAL;
-    const Layout L = lay_out(jobs, n);
-    if (!L.ok) return PNMN_ESHAPE;
-    for (int k = 0; k < n; ++k) {
-        const pnmn_lstm_stack_job& j = jobs[k];
-        if (!j.w_hh || !j.hs || !j.cs) return PNMN_EINVAL;
-        if (j.dep >= 0 ? (!j.w_ih || !j.bias) : !j.xp) return PNMN_EINVAL;
-    }
+// What both launches do first: the layout, the per-direction pointer check (`need`), the dropout block, the counter block.
+struct Launch {
+    Layout L;
     Drop D;
     bool any;
-    if (const int rc = drop_block(L, jobs, drops, n, false, &D, &any)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int* sync = nullptr;
-    hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
-    if (e != hipSuccess) return (int)e;
-    if (any)
-        hipLaunchKernelGGL(lstm_stack_fwd_kernel<true>, dim3(S * L.vtiles), dim3(512), 0, st, L.jobs, sync, D);
-    else
-        hipLaunchKernelGGL(lstm_stack_fwd_kernel<false>, dim3(S * L.vtiles), dim3(512), 0, st, L.jobs, sync, D);
+    int* sync;
+    hipStream_t st;
+};
+template <typename Need>
+int prepare(const pnmn_lstm_stack_job* jobs, const pnmn_lstm_dropout_desc* drops, int n, bool backward, void* workspace, void* stream,
+            Need need, Launch* P) {
+    if (!jobs || !workspace) return PNMN_EINVAL;
+    P->L = lay_out(jobs, n);
+    if (!P->L.ok) return PNMN_ESHAPE;
+    for (int k = 0; k < n; ++k)
+        if (!need(jobs[k])) return PNMN_EINVAL;
+    if (const int rc = drop_block(P->L, jobs, drops, n, backward, &P->D, &P->any)) return rc;
+    P->st = static_cast<hipStream_t>(stream);
+    P->sync = nullptr;
+    return (int)pnmn::cluster_sync_block(workspace, P->st, &P->sync);
+}
+
+int stack_fwd(const pnmn_lstm_stack_job* jobs, const pnmn_lstm_dropout_desc* drops, int n, void* workspace, void* stream) {
+    if (n <= 0) return 0;
+    Launch P;
+    const auto need = [](const pnmn_lstm_stack_job& j) {
+        return j.w_hh && j.hs && j.cs && (j.dep >= 0 ? (j.w_ih && j.bias) : j.xp != nullptr);
+    };
+    if (const int rc = prepare(jobs, drops, n, false, workspace, stream, need, &P)) return rc;
+    const auto kernel = P.any ? lstm_stack_fwd_kernel<true> : lstm_stack_fwd_kernel<false>;
+    hipLaunchKernelGGL(kernel, dim3(S * P.L.vtiles), dim3(512), 0, P.st, P.L.jobs, P.sync, P.D);
     return (int)hipGetLastError();
 }
 
 int stack_bwd(const pnmn_lstm_stack_job* jobs, const pnmn_lstm_dropout_desc* drops, int n, void* workspace, void* stream) {
     if (n <= 0) return 0;
-    if (!jobs || !workspace) return PNMN_EINVAL;
-    const Layout L = lay_out(jobs, n);
-    if (!L.ok) return PNMN_ESHAPE;
-    for (int k = 0; k < n; ++k) {
-        const pnmn_lstm_stack_job& j = jobs[k];
-        if (!j.w_hh || !j.act || !j.cs || !j.dgates) return PNMN_EINVAL;
-        if (j.dep >= 0 ? !j.w_ih : !j.dhs) return PNMN_EINVAL;
-    }
-    Drop D;
-    bool any;
-    if (const int rc = drop_block(L, jobs, drops, n, true, &D, &any)) return rc;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int* sync = nullptr;
-    hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
-    if (e != hipSuccess) return (int)e;
+    Launch P;
+    const auto need = [](const pnmn_lstm_stack_job& j) {
+        return j.w_hh && j.act && j.cs && j.dgates && (j.dep >= 0 ? j.w_ih != nullptr : j.dhs != nullptr);
+    };
+    if (const int rc = prepare(jobs, drops, n, true, workspace, stream, need, &P)) return rc;
     // exchange buffers behind the (capture-time) counter block
-    Jobs J = L.jobs;
     char* at = static_cast<char*>(workspace) + pnmn::CLUSTER_SYNC_BYTES;
     for (int k = 0; k < n; ++k) {
-        J.px[k] = reinterpret_cast<float*>(at);
+        P.L.jobs.px[k] = reinterpret_cast<float*>(at);
         at += (size_t)((jobs[k].B + LROWS - 1) / LROWS) * 2 * S * LROWS * LH * sizeof(float);
     }
-    if (any) {
-        static std::atomic<uint64_t> cfg{0};
-        if (const int rc = pnmn::opt_in_lds(reinterpret_cast<const void*>(lstm_stack_bwd_kernel<true>), BWD_DYN_LDS, cfg)) return rc;
-        hipLaunchKernelGGL(lstm_stack_bwd_kernel<true>, dim3(S * L.vtiles), dim3(512), BWD_DYN_LDS, st, J, sync, D);
-    } else {
-        static std::atomic<uint64_t> cfg{0};
-        if (const int rc = pnmn::opt_in_lds(reinterpret_cast<const void*>(lstm_stack_bwd_kernel<false>), BWD_DYN_LDS, cfg)) return rc;
-        hipLaunchKernelGGL(lstm_stack_bwd_kernel<false>, dim3(S * L.vtiles), dim3(512), BWD_DYN_LDS, st, J, sync, D);
-    }
+    static std::atomic<uint64_t> cfg[2];  // (per instantiation and device: lds_optin.h)
+    const auto kernel = P.any ? lstm_stack_bwd_kernel<true> : lstm_stack_bwd_kernel<false>;
+    if (const int rc = pnmn::opt_in_lds(reinterpret_cast<const void*>(kernel), BWD_DYN_LDS, cfg[P.any])) return rc;
+    hipLaunchKernelGGL(kernel, dim3(S * P.L.vtiles), dim3(512), BWD_DYN_LDS, P.st, P.L.jobs, P.sync, P.D);
     return (int)hipGetLastError();
 }
 

@@ -26,7 +26,7 @@
 namespace {
 
 using pnmn::sigm;
-typedef pnmn::stage_f32x4 f32x4;
+using pnmn::f32x4;
 constexpr int H = 256;          // hidden = input size the kernel is built for
 constexpr int ROWS = 16;        // batch rows per workgroup
 constexpr int LD = H + 4;       // LDS row stride (floats), as LLD of the layer kernels
@@ -130,10 +130,7 @@ __global__ __launch_bounds__(512) void prior_sample_kernel(const typename prior_
                 for (int ut = 0; ut < 2; ++ut) {
                     const size_t fo = ((size_t)((gate * (H / 16) + 2 * wave + ut) * (H / 16) + kb) * 64 + lane) * 4;
                     const f32x4 b = *reinterpret_cast<const f32x4*>(a.w_hh0 + fo);
-                    acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.x, b.x, acc[gate][ut], 0, 0, 0);
-                    acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.y, b.y, acc[gate][ut], 0, 0, 0);
-                    acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.z, b.z, acc[gate][ut], 0, 0, 0);
-                    acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.w, b.w, acc[gate][ut], 0, 0, 0);
+                    acc[gate][ut] = pnmn::mfma4(ah, b, acc[gate][ut]);
                 }
         }
         __syncthreads();  // every wave has read h0 of step t - 1
@@ -163,10 +160,7 @@ __global__ __launch_bounds__(512) void prior_sample_kernel(const typename prior_
                 for (int ut = 0; ut < 2; ++ut) {
                     const size_t fo = ((size_t)((2 * wave + ut) * (H / 16) + kb) * 64 + lane) * 4;
                     const f32x4 b = *reinterpret_cast<const f32x4*>(a.w_proj + fo);
-                    pacc[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.x, b.x, pacc[ut], 0, 0, 0);
-                    pacc[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.y, b.y, pacc[ut], 0, 0, 0);
-                    pacc[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.z, b.z, pacc[ut], 0, 0, 0);
-                    pacc[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(ah.w, b.w, pacc[ut], 0, 0, 0);
+                    pacc[ut] = pnmn::mfma4(ah, b, pacc[ut]);
                 }
             }
 #pragma unroll

@@ -9,7 +9,6 @@
 
 namespace pnmn {
 
-__device__ __forceinline__ float sigm(float z) { return 1.f / (1.f + expf(-z)); }
 // Wave-wide sum / max on the VALU's data-parallel primitives (DPP): four steps inside each row of 16 lanes
 // (quad swaps, half-row and row mirrors), two row broadcasts, one v_readlane -- every lane gets the result.  The
 // __shfl_xor butterfly these replace compiles to six ds_bpermute_b32, i.e. six dependent trips through the LDS

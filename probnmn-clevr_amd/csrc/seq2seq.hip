@@ -13,11 +13,12 @@
 #include "../../include/probnmn_hip.h"
 #include "lds_optin.h"
 #include "cluster.h"
+#include "recurrent_tile.h"
 #include "sampling.h"
 
 namespace {
 
-__device__ __forceinline__ float sigm(float z) { return 1.f / (1.f + expf(-z)); }
+using pnmn::sigm;
 
 // gates: [B][4*Hd] pre-activations in torch order (i, f, g, o)
 __global__ __launch_bounds__(256) void lstm_cell_fwd_kernel(const float* __restrict__ gates,
@@ -66,9 +67,8 @@ __global__ __launch_bounds__(256) void lstm_cell_bwd_kernel(const float* __restr
     dc_prev[idx] = dc * f;
 }
 
-// one draw per (seed, row, step): pnmn::philox_uniform (sampling.h), the stream the decoder kernels draw from
-__device__ __forceinline__ float wave_max(float v) { return pnmn::wmax(v); }  // (the decoder kernels' DPP reductions:
-__device__ __forceinline__ float wave_sum(float v) { return pnmn::wsum(v); }  //  same summation order, same tokens)
+// one draw per (seed, row, step): pnmn::philox_uniform (sampling.h), the stream the decoder kernels draw from; the
+// reductions are the decoder kernels' DPP ones (pnmn::wmax, pnmn::wsum): same summation order, same tokens
 
 // one wave per row; V up to 64*MAXV
 constexpr int MAXV = 8;
@@ -91,11 +91,11 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
         v[k] = j < V ? z[j] : -INFINITY;
         mx = fmaxf(mx, v[k]);
     }
-    mx = wave_max(mx);
+    mx = pnmn::wmax(mx);
     float se = 0.f;
 #pragma unroll
     for (int k = 0; k < MAXV; ++k) se += (lane + 64 * k < V) ? expf(v[k] - mx) : 0.f;
-    se = wave_sum(se);
+    se = pnmn::wsum(se);
     const float lse = mx + logf(se);
     int choice;
     if (greedy) {
@@ -125,7 +125,7 @@ __global__ __launch_bounds__(256) void sample_tokens_kernel(const float* __restr
             w[k] = ok ? expf(v[k] - lse) : 0.f;
             tot += w[k];
         }
-        tot = wave_sum(tot);
+        tot = pnmn::wsum(tot);
         // token order = index order: chunk k holds indices [64k, 64k+64)
         const float u = pnmn::philox_uniform(seed, row_offset + (uint64_t)row, step);
         if (tot > 0.f) {  // (a NaN or +inf anywhere in the row makes the total NaN)
@@ -223,17 +223,18 @@ int pnmn_sample_tokens_filtered(const float* logits, int64_t* tokens, float* log
 // =====================================================================================================
 namespace {
 
-typedef float f32x4_ __attribute__((ext_vector_type(4)));
-constexpr int LH = 256;        // hidden size the kernel is built for
-constexpr int LROWS = 16;      // batch rows per workgroup
-constexpr int LLD = LH + 4;    // LDS row stride (floats): 16-byte aligned, breaks the 1 KiB bank period
+using pnmn::batch_row;
+using pnmn::f32x4;
+using pnmn::mfma4;
+constexpr int LH = pnmn::TILE_H;        // hidden size the kernel is built for
+constexpr int LROWS = pnmn::TILE_ROWS;  // batch rows per workgroup
+constexpr int LLD = pnmn::TILE_LD;      // LDS row stride (floats)
 
 // Rows grouped by length (pnmn_lstm_seq_fwd_ordered / _bwd_ordered).  `order` turns a tile's SLOT into the batch row
-// it holds -- every tensor stays in batch order, only which rows share a tile changes -- and `tile_steps[tile]` is
-// how many steps the tile runs: its longest row's.  Both null: slot = row, T steps (the unordered entry points).
-// A row's accumulation order over k does not depend on the lane or the tile that holds it, so what a row gets at
-// its valid steps is bit for bit what the unordered call of the same kernel gives it.
-__device__ __forceinline__ int batch_row(const int32_t* __restrict__ order, int slot) { return order ? order[slot] : slot; }
+// it holds (pnmn::batch_row) -- every tensor stays in batch order, only which rows share a tile changes -- and
+// `tile_steps[tile]` is how many steps the tile runs: its longest row's.  Both null: slot = row, T steps (the unordered
+// entry points).  A row's accumulation order over k does not depend on the lane or the tile that holds it, so what a row
+// gets at its valid steps is bit for bit what the unordered call of the same kernel gives it.
 
 __device__ __forceinline__ int steps_of_tile(const int32_t* __restrict__ tile_steps, int tile, int T) {
     return tile_steps ? min(max(tile_steps[tile], 1), T) : T;
@@ -248,12 +249,12 @@ __device__ __forceinline__ void zero_skipped_steps(float* __restrict__ out, int 
     constexpr int W4 = W / 4;
     const int n = (T - steps) * groups * W4;
     if (n <= 0) return;
-    const f32x4_ zero = f32x4_{0.f, 0.f, 0.f, 0.f};
+    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int rl = 0; rl < LROWS && row0 + rl < B; ++rl) {
         float* base = out + (size_t)batch_row(order, row0 + rl) * T * ld + col0;
         for (int i = threadIdx.x; i < n; i += 512) {
             const int c4 = i % W4, q = (i / W4) % groups, t = steps + i / (W4 * groups);
-            *reinterpret_cast<f32x4_*>(base + (size_t)t * ld + q * LH + 4 * c4) = zero;
+            *reinterpret_cast<f32x4*>(base + (size_t)t * ld + q * LH + 4 * c4) = zero;
         }
     }
 }
@@ -286,7 +287,7 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_kernel(const float* __restri
 
     for (int t = 0; t < steps; ++t) {
         const int cur = t & 1, nxt = cur ^ 1;
-        f32x4_ acc[4][2];
+        f32x4 acc[4][2];
         // start from the input projection
 #pragma unroll
         for (int gate = 0; gate < 4; ++gate)
@@ -301,17 +302,14 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_kernel(const float* __restri
         if (t > 0) {
 #pragma unroll 4
             for (int kb = 0; kb < LH / 16; ++kb) {
-                const f32x4_ a = *reinterpret_cast<const f32x4_*>(&hl[cur][li][kb * 16 + 4 * g]);
+                const f32x4 a = *reinterpret_cast<const f32x4*>(&hl[cur][li][kb * 16 + 4 * g]);
 #pragma unroll
                 for (int gate = 0; gate < 4; ++gate)
 #pragma unroll
                     for (int ut = 0; ut < 2; ++ut) {
                         const int ntile = gate * (LH / 16) + 2 * wave + ut;
-                        const f32x4_ b = *reinterpret_cast<const f32x4_*>(w_hh + ((size_t)(ntile * (LH / 16) + kb) * 64 + lane) * 4);
-                        acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[gate][ut], 0, 0, 0);
-                        acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[gate][ut], 0, 0, 0);
-                        acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[gate][ut], 0, 0, 0);
-                        acc[gate][ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[gate][ut], 0, 0, 0);
+                        const f32x4 b = *reinterpret_cast<const f32x4*>(w_hh + ((size_t)(ntile * (LH / 16) + kb) * 64 + lane) * 4);
+                        acc[gate][ut] = mfma4(a, b, acc[gate][ut]);
                     }
             }
         }
@@ -408,21 +406,18 @@ __global__ __launch_bounds__(512) void lstm_seq_bwd_kernel(const float* __restri
             }
         __syncthreads();
         // dh_{t-1} = dgates_t @ W_hh : [16 x 1024] x [1024 x 256]; this wave's 32 hidden units
-        f32x4_ acc[2];
-        acc[0] = f32x4_{0.f, 0.f, 0.f, 0.f};
-        acc[1] = f32x4_{0.f, 0.f, 0.f, 0.f};
+        f32x4 acc[2];
+        acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+        acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
         if (t > 0) {
 #pragma unroll 4
             for (int kb = 0; kb < (4 * LH) / 16; ++kb) {
-                const f32x4_ a = *reinterpret_cast<const f32x4_*>(&dgl[li][kb * 16 + 4 * g]);
+                const f32x4 a = *reinterpret_cast<const f32x4*>(&dgl[li][kb * 16 + 4 * g]);
 #pragma unroll
                 for (int ut = 0; ut < 2; ++ut) {
                     const int ntile = 2 * wave + ut;
-                    const f32x4_ b = *reinterpret_cast<const f32x4_*>(w_hh_t + ((size_t)(ntile * (4 * LH / 16) + kb) * 64 + lane) * 4);
-                    acc[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, b.x, acc[ut], 0, 0, 0);
-                    acc[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, b.y, acc[ut], 0, 0, 0);
-                    acc[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, b.z, acc[ut], 0, 0, 0);
-                    acc[ut] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, b.w, acc[ut], 0, 0, 0);
+                    const f32x4 b = *reinterpret_cast<const f32x4*>(w_hh_t + ((size_t)(ntile * (4 * LH / 16) + kb) * 64 + lane) * 4);
+                    acc[ut] = mfma4(a, b, acc[ut]);
                 }
             }
         }
@@ -477,11 +472,10 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_cluster_kernel(const float* 
     constexpr int J = UW * 16 / 512;    // (row, unit) pairs per thread in the cell update
     constexpr int GLD = UW + 4;
     __shared__ float gl[4][LROWS][GLD];
-    // h_{t-1} of the tile, staged ONCE per step by the whole workgroup (two coalesced 16-byte loads per thread)
-    // and read back as MFMA operands from LDS: every wave needs all 16 x 256 values, and 16 scattered 16-byte
+    // h_{t-1} of the tile, staged ONCE per step by the whole workgroup (pnmn::stage_step: two coalesced 16-byte loads
+    // per thread) and read back as MFMA operands from LDS: every wave needs all 16 x 256 values, and 16 scattered 16-byte
     // loads per lane straight from L2 kept the matrix pipe waiting ~4 000 cycles per step (cycle stamps)
-    constexpr int HLD = LH + 4;
-    __shared__ __attribute__((aligned(16))) float hl[LROWS][HLD];
+    __shared__ __attribute__((aligned(16))) float hl[LROWS][LLD];
     int tile, part;
     pnmn::cluster_coords<S>(tile, part);
     if (tile >= tiles) return;
@@ -494,14 +488,9 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_cluster_kernel(const float* 
     pnmn::Cluster cl;
     cl.start(sync + tile * pnmn::CLUSTER_COUNTER_STRIDE, S);
 
-    f32x4_ wreg[UB][LH / 16];
+    f32x4 wreg[UB][LH / 16];
 #pragma unroll
-    for (int ub = 0; ub < UB; ++ub)
-#pragma unroll
-        for (int kb = 0; kb < LH / 16; ++kb) {
-            const int ntile = gate * (LH / 16) + u0 / 16 + ub0 + ub;
-            wreg[ub][kb] = *reinterpret_cast<const f32x4_*>(w_hh + ((size_t)(ntile * (LH / 16) + kb) * 64 + lane) * 4);
-        }
+    for (int ub = 0; ub < UB; ++ub) pnmn::load_wslice<LH / 16>(wreg[ub], w_hh, gate * (LH / 16) + u0 / 16 + ub0 + ub, LH / 16, 0, lane);
     float creg[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) creg[j] = 0.f;
@@ -522,13 +511,12 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_cluster_kernel(const float* 
     }
     // the batch rows this thread stages h_{t-1} of, and those of its (row, unit) pairs in the cell update
     int hrow[2], crow[J];
-#pragma unroll
-    for (int k = 0; k < 2; ++k) hrow[k] = batch_row(order, min(row0 + (tid + 512 * k) / (LH / 4), B - 1));
+    pnmn::stage_rows(hrow, order, row0, B);
 #pragma unroll
     for (int j = 0; j < J; ++j) crow[j] = batch_row(order, min(row0 + (tid + 512 * j) / UW, B - 1));
 
     for (int t = 0; t < steps; ++t) {
-        f32x4_ acc[UB];
+        f32x4 acc[UB];
 #pragma unroll
         for (int ub = 0; ub < UB; ++ub)
 #pragma unroll
@@ -538,34 +526,15 @@ __global__ __launch_bounds__(512) void lstm_seq_fwd_cluster_kernel(const float* 
         for (int r = 0; r < 4; ++r) xrow[r] = TOK ? trow[r][min(t + 1, T - 1)] : xrow[r] + 1;
         if (t > 0) {
             cl.wait();
-            {   // both loads in flight before the first LDS store (written as a loop the compiler issues load,
-                // vmcnt(0), store, load, vmcnt(0), store: two L2 round trips on the step's critical path)
-                static_assert(LROWS * LH / 4 == 2 * 512, "two 16-byte pieces per thread");
-                f32x4_ piece[2];
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int c4 = (tid + 512 * k) % (LH / 4);
-                    piece[k] = *reinterpret_cast<const f32x4_*>(hs + ((size_t)hrow[k] * T + (t - 1)) * LH + 4 * c4);
-                }
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int i = tid + 512 * k, rl = i / (LH / 4), c4 = i % (LH / 4);
-                    *reinterpret_cast<f32x4_*>(&hl[rl][4 * c4]) = piece[k];
-                }
-            }
+            pnmn::stage_step(hs, hrow, T, t - 1, hl);
             __syncthreads();
-            f32x4_ a[LH / 16];
+            f32x4 a[LH / 16];
 #pragma unroll
-            for (int kb = 0; kb < LH / 16; ++kb) a[kb] = *reinterpret_cast<const f32x4_*>(&hl[li][kb * 16 + 4 * g]);
+            for (int kb = 0; kb < LH / 16; ++kb) a[kb] = *reinterpret_cast<const f32x4*>(&hl[li][kb * 16 + 4 * g]);
 #pragma unroll
             for (int kb = 0; kb < LH / 16; ++kb)
 #pragma unroll
-                for (int ub = 0; ub < UB; ++ub) {
-                    acc[ub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kb].x, wreg[ub][kb].x, acc[ub], 0, 0, 0);
-                    acc[ub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kb].y, wreg[ub][kb].y, acc[ub], 0, 0, 0);
-                    acc[ub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kb].z, wreg[ub][kb].z, acc[ub], 0, 0, 0);
-                    acc[ub] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[kb].w, wreg[ub][kb].w, acc[ub], 0, 0, 0);
-                }
+                for (int ub = 0; ub < UB; ++ub) acc[ub] = mfma4(a[kb], wreg[ub][kb], acc[ub]);
         }
 #pragma unroll
         for (int ub = 0; ub < UB; ++ub)
@@ -629,15 +598,12 @@ __global__ __launch_bounds__(512) void lstm_seq_bwd_cluster_kernel(const float* 
     float* ptile = px + (size_t)tile * 2 * S * LROWS * LH;  // [parity][source part][16][H]
 
     // this wave's two 16-unit output tiles x this workgroup's gate columns, register resident
-    f32x4_ wreg[2][KB];
+    f32x4 wreg[2][KB];
 #pragma unroll
     for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-        for (int kl = 0; kl < KB; ++kl) {
-            const int q = kl / (UW / 16), jj = kl % (UW / 16);
-            const int kb = (q * LH + u0) / 16 + jj;
-            wreg[nt][kl] = *reinterpret_cast<const f32x4_*>(w_hh_t + ((size_t)((2 * wave + nt) * (4 * LH / 16) + kb) * 64 + lane) * 4);
-        }
+        for (int q = 0; q < 4; ++q)  // gate q's columns of this member: UW / 16 k blocks from column q LH + u0
+            pnmn::load_wslice<UW / 16>(wreg[nt] + q * (UW / 16), w_hh_t, 2 * wave + nt, 4 * LH / 16, (q * LH + u0) / 16, lane);
     float dh_rec[J], dc_rec[J];
 #pragma unroll
     for (int j = 0; j < J; ++j) dh_rec[j] = dc_rec[j] = 0.f;
@@ -705,26 +671,21 @@ __global__ __launch_bounds__(512) void lstm_seq_bwd_cluster_kernel(const float* 
         }
         if (t == 0) break;
         __syncthreads();
-        f32x4_ acc[2];
-        acc[0] = f32x4_{0.f, 0.f, 0.f, 0.f};
-        acc[1] = f32x4_{0.f, 0.f, 0.f, 0.f};
+        f32x4 acc[2];
+        acc[0] = f32x4{0.f, 0.f, 0.f, 0.f};
+        acc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int kl = 0; kl < KB; ++kl) {
-            const f32x4_ a = *reinterpret_cast<const f32x4_*>(&dgl[li][kl * 16 + 4 * g]);
+            const f32x4 a = *reinterpret_cast<const f32x4*>(&dgl[li][kl * 16 + 4 * g]);
 #pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                // (weights as the A operand: the product comes out transposed, each lane holding four
-                // consecutive units of one row -- one 16-byte store per tile instead of four 4-byte ones)
-                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[nt][kl].x, a.x, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[nt][kl].y, a.y, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[nt][kl].z, a.z, acc[nt], 0, 0, 0);
-                acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[nt][kl].w, a.w, acc[nt], 0, 0, 0);
-            }
+            // (weights as the A operand: the product comes out transposed, each lane holding four
+            // consecutive units of one row -- one 16-byte store per tile instead of four 4-byte ones)
+            for (int nt = 0; nt < 2; ++nt) acc[nt] = mfma4(wreg[nt][kl], a, acc[nt]);
         }
         float* po = ptile + ((size_t)(t & 1) * S + part) * LROWS * LH;
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt)
-            *reinterpret_cast<f32x4_*>(po + (size_t)li * LH + 16 * (2 * wave + nt) + 4 * g) = acc[nt];
+            *reinterpret_cast<f32x4*>(po + (size_t)li * LH + 16 * (2 * wave + nt) + 4 * g) = acc[nt];
         cl.signal();  // also: everyone is done reading dgl
     }
     zero_skipped_steps<UW>(dgates, 4 * LH, 4, u0, order, row0, B, T, steps);
@@ -733,6 +694,25 @@ __global__ __launch_bounds__(512) void lstm_seq_bwd_cluster_kernel(const float* 
 
 using pnmn::cluster_split;
 constexpr size_t SYNC_BYTES = pnmn::CLUSTER_SYNC_BYTES;
+
+// The row ranges of a multi-CU pass, one launch each, one after the other (a single range when the batch's tiles fit the
+// chip: lstm_chunk_tiles).  `launch` gets the range's tiles nt and members S, its rows, the first batch row b0 the tensor
+// bases point at (0 with an order: the tensors are then addressed by batch row through it, and only the two index arrays
+// move), its first slot r0 and tile t0, and the grid.
+template <typename F>
+int for_row_ranges(int B, int tiles, int ctiles, bool ordered, F launch) {
+    for (int t0 = 0; t0 < tiles; t0 += ctiles) {
+        const int nt = tiles - t0 < ctiles ? tiles - t0 : ctiles;
+        const int S = cluster_split(nt);
+        if (!S) return PNMN_ESHAPE;
+        const size_t r0 = (size_t)t0 * LROWS;
+        const int rows = (int)((size_t)B - r0 < (size_t)nt * LROWS ? (size_t)B - r0 : (size_t)nt * LROWS);
+        launch(nt, S, rows, ordered ? (size_t)0 : r0, r0, t0, dim3(8 * S * ((nt + 7) / 8)));
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
 
 }  // namespace
 
@@ -776,14 +756,7 @@ static int lstm_seq_fwd_launch(const float* xp, const int64_t* tokens, int64_t t
         int* sync = nullptr;
         hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
         if (e != hipSuccess) return (int)e;
-        for (int t0 = 0; t0 < tiles; t0 += ctiles) {
-            const int nt = tiles - t0 < ctiles ? tiles - t0 : ctiles;
-            const int S = cluster_split(nt);
-            if (!S) return PNMN_ESHAPE;
-            const size_t r0 = (size_t)t0 * LROWS;
-            const int rows = (int)((size_t)B - r0 < (size_t)nt * LROWS ? (size_t)B - r0 : (size_t)nt * LROWS);
-            const dim3 grid(8 * S * ((nt + 7) / 8));
-            const size_t b0 = order ? 0 : r0;  // first batch row the tensor bases point at
+        return for_row_ranges(B, tiles, ctiles, order != nullptr, [&](int nt, int S, int rows, size_t b0, size_t r0, int t0, dim3 grid) {
             auto kern = S == 8 ? (tokens ? lstm_seq_fwd_cluster_kernel<8, true> : lstm_seq_fwd_cluster_kernel<8, false>)
                                : (tokens ? lstm_seq_fwd_cluster_kernel<4, true> : lstm_seq_fwd_cluster_kernel<4, false>);
             // (with tokens, xp is the per-token table: only the token rows move with the range)
@@ -791,9 +764,7 @@ static int lstm_seq_fwd_launch(const float* xp, const int64_t* tokens, int64_t t
                                tokens ? tokens + b0 * tstride : nullptr, tstride, w_hh, hs + b0 * T * LH, cs + b0 * T * LH,
                                act ? act + b0 * T * (4 * LH) : nullptr, sync, rows, T, nt, order ? order + r0 : nullptr,
                                tile_steps ? tile_steps + t0 : nullptr);
-            if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        }
-        return 0;
+        });
     }
     hipLaunchKernelGGL(lstm_seq_fwd_kernel, dim3(tiles), dim3(512), 0, st, xp, tokens, tstride, w_hh, hs, cs, act, B, T,
                        order, tile_steps);
@@ -826,27 +797,12 @@ static int lstm_seq_bwd_launch(const float* dhs, const float* act, const float* 
         hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
         if (e != hipSuccess) return (int)e;
         float* px = reinterpret_cast<float*>(static_cast<char*>(workspace) + SYNC_BYTES);
-        for (int t0 = 0; t0 < tiles; t0 += ctiles) {  // (row ranges, as in pnmn_lstm_seq_fwd; px is reused)
-            const int nt = tiles - t0 < ctiles ? tiles - t0 : ctiles;
-            const int S = cluster_split(nt);
-            if (!S) return PNMN_ESHAPE;
-            const size_t r0 = (size_t)t0 * LROWS;
-            const int rows = (int)((size_t)B - r0 < (size_t)nt * LROWS ? (size_t)B - r0 : (size_t)nt * LROWS);
-            const dim3 grid(8 * S * ((nt + 7) / 8));
-            const size_t b0 = order ? 0 : r0;  // (as in the forward)
-            const float* d = dhs + b0 * T * LH;
-            const float* a = act + b0 * T * (4 * LH);
-            const float* c = cs + b0 * T * LH;
-            float* dg = dgates + b0 * T * (4 * LH);
-            const int32_t* ord = order ? order + r0 : nullptr;
-            const int32_t* ts = tile_steps ? tile_steps + t0 : nullptr;
-            if (S == 8)
-                hipLaunchKernelGGL(lstm_seq_bwd_cluster_kernel<8>, grid, dim3(512), 0, st, d, a, c, w_hh_t, dg, px, sync, rows, T, nt, ord, ts);
-            else
-                hipLaunchKernelGGL(lstm_seq_bwd_cluster_kernel<4>, grid, dim3(512), 0, st, d, a, c, w_hh_t, dg, px, sync, rows, T, nt, ord, ts);
-            if ((e = hipGetLastError()) != hipSuccess) return (int)e;
-        }
-        return 0;
+        return for_row_ranges(B, tiles, ctiles, order != nullptr, [&](int nt, int S, int rows, size_t b0, size_t r0, int t0, dim3 grid) {
+            auto kern = S == 8 ? lstm_seq_bwd_cluster_kernel<8> : lstm_seq_bwd_cluster_kernel<4>;  // (px is reused by every range)
+            hipLaunchKernelGGL(kern, grid, dim3(512), 0, st, dhs + b0 * T * LH, act + b0 * T * (4 * LH), cs + b0 * T * LH, w_hh_t,
+                               dgates + b0 * T * (4 * LH), px, sync, rows, T, nt, order ? order + r0 : nullptr,
+                               tile_steps ? tile_steps + t0 : nullptr);
+        });
     }
     constexpr size_t lds = (size_t)LROWS * (4 * LH + 4) * sizeof(float);
     static std::atomic<uint64_t> cfg{0};  // (per device: lds_optin.h)

@@ -106,6 +106,93 @@ def test_stack_equals_separate_layers(shapes):
             assert _close(o[name], ref[name]), name
 
 
+def test_stack_layer_and_decoder_launches_share_one_zeroed_counter_block():
+    """Every multi-CU launch leaves the stream's hand-off counter block zeroed for the next one, whichever kernel that is
+    (csrc/cluster.h: a stack launch uses five words of a tile's line, the layer and decoder kernels three).  On ONE stream:
+    a stack forward (a linked FIRST + SECOND pair of 40 rows x 4 steps -- three tiles, the last of 8 rows -- and an
+    independent job of 20 rows x 3 steps), a multi-CU layer forward, a multi-CU teacher-forced decoder forward, the stack
+    backward of the same jobs, a multi-CU layer backward; three rounds, every tensor equal to its call's run alone."""
+    from probnmn.modules.seq2seq_base import _AttnLSTMDecoder
+
+    lib, st = _hip.lib(), _hip.stream_ptr(torch.device(DEV))
+    B, T, B3, T3, S, V = 40, 4, 20, 3, 5, 40
+    g = torch.Generator(device=DEV).manual_seed(11)
+    r = lambda *s, scale=1.0: (torch.rand(*s, device=DEV, generator=g) - 0.5) * scale  # noqa: E731
+    l1, l2, l3 = _layer(1), _layer(2), _layer(3)
+    table, tokens = r(V, 1024), torch.randint(0, V, (B, T), device=DEV, generator=g)
+    xp3, xp = r(B3, T3, 1024), r(B, T, 1024)
+    dhs2, dhs3, dhs = r(B, T, 256, scale=2.0), r(B3, T3, 256, scale=2.0), r(B, T, 256, scale=2.0)
+    xe, enc, h0 = r(B, T, 1024), r(B, S, 256, scale=2.0), r(B, 256, scale=2.0)
+    mask = (torch.arange(S, device=DEV)[None, :] < torch.randint(1, S + 1, (B,), device=DEV, generator=g)[:, None]).float()
+    w_c, w_p, b_p = r(1024, 256, scale=0.1), r(V, 256, scale=0.6), r(V)
+    packs = dict(hh1=pack_fragments(l1["w_hh"]), hh2=pack_fragments(l2["w_hh"]), ih2=pack_fragments(l2["w_ih"]), hh3=pack_fragments(l3["w_hh"]),
+                 hh1t=pack_fragments(l1["w_hh"].t()), hh2t=pack_fragments(l2["w_hh"].t()), ih2t=pack_fragments(l2["w_ih"].t()),
+                 hh3t=pack_fragments(l3["w_hh"].t()))
+    assert int(lib.pnmn_lstm_seq_workspace_bytes(B, 0)) > 0  # (the layer calls below take the multi-CU kernels)
+    fresh = lambda rows, steps, w: torch.full((rows, steps, w), float("nan"), device=DEV)  # noqa: E731
+
+    def launch(fn, jobs, backward):
+        nbytes = int(lib.pnmn_lstm_stack_workspace_bytes(jobs.ctypes.data, len(jobs), backward))
+        assert nbytes > 0
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+        _hip.check(fn(jobs.ctypes.data, len(jobs), ws.data_ptr(), st), "lstm_stack")
+
+    def stack_fwd():
+        o = dict(hs1=fresh(B, T, 256), cs1=fresh(B, T, 256), act1=fresh(B, T, 1024), hs2=fresh(B, T, 256), cs2=fresh(B, T, 256),
+                 act2=fresh(B, T, 1024), hs3=fresh(B3, T3, 256), cs3=fresh(B3, T3, 256), act3=fresh(B3, T3, 1024))
+        j = np.zeros(3, _hip.LSTM_STACK_JOB)
+        a, b, c = j[0], j[1], j[2]
+        a["xp"], a["tokens"], a["token_stride"], a["w_hh"] = table.data_ptr(), tokens.data_ptr(), T, packs["hh1"].data_ptr()
+        a["hs"], a["cs"], a["act"], a["B"], a["T"], a["dep"] = o["hs1"].data_ptr(), o["cs1"].data_ptr(), o["act1"].data_ptr(), B, T, -1
+        b["w_hh"], b["w_ih"], b["bias"] = packs["hh2"].data_ptr(), packs["ih2"].data_ptr(), l2["b"].data_ptr()
+        b["hs"], b["cs"], b["act"], b["B"], b["T"], b["dep"] = o["hs2"].data_ptr(), o["cs2"].data_ptr(), o["act2"].data_ptr(), B, T, 0
+        c["xp"], c["w_hh"] = xp3.data_ptr(), packs["hh3"].data_ptr()
+        c["hs"], c["cs"], c["act"], c["B"], c["T"], c["dep"] = o["hs3"].data_ptr(), o["cs3"].data_ptr(), o["act3"].data_ptr(), B3, T3, -1
+        launch(lib.pnmn_lstm_stack_fwd, j, 0)
+        return o
+
+    def stack_bwd(f):
+        o = dict(dg2=fresh(B, T, 1024), dg1=fresh(B, T, 1024), dg3=fresh(B3, T3, 1024))
+        j = np.zeros(3, _hip.LSTM_STACK_JOB)
+        a, b, c = j[0], j[1], j[2]
+        a["dhs"], a["act"], a["cs"], a["w_hh"], a["dgates"] = dhs2.data_ptr(), f["act2"].data_ptr(), f["cs2"].data_ptr(), packs["hh2t"].data_ptr(), o["dg2"].data_ptr()
+        a["B"], a["T"], a["dep"] = B, T, -1
+        b["act"], b["cs"], b["w_hh"], b["w_ih"], b["dgates"] = f["act1"].data_ptr(), f["cs1"].data_ptr(), packs["hh1t"].data_ptr(), packs["ih2t"].data_ptr(), o["dg1"].data_ptr()
+        b["B"], b["T"], b["dep"] = B, T, 0
+        c["dhs"], c["act"], c["cs"], c["w_hh"], c["dgates"] = dhs3.data_ptr(), f["act3"].data_ptr(), f["cs3"].data_ptr(), packs["hh3t"].data_ptr(), o["dg3"].data_ptr()
+        c["B"], c["T"], c["dep"] = B3, T3, -1
+        launch(lib.pnmn_lstm_stack_bwd, j, 1)
+        return o
+
+    def layer_fwd():
+        return dict(zip(("hs", "cs", "act"), _seq_fwd(xp, None, l3["w_hh"], B, T)))
+
+    def decoder_fwd():
+        with torch.no_grad():
+            hs, _ = _AttnLSTMDecoder.apply(xe, None, enc, mask, h0, w_c, l1["w_hh"], w_p, b_p, 0, T, 5, 3, 0, 1, 2)
+        return dict(dec_hs=hs)
+
+    def alone(fn, *args):
+        out = fn(*args)
+        torch.cuda.synchronize()
+        return out
+
+    assert _hip.decoder_workspace_bytes([B], False) > 0  # (the decoder call takes the multi-CU kernel)
+    want_f = alone(stack_fwd)
+    want_l = alone(layer_fwd)
+    layer_bwd = lambda: dict(dg=_seq_bwd(dhs, want_l["act"], want_l["cs"], l3["w_hh"], B, T))  # noqa: E731
+    calls = [(stack_fwd, (), want_f), (layer_fwd, (), want_l), (decoder_fwd, (), alone(decoder_fwd)),
+             (stack_bwd, (want_f,), alone(stack_bwd, want_f)), (layer_bwd, (), alone(layer_bwd))]
+    for want in (c[2] for c in calls):
+        assert all(torch.isfinite(v).all() for v in want.values())
+    for rnd in range(3):
+        got = [fn(*args) for fn, args, _ in calls]  # back to back, nothing but the stream orders them
+        torch.cuda.synchronize()
+        for (_, _, want), out in zip(calls, got):
+            for name in want:
+                assert torch.equal(out[name], want[name]), (rnd, name)
+
+
 def test_does_not_fit_reports_zero_workspace():
     jobs = np.zeros(2, _hip.LSTM_STACK_JOB)
     jobs["B"], jobs["T"], jobs["dep"] = 1024, 10, -1
