@@ -28,6 +28,12 @@
  *     `struct pnmn_x` in prototypes; the binding derives its dtype too, beside the records, not among them
  *   - a constant is `#define PNMN_NAME <integer>` or `(<negative integer>)`
  * A pnmn_ declaration written any other way makes the import fail with its text (tests/test_abi.py).
+ *
+ * Options.  An option is a nullable trailing argument of the entry point it modifies, never a second entry point.  For the
+ * decoders (pnmn_sample_tokens, pnmn_attn_lstm_fwd, _fwd_group, _beam, pnmn_prior_sample):
+ *   - filter == NULL (group: filters == NULL) means the identity filter;
+ *   - token_class, next_state and min_left all NULL means unconstrained: end_index, n_states and n_classes are then ignored
+ *     (but for pnmn_attn_lstm_beam's end_index, which the search itself uses); some but not all of the three given returns PNMN_EINVAL.
  */
 #ifndef PROBNMN_HIP_H
 #define PROBNMN_HIP_H
@@ -552,6 +558,56 @@ int pnmn_lstm_seq_bwd_ordered(const float* dhs, const float* act, const float* c
 int pnmn_cluster_reserve_cus(int cus);
 
 /* ---------------------------------------------------------------------------------------------
+ * One decoding step's token choice                                   seq2seq_base.py:203-220
+ *   greedy:   tokens[b] = argmax softmax(logits[b])            (first maximum)
+ *   sampling: weights = softmax(logits[b]) with pad/unk/start zeroed; tokens[b] ~ weights
+ *             (inverse CDF in index order; u from Philox4x32-10 keyed by `seed`, counter =
+ *             (row_offset + b, step) -- shard-invariant under data parallelism)
+ *   logprobs[b] = log_softmax(logits[b])[tokens[b]]            (unmodified distribution)
+ * V <= 512.
+ * Token choice is always an index in [0, V), also for rows that are not all finite (the same rule in the decoder kernels):
+ *   greedy:   torch.argmax semantics -- a NaN counts as the maximum, the first index wins.
+ *   sampling, no NaN or +inf in the row but the allowed weights underflow to a total of 0: the weights are recomputed
+ *             relative to the largest allowed logit (the same distribution without the underflow).
+ *   sampling, a NaN or +inf in the row, or every allowed logit -inf: the first allowed index with the largest logit,
+ *             a NaN counting as the largest; logprobs stays log_softmax(logits[b])[tokens[b]] (NaN propagates).
+ *   no allowed token (V <= 3, pad / unk / start cover the row): the greedy choice.
+ * A finite row with a positive allowed total never reaches these rules (its draw does not change).
+ *
+ * The filter rule: temperature, top-k and nucleus (top-p) truncation of the distribution a token is drawn from.
+ * A filter is (temperature, top_k, top_p); (1, 0, 1) is the identity.  It applies to sampling only: a greedy choice and
+ * a teacher-forced pass ignore it.  For one row of logits z[0..V):
+ *   A      = every index but pad, unk and start (the allowed set, as above)
+ *   s_j    = z_j / temperature, w_j = exp(s_j - max_A s)                                  for j in A
+ *   rank   j ranks before i when w_j > w_i, or w_j == w_i and j < i                       (within A)
+ *   top_k > 0: keep the top_k first-ranked indices (top_k >= |A| keeps all of A)
+ *   top_p < 1: of those, keep i iff the summed weight of the kept indices ranked before i is < top_p * total, total = the
+ *              weight top-k kept; the first-ranked index is always kept
+ *   draw   inverse CDF in INDEX order over the kept weights, from the uniform pnmn_sample_tokens draws: Philox4x32-10,
+ *          counter (row_offset + row, step) -- a filtered and an unfiltered decode from one seed share their random numbers
+ *   logprobs (and any loss built from them) stay log_softmax(z)[token] of the UNMODIFIED distribution, as the reference
+ *          already scores a draw from which pad / unk / start were removed (seq2seq_base.py:204,220)
+ * A row that holds a NaN or +inf, or whose allowed weights sum to 0 in the unfiltered rule, follows that rule's fallback
+ * unchanged and ignores the filter; a token is always in [0, V).  With the identity filter, as with a null one, an entry
+ * point runs its unfiltered kernel: the same output, bit for bit.  It returns PNMN_EINVAL and launches nothing for a
+ * temperature that is not finite or <= 0, top_k < 0, or a top_p outside (0, 1] (NaN included), also where the filter
+ * would be ignored.  The filters are HOST memory, read before the call returns, and travel by value in the launch
+ * arguments: no device allocation, no copy, no synchronisation.
+ * pnmn_attn_lstm_fwd_group: filters[i] belongs to jobs[i] and applies when that job's sample == 1; for any other job it
+ * is checked and ignored.
+ * ------------------------------------------------------------------------------------------- */
+struct pnmn_sampling_filter {
+    float temperature;
+    int32_t top_k;
+    float top_p;
+    int32_t reserved;
+};                         /* 16 bytes; a host argument block (see the declaration conventions), not a work-item record */
+int pnmn_sample_tokens(const float* logits, int64_t* tokens, float* logprobs, int B, int V,
+                       int greedy, uint64_t seed, uint64_t row_offset, uint32_t step, int pad_index,
+                       int unk_index, int start_index, const struct pnmn_sampling_filter* filter /* HOST, may be NULL */,
+                       void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Persistent attention-LSTM decoder (hidden = 256): the whole decoding loop of
  * Seq2SeqBase._forward_loop (seq2seq_base.py:186-224 -> allennlp _prepare_output_projections) in one
  * launch; one workgroup owns 16 batch rows for all T steps.
@@ -565,14 +621,54 @@ int pnmn_cluster_reserve_cus(int cus);
  *   saved for backward: act, cs, hs, ctx, probs (softmax before masking).
  * backward: dhs (gradient wrt every h_t) -> dgates (= d xe), denc (+=, zero on entry), dh0.
  * S <= 64 encoder positions, V <= 128 sampled vocabulary.
+ * One forward pass = one pnmn_decoder_fwd_job record, its fields named as above; pnmn_attn_lstm_fwd takes ONE record in
+ * HOST memory, pnmn_attn_lstm_fwd_group (below) an array of them.  `filter` (may be NULL) applies to a sample == 1 pass by
+ * the filter rule beside pnmn_sample_tokens; it is checked whatever the mode.  B <= 0 or T <= 0 returns 0 without a launch.
  * ------------------------------------------------------------------------------------------- */
-int pnmn_attn_lstm_fwd(const float* xe, const float* etable, const float* enc, const float* mask,
-                       const float* h0, const float* w_c, const float* w_hh, const float* w_p,
-                       const float* b_p, float* hs, float* cs, float* act, float* ctx, float* probs,
-                       int64_t* tokens, int B, int T, int S, int V, int hidden, int sample,
-                       int pad_index, int unk_index, int start_index, uint64_t seed,
-                       uint64_t row_offset, const int64_t* in_tokens, int64_t in_token_stride,
-                       void* stream);
+typedef struct pnmn_decoder_fwd_job {
+    const float *xe, *etable, *enc, *mask, *h0, *w_c, *w_hh, *w_p, *b_p;
+    float *hs, *cs, *act, *ctx, *probs;
+    int64_t* tokens;
+    const int64_t* in_tokens;
+    int64_t in_token_stride;
+    uint64_t seed, row_offset;
+    int32_t B, T, S, V, sample, pad_index, unk_index, start_index;
+} pnmn_decoder_fwd_job;    /* 184 bytes */
+/* The automaton rule: sampling and greedy decoding under a token automaton.  The free-running modes of pnmn_attn_lstm_fwd /
+ * _fwd_group emit only strings the automaton accepts.  INFERENCE ONLY: a constrained draw is not a draw from the model's
+ * distribution, and no trainer uses it.  The tables (token_class, next_state, min_left, n_states, n_classes, state 0 = start,
+ * 255 = no completion) and the test of a candidate are those of pnmn_attn_lstm_beam below: HOST pointers, every entry checked,
+ * passed by value in the launch arguments and staged into LDS once per workgroup -- no device allocation, no copy, no
+ * synchronisation.
+ * Every row carries an automaton state (0 at the start) and a finished flag (false at the start).  At step t (0-based) of T a
+ * row in state s that has not finished has the allowed set A_c(s, t):
+ *   token v, not pad / unk / start and v != end_index   iff  min_left[next_state[s][token_class[v]]] <= T - 1 - t
+ *   end_index                                           iff  min_left[s] == 0
+ * and its token is chosen as by pnmn_sample_tokens, with or without a filter, with A_c in the place of A:
+ *   sample == 1: inverse CDF in index order over softmax(z) restricted to A_c, the uniform from the same Philox counter
+ *                (row_offset + row, t) -- a constrained and an unconstrained decode from one seed share their random numbers;
+ *                under a filter other than the identity: rank, top-k and top-p WITHIN A_c, then the same draw
+ *   sample == 2: the first index of the largest logit WITHIN A_c (the unconstrained arg-max looks at all of [0, V))
+ *   a row that holds a NaN or +inf (greedy: a NaN), or whose A_c weights sum to 0, follows the fallback rule stated beside
+ *                pnmn_sample_tokens with A_c as the allowed set (greedy: the arg-max of that rule within A_c): still in A_c
+ *   a row that has emitted end_index is finished: every later step of it emits end_index, its state is frozen, and the token
+ *                is fed to the next step as usual
+ *   state:       unchanged on end_index, otherwise s <- next_state[s][token_class[token]]
+ * By induction min_left[s] <= T - t before every step, so A_c is never empty, and every row, cut at its first end_index, is
+ * accepted by the automaton.  With one state, one class and min_left = {0} a sampling pass emits what the unconstrained pass
+ * emits up to and including each row's first end_index.  logprobs, and any loss built from the tokens, stay
+ * log_softmax(z)[token] of the UNMODIFIED distribution, exactly as for the filtered draw.
+ * A filter (null or the identity: the unfiltered draw) applies to sample == 1 within A_c, as stated.
+ * pnmn_attn_lstm_fwd_group: the automaton applies to every job with sample != 0, which share one vocabulary size V; for a job
+ * with sample == 0 it is checked as far as it can be without a vocabulary, and ignored.
+ * A call with tables returns PNMN_EINVAL and launches nothing for: some but not all of the tables, a table entry out of range
+ * (token_class[v] >= n_classes for v < V, next_state >= n_states), n_states outside 1..PNMN_BEAM_MAX_STATES, n_classes outside
+ * 1..PNMN_BEAM_MAX_CLASSES, V outside 1..128, end_index outside [0, V), min_left[0] > T (no accepted string fits; group: any
+ * free-running job's T), an invalid filter.  Otherwise: the arguments, limits and return codes of the call without tables. */
+int pnmn_attn_lstm_fwd(const pnmn_decoder_fwd_job* job /* HOST, one record */, int hidden,
+                       const struct pnmn_sampling_filter* filter /* HOST, may be NULL */, int end_index,
+                       const uint8_t* token_class /* HOST */, const uint8_t* next_state /* HOST */,
+                       const uint8_t* min_left /* HOST */, int n_states, int n_classes, void* stream);
 int pnmn_attn_lstm_bwd(const float* dhs, const float* act, const float* cs, const float* hs,
                        const float* ctx, const float* probs, const float* enc, const float* mask,
                        const float* h0, const float* w_c_t, const float* w_hh_t, float* dgates,
@@ -593,14 +689,9 @@ int pnmn_attn_lstm_bwd(const float* dhs, const float* act, const float* cs, cons
  *          scores [B][beam]; optional trace of every step, [B][T][beam] each (all three or none): the token, the
  *          back-pointer (slot of the previous step) and the running score of every slot.
  * Limits: hidden = 256, 1 <= S <= 64, 1 <= V <= 128, T <= 64, beam in {1, 2, 4, 8, 16}, start / end index inside [0, V);
- * anything else (or a missing pointer) returns PNMN_EINVAL. */
-int pnmn_attn_lstm_beam(const float* etable, const float* enc, const float* mask, const float* h0,
-                        const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
-                        int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
-                        float* trace_scores, int B, int T, int S, int V, int hidden, int beam,
-                        int pad_index, int unk_index, int start_index, int end_index, void* stream);
-
-/* pnmn_attn_lstm_beam under a token automaton: only hypotheses the automaton accepts leave the decoder.
+ * anything else (or a missing pointer) returns PNMN_EINVAL.
+ *
+ * The beam-automaton rule: with the three tables given, only hypotheses the automaton accepts leave the decoder.
  *   token_class [V]                    class of every target token, each < n_classes
  *   next_state  [n_states][n_classes]  each < n_states; state 0 is the start state
  *   min_left    [n_states]             fewest further tokens from the state to an accepting one: 0 = accepting,
@@ -613,27 +704,27 @@ int pnmn_attn_lstm_beam(const float* etable, const float* enc, const float* mask
  *   end_index                                  only if  min_left[s] == 0
  * and every other candidate of it is -inf; a finished hypothesis offers only end_index at its own score, as above.
  * A survivor's state is the one reached from its parent's (by back-pointer) on its token; on end_index, the parent's.
- * Selection, ties, the slot without a finite candidate, the back-track and the trace are those of pnmn_attn_lstm_beam.
+ * Selection, ties, the slot without a finite candidate, the back-track and the trace are the unconstrained ones.
  * Consequence: every hypothesis with a finite score, cut at its first end_index, is accepted by the automaton; when
  * min_left[0] <= T, slot 0 of every question is finite.  With one state, one class and min_left = {0} the call computes
- * what pnmn_attn_lstm_beam computes, bit for bit.
- * Limits: those of pnmn_attn_lstm_beam, 1 <= n_states <= 32, 1 <= n_classes <= 16; a null table or an entry out of range
+ * what it computes without tables, bit for bit.
+ * Limits with tables: 1 <= n_states <= 32, 1 <= n_classes <= 16; some but not all of the tables, or an entry out of range,
  * returns PNMN_EINVAL. */
 #define PNMN_BEAM_MAX_STATES 32
 #define PNMN_BEAM_MAX_CLASSES 16
-int pnmn_attn_lstm_beam_constrained(const float* etable, const float* enc, const float* mask, const float* h0,
-                                    const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
-                                    int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
-                                    float* trace_scores, int B, int T, int S, int V, int hidden, int beam,
-                                    int pad_index, int unk_index, int start_index, int end_index,
-                                    const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left,
-                                    int n_states, int n_classes, void* stream);
+int pnmn_attn_lstm_beam(const float* etable, const float* enc, const float* mask, const float* h0,
+                        const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
+                        int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
+                        float* trace_scores, int B, int T, int S, int V, int hidden, int beam,
+                        int pad_index, int unk_index, int start_index, int end_index,
+                        const uint8_t* token_class /* HOST */, const uint8_t* next_state /* HOST */,
+                        const uint8_t* min_left /* HOST */, int n_states, int n_classes, void* stream);
 
-/* Multi-CU variants of the two kernels above (decoder_multi.hip): eight workgroups per 16-row tile,
+/* Multi-CU variants of pnmn_attn_lstm_fwd / _bwd (decoder_multi.hip): eight workgroups per 16-row tile,
  * each keeping its rows' encoder outputs in LDS and its slices of W_c / W_hh in registers, two L2
  * hand-offs per step.  A job = the arguments and saved tensors of pnmn_attn_lstm_fwd / _bwd for one pass; every call
  * also takes a device `workspace` of pnmn_attn_lstm_group_workspace_bytes(rows, n, backward) bytes, rows[i] = B of
- * job i (n = 1: 0 = device too small, use the kernels above).
+ * job i (n = 1: 0 = device too small, use pnmn_attn_lstm_fwd / _bwd).
  * The backward emits dctx [B,T,H] (gradient wrt every context vector) and dscore [B,T,S] (gradient
  * wrt the attention scores) instead of accumulating denc; the caller forms
  *     denc = w^T dctx + dscore^T h_prev      (two GEMMs per row over the T steps; w = the masked, renormalised
@@ -651,23 +742,19 @@ int pnmn_attn_lstm_beam_constrained(const float* etable, const float* enc, const
  * together (512 rows on 256 CUs, at most 128 tiles).  Jobs that do not fit go out as the first n - 1 by the same rule,
  * then the last alone (identical results): three -> pair + single, pair -> single, single.  A single job beyond what
  * fits the chip at once runs as successive launches over its rows; one with B <= 0 or T <= 0 is skipped.
- * n out of range or a missing jobs / workspace pointer returns PNMN_EINVAL (the workspace query: 0). */
-typedef struct pnmn_decoder_fwd_job {
-    const float *xe, *etable, *enc, *mask, *h0, *w_c, *w_hh, *w_p, *b_p;
-    float *hs, *cs, *act, *ctx, *probs;
-    int64_t* tokens;
-    const int64_t* in_tokens;
-    int64_t in_token_stride;
-    uint64_t seed, row_offset;
-    int32_t B, T, S, V, sample, pad_index, unk_index, start_index;
-} pnmn_decoder_fwd_job;    /* 184 bytes */
+ * n out of range or a missing jobs / workspace pointer returns PNMN_EINVAL (the workspace query: 0).
+ * Forward options: `filters` (HOST, one per job, or NULL: none) by the filter rule beside pnmn_sample_tokens, the tables by
+ * the automaton rule beside pnmn_attn_lstm_fwd.  Neither changes the fit and fall-back rule. */
 typedef struct pnmn_decoder_bwd_job {
     const float *dhs, *act, *cs, *hs, *probs, *enc, *mask, *h0, *w_c_t, *w_hh_t;
     float *dgates, *dctx, *dscore, *weights, *dh0;
     int32_t B, T, S, reserved;
 } pnmn_decoder_bwd_job;    /* 136 bytes */
 int64_t pnmn_attn_lstm_group_workspace_bytes(const int32_t* rows, int n, int backward);
-int pnmn_attn_lstm_fwd_group(const pnmn_decoder_fwd_job* jobs, int n, int hidden, void* workspace, void* stream);
+int pnmn_attn_lstm_fwd_group(const pnmn_decoder_fwd_job* jobs, const struct pnmn_sampling_filter* filters /* HOST, may be NULL */,
+                             int end_index, const uint8_t* token_class /* HOST */, const uint8_t* next_state /* HOST */,
+                             const uint8_t* min_left /* HOST */, int n_states, int n_classes,
+                             int n, int hidden, void* workspace, void* stream);
 int pnmn_attn_lstm_bwd_group(const pnmn_decoder_bwd_job* jobs, int n, int hidden, void* workspace, void* stream);
 /* The encoder-output gradient from what pnmn_attn_lstm_bwd_group emits, in one bandwidth-bound launch instead of two
  * strided-batched library GEMMs of B tiny [S x T].[T x 256] products (allennlp SimpleSeq2Seq._prepare_attended_input /
@@ -676,112 +763,6 @@ int pnmn_attn_lstm_bwd_group(const pnmn_decoder_bwd_job* jobs, int n, int hidden
  * hidden = 256, T <= 64. */
 int pnmn_attn_denc(const float* weights, const float* dscore, const float* dctx, const float* hs, const float* h0,
                    float* denc, int B, int T, int S, int hidden, void* stream);
-
-/* ---------------------------------------------------------------------------------------------
- * One decoding step's token choice                                   seq2seq_base.py:203-220
- *   greedy:   tokens[b] = argmax softmax(logits[b])            (first maximum)
- *   sampling: weights = softmax(logits[b]) with pad/unk/start zeroed; tokens[b] ~ weights
- *             (inverse CDF in index order; u from Philox4x32-10 keyed by `seed`, counter =
- *             (row_offset + b, step) -- shard-invariant under data parallelism)
- *   logprobs[b] = log_softmax(logits[b])[tokens[b]]            (unmodified distribution)
- * V <= 512.
- * Token choice is always an index in [0, V), also for rows that are not all finite (the same rule in the decoder kernels):
- *   greedy:   torch.argmax semantics -- a NaN counts as the maximum, the first index wins.
- *   sampling, no NaN or +inf in the row but the allowed weights underflow to a total of 0: the weights are recomputed
- *             relative to the largest allowed logit (the same distribution without the underflow).
- *   sampling, a NaN or +inf in the row, or every allowed logit -inf: the first allowed index with the largest logit,
- *             a NaN counting as the largest; logprobs stays log_softmax(logits[b])[tokens[b]] (NaN propagates).
- *   no allowed token (V <= 3, pad / unk / start cover the row): the greedy choice.
- * A finite row with a positive allowed total never reaches these rules (its draw does not change).
- * ------------------------------------------------------------------------------------------- */
-int pnmn_sample_tokens(const float* logits, int64_t* tokens, float* logprobs, int B, int V,
-                       int greedy, uint64_t seed, uint64_t row_offset, uint32_t step, int pad_index,
-                       int unk_index, int start_index, void* stream);
-
-/* Sampling under a filter: temperature, top-k and nucleus (top-p) truncation of the distribution a token is drawn from.
- * A filter is (temperature, top_k, top_p); (1, 0, 1) is the identity.  It applies to sampling only: a greedy choice and
- * a teacher-forced pass ignore it.  For one row of logits z[0..V):
- *   A      = every index but pad, unk and start (the allowed set, as above)
- *   s_j    = z_j / temperature, w_j = exp(s_j - max_A s)                                  for j in A
- *   rank   j ranks before i when w_j > w_i, or w_j == w_i and j < i                       (within A)
- *   top_k > 0: keep the top_k first-ranked indices (top_k >= |A| keeps all of A)
- *   top_p < 1: of those, keep i iff the summed weight of the kept indices ranked before i is < top_p * total, total = the
- *              weight top-k kept; the first-ranked index is always kept
- *   draw   inverse CDF in INDEX order over the kept weights, from the uniform pnmn_sample_tokens draws: Philox4x32-10,
- *          counter (row_offset + row, step) -- a filtered and an unfiltered decode from one seed share their random numbers
- *   logprobs (and any loss built from them) stay log_softmax(z)[token] of the UNMODIFIED distribution, as the reference
- *          already scores a draw from which pad / unk / start were removed (seq2seq_base.py:204,220)
- * A row that holds a NaN or +inf, or whose allowed weights sum to 0 in the unfiltered rule, follows that rule's fallback
- * unchanged and ignores the filter; a token is always in [0, V).  With the identity filter each entry point below runs
- * the kernel of its unfiltered counterpart: the same output, bit for bit.  Each returns PNMN_EINVAL and launches nothing
- * for a null filter, a temperature that is not finite or <= 0, top_k < 0, or a top_p outside (0, 1] (NaN included).
- * The filters are HOST memory, read before the call returns, and travel by value in the launch arguments: no device
- * allocation, no copy, no synchronisation.  Otherwise: the arguments, limits and return codes of the counterpart.
- * pnmn_attn_lstm_fwd_group_filtered: filters[i] belongs to jobs[i] and applies when that job's sample == 1; for any
- * other job it is checked and ignored.  The fit and fall-back rule of pnmn_attn_lstm_fwd_group is unchanged. */
-struct pnmn_sampling_filter {
-    float temperature;
-    int32_t top_k;
-    float top_p;
-    int32_t reserved;
-};                         /* 16 bytes; a host argument block (see the declaration conventions), not a work-item record */
-int pnmn_sample_tokens_filtered(const float* logits, int64_t* tokens, float* logprobs, int B, int V,
-                                int greedy, uint64_t seed, uint64_t row_offset, uint32_t step, int pad_index,
-                                int unk_index, int start_index, const struct pnmn_sampling_filter* filter /* HOST */,
-                                void* stream);
-int pnmn_attn_lstm_fwd_filtered(const float* xe, const float* etable, const float* enc, const float* mask,
-                                const float* h0, const float* w_c, const float* w_hh, const float* w_p,
-                                const float* b_p, float* hs, float* cs, float* act, float* ctx, float* probs,
-                                int64_t* tokens, int B, int T, int S, int V, int hidden, int sample,
-                                int pad_index, int unk_index, int start_index, uint64_t seed,
-                                uint64_t row_offset, const int64_t* in_tokens, int64_t in_token_stride,
-                                const struct pnmn_sampling_filter* filter /* HOST */, void* stream);
-int pnmn_attn_lstm_fwd_group_filtered(const pnmn_decoder_fwd_job* jobs, const struct pnmn_sampling_filter* filters /* HOST, one per job */,
-                                      int n, int hidden, void* workspace, void* stream);
-
-/* Sampling and greedy decoding under a token automaton: the free-running modes of pnmn_attn_lstm_fwd / _fwd_group emit only
- * strings the automaton accepts.  INFERENCE ONLY: a constrained draw is not a draw from the model's distribution, and no
- * trainer uses it.  The tables (token_class, next_state, min_left, n_states, n_classes, state 0 = start, 255 = no completion)
- * and the test of a candidate are those of pnmn_attn_lstm_beam_constrained above: HOST pointers, every entry checked, passed
- * by value in the launch arguments and staged into LDS once per workgroup -- no device allocation, no copy, no synchronisation.
- * Every row carries an automaton state (0 at the start) and a finished flag (false at the start).  At step t (0-based) of T a
- * row in state s that has not finished has the allowed set A_c(s, t):
- *   token v, not pad / unk / start and v != end_index   iff  min_left[next_state[s][token_class[v]]] <= T - 1 - t
- *   end_index                                           iff  min_left[s] == 0
- * and its token is chosen as by pnmn_sample_tokens / pnmn_sample_tokens_filtered with A_c in the place of A:
- *   sample == 1: inverse CDF in index order over softmax(z) restricted to A_c, the uniform from the same Philox counter
- *                (row_offset + row, t) -- a constrained and an unconstrained decode from one seed share their random numbers;
- *                under a filter other than the identity: rank, top-k and top-p WITHIN A_c, then the same draw
- *   sample == 2: the first index of the largest logit WITHIN A_c (the unconstrained arg-max looks at all of [0, V))
- *   a row that holds a NaN or +inf (greedy: a NaN), or whose A_c weights sum to 0, follows the fallback rule stated beside
- *                pnmn_sample_tokens with A_c as the allowed set (greedy: the arg-max of that rule within A_c): still in A_c
- *   a row that has emitted end_index is finished: every later step of it emits end_index, its state is frozen, and the token
- *                is fed to the next step as usual
- *   state:       unchanged on end_index, otherwise s <- next_state[s][token_class[token]]
- * By induction min_left[s] <= T - t before every step, so A_c is never empty, and every row, cut at its first end_index, is
- * accepted by the automaton.  With one state, one class and min_left = {0} a sampling pass emits what the unconstrained pass
- * emits up to and including each row's first end_index.  logprobs, and any loss built from the tokens, stay
- * log_softmax(z)[token] of the UNMODIFIED distribution, exactly as for the filtered draw.
- * `filter` is required (the identity (1, 0, 1) is allowed and draws as the unfiltered rule does); it applies to sample == 1.
- * pnmn_attn_lstm_fwd_group_constrained: filters[i] belongs to jobs[i]; the automaton applies to every job with sample != 0;
- * for a job with sample == 0 both are checked and ignored.  The fit and fall-back rule of pnmn_attn_lstm_fwd_group is unchanged.
- * Each returns PNMN_EINVAL and launches nothing for: a null table, a table entry out of range (token_class[v] >= n_classes for
- * v < V, next_state >= n_states), n_states outside 1..PNMN_BEAM_MAX_STATES, n_classes outside 1..PNMN_BEAM_MAX_CLASSES, V outside
- * 1..128, end_index outside [0, V), min_left[0] > T (no accepted string fits; group: any job's T), a null or invalid filter.
- * Otherwise: the arguments, limits and return codes of the unconstrained counterpart. */
-int pnmn_attn_lstm_fwd_constrained(const float* xe, const float* etable, const float* enc, const float* mask,
-                                   const float* h0, const float* w_c, const float* w_hh, const float* w_p,
-                                   const float* b_p, float* hs, float* cs, float* act, float* ctx, float* probs,
-                                   int64_t* tokens, int B, int T, int S, int V, int hidden, int sample,
-                                   int pad_index, int unk_index, int start_index, uint64_t seed,
-                                   uint64_t row_offset, const int64_t* in_tokens, int64_t in_token_stride,
-                                   const struct pnmn_sampling_filter* filter /* HOST */, int end_index,
-                                   const uint8_t* token_class /* HOST */, const uint8_t* next_state /* HOST */,
-                                   const uint8_t* min_left /* HOST */, int n_states, int n_classes, void* stream);
-int pnmn_attn_lstm_fwd_group_constrained(const pnmn_decoder_fwd_job* jobs, const struct pnmn_sampling_filter* filters /* HOST, one per job */,
-                                         int end_index, const uint8_t* token_class /* HOST */, const uint8_t* next_state /* HOST */,
-                                         const uint8_t* min_left /* HOST */, int n_states, int n_classes,
-                                         int n, int hidden, void* workspace, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Free-running samples from the program prior p(z), all T steps in one launch       program_prior.py:174-301
@@ -798,9 +779,9 @@ int pnmn_attn_lstm_fwd_group_constrained(const pnmn_decoder_fwd_job* jobs, const
  *   proj[b][t][0..256) = p  when `proj` is not null;   last = token
  * A row keeps running after end_index, as the reference's loop does; the caller trims.
  * w_hh0, w_ih1, w_hh1 ([1024][256]) and w_proj ([256][256]) are in MFMA fragment order (see pnmn_lstm_seq_fwd).
- * `filter` (HOST, may be null = the identity) applies to mode 1 only, by the rule beside pnmn_sample_tokens_filtered.  The
+ * `filter` (HOST, may be null = the identity) applies to mode 1 only, by the rule beside pnmn_sample_tokens.  The
  * automaton tables (HOST; all three null = unconstrained) apply to modes 1 and 2 by the rule beside
- * pnmn_attn_lstm_fwd_constrained: A_c in the place of the allowed set, a finished row emits end_index, its state frozen; mode 0
+ * pnmn_attn_lstm_fwd: A_c in the place of the allowed set, a finished row emits end_index, its state frozen; mode 0
  * checks them as far as it can without a vocabulary and ignores them.  The non-finite fallbacks of pnmn_sample_tokens apply,
  * so a token is always in [0, V).  With the identity filter and no automaton the plain kernel runs: the same output, bit for
  * bit, as with filter = null.
@@ -808,7 +789,7 @@ int pnmn_attn_lstm_fwd_group_constrained(const pnmn_decoder_fwd_job* jobs, const
  * workgroups: no workspace, no counters, no co-residency.
  * Returns PNMN_EINVAL and launches nothing for: hidden != 256, V outside 1..128, T < 1, B < 0, mode outside 0..2, start_index
  * outside [0, V), mode 0 without in_tokens, a null required pointer (everything but proj, in_tokens, filter and the tables), an
- * invalid filter, some but not all of the tables, and whatever pnmn_attn_lstm_fwd_constrained refuses in its tables (min_left[0] > T
+ * invalid filter, some but not all of the tables, and whatever pnmn_attn_lstm_fwd refuses in its tables (min_left[0] > T
  * included).  B == 0 returns 0 without a launch.
  * ------------------------------------------------------------------------------------------- */
 int pnmn_prior_sample(const float* table0, const float* w_hh0, const float* w_ih1, const float* w_hh1, const float* b1,
@@ -1202,7 +1183,7 @@ int64_t pnmn_colsum_workspace_bytes(int R, int C);
 /* Library self-description (no GPU needed).  13 also carries pnmn_valid_rows / pnmn_gemm_rows (new functions only: no record changes).  12: pnmn_gemm_desc gains colsum / colsum2 (120 bytes), pnmn_gemm_workspace_bytes includes the column-sum partials.  11 = round 6: pnmn_gemm / pnmn_colsum / pnmn_token_rows, an accumulate flag on pnmn_embedding_grad, row stride + second bias output on pnmn_token_table_bwd.  10 = round 5.  8 = round 4: the trunk executor of version 7 removed again (pnmn_trunk_exec, pnmn_plan_batch_owners, the EXEC launch op; pnmn_trunk_io shrinks to 224 bytes), streamed convolution kernel behind the same pnmn_conv_nhwc entry points (split 16 gone).  7: the trunk executor (pnmn_trunk_exec, EXEC launch op, pnmn_trunk_io grows to 232 bytes), conv segments in one launch; 6 = round 3: pnmn_conv_nhwc_cus, paired decoder launches, pnmn_attn_denc, pnmn_joint_objective, ingest by copy engine; 5: the trunk planner (pnmn_trunk_*), pnmn_set_rows, SET_ROWS / ACCUMULATE / ZERO launch ops; 4: pnmn_cluster_reserve_cus.  3 = round 2: 28x28 maps in the conv / weight-gradient / layout /
  * pool entry points, pnmn_conv_nhwc_launches takes H and W, sequence-loss / ELBO / feature-ingest entry points
  * added, the persistent dataflow executor (pnmn_dataflow) removed. */
-#define PNMN_ABI_VERSION 13   /* what pnmn_abi_version() returns; the binding refuses a library built from another */
+#define PNMN_ABI_VERSION 14   /* what pnmn_abi_version() returns; the binding refuses a library built from another */
 int pnmn_abi_version(void);
 
 #ifdef __cplusplus

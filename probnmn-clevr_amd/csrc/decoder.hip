@@ -424,79 +424,45 @@ __global__ __launch_bounds__(512) void attn_lstm_bwd_kernel(const BwdArgs a) {
 
 extern "C" {
 
-// `filter`: null (pnmn_attn_lstm_fwd) or a filter to check; it applies to a sampling pass unless it is the identity
+// `filter`: null or a checked filter; it applies to a sampling pass unless it is the identity
 // `automaton`: null, or the checked tables of a constrained call: a free-running pass then runs the constrained kernels
-static int attn_lstm_fwd_launch(const float* xe, const float* etable, const float* enc, const float* mask, const float* h0,
-                                const float* w_c, const float* w_hh, const float* w_p, const float* b_p, float* hs, float* cs,
-                                float* act, float* ctx, float* probs, int64_t* tokens, int B, int T, int S, int V, int hidden,
-                                int sample, int pad_index, int unk_index, int start_index, uint64_t seed, uint64_t row_offset,
-                                const int64_t* in_tokens, int64_t in_token_stride, const pnmn_sampling_filter* filter,
+static int attn_lstm_fwd_launch(const pnmn_decoder_fwd_job& j, int hidden, const pnmn_sampling_filter* filter,
                                 const pnmn::TokenAutomaton* automaton, void* stream) {
-    if (filter && !pnmn::filter_valid(filter)) return PNMN_EINVAL;
-    if (B <= 0 || T <= 0) return 0;
-    if (!enc || !mask || !h0 || !w_c || !w_hh || !hs || !cs || !act || !ctx || !probs) return PNMN_EINVAL;
-    if (sample ? (!etable || !w_p || !b_p || !tokens) : (!xe && !(etable && in_tokens))) return PNMN_EINVAL;
-    if (hidden != H || S < 1 || S > MAXS || (sample && (V < 1 || V > MAXV))) return PNMN_ESHAPE;
-    FwdArgs a{xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, hs, cs, act, ctx, probs, tokens, (!sample && !xe) ? in_tokens : nullptr,
-              (long)in_token_stride, B, T, S, V, sample, pad_index, unk_index, start_index, seed, row_offset};
-    const dim3 grid((B + ROWS - 1) / ROWS);
+    const int sample = j.sample;
+    if (j.B <= 0 || j.T <= 0) return 0;
+    if (!j.enc || !j.mask || !j.h0 || !j.w_c || !j.w_hh || !j.hs || !j.cs || !j.act || !j.ctx || !j.probs) return PNMN_EINVAL;
+    if (sample ? (!j.etable || !j.w_p || !j.b_p || !j.tokens) : (!j.xe && !(j.etable && j.in_tokens))) return PNMN_EINVAL;
+    if (hidden != H || j.S < 1 || j.S > MAXS || (sample && (j.V < 1 || j.V > MAXV))) return PNMN_ESHAPE;
+    FwdArgs a{j.xe, j.etable, j.enc, j.mask, j.h0, j.w_c, j.w_hh, j.w_p, j.b_p, j.hs, j.cs, j.act, j.ctx, j.probs, j.tokens,
+              (!sample && !j.xe) ? j.in_tokens : nullptr, (long)j.in_token_stride, j.B, j.T, j.S, j.V, sample, j.pad_index,
+              j.unk_index, j.start_index, j.seed, j.row_offset};
+    const dim3 grid((j.B + ROWS - 1) / ROWS);
+    const bool filtered = filter && sample == 1 && !pnmn::filter_is_identity(*filter);
+    const pnmn::SamplingFilter f = filtered ? pnmn::SamplingFilter{filter->temperature, filter->top_k, filter->top_p}
+                                            : pnmn::SamplingFilter{1.f, 0, 1.f};
     if (automaton && sample) {
         ConstrainedFwdArgs c{};
         static_cast<FwdArgs&>(c) = a;
         c.automaton = *automaton;
-        if (sample == 1 && !pnmn::filter_is_identity(*filter))
-            hipLaunchKernelGGL((attn_lstm_fwd_kernel<true, true>), grid, dim3(512), 0, static_cast<hipStream_t>(stream), c,
-                               pnmn::SamplingFilter{filter->temperature, filter->top_k, filter->top_p});
-        else
-            hipLaunchKernelGGL((attn_lstm_fwd_kernel<false, true>), grid, dim3(512), 0, static_cast<hipStream_t>(stream), c,
-                               pnmn::SamplingFilter{1.f, 0, 1.f});
-        return (int)hipGetLastError();
+        if (filtered) hipLaunchKernelGGL((attn_lstm_fwd_kernel<true, true>), grid, dim3(512), 0, static_cast<hipStream_t>(stream), c, f);
+        else hipLaunchKernelGGL((attn_lstm_fwd_kernel<false, true>), grid, dim3(512), 0, static_cast<hipStream_t>(stream), c, f);
+    } else {
+        if (filtered) hipLaunchKernelGGL(attn_lstm_fwd_kernel<true>, grid, dim3(512), 0, static_cast<hipStream_t>(stream), a, f);
+        else hipLaunchKernelGGL(attn_lstm_fwd_kernel<false>, grid, dim3(512), 0, static_cast<hipStream_t>(stream), a, f);
     }
-    if (filter && sample == 1 && !pnmn::filter_is_identity(*filter))
-        hipLaunchKernelGGL(attn_lstm_fwd_kernel<true>, grid, dim3(512), 0, static_cast<hipStream_t>(stream), a,
-                           pnmn::SamplingFilter{filter->temperature, filter->top_k, filter->top_p});
-    else
-        hipLaunchKernelGGL(attn_lstm_fwd_kernel<false>, grid, dim3(512), 0, static_cast<hipStream_t>(stream), a,
-                           pnmn::SamplingFilter{1.f, 0, 1.f});
     return (int)hipGetLastError();
 }
 
-int pnmn_attn_lstm_fwd(const float* xe, const float* etable, const float* enc, const float* mask, const float* h0,
-                       const float* w_c, const float* w_hh, const float* w_p, const float* b_p, float* hs, float* cs,
-                       float* act, float* ctx, float* probs, int64_t* tokens, int B, int T, int S, int V, int hidden,
-                       int sample, int pad_index, int unk_index, int start_index, uint64_t seed, uint64_t row_offset,
-                       const int64_t* in_tokens, int64_t in_token_stride, void* stream) {
-    return attn_lstm_fwd_launch(xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, hs, cs, act, ctx, probs, tokens, B, T, S, V, hidden,
-                                sample, pad_index, unk_index, start_index, seed, row_offset, in_tokens, in_token_stride, nullptr,
-                                nullptr, stream);
-}
-
-int pnmn_attn_lstm_fwd_filtered(const float* xe, const float* etable, const float* enc, const float* mask, const float* h0,
-                                const float* w_c, const float* w_hh, const float* w_p, const float* b_p, float* hs, float* cs,
-                                float* act, float* ctx, float* probs, int64_t* tokens, int B, int T, int S, int V, int hidden,
-                                int sample, int pad_index, int unk_index, int start_index, uint64_t seed, uint64_t row_offset,
-                                const int64_t* in_tokens, int64_t in_token_stride, const pnmn_sampling_filter* filter,
-                                void* stream) {
-    if (!pnmn::filter_valid(filter)) return PNMN_EINVAL;
-    return attn_lstm_fwd_launch(xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, hs, cs, act, ctx, probs, tokens, B, T, S, V, hidden,
-                                sample, pad_index, unk_index, start_index, seed, row_offset, in_tokens, in_token_stride, filter,
-                                nullptr, stream);
-}
-
-int pnmn_attn_lstm_fwd_constrained(const float* xe, const float* etable, const float* enc, const float* mask, const float* h0,
-                                   const float* w_c, const float* w_hh, const float* w_p, const float* b_p, float* hs, float* cs,
-                                   float* act, float* ctx, float* probs, int64_t* tokens, int B, int T, int S, int V, int hidden,
-                                   int sample, int pad_index, int unk_index, int start_index, uint64_t seed, uint64_t row_offset,
-                                   const int64_t* in_tokens, int64_t in_token_stride, const pnmn_sampling_filter* filter,
-                                   int end_index, const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left,
-                                   int n_states, int n_classes, void* stream) {
-    if (!pnmn::filter_valid(filter)) return PNMN_EINVAL;
+int pnmn_attn_lstm_fwd(const pnmn_decoder_fwd_job* job, int hidden, const pnmn_sampling_filter* filter, int end_index,
+                       const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left, int n_states,
+                       int n_classes, void* stream) {
+    if (!job || (filter && !pnmn::filter_valid(filter))) return PNMN_EINVAL;
+    if (!token_class && !next_state && !min_left) return attn_lstm_fwd_launch(*job, hidden, filter, nullptr, stream);
     pnmn::TokenAutomaton automaton;
-    if (const int e = pnmn::fill_automaton(automaton, token_class, next_state, min_left, n_states, n_classes, sample ? V : 0, T, end_index))
+    if (const int e = pnmn::fill_automaton(automaton, token_class, next_state, min_left, n_states, n_classes,
+                                           job->sample ? job->V : 0, job->T, end_index))
         return e;
-    return attn_lstm_fwd_launch(xe, etable, enc, mask, h0, w_c, w_hh, w_p, b_p, hs, cs, act, ctx, probs, tokens, B, T, S, V, hidden,
-                                sample, pad_index, unk_index, start_index, seed, row_offset, in_tokens, in_token_stride, filter,
-                                &automaton, stream);
+    return attn_lstm_fwd_launch(*job, hidden, filter, &automaton, stream);
 }
 
 int pnmn_attn_lstm_bwd(const float* dhs, const float* act, const float* cs, const float* hs, const float* ctx,

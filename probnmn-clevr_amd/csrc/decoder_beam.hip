@@ -20,7 +20,7 @@
 // kernel's stores for the backward.
 // Nothing is saved for a backward pass: the only global writes are tokens / scores and the optional per-step trace.
 //
-// Constrained variant (pnmn_attn_lstm_beam_constrained, template parameter C): every slot also carries one byte, the state
+// Constrained variant (pnmn_attn_lstm_beam with tables, template parameter C): every slot also carries one byte, the state
 // of a token automaton (class of every token, next state per class, fewest further tokens to an accepting state).  The
 // three tables arrive by value in the launch arguments and are staged into LDS once; the candidate stage alone differs:
 // a live hypothesis offers a token only if an accepting state stays reachable in the steps that remain, and @end@ only in
@@ -467,11 +467,15 @@ int launch_beam_width(int beam, const typename beam_args<C>::type& a, hipStream_
     }
 }
 
-// The argument checks both entry points share: 0 = launch, 1 = nothing to do, PNMN_EINVAL.
-int check_beam_arguments(const float* etable, const float* enc, const float* mask, const float* h0, const float* w_c,
-                         const float* w_hh, const float* w_p, const float* b_p, const int64_t* tokens, const float* scores,
-                         const int32_t* trace_tokens, const int32_t* trace_backptr, const float* trace_scores, int B, int T, int S,
-                         int V, int hidden, int beam, int start_index, int end_index) {
+}  // namespace
+
+extern "C" int pnmn_attn_lstm_beam(const float* etable, const float* enc, const float* mask, const float* h0,
+                                   const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
+                                   int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
+                                   float* trace_scores, int B, int T, int S, int V, int hidden, int beam, int pad_index,
+                                   int unk_index, int start_index, int end_index, const uint8_t* token_class,
+                                   const uint8_t* next_state, const uint8_t* min_left, int n_states, int n_classes,
+                                   void* stream) {
     if (B < 0 || T < 0) return PNMN_EINVAL;
     if (!etable || !enc || !mask || !h0 || !w_c || !w_hh || !w_p || !b_p || !tokens || !scores) return PNMN_EINVAL;
     const int traced = (trace_tokens != nullptr) + (trace_backptr != nullptr) + (trace_scores != nullptr);
@@ -480,34 +484,10 @@ int check_beam_arguments(const float* etable, const float* enc, const float* mas
     // every index the kernel looks a table row up by, or writes as a token, is inside the vocabulary
     if (start_index < 0 || start_index >= V || end_index < 0 || end_index >= V) return PNMN_EINVAL;
     if (beam != 1 && beam != 2 && beam != 4 && beam != 8 && beam != 16) return PNMN_EINVAL;
-    return B == 0 || T == 0 ? 1 : 0;
-}
-
-}  // namespace
-
-extern "C" int pnmn_attn_lstm_beam(const float* etable, const float* enc, const float* mask, const float* h0,
-                                   const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
-                                   int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
-                                   float* trace_scores, int B, int T, int S, int V, int hidden, int beam, int pad_index,
-                                   int unk_index, int start_index, int end_index, void* stream) {
-    const int todo = check_beam_arguments(etable, enc, mask, h0, w_c, w_hh, w_p, b_p, tokens, scores, trace_tokens, trace_backptr,
-                                          trace_scores, B, T, S, V, hidden, beam, start_index, end_index);
-    if (todo != 0) return todo < 0 ? todo : 0;
-    const BeamArgs a{etable, enc, mask, h0, w_c, w_hh, w_p, b_p, tokens, scores, trace_tokens, trace_backptr, trace_scores,
-                     B, T, S, V, pad_index, unk_index, start_index, end_index};
-    return launch_beam_width<false>(beam, a, static_cast<hipStream_t>(stream));
-}
-
-extern "C" int pnmn_attn_lstm_beam_constrained(const float* etable, const float* enc, const float* mask, const float* h0,
-                                               const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
-                                               int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
-                                               float* trace_scores, int B, int T, int S, int V, int hidden, int beam,
-                                               int pad_index, int unk_index, int start_index, int end_index,
-                                               const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left,
-                                               int n_states, int n_classes, void* stream) {
-    const int todo = check_beam_arguments(etable, enc, mask, h0, w_c, w_hh, w_p, b_p, tokens, scores, trace_tokens, trace_backptr,
-                                          trace_scores, B, T, S, V, hidden, beam, start_index, end_index);
-    if (todo < 0) return todo;
+    const BeamArgs plain{etable, enc, mask, h0, w_c, w_hh, w_p, b_p, tokens, scores, trace_tokens, trace_backptr, trace_scores,
+                         B, T, S, V, pad_index, unk_index, start_index, end_index};
+    if (!token_class && !next_state && !min_left)
+        return B == 0 || T == 0 ? 0 : launch_beam_width<false>(beam, plain, static_cast<hipStream_t>(stream));
     if (!token_class || !next_state || !min_left) return PNMN_EINVAL;
     if (n_states < 1 || n_states > MAX_STATES || n_classes < 1 || n_classes > MAX_CLASSES) return PNMN_EINVAL;
     // every table entry the kernel indexes with stays inside the tables (min_left is only compared)
@@ -521,9 +501,8 @@ extern "C" int pnmn_attn_lstm_beam_constrained(const float* etable, const float*
         a.next_state[i] = next_state[i];
     }
     for (int s = 0; s < n_states; ++s) a.min_left[s] = min_left[s];
-    if (todo != 0) return 0;
-    static_cast<BeamArgs&>(a) = BeamArgs{etable, enc, mask, h0, w_c, w_hh, w_p, b_p, tokens, scores, trace_tokens, trace_backptr,
-                                         trace_scores, B, T, S, V, pad_index, unk_index, start_index, end_index};
+    if (B == 0 || T == 0) return 0;
+    static_cast<BeamArgs&>(a) = plain;
     a.n_classes = n_classes;
     return launch_beam_width<true>(beam, a, static_cast<hipStream_t>(stream));
 }

@@ -534,7 +534,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
-// ... and under a token automaton (pnmn_attn_lstm_fwd_group_constrained): every free-running pass of the launch is constrained
+// ... and under a token automaton (the tables of pnmn_attn_lstm_fwd_group): every free-running pass of the launch is constrained
 // by the one automaton `au`.  M: 0 teacher forced, 1 constrained (sampling under the identity filter, or greedy), 2 constrained
 // sampling under its filter.  The pair is instantiated for M0 <= M1 only: the host puts the passes in that order.
 template <bool OVERLAP, bool FILT>
@@ -1162,7 +1162,7 @@ int launch_fwd_constrained(const pnmn_decoder_fwd_job* j, const pnmn_sampling_fi
     int m[2] = {0, 0};
     pnmn::SamplingFilter ff[2] = {{1.f, 0, 1.f}, {1.f, 0, 1.f}};
     for (int i = 0; i < n; ++i) {
-        m[i] = j[i].sample == 0 ? 0 : (j[i].sample == 1 && !pnmn::filter_is_identity(f[i])) ? 2 : 1;
+        m[i] = j[i].sample == 0 ? 0 : (f && j[i].sample == 1 && !pnmn::filter_is_identity(f[i])) ? 2 : 1;
         if (m[i] == 2) ff[i] = pnmn::SamplingFilter{f[i].temperature, f[i].top_k, f[i].top_p};
     }
     int* sync = nullptr;
@@ -1246,26 +1246,16 @@ int64_t pnmn_attn_lstm_group_workspace_bytes(const int32_t* rows, int n, int bac
     return workspace_bytes(rows, n, backward != 0);
 }
 
-int pnmn_attn_lstm_fwd_group(const pnmn_decoder_fwd_job* jobs, int n, int hidden, void* workspace, void* stream) {
+int pnmn_attn_lstm_fwd_group(const pnmn_decoder_fwd_job* jobs, const pnmn_sampling_filter* filters, int end_index,
+                             const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left, int n_states,
+                             int n_classes, int n, int hidden, void* workspace, void* stream) {
     if (!jobs || !workspace || n < 1 || n > 2) return PNMN_EINVAL;
-    return launch_fwd(jobs, nullptr, n, hidden, workspace, static_cast<hipStream_t>(stream));
-}
-
-int pnmn_attn_lstm_fwd_group_filtered(const pnmn_decoder_fwd_job* jobs, const pnmn_sampling_filter* filters, int n, int hidden,
-                                      void* workspace, void* stream) {
-    if (!jobs || !filters || !workspace || n < 1 || n > 2) return PNMN_EINVAL;
-    for (int i = 0; i < n; ++i)
+    for (int i = 0; filters && i < n; ++i)
         if (!pnmn::filter_valid(filters + i)) return PNMN_EINVAL;
-    return launch_fwd(jobs, filters, n, hidden, workspace, static_cast<hipStream_t>(stream));
-}
-
-int pnmn_attn_lstm_fwd_group_constrained(const pnmn_decoder_fwd_job* jobs, const pnmn_sampling_filter* filters, int end_index,
-                                         const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left,
-                                         int n_states, int n_classes, int n, int hidden, void* workspace, void* stream) {
-    if (!jobs || !filters || !workspace || n < 1 || n > 2) return PNMN_EINVAL;
+    if (!token_class && !next_state && !min_left)
+        return launch_fwd(jobs, filters, n, hidden, workspace, static_cast<hipStream_t>(stream));
     int V = 0, T = INT_MAX;  // of the free-running jobs: one automaton, one vocabulary; the fewest steps
     for (int i = 0; i < n; ++i) {
-        if (!pnmn::filter_valid(filters + i)) return PNMN_EINVAL;
         if (jobs[i].sample == 0) continue;
         if (V != 0 && jobs[i].V != V) return PNMN_EINVAL;
         V = jobs[i].V;

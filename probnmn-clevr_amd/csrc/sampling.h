@@ -163,14 +163,14 @@ __device__ inline int choose_token_fallback(const float (&v)[K], int V, bool gre
     return first_argmax(v, in_row);  // greedy, or no allowed token at all
 }
 
-// A sampling filter (temperature, top-k, top-p): the rule is stated beside pnmn_sample_tokens_filtered in
+// A sampling filter (temperature, top-k, top-p): the rule is stated beside pnmn_sample_tokens in
 // include/probnmn_hip.h.  It travels by value in the launch arguments of the filtered kernels only.
 struct SamplingFilter {
     float temperature;
     int top_k;
     float top_p;
 };
-// what every filtered entry point checks before it launches anything, and which filters change nothing
+// what an entry point checks of a filter it is given before it launches anything, and which filters change nothing
 inline bool filter_valid(const pnmn_sampling_filter* f) {
     return f && isfinite(f->temperature) && f->temperature > 0.f && f->top_k >= 0 && f->top_p > 0.f && f->top_p <= 1.f;
 }
@@ -315,7 +315,7 @@ __device__ inline int choose_row_token(const float* logits, int V, int mode, int
     return min(max(choice, 0), V - 1);
 }
 
-// ---- the token automaton of the constrained decoders (the rule: include/probnmn_hip.h, beside pnmn_attn_lstm_fwd_constrained) ----
+// ---- the token automaton of the constrained decoders (the rule: include/probnmn_hip.h, beside pnmn_attn_lstm_fwd) ----
 // The tables as the entry points check them and as they travel BY VALUE in the launch arguments; a workgroup stages them
 // into LDS once (stage_automaton).  Unused entries are 0.
 constexpr int AUTOMATON_STATES = PNMN_BEAM_MAX_STATES, AUTOMATON_CLASSES = PNMN_BEAM_MAX_CLASSES, AUTOMATON_TOKENS = 128;
@@ -328,7 +328,7 @@ struct TokenAutomaton {
 constexpr int AUTOMATON_LDS_BYTES = AUTOMATON_TOKENS + AUTOMATON_STATES * AUTOMATON_CLASSES + AUTOMATON_STATES;  // 672
 static_assert(AUTOMATON_STATES * AUTOMATON_CLASSES == 512 && AUTOMATON_TOKENS <= 512, "staged by 512 threads, one entry each");
 
-// What the constrained entry points check before they launch anything: 0 and `out` filled, or PNMN_EINVAL.  V, T: of the
+// What an entry point checks of the tables it is given before it launches anything: 0 and `out` filled, or PNMN_EINVAL.  V, T: of the
 // free-running passes the automaton applies to; V = 0 when there is none (a teacher-forced call: the tables are checked as far
 // as they can be without a vocabulary, and ignored).
 inline int fill_automaton(TokenAutomaton& out, const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left,

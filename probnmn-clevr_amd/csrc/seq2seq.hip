@@ -172,29 +172,19 @@ int pnmn_lstm_cell_bwd(const float* act, const float* c_prev, const float* c, co
 
 int pnmn_sample_tokens(const float* logits, int64_t* tokens, float* logprobs, int B, int V, int greedy,
                        uint64_t seed, uint64_t row_offset, uint32_t step, int pad_index, int unk_index,
-                       int start_index, void* stream) {
+                       int start_index, const pnmn_sampling_filter* filter, void* stream) {
+    if (filter && !pnmn::filter_valid(filter)) return PNMN_EINVAL;
     if (B <= 0) return 0;
     if (!logits || !tokens || !logprobs || V <= 0) return PNMN_EINVAL;
     if (V > 64 * MAXV) return PNMN_ESHAPE;
-    hipLaunchKernelGGL(sample_tokens_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
-                       tokens, logprobs, B, V, greedy, seed, row_offset, step, pad_index, unk_index, start_index,
-                       pnmn::SamplingFilter{1.f, 0, 1.f});
-    return (int)hipGetLastError();
-}
-
-int pnmn_sample_tokens_filtered(const float* logits, int64_t* tokens, float* logprobs, int B, int V, int greedy,
-                                uint64_t seed, uint64_t row_offset, uint32_t step, int pad_index, int unk_index,
-                                int start_index, const pnmn_sampling_filter* filter, void* stream) {
-    if (!pnmn::filter_valid(filter)) return PNMN_EINVAL;
-    if (greedy || pnmn::filter_is_identity(*filter))
-        return pnmn_sample_tokens(logits, tokens, logprobs, B, V, greedy, seed, row_offset, step, pad_index, unk_index,
-                                  start_index, stream);
-    if (B <= 0) return 0;
-    if (!logits || !tokens || !logprobs || V <= 0) return PNMN_EINVAL;
-    if (V > 64 * MAXV) return PNMN_ESHAPE;
-    hipLaunchKernelGGL(sample_tokens_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
-                       tokens, logprobs, B, V, 0, seed, row_offset, step, pad_index, unk_index, start_index,
-                       pnmn::SamplingFilter{filter->temperature, filter->top_k, filter->top_p});
+    if (!filter || greedy || pnmn::filter_is_identity(*filter))
+        hipLaunchKernelGGL(sample_tokens_kernel<false>, dim3((B + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
+                           tokens, logprobs, B, V, greedy, seed, row_offset, step, pad_index, unk_index, start_index,
+                           pnmn::SamplingFilter{1.f, 0, 1.f});
+    else
+        hipLaunchKernelGGL(sample_tokens_kernel<true>, dim3((B + 3) / 4), dim3(256), 0, static_cast<hipStream_t>(stream), logits,
+                           tokens, logprobs, B, V, 0, seed, row_offset, step, pad_index, unk_index, start_index,
+                           pnmn::SamplingFilter{filter->temperature, filter->top_k, filter->top_p});
     return (int)hipGetLastError();
 }
 

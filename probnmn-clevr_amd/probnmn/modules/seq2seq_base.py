@@ -634,15 +634,15 @@ def _decoder_forward(tensors, metas) -> _DecoderLaunch:
     ws = _decoder_workspace([sd[0][0].size(0) for sd in sides], False, dev)
     lib = _hip.lib()
     # ``meta["filter"]``: the pass's sampling filter (``sampling_filter``), honoured when it samples; with none anywhere the
-    # unfiltered entry points are called, as ever
+    # library gets a null ``filters``
     filters = None
     if any(m.get("filter") is not None for m in metas):
         filters = np.zeros(n, _hip.SAMPLING_FILTER)
         for k, m in enumerate(metas):
             filters[k] = (*(m.get("filter") or IDENTITY_FILTER), 0)
     # ``meta["constraint"]``: (token_class, next_state, min_left, end index) of a free-running pass that decodes under a token
-    # automaton (``constraint_tables``).  The constrained entry points apply ONE automaton to every free-running pass of the
-    # launch, so passes side by side name the same one, or none
+    # automaton (``constraint_tables``).  The library applies ONE automaton to every free-running pass of the launch, so
+    # passes side by side name the same one, or none
     constraint = None
     for m in metas:
         c = m.get("constraint")
@@ -651,36 +651,18 @@ def _decoder_forward(tensors, metas) -> _DecoderLaunch:
         if c is not None and constraint is not None and c is not constraint:
             raise ValueError("decoder passes side by side decode under one token automaton")
         constraint = c if c is not None else constraint
+    automaton = (0, 0, 0, 0, 0, 0)  # (end index, three tables, n_states, n_classes): null tables = unconstrained
     if constraint is not None:
         if any(m["mode"] != 0 and m.get("constraint") is None for m in metas):
             raise ValueError("a constrained and an unconstrained free-running pass cannot share a launch")
-        if filters is None:
-            filters = np.zeros(n, _hip.SAMPLING_FILTER)
-            filters[:] = (*IDENTITY_FILTER, 0)
         tc, ns, ml, end = constraint  # (host arrays: the library checks every entry and passes them by value)
         automaton = (end, tc.ctypes.data, ns.ctypes.data, ml.ctypes.data, ns.shape[0], ns.shape[1])
-        if ws is not None:
-            _hip.check(lib.pnmn_attn_lstm_fwd_group_constrained(jobs.ctypes.data, filters.ctypes.data, *automaton, n, Hd, ws.data_ptr(),
-                                                                _hip.stream_ptr(dev)), "attn_lstm_fwd_group_constrained")
-        elif n == 1:
-            j = jobs[0].item()
-            _hip.check(lib.pnmn_attn_lstm_fwd_constrained(*j[:15], *j[19:23], Hd, *j[23:27], j[17], j[18], j[15], j[16],
-                                                          filters.ctypes.data, *automaton, _hip.stream_ptr(dev)),
-                       "attn_lstm_fwd_constrained")
-        else:
-            raise _hip.HipLibraryError("decoder passes side by side need the multi-CU decoder kernels (none on this device)")
-    elif ws is not None and filters is not None:
-        _hip.check(lib.pnmn_attn_lstm_fwd_group_filtered(jobs.ctypes.data, filters.ctypes.data, n, Hd, ws.data_ptr(),
-                                                         _hip.stream_ptr(dev)), "attn_lstm_fwd_group_filtered")
-    elif ws is not None:
-        _hip.check(lib.pnmn_attn_lstm_fwd_group(jobs.ctypes.data, n, Hd, ws.data_ptr(), _hip.stream_ptr(dev)), "attn_lstm_fwd_group")
+    options = (0 if filters is None else filters.ctypes.data, *automaton)
+    if ws is not None:
+        _hip.check(lib.pnmn_attn_lstm_fwd_group(jobs.ctypes.data, *options, n, Hd, ws.data_ptr(), _hip.stream_ptr(dev)),
+                   "attn_lstm_fwd_group")
     elif n == 1:
-        j = jobs[0].item()  # (the record's fields in order: 16 pointers, stride, seed, row offset, 8 ints)
-        args = (*j[:15], *j[19:23], Hd, *j[23:27], j[17], j[18], j[15], j[16])
-        if filters is not None:
-            _hip.check(lib.pnmn_attn_lstm_fwd_filtered(*args, filters.ctypes.data, _hip.stream_ptr(dev)), "attn_lstm_fwd_filtered")
-        else:
-            _hip.check(lib.pnmn_attn_lstm_fwd(*args, _hip.stream_ptr(dev)), "attn_lstm_fwd")
+        _hip.check(lib.pnmn_attn_lstm_fwd(jobs.ctypes.data, Hd, *options, _hip.stream_ptr(dev)), "attn_lstm_fwd")
     else:
         raise _hip.HipLibraryError("decoder passes side by side need the multi-CU decoder kernels (none on this device)")
     return _DecoderLaunch(tuple(t for sd in sides for t in sd[0]), tuple(t for sd in sides for t in sd[1]),
@@ -833,7 +815,7 @@ IDENTITY_FILTER = (1.0, 0, 1.0)
 
 def sampling_filter(temperature=1.0, top_k=0, top_p=1.0):
     """(temperature, top_k, top_p) as the kernels take them (the rule: include/probnmn_hip.h, beside
-    ``pnmn_sample_tokens_filtered``), or None for the identity filter (1, 0, 1).  ``ValueError`` for a temperature that is not
+    ``pnmn_sample_tokens``), or None for the identity filter (1, 0, 1).  ``ValueError`` for a temperature that is not
     finite or not positive, a negative or non-integer ``top_k``, a ``top_p`` outside (0, 1]."""
     try:
         t, p = float(temperature), float(top_p)
@@ -871,15 +853,10 @@ def choose_tokens(logits: torch.Tensor, greedy: bool, seed: int, row_offset: int
     B, V = logits.shape
     tokens = torch.empty(B, dtype=torch.long, device=logits.device)
     lp = torch.empty(B, dtype=torch.float32, device=logits.device)
-    if filt is None:
-        _hip.check(_hip.lib().pnmn_sample_tokens(logits.data_ptr(), tokens.data_ptr(), lp.data_ptr(), B, V, int(greedy),
-                                                 seed, row_offset, step, pad, unk, start,
-                                                 _hip.stream_ptr(logits.device)), "sample_tokens")
-    else:
-        rec = np.array([(*filt, 0)], _hip.SAMPLING_FILTER)
-        _hip.check(_hip.lib().pnmn_sample_tokens_filtered(logits.data_ptr(), tokens.data_ptr(), lp.data_ptr(), B, V, int(greedy),
-                                                          seed, row_offset, step, pad, unk, start, rec.ctypes.data,
-                                                          _hip.stream_ptr(logits.device)), "sample_tokens_filtered")
+    rec = None if filt is None else np.array([(*filt, 0)], _hip.SAMPLING_FILTER)
+    _hip.check(_hip.lib().pnmn_sample_tokens(logits.data_ptr(), tokens.data_ptr(), lp.data_ptr(), B, V, int(greedy),
+                                             seed, row_offset, step, pad, unk, start, 0 if rec is None else rec.ctypes.data,
+                                             _hip.stream_ptr(logits.device)), "sample_tokens")
     return tokens, lp
 
 
@@ -1337,8 +1314,8 @@ class Seq2SeqBase(nn.Module):
                            temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0) -> Dict[str, torch.Tensor]:
         """A sampled (or, ``greedy``, arg-max) free-running decode over ``max_decoding_steps`` steps in which every row is a
         string the token automaton ``constraint`` accepts (``ProgramCompiler.decoding_automaton``: a valid program), on the
-        persistent decoder kernels the unconstrained decode runs on (``pnmn_attn_lstm_fwd_group_constrained`` /
-        ``pnmn_attn_lstm_fwd_constrained``; the rule is stated in include/probnmn_hip.h).  At every step a row may take only
+        persistent decoder kernels the unconstrained decode runs on (``pnmn_attn_lstm_fwd_group`` / ``pnmn_attn_lstm_fwd``
+        with their tables; the rule is stated in include/probnmn_hip.h beside the latter).  At every step a row may take only
         the tokens from which an accepted string can still be completed in the steps that remain, and @end@ only where the
         string so far is accepted; the draw is the usual one restricted to that set (with ``temperature`` / ``top_k`` /
         ``top_p``: rank, top-k and nucleus within the set), the greedy choice the first largest logit within it.  The
@@ -1402,10 +1379,9 @@ class Seq2SeqBase(nn.Module):
         step-by-step path for this mode: shapes outside the kernel's limits raise ``NotImplementedError``.
 
         ``constraint``: a token automaton (``token_class`` [V], ``next_state`` [n_states, n_classes], ``min_left``
-        [n_states] as uint8 numpy arrays -- ``ProgramCompiler.decoding_automaton``).  The search then runs in
-        ``pnmn_attn_lstm_beam_constrained``: a hypothesis offers a token only while an accepted completion stays reachable
-        in the steps that remain, so every hypothesis with a finite score is accepted by the automaton.  The same keys
-        come back.  ``None``: ``pnmn_attn_lstm_beam``, unconstrained."""
+        [n_states] as uint8 numpy arrays -- ``ProgramCompiler.decoding_automaton``).  The same call then gets its tables:
+        a hypothesis offers a token only while an accepted completion stays reachable in the steps that remain, so every
+        hypothesis with a finite score is accepted by the automaton.  The same keys come back.  ``None``: unconstrained."""
         self._check_beam_arguments(None, beam_size)
         tables = None
         if constraint is not None:
@@ -1440,16 +1416,15 @@ class Seq2SeqBase(nn.Module):
             tr = (torch.empty(B, T, K, dtype=torch.int32, device=dev), torch.empty(B, T, K, dtype=torch.int32, device=dev),
                   torch.empty(B, T, K, dtype=torch.float32, device=dev))
         if B > 0 and T > 0:
-            common = (etable.data_ptr(), enc.data_ptr(), fmask.data_ptr(), h.data_ptr(), w_c_p.data_ptr(), w_hh_p.data_ptr(),
-                      w_p.data_ptr(), b_p.data_ptr(), raw.data_ptr(), scores.data_ptr(),
-                      tr[0].data_ptr() if tr else None, tr[1].data_ptr() if tr else None, tr[2].data_ptr() if tr else None,
-                      B, T, S, V, Hd, K, self._pad_index, self._unk_index, self._start_index, self._end_index)
-            if tables is None:
-                _hip.check(_hip.lib().pnmn_attn_lstm_beam(*common, _hip.stream_ptr(dev)), "attn_lstm_beam")
-            else:  # (the tables are host arrays: the library checks every entry and passes them by value)
-                _hip.check(_hip.lib().pnmn_attn_lstm_beam_constrained(
-                    *common, tables[0].ctypes.data, tables[1].ctypes.data, tables[2].ctypes.data,
-                    tables[1].shape[0], tables[1].shape[1], _hip.stream_ptr(dev)), "attn_lstm_beam_constrained")
+            automaton = (0, 0, 0, 0, 0)  # (null tables: unconstrained)
+            if tables is not None:  # (the tables are host arrays: the library checks every entry and passes them by value)
+                automaton = (tables[0].ctypes.data, tables[1].ctypes.data, tables[2].ctypes.data, *tables[1].shape)
+            _hip.check(_hip.lib().pnmn_attn_lstm_beam(
+                etable.data_ptr(), enc.data_ptr(), fmask.data_ptr(), h.data_ptr(), w_c_p.data_ptr(), w_hh_p.data_ptr(),
+                w_p.data_ptr(), b_p.data_ptr(), raw.data_ptr(), scores.data_ptr(),
+                tr[0].data_ptr() if tr else None, tr[1].data_ptr() if tr else None, tr[2].data_ptr() if tr else None,
+                B, T, S, V, Hd, K, self._pad_index, self._unk_index, self._start_index, self._end_index, *automaton,
+                _hip.stream_ptr(dev)), "attn_lstm_beam")
         beams = self._trim_predictions(raw.view(B * K, T)).view(B, K, T)
         best = beams[:, 0]
         n = (best != self._pad_index).sum(-1).to(scores.dtype)

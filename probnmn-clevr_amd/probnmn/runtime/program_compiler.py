@@ -218,7 +218,7 @@ class ProgramCompiler:
     # ---------------------------------------------------------------------------------
     def decoding_automaton(self, exclude: Sequence[int] = ()) -> "DecodingAutomaton":
         """The validity rule as a left-to-right automaton over token classes, for grammar-constrained beam search
-        (``pnmn_attn_lstm_beam_constrained``): a token string is accepted exactly when ``compile`` calls it valid.
+        (the tables of ``pnmn_attn_lstm_beam``): a token string is accepted exactly when ``compile`` calls it valid.
 
         ``_compile`` reads a program right to left and its verdict depends on the channel counts of the two registers
         alone -- a small deterministic machine over ``register_step``.  A decoder emits left to right, so this is the
@@ -265,7 +265,7 @@ NO_COMPLETION = 255
 
 class DecodingAutomaton:
     """``token_class`` [V], ``next_state`` [n_states, n_classes], ``min_left`` [n_states]: read-only contiguous uint8
-    arrays, state 0 the start state (the layout ``pnmn_attn_lstm_beam_constrained`` takes)."""
+    arrays, state 0 the start state (the layout ``pnmn_attn_lstm_beam`` takes)."""
 
     __slots__ = ("token_class", "next_state", "min_left")
 

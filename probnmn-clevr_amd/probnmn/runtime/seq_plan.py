@@ -580,7 +580,8 @@ class Seq2SeqPlan:
         for j, p in zip(jobs, dec.passes):
             self._decoder_fwd_job(j, dec, p)
         ws = self.bytes_buf(ws_name, _hip.decoder_workspace_bytes(rows, False))
-        calls.add("pnmn_attn_lstm_fwd_group", jobs.ctypes.data, len(jobs), 256, ws.data_ptr(), self.stream)
+        calls.add("pnmn_attn_lstm_fwd_group", jobs.ctypes.data, None, 0, None, None, None, 0, 0,  # (no filters, no automaton)
+                  len(jobs), 256, ws.data_ptr(), self.stream)
         return jobs
 
     def _decoder_losses(self, calls: _Calls, dec: _DecoderSet) -> None:

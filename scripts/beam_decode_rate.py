@@ -15,7 +15,7 @@ whole ``decode_beam`` call -- the per-call token table, the trim and the loss wi
 (min, max) and the ratios beam / greedy.
 
 ``--constrained``: what the grammar constraint costs.  The variants are then "beam" and "beam_constrained" -- the same
-``decode_beam`` under the program compiler's decoding automaton (``pnmn_attn_lstm_beam_constrained``) -- alternating
+``decode_beam`` under the program compiler's decoding automaton (``pnmn_attn_lstm_beam`` with its tables) -- alternating
 inside each round, and the ratio printed is constrained / unconstrained.  ``--variants``: any subset, in the order given
 (e.g. ``beam`` alone, to compare two builds of the library process against process)."""
 import argparse

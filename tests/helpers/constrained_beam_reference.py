@@ -1,5 +1,5 @@
 """Host reference of the grammar-constrained beam search (test infrastructure): the selection rule of
-``pnmn_attn_lstm_beam_constrained`` (include/probnmn_hip.h) in torch on the CPU, fp64 by default.  It is the search of
+``pnmn_attn_lstm_beam`` with its tables (include/probnmn_hip.h) in torch on the CPU, fp64 by default.  It is the search of
 tests/helpers/beam_reference.py with one more stage between the candidate table and the selection:
 
     state[b][k] = 0 at the start; at step t (0-based) of T, hypothesis k in state s, not finished:

@@ -1,4 +1,4 @@
-"""Host reference of the grammar-constrained token choice (``pnmn_attn_lstm_fwd_constrained``), numpy only, fp64.
+"""Host reference of the grammar-constrained token choice (the automaton rule beside ``pnmn_attn_lstm_fwd``), numpy only, fp64.
 
 Written from the rule stated beside the entry point in include/probnmn_hip.h, not from device output.  A row carries an
 automaton state (0 at the start) and a finished flag.  At step t of T its allowed set A_c holds

@@ -1,6 +1,6 @@
 """Host reference of the filtered token choice (temperature, top-k, top-p), numpy only, fp64.
 
-Written from the rule stated beside ``pnmn_sample_tokens_filtered`` in include/probnmn_hip.h, not from device output.
+Written from the filter rule stated beside ``pnmn_sample_tokens`` in include/probnmn_hip.h, not from device output.
 For one row of logits z and the filter (temperature, top_k, top_p):
 
 * the allowed set A is every index but pad, unk and start; ``s_j = z_j / temperature``, ``w_j = exp(s_j - max_A s)``;

@@ -75,6 +75,34 @@ def emulate_decoder_logits(d, T, choose):
     return torch.stack(out, 1).reshape(B * T, -1).numpy()
 
 
+NO_TABLES = (0, 0, 0, 0, 0, 0)  # (end index, token_class, next_state, min_left, n_states, n_classes): unconstrained
+
+
+def decoder_entry_calls(jobs, sides, ws, filters, tail=NO_TABLES):
+    """Every decoder forward entry on the job records ``jobs`` (``sides[k]``: what ``_prepare_decoder_side`` returned for
+    ``jobs[k]``): ``pnmn_attn_lstm_fwd`` on ``jobs[0]`` and, with a workspace ``ws``, ``pnmn_attn_lstm_fwd_group`` with
+    n = 1 .. len(jobs).  ``filters``: a ``SAMPLING_FILTER`` array, or None for a null pointer; ``tail``: the automaton
+    arguments.  hs, cs and tokens of every job are set to -7 before each call.  Returns [(entry, return code, [copies of
+    hs, cs, tokens of each job])], every job listed whether the call covers it or not: one it does not stays at -7."""
+    from probnmn import _hip
+
+    lib, stream = _hip.lib(), _hip.stream_ptr(sides[0][0][0].device)
+    fptr = 0 if filters is None else filters.ctypes.data
+    calls = [("fwd", lambda: lib.pnmn_attn_lstm_fwd(jobs[0:1].ctypes.data, H, fptr, *tail, stream))]
+    if ws is not None:
+        calls += [("group n=%d" % n, lambda n=n: lib.pnmn_attn_lstm_fwd_group(jobs.ctypes.data, fptr, *tail, n, H, ws.data_ptr(), stream))
+                  for n in range(1, len(jobs) + 1)]
+    out = []
+    for entry, call in calls:
+        outputs = [t for sd in sides for t in (sd[0][0], sd[1][1], sd[0][1])]
+        for t in outputs:
+            t.fill_(-7)
+        rc = call()
+        torch.cuda.synchronize()
+        out.append((entry, rc, [t.clone() for t in outputs]))
+    return out
+
+
 def excused_cap(rows):
     """Rows of a case that may differ from the reference (each still inside the kept set widened by one rank)."""
     return int(np.floor(0.05 * rows)) + 5

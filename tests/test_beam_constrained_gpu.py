@@ -1,4 +1,4 @@
-"""Grammar-constrained beam search on the device (``pnmn_attn_lstm_beam_constrained``, ``decode_beam(constraint=...)``,
+"""Grammar-constrained beam search on the device (the tables of ``pnmn_attn_lstm_beam``, ``decode_beam(constraint=...)``,
 ``predict_answers(constrained=True)``) against the fp64 host reference of tests/helpers/constrained_beam_reference.py.
 
 As in tests/test_beam_gpu.py the main check REPLAYS the device's own prefixes in fp64, here against the CONSTRAINED
@@ -279,9 +279,9 @@ def test_c_abi_refuses_bad_tables():
     def call(B=0, n_states=2, n_classes=3, beam=4, drop=None, **tables):
         t = dict(good, **tables)
         ptr = {k: (None if k == drop else np.ascontiguousarray(v).ctypes.data) for k, v in t.items()}
-        code = lib.pnmn_attn_lstm_beam_constrained(p, p, p, p, p, p, p, p, i.data_ptr(), p, None, None, None, B, 4, 8, V, 256, beam,
-                                                   0, 1, 2, 3, ptr["token_class"], ptr["next_state"], ptr["min_left"],
-                                                   n_states, n_classes, None)
+        code = lib.pnmn_attn_lstm_beam(p, p, p, p, p, p, p, p, i.data_ptr(), p, None, None, None, B, 4, 8, V, 256, beam,
+                                       0, 1, 2, 3, ptr["token_class"], ptr["next_state"], ptr["min_left"],
+                                       n_states, n_classes, None)
         del t
         return code
 

@@ -262,7 +262,7 @@ def test_c_abi_refuses_bad_arguments():
 
     def call(B=1, T=4, S=8, V=44, hidden=256, beam=4, tokens=i.data_ptr(), trace=(None, None, None), start=2, end=3):
         return lib.pnmn_attn_lstm_beam(p, p, p, p, p, p, p, p, tokens, p, trace[0], trace[1], trace[2], B, T, S, V, hidden, beam,
-                                       0, 1, start, end, None)
+                                       0, 1, start, end, None, None, None, 0, 0, None)
 
     for kwargs in (dict(beam=3), dict(beam=32), dict(hidden=128), dict(S=65), dict(S=0), dict(V=129), dict(T=65), dict(tokens=None),
                    dict(trace=(p, None, None)), dict(end=44), dict(start=-1), dict(B=-1)):

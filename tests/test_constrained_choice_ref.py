@@ -178,5 +178,6 @@ def test_python_layer_refuses_bad_constrained_calls(grammar):
         predict_answers(None, None, [], None, constrained=True)
     from probnmn import _hip
 
-    for name in ("pnmn_attn_lstm_fwd_constrained", "pnmn_attn_lstm_fwd_group_constrained"):
+    for name in ("pnmn_attn_lstm_fwd", "pnmn_attn_lstm_fwd_group", "pnmn_attn_lstm_beam"):
         assert name in _hip.SIGNATURES
+        assert name + "_constrained" not in _hip.SIGNATURES  # (an option is an argument, not a second entry point)

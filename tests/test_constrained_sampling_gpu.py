@@ -1,5 +1,5 @@
 """Sampling and greedy decoding under the grammar automaton inside the persistent decoder kernels
-(``pnmn_attn_lstm_fwd_constrained``, ``pnmn_attn_lstm_fwd_group_constrained``; ``Seq2SeqBase.decode_constrained``,
+(the tables of ``pnmn_attn_lstm_fwd`` and ``pnmn_attn_lstm_fwd_group``; ``Seq2SeqBase.decode_constrained``,
 ``predict_answers(constrained_sampling=True)``), token for token against the fp64 host reference of
 tests/helpers/constrained_choice.py: one workgroup per tile and multi-CU, the identity filter, every filter of
 tests/helpers/filtered_inputs.py and the greedy mode, the paired launch, a row that is not finite, the argument checks of the C
@@ -250,34 +250,30 @@ def test_constrained_entry_points_refuse_bad_arguments_and_launch_nothing(gramma
                  dict(tc=with_entry(tc, V - 1, n_classes)), dict(tc=with_entry(tc, 0, 255)),
                  dict(ns=with_entry(ns, n_states * n_classes - 1, n_states)), dict(ns=with_entry(ns, 0, 255)),
                  dict(n_states=0), dict(n_states=_hip.BEAM_MAX_STATES + 1), dict(n_classes=0), dict(n_classes=_hip.BEAM_MAX_CLASSES + 1),
-                 dict(end=-1), dict(end=V), dict(ml=long_left), dict(filt=None),
+                 dict(end=-1), dict(end=V), dict(ml=long_left),
                  dict(filt=np.array([(0.0, 0, 1.0, 0)] * 2, _hip.SAMPLING_FILTER)),
                  dict(filt=np.array([(1.0, -1, 1.0, 0)] * 2, _hip.SAMPLING_FILTER)),
                  dict(filt=np.array([(1.0, 0, float("nan"), 0)] * 2, _hip.SAMPLING_FILTER))]
     ptr = lambda a: 0 if a is None else a.ctypes.data  # noqa: E731
-    for change in [{}] + bad_calls:
-        c = {**ok, **change}
+
+    def calls(c):
         tail = (c["end"], ptr(c["tc"]), ptr(c["ns"]), ptr(c["ml"]), c["n_states"], c["n_classes"])
-        want = _hip.EINVAL if change else 0
-        for sd in sides:
-            sd[0][1].fill_(-7)
-        j = jobs[0].item()
-        rc = lib.pnmn_attn_lstm_fwd_constrained(*j[:15], *j[19:23], H, *j[23:27], j[17], j[18], j[15], j[16], ptr(c["filt"]), *tail,
-                                                _hip.stream_ptr(dev))
-        assert rc == want, change
-        torch.cuda.synchronize()
-        if change:
-            assert bool((sides[0][0][1] == -7).all()), change
-        if ws is not None:
-            for n in (1, 2):
-                rc = lib.pnmn_attn_lstm_fwd_group_constrained(jobs.ctypes.data, ptr(c["filt"]), *tail, n, H, ws.data_ptr(),
-                                                              _hip.stream_ptr(dev))
-                assert rc == want, (change, n)
-            torch.cuda.synchronize()
+        return fi.decoder_entry_calls(jobs, sides, ws, c["filt"], tail)
+
+    for change in [{}] + bad_calls:
+        for entry, rc, outputs in calls({**ok, **change}):
+            assert rc == (_hip.EINVAL if change else 0), (change, entry)
+            tokens = outputs[2::3] if entry == "group n=2" else outputs[2:3]  # (of the jobs the call covers)
             if change:
-                assert all(bool((sd[0][1] == -7).all()) for sd in sides), change
+                assert all(bool((t == -7).all()) for t in outputs), (change, entry)
             else:
-                assert all(bool((sd[0][1] >= 0).all()) for sd in sides)
+                assert all(bool((t >= 0).all()) for t in tokens), entry
+    # a null filter under the automaton is not an error: the identity for every job, bit for bit
+    identity = np.array([(1.0, 0, 1.0, 0)] * 2, _hip.SAMPLING_FILTER)
+    for (entry, rc_n, out_n), (_, rc_r, out_r) in zip(calls({**ok, "filt": None}), calls({**ok, "filt": identity})):
+        assert rc_n == 0 and rc_r == 0, entry
+        assert bool((out_n[2] >= 0).all()), entry
+        assert all(torch.equal(a, b) for a, b in zip(out_n, out_r)), entry  # (hs, cs and tokens of every job)
 
 
 # ---- 8. the model surface ---------------------------------------------------------------------------------------------

@@ -120,8 +120,9 @@ def test_sampling_filter_block_matches_the_c_struct(tmp_path):
     subprocess.check_call(["gcc", "-I", os.path.dirname(_hip.HEADER_PATH), str(src), "-o", str(exe)])
     seen = [int(x) for x in subprocess.check_output([str(exe)]).decode().split()]
     assert seen == [16, 0, 4, 8, 12] == [dtype.itemsize] + [dtype.fields[f][1] for f in dtype.names]
-    for name in ("pnmn_sample_tokens_filtered", "pnmn_attn_lstm_fwd_filtered", "pnmn_attn_lstm_fwd_group_filtered"):
+    for name in ("pnmn_sample_tokens", "pnmn_attn_lstm_fwd", "pnmn_attn_lstm_fwd_group"):
         assert name in _hip.SIGNATURES
+        assert name + "_filtered" not in _hip.SIGNATURES  # (an option is an argument, not a second entry point)
     # the reader takes a plain struct by the same field rules, and refuses what it refuses in a record
     _hip.read_header(text="struct pnmn_blk { float a; int32_t n[2]; };\nint pnmn_f(const struct pnmn_blk* b, void* stream);")
     assert _hip.HOST_BLOCKS.pop("pnmn_blk").itemsize == 12

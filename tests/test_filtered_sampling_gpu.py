@@ -1,5 +1,5 @@
 """Sampling under a filter (temperature, top-k, top-p), token for token against the host reference of
-tests/helpers/filtered_choice.py: the standalone ``pnmn_sample_tokens_filtered`` (through ``choose_tokens``), the draws
+tests/helpers/filtered_choice.py: the standalone ``pnmn_sample_tokens`` under a filter (through ``choose_tokens``), the draws
 inside the persistent decoder kernels (one workgroup per tile, multi-CU, paired launch), the identity filter, a known
 distribution, rows that are not all finite, the argument checks of the C entry points, and the model surface.
 
@@ -133,20 +133,21 @@ def test_paired_launch_draws_the_filtered_reference_token():
 @pytest.mark.parametrize("cluster", ["0", "1"])
 @pytest.mark.parametrize("B,T,S,V", [s for s in fi.DECODER_SHAPES if s[0] >= 17])
 def test_identity_filter_in_the_decoders_is_the_unfiltered_entry(B, T, S, V, cluster, monkeypatch):
-    """``meta["filter"] = (1, 0, 1)`` goes through the ``_filtered`` entry points, which run the unfiltered kernels."""
+    """``meta["filter"] = (1, 0, 1)`` reaches the one entry point of the path as a filter record, no filter as a null
+    pointer; either way the unfiltered kernels run."""
     from probnmn import _hip
 
     monkeypatch.setenv("PNMN_DECODER_CLUSTER", cluster)
     d = _decoder_inputs(B, S, V, 3 * B + V)
-    called = []
+    called = []  # (entry point, its filter argument) of every decoder forward call
     lib = _hip.lib()
-    for name in ("pnmn_attn_lstm_fwd_filtered", "pnmn_attn_lstm_fwd_group_filtered"):
+    for name, at in (("pnmn_attn_lstm_fwd", 2), ("pnmn_attn_lstm_fwd_group", 1)):
         real = getattr(lib, name)
-        monkeypatch.setattr(lib, name, lambda *a, _real=real, _name=name: (called.append(_name), _real(*a))[1])
+        monkeypatch.setattr(lib, name, lambda *a, _real=real, _name=name, _at=at: (called.append((_name, a[_at])), _real(*a))[1])
     hs, tok = _decode(d, 1, T, 99, 16)
-    assert not called
+    assert len(called) == 1 and called[0][1] == 0
     hs_f, tok_f = _decode(d, 1, T, 99, 16, (1.0, 0, 1.0))
-    assert len(called) == 1
+    assert len(called) == 2 and called[1][0] == called[0][0] and called[1][1] != 0
     assert torch.equal(tok_f, tok) and torch.equal(hs_f, hs)
     # greedy ignores a filter
     hs_g, tok_g = _decode(d, 2, T, 99, 16)
@@ -166,9 +167,9 @@ def test_identity_filter_standalone_is_the_unfiltered_entry(V):
     out_lp = torch.full((B,), -7.0, device=DEV)
     rec = np.array([(1.0, 0, 1.0, 0)], _hip.SAMPLING_FILTER)
     for greedy in (0, 1):
-        rc = _hip.lib().pnmn_sample_tokens_filtered(logits.data_ptr(), out_tok.data_ptr(), out_lp.data_ptr(), B, V, greedy,
-                                                    2 ** 62 - 1, 2 ** 32 - 5, 7, PAD, UNK, START, rec.ctypes.data,
-                                                    _hip.stream_ptr(torch.device(DEV)))
+        rc = _hip.lib().pnmn_sample_tokens(logits.data_ptr(), out_tok.data_ptr(), out_lp.data_ptr(), B, V, greedy,
+                                           2 ** 62 - 1, 2 ** 32 - 5, 7, PAD, UNK, START, rec.ctypes.data,
+                                           _hip.stream_ptr(torch.device(DEV)))
         assert rc == 0
         want_tok, want_lp = (tok, lp) if not greedy else choose_tokens(logits, True, 0, 0, 0, PAD, UNK, START)
         assert torch.equal(out_tok, want_tok) and torch.equal(out_lp, want_lp)
@@ -265,49 +266,111 @@ def test_nonfinite_decoder_rows_stay_in_range_and_to_themselves(cluster, monkeyp
 
 # ---- f. PNMN_EINVAL ---------------------------------------------------------------------------------------------------
 _BAD_FILTERS = [(0.0, 0, 1.0), (-1.0, 0, 1.0), (float("inf"), 0, 1.0), (float("nan"), 0, 1.0), (1.0, -1, 1.0),
-                (1.0, 0, 0.0), (1.0, 0, -0.5), (1.0, 0, 1.5), (1.0, 0, float("nan")), None]
+                (1.0, 0, 0.0), (1.0, 0, -0.5), (1.0, 0, 1.5), (1.0, 0, float("nan"))]
+
+
+def _sample_tokens(logits, filters, greedy=0):
+    """``pnmn_sample_tokens`` into outputs preset to -7: (return code, tokens, logprobs)."""
+    from probnmn import _hip
+
+    B, V = logits.shape
+    tok = torch.full((B,), -7, dtype=torch.long, device=DEV)
+    lp = torch.full((B,), -7.0, device=DEV)
+    rc = _hip.lib().pnmn_sample_tokens(logits.data_ptr(), tok.data_ptr(), lp.data_ptr(), B, V, greedy, 5, 3, 2, PAD, UNK, START,
+                                       0 if filters is None else filters.ctypes.data, _hip.stream_ptr(torch.device(DEV)))
+    torch.cuda.synchronize()
+    return rc, tok, lp
+
+
+def _two_jobs(B, T, S, V, modes, seed=5):
+    """(job records, sides, workspace or None) of two decoder passes over one set of inputs, pass k in ``modes[k]``."""
+    from probnmn import _hip
+    from probnmn.modules.seq2seq_base import _decoder_workspace, _prepare_decoder_side
+
+    d = _decoder_inputs(B, S, V, seed)
+    tf_tokens = torch.randint(3, V, (B, T), generator=torch.Generator().manual_seed(seed)).to(DEV)
+    jobs = np.zeros(2, _hip.DECODER_FWD_JOB)
+    sides = []
+    for k, mode in enumerate(modes):
+        meta = dict(packs=None, mode=mode, T=T, start=START, pad=PAD, unk=UNK, seed=1, row_offset=0, w_p=d["w_p"], b_p=d["b_p"])
+        if mode == 0:
+            meta = dict(packs=None, mode=0, T=T, start=START, in_tokens=tf_tokens)
+        sides.append(_prepare_decoder_side(jobs, k, d["etable"], d["enc"], d["mask"], d["h0"], d["w_c"], d["w_hh"], meta))
+    return jobs, sides, _decoder_workspace([B, B], False, torch.device(DEV))
 
 
 def test_filtered_entry_points_refuse_a_bad_filter_and_launch_nothing():
     from probnmn import _hip
-    from probnmn.modules.seq2seq_base import _decoder_workspace, _prepare_decoder_side
 
-    lib, dev = _hip.lib(), torch.device(DEV)
     B, T, S, V = 20, 4, 5, 44
     logits = fi.standalone_logits(B, V, 1).to(DEV)
-    d = _decoder_inputs(B, S, V, 5)
-    meta = dict(packs=None, mode=1, T=T, start=START, pad=PAD, unk=UNK, seed=1, row_offset=0, w_p=d["w_p"], b_p=d["b_p"])
-    jobs = np.zeros(2, _hip.DECODER_FWD_JOB)
-    sides = [_prepare_decoder_side(jobs, k, d["etable"], d["enc"], d["mask"], d["h0"], d["w_c"], d["w_hh"], meta) for k in (0, 1)]
-    ws = _decoder_workspace([B, B], False, dev)
+    jobs, sides, ws = _two_jobs(B, T, S, V, (1, 1))
+    greedy = jobs.copy()
+    greedy["sample"] = 2
     for bad in _BAD_FILTERS:
-        rec = None if bad is None else np.array([(*bad, 0), (1.0, 0, 1.0, 0)], _hip.SAMPLING_FILTER)
-        ptr = 0 if rec is None else rec.ctypes.data
-        tok = torch.full((B,), -7, dtype=torch.long, device=DEV)
-        lp = torch.full((B,), -7.0, device=DEV)
-        rc = lib.pnmn_sample_tokens_filtered(logits.data_ptr(), tok.data_ptr(), lp.data_ptr(), B, V, 0, 0, 0, 0, PAD, UNK,
-                                             START, ptr, _hip.stream_ptr(dev))
+        rec = np.array([(*bad, 0), (1.0, 0, 1.0, 0)], _hip.SAMPLING_FILTER)
+        rc, tok, lp = _sample_tokens(logits, rec)
         assert rc == _hip.EINVAL, bad
         assert bool((tok == -7).all()) and bool((lp == -7.0).all())
-        for sd in sides:
-            sd[0][1].fill_(-7)
-        j = jobs[0].item()
-        rc = lib.pnmn_attn_lstm_fwd_filtered(*j[:15], *j[19:23], H, *j[23:27], j[17], j[18], j[15], j[16], ptr, _hip.stream_ptr(dev))
-        assert rc == _hip.EINVAL, bad
-        if ws is not None:
-            for n in (1, 2):
-                assert lib.pnmn_attn_lstm_fwd_group_filtered(jobs.ctypes.data, ptr, n, H, ws.data_ptr(),
-                                                             _hip.stream_ptr(dev)) == _hip.EINVAL, (bad, n)
-            if rec is not None:  # the bad filter second: checked although the first is fine; and beside a greedy job
-                rec2 = rec[::-1].copy()
-                assert lib.pnmn_attn_lstm_fwd_group_filtered(jobs.ctypes.data, rec2.ctypes.data, 2, H, ws.data_ptr(),
-                                                             _hip.stream_ptr(dev)) == _hip.EINVAL, bad
-                greedy = jobs.copy()
-                greedy["sample"] = 2
-                assert lib.pnmn_attn_lstm_fwd_group_filtered(greedy.ctypes.data, rec.ctypes.data, 1, H, ws.data_ptr(),
-                                                             _hip.stream_ptr(dev)) == _hip.EINVAL, bad
+        # the bad filter first; second: checked although the first is fine; and beside a greedy job
+        for records, filters in ((jobs, rec), (jobs, rec[::-1].copy()), (greedy, rec)):
+            for entry, rc, outputs in fi.decoder_entry_calls(records, sides, ws, filters):
+                if filters is rec or entry == "group n=2":
+                    assert rc == _hip.EINVAL, (bad, entry)
+                    assert all(bool((t == -7).all()) for t in outputs), (bad, entry)
+
+
+def test_null_options_are_the_identity_options():
+    """A null filter is the identity filter and null tables are no automaton: what an entry point returns and writes
+    with a null option is, bit for bit, what it does with the identity record (beam: with the automaton that accepts
+    every string).  This is what the null filter of the argument tests, once PNMN_EINVAL, now means."""
+    from probnmn import _hip
+    from probnmn.modules.seq2seq_base import constraint_tables
+    from probnmn.runtime.program_compiler import ProgramCompiler
+    from probnmn.vocabulary import Vocabulary
+
+    B, T, S, V, END = 20, 4, 5, 44, 3
+    vocab = Vocabulary.clevr()
+    assert vocab.get_vocab_size("programs") == V and vocab.get_token_index("@end@", namespace="programs") == END
+    auto = ProgramCompiler(vocab.get_index_to_token_vocabulary("programs")).decoding_automaton(exclude=(PAD, UNK, START, END))
+    tc, ns, ml, _ = constraint_tables(auto, V, END)
+    grammar = (END, tc.ctypes.data, ns.ctypes.data, ml.ctypes.data, *ns.shape)
+    identity = np.array([(1.0, 0, 1.0, 0)] * 2, _hip.SAMPLING_FILTER)
+    # the decoders: one workgroup per tile, and the group entry with one job and with a teacher-forced second one
+    for mode in (1, 2):
+        jobs, sides, ws = _two_jobs(B, T, S, V, (mode, 0))
+        for tail in (fi.NO_TABLES, grammar):
+            null = fi.decoder_entry_calls(jobs, sides, ws, None, tail)
+            record = fi.decoder_entry_calls(jobs, sides, ws, identity, tail)
+            assert [e for e, _, _ in null] == ["fwd"] + (["group n=1", "group n=2"] if ws is not None else [])
+            for (entry, rc_n, out_n), (_, rc_r, out_r) in zip(null, record):
+                what = (mode, tail is grammar, entry)
+                assert rc_n == 0 and rc_r == 0, what
+                assert bool((out_n[2] >= 0).all()) and bool((out_n[2] < V).all()), what  # (job 0's tokens were written)
+                assert all(torch.equal(a, b) for a, b in zip(out_n, out_r)), what
+    # one step's token choice
+    for Vs in (44, 512):
+        logits = fi.standalone_logits(B, Vs, Vs).to(DEV)
+        rc_n, tok_n, lp_n = _sample_tokens(logits, None)
+        rc_r, tok_r, lp_r = _sample_tokens(logits, identity)
+        assert rc_n == 0 and rc_r == 0 and bool((tok_n >= 0).all())
+        assert torch.equal(tok_n, tok_r) and torch.equal(lp_n, lp_r)
+    # beam search: null tables against one state, one class, min_left = {0}
+    Bq, Sq, beam = 3, 8, 4
+    d = _decoder_inputs(Bq, Sq, V, 7)
+    one = np.zeros(V, np.uint8), np.zeros((1, 1), np.uint8), np.zeros(1, np.uint8)
+    got = []
+    for tables in ((0, 0, 0, 0, 0), (one[0].ctypes.data, one[1].ctypes.data, one[2].ctypes.data, 1, 1)):
+        tok = torch.full((Bq, beam, T), -7, dtype=torch.long, device=DEV)
+        scores = torch.full((Bq, beam), -7.0, device=DEV)
+        rc = _hip.lib().pnmn_attn_lstm_beam(d["etable"].data_ptr(), d["enc"].data_ptr(), d["mask"].data_ptr(), d["h0"].data_ptr(),
+                                            d["w_c"].data_ptr(), d["w_hh"].data_ptr(), d["w_p"].data_ptr(), d["b_p"].data_ptr(),
+                                            tok.data_ptr(), scores.data_ptr(), None, None, None, Bq, T, Sq, V, H, beam, PAD, UNK,
+                                            START, END, *tables, _hip.stream_ptr(torch.device(DEV)))
         torch.cuda.synchronize()
-        assert all(bool((sd[0][1] == -7).all()) for sd in sides), bad
+        assert rc == 0 and bool((tok >= 0).all())
+        got.append((tok, scores))
+    assert torch.equal(got[0][0], got[1][0]) and torch.equal(got[0][1], got[1][1])
 
 
 # ---- g. Seq2SeqBase and predict_answers -------------------------------------------------------------------------------

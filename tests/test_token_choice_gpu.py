@@ -109,7 +109,7 @@ def test_sample_tokens_kernel_rejects_a_wider_vocabulary():
     tok = torch.full((2,), -7, dtype=torch.long, device=DEV)
     lp = torch.empty(2, device=DEV)
     rc = _hip.lib().pnmn_sample_tokens(x.data_ptr(), tok.data_ptr(), lp.data_ptr(), 2, 513, 0, 0, 0, 0, PAD, UNK, START,
-                                       _hip.stream_ptr(torch.device(DEV)))
+                                       None, _hip.stream_ptr(torch.device(DEV)))
     assert rc == _hip.ESHAPE
     assert tok.cpu().tolist() == [-7, -7]  # nothing launched
 
