@@ -318,6 +318,36 @@ int pnmn_answer_loss(const float* logits, const int64_t* answers, const int32_t*
                      int unknown_index, float scale, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Marginal answer over several programs (csrc/answer_marginal.hip).  Not in the reference, which answers from ONE
+ * program: it extends nmn.py:245-269 (log-softmax and first arg-max of one row of logits, @@UNKNOWN@@ for an invalid
+ * program) and scripts/inference.py:76-91 (one sampled program per question) to
+ *     p(a | x, image) = sum_z q(z | x) p(a | z, image)
+ * over the hypothesis rows of each question.  Rows [group_start[g], group_start[g + 1]) are group g's, in that order.
+ *   row r is USABLE when (valid == NULL or valid[r] != 0) and (log_weight == NULL or log_weight[r] is finite)
+ *   support[g]         = number of usable rows of group g
+ *   w_r                = exp(log_weight[r] - logsumexp of log_weight over the group's usable rows);
+ *                        log_weight == NULL: w_r = 1 / support[g]
+ *   row_weight[r]      = w_r for a usable row, 0 otherwise
+ *   row_predictions[r] = first arg-max of logits[r] (pnmn_answer_loss's rule); unknown_index where valid[r] == 0
+ *   log_marginal[g][a] = log sum over usable rows of w_r * softmax(logits[r])[a], in log space with the maxima subtracted
+ *                        (finite fp32 logits)
+ *   predictions[g]     = first arg-max of log_marginal[g] as stored
+ *   support[g] == 0 (no rows, all invalid, or no finite weight): log_marginal[g][:] = -inf, predictions[g] = unknown_index
+ * Group bounds are clamped into [0, n_rows] with end >= start before use, so no group_start reads or writes outside the
+ * arrays; a row that no group covers is not written, a row that two groups cover is written by both.  A group's outputs
+ * depend only on its own rows in their order: the same bits alone or inside a batch, and from run to run.  One launch,
+ * one wavefront per group, no LDS, no atomics, no wait on another workgroup.
+ * n_groups == 0 returns 0 without a launch.  PNMN_EINVAL, with no launch and no HIP call: a null logits (n_rows > 0),
+ * group_start, log_marginal or predictions; num_answers < 1; n_rows < 0; n_groups < 0.  num_answers > 1024: PNMN_ESHAPE.
+ * ------------------------------------------------------------------------------------------- */
+int pnmn_answer_marginal(const float* logits /* [n_rows][num_answers] */, const int32_t* valid /* [n_rows], may be NULL */,
+                         const float* log_weight /* [n_rows], may be NULL */, const int32_t* group_start /* DEVICE [n_groups + 1] */,
+                         float* log_marginal /* [n_groups][num_answers] */, int64_t* predictions /* [n_groups] */,
+                         int64_t* row_predictions /* [n_rows], may be NULL */, float* row_weight /* [n_rows], may be NULL */,
+                         int32_t* support /* [n_groups], may be NULL */, int n_groups, int n_rows, int num_answers,
+                         int unknown_index, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Glue of the seq2seq passes (csrc/seqglue.hip): what the reference -- through AllenNLP 0.9.0 -- does with
  * chains of small tensor ops and per-row Python loops, one launch each.
  *

@@ -10,12 +10,15 @@ Stand-alone layout only (when the models are grafted onto the reference's packag
     answers on those; accuracy = #(prediction == answer) / N (an invalid program predicts @@UNKNOWN@@);
   * inference samples programs (``program_generator(question)`` with the default strategy, in eval mode)
     and lets the NMN answer without gold answers; with ``beam_size`` it beam-searches them instead (not in the
-    reference) and can prefer the best-ranked hypothesis that is a valid program;
+    reference) and can prefer the best-ranked hypothesis that is a valid program; with ``marginal`` / ``num_programs`` (not
+    in the reference either) the answer is the MARGINAL over several programs, sum_z q(z | x) p(a | z, image), with its
+    probability and the hypotheses that voted;
   * ``explain`` (not in the reference either) adds to each answer where its program looked: the attention map of every
     step, and that map painted over the question's image (``attention_overlay``).
 Batches are dicts of DEVICE tensors with the reference's keys (a ``PrefetchingLoader`` yields them)."""
 from typing import Any, Callable, Dict, Iterable, List, Optional
 
+import numpy as np
 import torch
 
 from probnmn import _hip
@@ -183,12 +186,122 @@ def attention_overlay(attention: torch.Tensor, attention_mask: torch.Tensor, pix
     return out, index
 
 
+def group_hypotheses(tokens, log_weights, valid):
+    """The hypotheses of a batch of questions as the rows ``NeuralModuleNetwork.marginal_answers`` takes.  Host numpy:
+    ``tokens`` [B, K, T] (K programs per question), ``log_weights`` [B, K] or None (uniform), ``valid`` [B, K].
+
+    Per question: hypotheses that are invalid or have a weight that is not finite are dropped, identical token rows are
+    merged in first-occurrence order, the merged log-weight being the logsumexp of the merged rows' (``log count`` for
+    uniform weights).  A trained generator's samples are mostly the same program: merging is what keeps the NMN near B
+    rows instead of B * K.  Returns (programs int64 [R, T], question_rows int64 [R] -- non-decreasing; a question with
+    nothing left has no row --, log_weights float64 [R], first_slot int64 [R]: the slot k a merged row first appeared in)."""
+    tokens = np.asarray(tokens)
+    if tokens.ndim != 3:
+        raise ValueError("tokens [B, K, T]; got shape %s" % (tokens.shape,))
+    B, K, T = tokens.shape
+    valid = np.asarray(valid).reshape(B, K) != 0
+    weights = np.zeros((B, K)) if log_weights is None else np.asarray(log_weights, dtype=np.float64).reshape(B, K)
+    keep = valid & np.isfinite(weights)
+    programs, question_rows, merged, first_slot = [], [], [], []
+    for b in range(B):
+        seen: Dict[bytes, int] = {}
+        for k in np.nonzero(keep[b])[0].tolist():
+            row = np.ascontiguousarray(tokens[b, k], dtype=np.int64)
+            at = seen.setdefault(row.tobytes(), len(programs))
+            if at == len(programs):
+                programs.append(row)
+                question_rows.append(b)
+                merged.append([weights[b, k]])
+                first_slot.append(k)
+            else:
+                merged[at].append(weights[b, k])
+    out_weights = np.zeros(len(programs))
+    for i, w in enumerate(merged):
+        w = np.asarray(w)
+        out_weights[i] = w.max() + np.log(np.exp(w - w.max()).sum())
+    return (np.stack(programs).astype(np.int64) if programs else np.zeros((0, T), np.int64),
+            np.asarray(question_rows, dtype=np.int64), out_weights, np.asarray(first_slot, dtype=np.int64))
+
+
+def _marginal_options(beam_size, marginal, num_programs, explain) -> bool:
+    """The argument rules of ``marginal`` / ``num_programs`` (``predict_answers`` states them); true when the answers are
+    marginals."""
+    if num_programs is not None:
+        if isinstance(num_programs, bool) or not isinstance(num_programs, int):
+            raise ValueError("num_programs must be an int in 2 .. 64, got %r" % (num_programs,))
+        if not 2 <= num_programs <= 64:
+            raise ValueError("num_programs must be in 2 .. 64, got %d" % num_programs)
+        if beam_size is not None:
+            raise ValueError("num_programs samples the hypotheses; with beam_size they are searched (marginal=True)")
+    elif marginal and beam_size is None:
+        raise ValueError("marginal=True marginalises over the beam's hypotheses: give a beam_size (or num_programs)")
+    if (marginal or num_programs is not None) and explain:
+        raise ValueError("explain=True explains the one program an answer came from; a marginal answer has several")
+    return bool(marginal) or num_programs is not None
+
+
+class _HostCopies:
+    """Device tensors copied into page-locked buffers, two sets in turn (batch i + 1 is queued before batch i is read)."""
+
+    def __init__(self):
+        self._pinned: Dict[Any, torch.Tensor] = {}
+
+    def copy(self, name, iteration, t):
+        key = (name, iteration & 1, tuple(t.shape), t.dtype)
+        if key not in self._pinned:
+            self._pinned[key] = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
+        self._pinned[key].copy_(t, non_blocking=True)
+        return self._pinned[key]
+
+
+def _queue_hypotheses(program_generator, batch, iteration, copies, beam_size, num_programs, constraint, constrained_sampling,
+                      sampling, on_device):
+    """First stage of a marginal batch: the generator pass that yields K hypotheses per question and the asynchronous copy
+    of them to the host.  Returns (tokens [B, K, T], log-weights [B, K] or None, event or None)."""
+    question = batch["question"]
+    if num_programs is not None:  # every question num_programs times in ONE call: the rows draw independently
+        repeated = question.repeat_interleave(num_programs, 0)
+        if constrained_sampling:
+            out = program_generator(repeated, decoding_strategy="constrained_sampling", constraint=constraint, **sampling)
+        else:
+            out = program_generator(repeated, **sampling)
+        tokens = out["predictions"]
+        tokens, weights = tokens.reshape(question.size(0), num_programs, tokens.size(-1)), None
+    else:
+        extra = {} if constraint is None else {"constraint": constraint}
+        out = program_generator(question, decoding_strategy="beam", beam_size=beam_size, **extra)
+        tokens, weights = out["beam_predictions"], out["beam_log_probabilities"]
+    if not (tokens.is_cuda and on_device):
+        return tokens, weights, None
+    tokens = copies.copy("tokens", iteration, tokens)
+    if weights is not None:
+        weights = copies.copy("weights", iteration, weights)
+    copied = torch.cuda.Event()
+    copied.record()
+    return tokens, weights, copied
+
+
+def _finish_hypotheses(nmn, image, queued):
+    """Second stage: wait for the copy, keep the valid hypotheses (merged), run the NMN over them and marginalise.
+    Returns (``marginal_answers``' dict as host numpy, programs [R, T], group_start [B + 1])."""
+    tokens, weights, copied = queued
+    if copied is not None:
+        copied.synchronize()
+    arr = tokens.cpu().numpy()
+    B, K, T = arr.shape
+    valid = np.array([c.valid for c in nmn.engine.compiler.compile_batch(arr.reshape(B * K, T))], dtype=bool).reshape(B, K)
+    programs, question_rows, log_weights, _ = group_hypotheses(arr, None if weights is None else weights.cpu().numpy(), valid)
+    out = nmn.marginal_answers(image, torch.from_numpy(programs), question_rows, log_weights)
+    return ({k: v.cpu().numpy() for k, v in out.items()}, programs, np.searchsorted(question_rows, np.arange(B + 1)))
+
+
 @torch.no_grad()
 def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary,
                     beam_size: Optional[int] = None, prefer_valid: bool = True,
                     constrained: bool = False, extractor=None, temperature: float = 1.0, top_k: int = 0,
                     top_p: float = 1.0, constrained_sampling: bool = False, explain: bool = False,
-                    overlay_strength: int = 160, colormap: Optional[torch.Tensor] = None) -> List[Dict[str, Any]]:
+                    overlay_strength: int = 160, colormap: Optional[torch.Tensor] = None, marginal: bool = False,
+                    num_programs: Optional[int] = None) -> List[Dict[str, Any]]:
     """scripts/inference.py:76-91: sampled programs -> NMN -> answer strings, one record per question
     (``question_index`` from the batch when present, else a running index).
 
@@ -224,7 +337,19 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
     "attention": float32 numpy [H, W]}``.  When the batch has ``"pixels"`` an entry also has ``"overlay"``: uint8 numpy
     [Hi, Wi, 3], the map painted over the question's image (``attention_overlay`` with ``overlay_strength`` and
     ``colormap``).  An invalid program has no steps.  The answers are those of ``explain=False``: the maps are copied out
-    of the activations the pass leaves behind."""
+    of the activations the pass leaves behind.
+
+    ``marginal`` (needs ``beam_size``; works with ``constrained``): the answer is the marginal over the K hypotheses of the
+    beam, sum_z q(z | x) p(a | z, image), with q = ``beam_log_probabilities`` renormalised over the hypotheses that are
+    valid programs (``NeuralModuleNetwork.marginal_answers``; identical hypotheses are merged first: ``group_hypotheses``).
+    ``num_programs`` = N (2 .. 64, without ``beam_size``): each question is decoded N times in one generator call -- the
+    sampling options apply -- and the answer is the marginal over the draws, uniformly weighted.  A record then holds
+    ``"question_index"``, ``"answer"`` (the marginal prediction; ``@@UNKNOWN@@`` when no hypothesis is valid), its
+    ``"answer_probability"`` (0.0 then), the ``"support"`` (how many distinct valid hypotheses voted) and the
+    ``"hypotheses"``: ``{"program": token strings, "weight": its share, "answer": its own answer}`` each, in group order.
+    ``marginal`` without ``beam_size``, ``num_programs`` with it, either with ``explain``, or a ``num_programs`` that is
+    not an int in range, are a ``ValueError``."""
+    marginalise = _marginal_options(beam_size, marginal, num_programs, explain)
     if constrained and beam_size is None:
         raise ValueError("constrained=True constrains the beam search: give a beam_size")
     if constrained_sampling and beam_size is not None:
@@ -255,8 +380,13 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
                 raise ValueError("a batch of \"pixels\" needs an extractor (predict_answers(..., extractor=ResNet101Stage3))")
             return extractor.forward_pixels(batch["pixels"])
 
+        copies = _HostCopies()
+
         def queue(batch, iteration):
             image = features(batch)
+            if marginalise:
+                return _queue_hypotheses(program_generator, batch, iteration, copies, beam_size, num_programs, constraint,
+                                         constrained_sampling, sampling, image.is_cuda), image
             if constrained_sampling:
                 programs = program_generator(batch["question"], decoding_strategy="constrained_sampling", constraint=constraint,
                                              **sampling)["predictions"]
@@ -291,7 +421,26 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
                 valid = [c.valid for c in nmn.engine.compiler.compile_batch(arr[:, 0])]
             return beams[torch.arange(B), torch.tensor(ranks, dtype=torch.long)], ranks, valid
 
+        def token_strings(row):
+            return [vocabulary.get_token_from_index(int(t), namespace="programs") for t in row if t != pad]
+
+        def finish_marginal(batch, queued):
+            hypotheses, image = queued
+            out, programs, start = _finish_hypotheses(nmn, image, hypotheses)
+            B = len(start) - 1
+            index = batch["question_index"].cpu().tolist() if "question_index" in batch else range(len(records), len(records) + B)
+            for i, qi in enumerate(index):
+                a, n = int(out["predictions"][i]), int(out["support"][i])
+                records.append({
+                    "question_index": int(qi), "answer": vocabulary.get_token_from_index(a, namespace="answers"),
+                    "answer_probability": float(np.exp(out["log_probabilities"][i, a])) if n > 0 else 0.0, "support": n,
+                    "hypotheses": [{"program": token_strings(programs[r]), "weight": float(out["hypothesis_weights"][r]),
+                                    "answer": vocabulary.get_token_from_index(int(out["hypothesis_predictions"][r]), namespace="answers")}
+                                   for r in range(start[i], start[i + 1])]})
+
         def finish(batch, queued):
+            if marginalise:
+                return finish_marginal(batch, queued)
             programs, copied, image = queued
             if copied is not None:
                 copied.synchronize()
@@ -344,6 +493,68 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
     finally:
         program_generator.train(was_training[0])
         nmn.train(was_training[1])
+
+
+@torch.no_grad()
+def evaluate_marginal_answer_accuracy(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary=None,
+                                      beam_size: Optional[int] = None, num_programs: Optional[int] = None,
+                                      constrained: bool = False, constrained_sampling: bool = False,
+                                      num_batches: Optional[int] = None) -> Dict[str, float]:
+    """Answer accuracy of the MARGINAL answer over several programs per question -- the ``beam_size`` hypotheses of a beam
+    search (``constrained``: under the validity rule), weighted by their probabilities, or ``num_programs`` sampled ones
+    (``constrained_sampling``), uniformly weighted -- on batches with ``"answer"``; free-running decodes, unlike
+    ``answering_evaluator``'s teacher-forced greedy pass, which stays what it is.  Returns ``"answer_accuracy"``,
+    ``"single_answer_accuracy"`` (each question answered by its FIRST valid hypothesis alone -- the best beam, the first
+    draw --, from the same pass), ``"average_support"`` (distinct valid hypotheses per question) and
+    ``"average_rows_per_question"`` (NMN rows run per question).  ``vocabulary`` is not needed and only kept for symmetry
+    with ``predict_answers``; ``num_batches`` stops the loop as ``Evaluator.evaluate`` does."""
+    if beam_size is None and num_programs is None:
+        raise ValueError("give the hypotheses: beam_size (a beam search) or num_programs (samples)")
+    _marginal_options(beam_size, beam_size is not None, num_programs, False)
+    if constrained and beam_size is None:
+        raise ValueError("constrained=True constrains the beam search: give a beam_size")
+    if constrained_sampling and beam_size is not None:
+        raise ValueError("constrained_sampling=True samples the programs; with beam_size they are searched (constrained=True)")
+    was_training = (program_generator.training, nmn.training)
+    program_generator.eval()
+    nmn.eval()
+    constraint = None
+    if constrained or constrained_sampling:
+        exclude = [getattr(program_generator, name) for name in ("_pad_index", "_unk_index", "_start_index", "_end_index")]
+        constraint = nmn.engine.compiler.decoding_automaton(exclude=exclude)
+    copies = _HostCopies()
+    totals = {"questions": 0, "correct": 0, "single": 0, "support": 0, "rows": 0}
+
+    def finish(batch, queued):
+        out, programs, start = _finish_hypotheses(nmn, batch["image"], queued)
+        answers = batch["answer"].cpu().numpy()
+        has = start[1:] > start[:-1]
+        single = np.full(answers.shape[0], nmn._unknown_answer, np.int64)
+        single[has] = out["hypothesis_predictions"][start[:-1][has]]
+        totals["questions"] += answers.shape[0]
+        totals["correct"] += int((out["predictions"] == answers).sum())
+        totals["single"] += int((single == answers).sum())
+        totals["support"] += int(out["support"].sum())
+        totals["rows"] += int(programs.shape[0])
+
+    try:
+        pending = None
+        for iteration, batch in enumerate(batches):
+            queued = _queue_hypotheses(program_generator, batch, iteration, copies, beam_size, num_programs, constraint,
+                                       constrained_sampling, {}, batch["image"].is_cuda)
+            if pending is not None:
+                finish(*pending)
+            pending = (batch, queued)
+            if num_batches is not None and iteration > num_batches:
+                break
+        if pending is not None:
+            finish(*pending)
+    finally:
+        program_generator.train(was_training[0])
+        nmn.train(was_training[1])
+    n = max(totals["questions"], 1)
+    return {"answer_accuracy": totals["correct"] / n, "single_answer_accuracy": totals["single"] / n,
+            "average_support": totals["support"] / n, "average_rows_per_question": totals["rows"] / n}
 
 
 @torch.no_grad()

@@ -46,7 +46,7 @@ class _Trunk(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, features, engine, compiled, started, *params):
-        need_backward = any(ctx.needs_input_grad)  # false under torch.no_grad()
+        need_backward = any(ctx.needs_input_grad)  # (requires_grad of the inputs, whatever the grad mode)
         # the library compiles, plans and launches from the token matrix
         pooled, state, compiled.valid = engine.run_forward_tokens(features, compiled.tokens, need_backward, started)
         ctx.engine, ctx.state, ctx.n_params = engine, state, len(params)
@@ -320,7 +320,8 @@ class NeuralModuleNetwork(nn.Module):
         return self._engine
 
     def forward(self, features: torch.Tensor, programs: torch.Tensor, answers: Optional[torch.Tensor] = None,
-                started=None, trunk_stream=None, rows: Optional[torch.Tensor] = None, return_attention: bool = False):
+                started=None, trunk_stream=None, rows: Optional[torch.Tensor] = None, return_attention: bool = False,
+                return_logits: bool = False):
         # ``started``: token of ``begin(features)`` when the caller already launched the stem (optional)
         # ``rows``: run on ``features[rows]`` (programs / answers belong to those examples) without the gathered copy
         # ``trunk_stream``: run the trunk (stem, module programs, classifier conv + pool -- this build's own
@@ -329,7 +330,10 @@ class NeuralModuleNetwork(nn.Module):
         # the current stream (see DESIGN 6 for why the library GEMMs must not leave it)
         # ``return_attention``: the output dict gains "attention" [B, T, H, W] -- the one-channel map each program token's
         # module wrote, zeros where there is none -- and "attention_mask" [B, T] (``NMNEngine.attention_maps``); detached
-        return self.forward_head(self.forward_trunk(features, programs, started, trunk_stream, rows, return_attention), answers)
+        # ``return_logits``: the output dict gains "answer_logits" [B, A], what the classifier's last layer gave for every
+        # program, invalid ones included ("predictions" and "loss" apply the invalid-program overrides, these do not)
+        return self.forward_head(self.forward_trunk(features, programs, started, trunk_stream, rows, return_attention), answers,
+                                 return_logits)
 
     def forward_trunk(self, features: torch.Tensor, programs: torch.Tensor, started=None, trunk_stream=None,
                       rows: Optional[torch.Tensor] = None, return_attention: bool = False):
@@ -364,8 +368,9 @@ class NeuralModuleNetwork(nn.Module):
                 compiled.attention = engine.attention_maps(tokens.shape[1])
         return pooled, compiled, trunk_stream
 
-    def forward_head(self, trunk, answers: Optional[torch.Tensor] = None):
-        """Second half of ``forward``: the fully connected layers and the loss, on the current stream."""
+    def _answer_logits(self, trunk):
+        """The fully connected layers on a trunk pass, on the current stream: (answer logits [B, A], the validity of every
+        program as a host list and as an int32 device tensor)."""
         from probnmn import _hip
 
         pooled, compiled, trunk_stream = trunk
@@ -386,6 +391,12 @@ class NeuralModuleNetwork(nn.Module):
         if answer_logits.requires_grad:
             answer_logits.register_hook(lambda g: _hip.mark("d(answer logits) arrives"))
             pooled.register_hook(lambda g: _hip.mark("d(pooled) computed (FC backward done)"))
+        return answer_logits, valid_host, valid
+
+    def forward_head(self, trunk, answers: Optional[torch.Tensor] = None, return_logits: bool = False):
+        """Second half of ``forward``: the fully connected layers and the loss, on the current stream."""
+        compiled = trunk[1]
+        answer_logits, valid_host, valid = self._answer_logits(trunk)
 
         # log-softmax, arg-max, cross entropy (or -max log-probability without answers) and the
         # invalid-program overrides -- prediction @@UNKNOWN@@, constant loss 3.33, no gradient -- in one kernel
@@ -399,16 +410,85 @@ class NeuralModuleNetwork(nn.Module):
         output_dict = {"predictions": answer_predictions, "loss": loss}
         if compiled.attention is not None:
             output_dict["attention"], output_dict["attention_mask"] = compiled.attention
+        if return_logits:
+            output_dict["answer_logits"] = answer_logits.detach()
         if self.training and self.report_batch_metrics:
             output_dict["metrics"] = self.get_metrics(reset=True)
         return output_dict
+
+    @torch.no_grad()
+    def marginal_answers(self, features, programs: torch.Tensor, question_rows, log_weights=None, max_rows: int = 1024):
+        """The answer of every question from SEVERAL programs: p(a | x, image) = sum_z q(z | x) p(a | z, image) over the
+        hypotheses given for it (not in the reference, which answers from one program: nmn.py:245-269).  Evaluation only,
+        no gradient.
+
+        ``features``: the G questions' feature maps -- an NCHW or ``channels_last`` tensor, or a ``ResidentRows`` batch.
+        ``programs`` [R, T] (host or device): the hypotheses.  ``question_rows`` [R], non-decreasing, in 0 .. G - 1:
+        hypothesis r belongs to question ``question_rows[r]``; a question may have none.  ``log_weights`` [R]:
+        unnormalised log q(z | x) of each hypothesis (None: uniform); the weights are renormalised over the hypotheses of
+        a question that are valid programs and have a finite weight.
+
+        The NMN runs over the R hypothesis rows in passes of at most ``max_rows`` (the engine has ONE activation arena),
+        reading each row's feature map where it lies (``rows=`` / ``ResidentRows.subset``: nothing is gathered, but the
+        stem runs once per hypothesis row, not once per question); then ONE ``pnmn_answer_marginal`` launch.
+
+        Returns ``"predictions"`` int64 [G] (@@UNKNOWN@@ where no hypothesis counts), ``"log_probabilities"`` fp32 [G, A]
+        (-inf there), ``"hypothesis_predictions"`` int64 [R] (each hypothesis's own answer), ``"hypothesis_weights"``
+        fp32 [R] (0 for one that does not count) and ``"support"`` int32 [G] (how many count)."""
+        import numpy as np
+
+        from probnmn import _hip
+        from probnmn.data.feature_store import ResidentRows
+
+        if max_rows < 1:
+            raise ValueError("max_rows must be at least 1, got %r" % (max_rows,))
+        dev = features.device
+        G = int(features.size(0))
+        programs = programs.detach().cpu()
+        qrows = np.ascontiguousarray(torch.as_tensor(question_rows).detach().cpu().numpy(), dtype=np.int64)
+        R = int(qrows.size)
+        if programs.dim() != 2 or programs.size(0) != R or qrows.ndim != 1:
+            raise ValueError("programs [R, T] and question_rows [R]; got %s and %s" % (tuple(programs.shape), qrows.shape))
+        if R and (int(qrows.min()) < 0 or int(qrows.max()) >= G or bool((np.diff(qrows) < 0).any())):
+            raise ValueError("question_rows must be non-decreasing and in 0 .. %d" % (G - 1))
+        A = self.classifier[6].out_features
+        logits = torch.empty(R, A, dtype=torch.float32, device=dev)
+        valid = torch.empty(R, dtype=torch.int32, device=dev)
+        resident = isinstance(features, ResidentRows)
+        rows_dev = None if resident or R == 0 else _hip.to_device(qrows, dev).view(torch.long)
+        for lo in range(0, R, max_rows):
+            hi = min(lo + max_rows, R)
+            if resident:
+                trunk = self.forward_trunk(features.subset(qrows[lo:hi]), programs[lo:hi])
+            else:
+                trunk = self.forward_trunk(features, programs[lo:hi], rows=rows_dev[lo:hi])
+            logits[lo:hi], _, valid[lo:hi] = self._answer_logits(trunk)
+        weights = None
+        if log_weights is not None:
+            weights = torch.as_tensor(log_weights).detach().to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(weights.shape) != (R,):
+                raise ValueError("log_weights [%d]; got %s" % (R, tuple(weights.shape)))
+        group_start = _hip.small_to_device(np.searchsorted(qrows, np.arange(G + 1)).tolist(), torch.int32, dev)
+        out = {"predictions": torch.empty(G, dtype=torch.long, device=dev),
+               "log_probabilities": torch.empty(G, A, dtype=torch.float32, device=dev),
+               "hypothesis_predictions": torch.empty(R, dtype=torch.long, device=dev),
+               "hypothesis_weights": torch.empty(R, dtype=torch.float32, device=dev),
+               "support": torch.empty(G, dtype=torch.int32, device=dev)}
+        _hip.check(_hip.lib().pnmn_answer_marginal(
+            logits.data_ptr(), valid.data_ptr(), 0 if weights is None else weights.data_ptr(), group_start.data_ptr(),
+            out["log_probabilities"].data_ptr(), out["predictions"].data_ptr(), out["hypothesis_predictions"].data_ptr(),
+            out["hypothesis_weights"].data_ptr(), out["support"].data_ptr(), G, R, A, self._unknown_answer,
+            _hip.stream_ptr(dev)), "answer_marginal")
+        return out
 
     def begin(self, features: torch.Tensor, rows: Optional[torch.Tensor] = None):
         """Launch the program-independent part of ``forward`` (feature layout + stem) ahead of time;
         pass the returned token as ``forward(..., started=token)`` with the same ``features``.  ``rows`` (int64
         device tensor): the pass runs on ``features[rows]`` -- programs / answers of ``forward`` then belong to
         those examples -- without the gathered copy of the feature maps."""
-        trains = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        # (what ``_Trunk.forward`` will ask ``run_forward_tokens`` for: ``ctx.needs_input_grad`` reports ``requires_grad``
+        # whatever the grad mode, so under ``torch.no_grad()`` a token begun for "no backward" was refused there)
+        trains = any(p.requires_grad for p in self.parameters())
         return self._engine.begin_forward(features, trains, rows)
 
     def get_metrics(self, reset: bool = True) -> Dict[str, float]:
