@@ -387,6 +387,10 @@ typedef struct {
 int pnmn_token_prep(const int64_t* tokens, int64_t token_row_stride, int B, int T, int pad, int bos, int eos,
                     int drop_first, int64_t* out, float* fmask, int* last, void* stream);
 int pnmn_length_order(const int32_t* last, int B, int T, int32_t* order, int32_t* tile_steps, void* stream);
+/* A decoder pass's rows for pnmn_length_order: last[b] = max(steps_b, 1) - 1 with steps_b as pnmn_valid_rows (below) defines a
+ * decoder segment's, from the same mask tokens (the ones pnmn_seq_nll_fwd is given).  One launch, no atomics, no host
+ * synchronisation. */
+int pnmn_decoder_last(const int64_t* mask_tokens, int64_t mask_stride, int pad, int rows, int T, int32_t* last, void* stream);
 /* The valid (row, step) pairs of padded [rows][T][.] passes as lists of storage rows, for pnmn_gemm_rows.  n <= 8 segments
  * (HOST arrays of n entries each); segment i is a pass of rows[i] sequences of T[i] steps whose sequence b has
  *   steps_b = clamp(last[i][b] + 1, 1, T[i])                                  where last[i] != NULL (an encoder pass:
@@ -786,6 +790,32 @@ int pnmn_attn_lstm_fwd_group(const pnmn_decoder_fwd_job* jobs, const struct pnmn
                              const uint8_t* min_left /* HOST */, int n_states, int n_classes,
                              int n, int hidden, void* workspace, void* stream);
 int pnmn_attn_lstm_bwd_group(const pnmn_decoder_bwd_job* jobs, int n, int hidden, void* workspace, void* stream);
+/* Rows grouped by length: the same calls given, per job, pnmn_length_order's `order` [B] and `tile_steps` [ceil(B/16)] (device
+ * int32, with the meaning they have in pnmn_lstm_seq_fwd_ordered) of the steps pnmn_decoder_last counts.  `order` and
+ * `tile_steps` are HOST arrays of n device pointers (or both NULL); entry i belongs to job i, both NULL = the job runs as in the
+ * calls above, which forward here with NULLs.  For a job with an order
+ *   - slot s of 16-row tile k addresses batch row order[16 k + s] in EVERY tensor of the job; nothing is permuted in memory,
+ *     and a (row, step) the tile runs holds the bits the call without an order writes there;
+ *   - tile k runs tile_steps[k] steps (clamped to [1, T]): forward t = 0 .. tile_steps[k] - 1, backward from there down to 0
+ *     with zero d h / d c carried in;
+ *   - from tile_steps[k] on, the tile's rows hold ZEROS in what later calls read over all T steps: forward hs and ctx,
+ *     backward dgates, dctx, dscore and weights.  cs, act and probs, which only the backward of the same order reads, are
+ *     left unwritten there;
+ *   - backward contract, as for pnmn_lstm_seq_bwd_ordered: dhs[b][t] is not read for t >= tile_steps, and must be exactly
+ *     zero for t >= the row's own steps (pnmn_seq_nll_bwd writes zeros there) -- then dgates, dctx, dscore and dh0 are what
+ *     the call without an order computes at every step the row has, and zero behind it;
+ *   - the job goes out in launches of its own (a group that holds one falls back like a group that does not fit); cut into
+ *     row ranges, a range from slot r0 takes order + r0 and tile_steps + r0 / 16 and the job's own base pointers.
+ * An index in `order` is held inside [0, B).  A free-running job (sample != 0) given an order, one list without the other,
+ * or hidden / S outside the limits above with an order, returns PNMN_EINVAL. */
+int pnmn_attn_lstm_fwd_group_ordered(const pnmn_decoder_fwd_job* jobs, const struct pnmn_sampling_filter* filters /* HOST, may be NULL */,
+                                     int end_index, const uint8_t* token_class /* HOST */, const uint8_t* next_state /* HOST */,
+                                     const uint8_t* min_left /* HOST */, int n_states, int n_classes, int n, int hidden,
+                                     const int32_t* const* order /* HOST array, may be NULL */,
+                                     const int32_t* const* tile_steps /* HOST array, may be NULL */, void* workspace, void* stream);
+int pnmn_attn_lstm_bwd_group_ordered(const pnmn_decoder_bwd_job* jobs, int n, int hidden,
+                                     const int32_t* const* order /* HOST array, may be NULL */,
+                                     const int32_t* const* tile_steps /* HOST array, may be NULL */, void* workspace, void* stream);
 /* The encoder-output gradient from what pnmn_attn_lstm_bwd_group emits, in one bandwidth-bound launch instead of two
  * strided-batched library GEMMs of B tiny [S x T].[T x 256] products (allennlp SimpleSeq2Seq._prepare_attended_input /
  * DotProductAttention under autograd; seq2seq_base.py:201):

@@ -77,6 +77,14 @@ struct MFwdArgs {
     uint64_t seed, row_offset;
 };
 
+// What a launch with its rows grouped by length (ORD) takes besides: an argument of its own, so that every other kernel keeps
+// its arguments and its code.
+struct OrdArgs {
+    const int32_t* order;       // slot -> batch row of the pass, from the launch's first slot on
+    const int32_t* tile_steps;  // steps of every tile of the launch
+    int Bfull;                  // rows of the whole pass: what an entry of `order` may address
+};
+
 constexpr size_t FWD_FIXED_LDS = sizeof(float) * (4 * ROWS * GLD + RW * 4 * H + ROWS * MAXV + RW * MAXS) + sizeof(int) * ROWS;
 constexpr size_t FWD_OVERLAP_LDS = sizeof(float) * (ROWS * H + 64);  // (OVERLAP) the staged h_{t-1} tile + a sink for predicated stores
 
@@ -97,11 +105,19 @@ constexpr size_t FWD_OVERLAP_LDS = sizeof(float) * (ROWS * H + 64);  // (OVERLAP
 // and picks OVERLAP, with them counted).  A row's state and finished flag stay in scalar registers of the wave that chooses the
 // row's tokens -- wave w of EVERY member for rows 2w, 2w + 1, for all steps: a pure function of the row's own earlier tokens,
 // which the members already agree on, so the state needs no hand-off either.
-template <bool OVERLAP, bool SAMPLE, bool FILT = false, bool CONSTR = false>
+// ORD (teacher forced only): rows grouped by length, as in pnmn_lstm_seq_fwd_ordered.  Slot s of the tile is batch row
+// order[16 tile + s] wherever a row of a tensor is addressed -- nothing is permuted in memory, and a row's arithmetic does not
+// depend on its slot or its neighbours, so its bits are those of the unordered pass -- and the tile runs tile_steps[tile] steps.
+// What a later call reads over all T steps (hs: the logits product; ctx: the cell's input weight gradient) is zero filled from
+// there on; cs, act and probs, which only this pass's backward reads (over the same steps), stay unwritten.  Without ORD every
+// expression below is the one it was.
+template <bool OVERLAP, bool SAMPLE, bool FILT = false, bool CONSTR = false, bool ORD = false>
 __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, const int tile, const int part,
                                                          const pnmn::SamplingFilter& f = pnmn::SamplingFilter{1.f, 0, 1.f},
-                                                         const pnmn::TokenAutomaton* aut = nullptr) {
+                                                         const pnmn::TokenAutomaton* aut = nullptr,
+                                                         const OrdArgs& ord = OrdArgs{nullptr, nullptr, 0}) {
     static_assert(SAMPLE || !CONSTR, "the automaton constrains the free-running modes only");
+    static_assert(!ORD || !SAMPLE, "a free-running pass knows its lengths only as it runs");
     extern __shared__ __attribute__((aligned(16))) char raw[];
     const int T = a.T, S = a.S;
     float* encl = reinterpret_cast<float*>(raw);                                       // [RW][S][H]
@@ -112,16 +128,52 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
     float (*logl)[MAXV] = reinterpret_cast<float (*)[MAXV]>(&cpart[RW][0][0]);         // [16][128]
     float* hst = &logl[ROWS][0];                                                       // (OVERLAP) [4 parts][16 rows][64]
     float* sink = hst + ROWS * H;                                                      // (OVERLAP) [64]
+    int* rowl = reinterpret_cast<int*>(OVERLAP ? sink + 64 : hst);                     // (ORD) [16] batch row of every slot
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int row0 = tile * ROWS, myrow0 = row0 + RW * part, u0 = UW * part;
     pnmn::Cluster cl;
     cl.start(a.sync + tile * pnmn::CLUSTER_COUNTER_STRIDE, MEMBERS);
+    // (ORD) Every member of the tile reads this ONE word, which an earlier kernel on the stream wrote: all eight run the same
+    // number of steps, so the same number of signal / wait pairs -- the counter arithmetic of cluster.h holds as it is.
+    int steps = T;
+    if constexpr (ORD) {
+        steps = min(max(ord.tile_steps[tile], 1), T);
+        // the tile's row indices, once (a slot past the launch's last repeats it, as the clamped rows below do; an index is
+        // held inside the pass whatever the list holds)
+        if (tid < ROWS) rowl[tid] = min(max(ord.order[min(row0 + tid, a.B - 1)], 0), ord.Bfull - 1);
+        __syncthreads();
+        // zero fill of my rows from the tile's last step on: the whole width of hs and ctx
+        const int nz = (T - steps) * (H / 4);
+        for (int rl = 0; rl < RW; ++rl) {
+            if (myrow0 + rl >= a.B) continue;
+            const size_t o = ((size_t)rowl[RW * part + rl] * T + steps) * H;
+            for (int i = tid; i < nz; i += 512) {
+                *reinterpret_cast<f32x4*>(a.hs + o + 4 * (size_t)i) = f32x4{0.f, 0.f, 0.f, 0.f};
+                *reinterpret_cast<f32x4*>(a.ctx + o + 4 * (size_t)i) = f32x4{0.f, 0.f, 0.f, 0.f};
+            }
+        }
+    }
+    // batch row of slot sl of the tile: of a slot inside the launch / clamped to the launch's last row
+    auto grow = [&](const int sl) {
+        if constexpr (ORD) return rowl[sl];
+        else return row0 + sl;
+    };
+    auto crow = [&](const int sl) {
+        if constexpr (ORD) return rowl[sl];
+        else return min(row0 + sl, a.B - 1);
+    };
+    // ... of this member's attention row rl (the same rows, counted from the member's first: the expressions the kernels without
+    // an order always had)
+    auto mrow = [&](const int rl) {
+        if constexpr (ORD) return rowl[RW * part + rl];
+        else return myrow0 + rl;
+    };
 
     for (int i = tid; i < RW * S * (H / 4); i += 512) {
         const int rl = i / (S * (H / 4)), rem = i - rl * S * (H / 4);
         f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (myrow0 + rl < a.B) v = *reinterpret_cast<const f32x4*>(a.enc + (size_t)(myrow0 + rl) * S * H + 4 * rem);
+        if (myrow0 + rl < a.B) v = *reinterpret_cast<const f32x4*>(a.enc + (size_t)mrow(rl) * S * H + 4 * rem);
         *reinterpret_cast<f32x4*>(encl + (size_t)rl * S * H + 4 * rem) = v;
     }
     // this wave's gate tile: gate q = wave / 2, units u0 + 16 * (wave % 2) .. + 15
@@ -138,12 +190,12 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
     }
     if (tid < ROWS) tokl[tid] = a.start;
     // source mask of the row this wave attends for (constant over the steps)
-    const float row_mask = lane < S ? a.mask[(size_t)min(myrow0 + (wave >> 2), a.B - 1) * S + lane] : 0.f;
+    const float row_mask = lane < S ? a.mask[(size_t)(ORD ? mrow(wave >> 2) : min(myrow0 + (wave >> 2), a.B - 1)) * S + lane] : 0.f;
     float creg = 0.f;                       // cell state of (row tid / 32, unit u0 + tid % 32)
     const int arow = min(row0 + li, a.B - 1);  // A-operand row (padding rows read a real row; results dropped)
     // teacher forcing from the table: tokl holds the step's input tokens as in the sampling modes; thread r < 16
     // fetches row r's next one a step ahead
-    const int64_t* tf_row = (a.in_tokens && tid < ROWS) ? a.in_tokens + (size_t)min(row0 + tid, a.B - 1) * a.in_stride : nullptr;
+    const int64_t* tf_row = (a.in_tokens && tid < ROWS) ? a.in_tokens + (size_t)crow(tid) * a.in_stride : nullptr;
     if (tf_row) tokl[tid] = (int)tf_row[0];
 
     // A-operand tiles (16 rows x 256 columns of h_{t-1} or ctx_t) in LDS: four parts of 64 columns, slot s (16 bytes) of
@@ -151,7 +203,7 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
     // row, 128 columns apart.
     constexpr int PARTF = ROWS * 64;  // floats of a part
     const int s_row = tid >> 5, s_q = tid & 31;
-    const int s_rowc = min(row0 + s_row, a.B - 1);
+    const int s_rowc = crow(s_row);
     const int s_off = (s_q >> 4) * PARTF + s_row * 64 + 4 * ((s_q & 15) ^ s_row);
     // the four k-blocks of part p of a staged tile as this lane's MFMA fragments
     auto frags = [&](const float* tile_lds, const int p, f32x4 (&f)[4]) {
@@ -187,7 +239,7 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
     if constexpr (CONSTR) au = pnmn::stage_automaton(reinterpret_cast<unsigned char*>(OVERLAP ? sink + 64 : hst), *aut);
     __syncthreads();
 
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < steps; ++t) {
         // An opaque zero, added to the row indices below: the per-lane 64-bit addresses of a dozen tensors are then formed
         // where they are used (a few VALU each) instead of being hoisted out of the step loop, where they cost 2 VGPRs
         // each for the whole sequence -- beside the 128 weight registers that is what the allocator spilled.
@@ -198,17 +250,17 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
         auto load_inputs = [&] {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int rl = 4 * g + r, row = row0 + rl + zt;
+                const int rl = 4 * g + r, slot = row0 + rl + zt, row = ORD ? grow(rl) + zt : slot;
                 const int n = gate * H + u0 + 16 * ub + li;
                 float v = 0.f;
-                if (row < a.B) v = a.xe ? a.xe[((size_t)row * T + t) * G4 + n] : a.etable[(size_t)tokl[rl] * G4 + n];
+                if (slot < a.B) v = a.xe ? a.xe[((size_t)row * T + t) * G4 + n] : a.etable[(size_t)tokl[rl] * G4 + n];
                 acc[r] = v;
             }
         };
         // ---------------- attention for my rows: four waves per row split the source positions ----------------
         {
             const int rl = wave >> 2, q = wave & 3;
-            const int row = myrow0 + rl + zt, rowc = min(row, a.B - 1);
+            const int slot = myrow0 + rl + zt, row = ORD ? mrow(rl) + zt : slot, rowc = ORD ? row : min(row, a.B - 1);
             f32x4 hv;
             if constexpr (OVERLAP) {
                 const int r = RW * part + rl;  // my row within the tile; columns 4 lane .. + 3
@@ -276,7 +328,7 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
                 const float wgt = qv / (wsum(qv) + 1e-13f);
                 if (lane < S) {
                     scl[rl][lane] = wgt;
-                    if (row < a.B) a.probs[((size_t)row * T + t) * S + lane] = p;
+                    if (slot < a.B) a.probs[((size_t)row * T + t) * S + lane] = p;
                 }
             };
             if constexpr (OVERLAP) {
@@ -317,7 +369,7 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
             __syncthreads();
             const int rl2 = tid >> 8, k = tid & 255;
             const float cv = (cpart[rl2][0][k] + cpart[rl2][1][k]) + (cpart[rl2][2][k] + cpart[rl2][3][k]);
-            if (myrow0 + rl2 < a.B) a.ctx[((size_t)(myrow0 + rl2 + zt) * T + t) * H + k] = cv;
+            if (myrow0 + rl2 < a.B) a.ctx[((size_t)(mrow(rl2) + zt) * T + t) * H + k] = cv;
         }
         cl.signal();
         cl.wait();
@@ -353,7 +405,7 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
             constexpr int NB = 4, NPARTS = (H / 16) / NB, PART = 2 * ROWS * 64;
             float* stage = &cpart[0][0][0];  // [2 buffers][2 tensors][16 rows][64]
             const int s_tensor = tid >> 8, o_row = (tid >> 4) & 15, o_slot = tid & 15;
-            const int o_rowc = min(row0 + o_row, a.B - 1);
+            const int o_rowc = crow(o_row);
             const float* s_src = (s_tensor == 0 ? a.ctx + ((size_t)o_rowc * T + t) * H
                                                 : (t > 0 ? a.hs + ((size_t)o_rowc * T + (t - 1)) * H : a.h0 + (size_t)o_rowc * H)) + 4 * o_slot;
             float* s_dst = stage + (s_tensor * ROWS + o_row) * 64 + 4 * (o_slot ^ o_row);
@@ -387,13 +439,13 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
         // ---------------- cell: thread -> (row, unit) ----------------
         {
             const int rl = tid >> 5, ul = tid & 31;
-            const int row = row0 + rl + zt, u = u0 + ul;
+            const int slot = row0 + rl + zt, row = ORD ? grow(rl) + zt : slot, u = u0 + ul;
             const float ig = sigm(gl[0][rl][ul]), fg = sigm(gl[1][rl][ul]);
             const float gg = tanhf(gl[2][rl][ul]), og = sigm(gl[3][rl][ul]);
             const float c = fg * creg + ig * gg;
             const float h = og * tanhf(c);
             creg = c;
-            if (row < a.B) {
+            if (slot < a.B) {
                 const size_t o = ((size_t)row * T + t) * H + u;
                 a.hs[o] = h;
                 a.cs[o] = c;
@@ -405,7 +457,7 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
             }
         }
         if (tf_row) tokl[tid] = tf_next;       // (read again behind the hand-off's barriers)
-        if (t + 1 == T && !SAMPLE) break;  // nobody needs h_T
+        if (t + 1 == steps && !SAMPLE) break;  // nobody needs the last h
         cl.signal();
         cl.wait();
         if constexpr (OVERLAP) {  // h_t of the whole tile: the next step's attention and W_hh product, the logits below
@@ -483,6 +535,16 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     pnmn::cluster_coords<MEMBERS>(tile, part);
     if (tile >= a.tiles) return;
     attn_lstm_fwd_multi_body<OVERLAP, SAMPLE>(a, tile, part);
+}
+
+// A teacher-forced pass with its rows grouped by length (ORD): a kernel of its own, so that the others keep their code.
+template <bool OVERLAP>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_lstm_fwd_multi_ordered_kernel(const MFwdArgs a,
+                                                                                                                    const OrdArgs ord) {
+    int tile, part;
+    pnmn::cluster_coords<MEMBERS>(tile, part);
+    if (tile >= a.tiles) return;
+    attn_lstm_fwd_multi_body<OVERLAP, false, false, false, true>(a, tile, part, pnmn::SamplingFilter{1.f, 0, 1.f}, nullptr, ord);
 }
 
 // TWO independent decoder passes in one launch (the reconstructor's teacher-forced decode and the generator's
@@ -586,8 +648,17 @@ struct MBwdArgs {
 
 constexpr int DLD = 4 * UW + 4;
 constexpr size_t BWD_FIXED_LDS = sizeof(float) * (ROWS * DLD + 2 * RW * H + 2 * RW * MAXS + RW * 4 * H + 64);  // (+ a sink for predicated stores)
+constexpr size_t ORDER_LDS = sizeof(int) * ROWS;  // (ORD, either direction) the tile's row indices, behind everything else
 
-__device__ __forceinline__ void attn_lstm_bwd_multi_body(const MBwdArgs& a, const int tile, const int part) {
+// ORD: the pass's rows grouped by length, as in the forward kernel: slot -> order[16 tile + slot] wherever a row of a tensor is
+// addressed (the exchange buffers x1 / x2 are the TILE's: they stay indexed by slot), and the tile runs the steps
+// tile_steps[tile] - 1 .. 0 from zero d h / d c carried in.  Contract, as for the LSTM layers: dhs[b][t] is not read for
+// t >= tile_steps, and is exactly zero for t >= the row's own steps (the loss backward sees to that) -- so the skipped steps
+// are the ones whose every gradient is an exact zero, and what the steps that run compute is what they computed.  The
+// outputs that later calls read over all T (dgates, dctx, dscore, weights) are zero filled from tile_steps on.
+template <bool ORD = false>
+__device__ __forceinline__ void attn_lstm_bwd_multi_body(const MBwdArgs& a, const int tile, const int part,
+                                                         const OrdArgs& ord = OrdArgs{nullptr, nullptr, 0}) {
     extern __shared__ __attribute__((aligned(16))) char raw[];
     const int T = a.T, S = a.S;
     float* encl = reinterpret_cast<float*>(raw);                                        // [RW][S][H]
@@ -604,11 +675,38 @@ __device__ __forceinline__ void attn_lstm_bwd_multi_body(const MBwdArgs& a, cons
     cl.start(a.sync + tile * pnmn::CLUSTER_COUNTER_STRIDE, MEMBERS);
     float* x1t = a.x1 + (size_t)tile * 2 * MEMBERS * 2 * ROWS * H;
     float* x2t = a.x2 + (size_t)tile * 2 * ROWS * H;
+    int* rowl = reinterpret_cast<int*>(sink + 64);                                       // (ORD) [16] batch row of every slot
+    // (ORD) Every member of the tile reads this ONE word, which an earlier kernel on the stream wrote: all eight run the same
+    // number of steps, so the same number of signal / wait pairs -- the counter arithmetic of cluster.h holds as it is.
+    int steps = T;
+    if constexpr (ORD) {
+        steps = min(max(ord.tile_steps[tile], 1), T);
+        if (tid < ROWS) rowl[tid] = min(max(ord.order[min(row0 + tid, a.B - 1)], 0), ord.Bfull - 1);
+        __syncthreads();
+        // zero fill of my rows from the tile's last step on
+        for (int rl = 0; rl < RW; ++rl) {
+            if (myrow0 + rl >= a.B) continue;
+            const size_t o = (size_t)rowl[RW * part + rl] * T + steps;  // (row, step) the zeros begin at
+            for (int i = tid; i < (T - steps) * (G4 / 4); i += 512)
+                *reinterpret_cast<f32x4*>(a.dgates + o * G4 + 4 * (size_t)i) = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int i = tid; i < (T - steps) * (H / 4); i += 512)
+                *reinterpret_cast<f32x4*>(a.dctx + o * H + 4 * (size_t)i) = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int i = tid; i < (T - steps) * S; i += 512) a.dscore[o * S + i] = 0.f, a.weights[o * S + i] = 0.f;
+        }
+    }
+    auto grow = [&](const int sl) {  // batch row of slot sl of the tile: of a slot inside the launch ...
+        if constexpr (ORD) return rowl[sl];
+        else return row0 + sl;
+    };
+    auto crow = [&](const int sl) {  // ... / clamped to the launch's last row
+        if constexpr (ORD) return rowl[sl];
+        else return min(row0 + sl, a.B - 1);
+    };
 
     for (int i = tid; i < RW * S * (H / 4); i += 512) {
         const int rl = i / (S * (H / 4)), rem = i - rl * S * (H / 4);
         f32x4 v = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (myrow0 + rl < a.B) v = *reinterpret_cast<const f32x4*>(a.enc + (size_t)(myrow0 + rl) * S * H + 4 * rem);
+        if (myrow0 + rl < a.B) v = *reinterpret_cast<const f32x4*>(a.enc + (size_t)grow(RW * part + rl) * S * H + 4 * rem);
         *reinterpret_cast<f32x4*>(encl + (size_t)rl * S * H + 4 * rem) = v;
     }
     // this wave's output tiles (units 32 * wave .. + 31 of all 256) x my 128 gate columns, both matrices
@@ -625,7 +723,7 @@ __device__ __forceinline__ void attn_lstm_bwd_multi_body(const MBwdArgs& a, cons
             wh[nt][kl] = *reinterpret_cast<const f32x4*>(a.w_hh_t + fo);
         }
     float dc_rec = 0.f;
-    const float row_mask = lane < S ? a.mask[(size_t)min(myrow0 + (wave >> 2), a.B - 1) * S + lane] : 0.f;
+    const float row_mask = lane < S ? a.mask[(size_t)crow(RW * part + (wave >> 2)) * S + lane] : 0.f;
     __syncthreads();
 
     // What a step reads of the forward pass (activated gates, cell states, the incoming d h, the attention
@@ -636,11 +734,11 @@ __device__ __forceinline__ void attn_lstm_bwd_multi_body(const MBwdArgs& a, cons
         float ig, fg, gg, og, c, cp, dhs, p;
     };
     const int c_rl = tid >> 5, c_ul = tid & 31;
-    const int c_row = row0 + c_rl, c_u = u0 + c_ul;
-    const int p_row = min(myrow0 + (wave >> 2), a.B - 1);
+    const int c_slot = row0 + c_rl, c_row = grow(c_rl), c_u = u0 + c_ul;
+    const int p_row = crow(RW * part + (wave >> 2));
     auto load_saved = [&](int t) {
         Saved v{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        if (c_row < a.B) {
+        if (c_slot < a.B) {
             const size_t o = ((size_t)c_row * T + t) * H + c_u;
             const float* ar = a.act + ((size_t)c_row * T + t) * G4;
             v.ig = ar[c_u], v.fg = ar[H + c_u], v.gg = ar[2 * H + c_u], v.og = ar[3 * H + c_u];
@@ -651,7 +749,7 @@ __device__ __forceinline__ void attn_lstm_bwd_multi_body(const MBwdArgs& a, cons
         if ((wave & 3) == 0 && lane < S) v.p = a.probs[((size_t)p_row * T + t) * S + lane];
         return v;
     };
-    Saved sv = load_saved(T - 1);
+    Saved sv = load_saved(steps - 1);
 
     // this wave's A fragments of the step's gate gradients (16 rows x my 128 gate columns, K block kl)
     auto dg_frag = [&](const int kl) { return *reinterpret_cast<const f32x4*>(&dgl[li][kl * 16 + 4 * g]); };
@@ -673,7 +771,7 @@ __device__ __forceinline__ void attn_lstm_bwd_multi_body(const MBwdArgs& a, cons
     // product are issued inside the attention backward (its scores, softmax backward and d h sums are latency, not issue
     // slots -- as in the forward kernel), every member publishes its partial with hand-off B, and the next step's cell
     // backward adds the eight partials (same order as the row owners added them before) to the row owner's attention part.
-    for (int t = T - 1; t >= 0; --t) {
+    for (int t = steps - 1; t >= 0; --t) {
         const Saved cur = sv;
         int zt = 0;  // (an opaque zero in the row indices: addresses formed where they are used, see the forward kernel)
         asm volatile("" : "+v"(zt));
@@ -682,13 +780,13 @@ __device__ __forceinline__ void attn_lstm_bwd_multi_body(const MBwdArgs& a, cons
             const int rl = c_rl, ul = c_ul;
             const int row = c_row + zt, u = c_u;
             float di = 0.f, df = 0.f, dg = 0.f, dout = 0.f, dcp = 0.f;
-            if (row < a.B) {
+            if (c_slot + zt < a.B) {
                 const float ig = cur.ig, fg = cur.fg, gg = cur.gg, og = cur.og;
                 const float c = cur.c;
                 const float cp = cur.cp;
                 const float tc = tanhf(c);
                 float dhp = 0.f;
-                if (t < T - 1) {
+                if (t < steps - 1) {
                     // d h_t from step t + 1: the members' partial products, then the row owner's attention part
                     const float* ph = x1t + (((size_t)((t + 1) & 1) * MEMBERS) * 2 + 1) * ROWS * H + (size_t)(rl + zt) * H + u;
                     float pv[MEMBERS];
@@ -748,12 +846,12 @@ __device__ __forceinline__ void attn_lstm_bwd_multi_body(const MBwdArgs& a, cons
 #pragma unroll
             for (int s = 0; s < MEMBERS; ++s) sc += pv[s];
             dctxl[rl2][k] = sc;
-            if (myrow0 + rl2 < a.B) a.dctx[((size_t)(myrow0 + rl2 + zt) * T + t) * H + k] = sc;
+            if (myrow0 + rl2 < a.B) a.dctx[((size_t)(grow(RW * part + rl2) + zt) * T + t) * H + k] = sc;
         }
         __syncthreads();
         {
             const int rl = wave >> 2, q = wave & 3;
-            const int row = myrow0 + rl + zt;
+            const int slot = myrow0 + rl + zt, row = ORD ? grow(RW * part + rl) + zt : slot;
             const float* er = encl + (size_t)rl * S * H + 4 * lane;
             const f32x4 dc4 = *reinterpret_cast<const f32x4*>(&dctxl[rl][4 * lane]);
             constexpr int NP = 4;  // (more in flight would spill beside the weight registers)
@@ -808,7 +906,7 @@ __device__ __forceinline__ void attn_lstm_bwd_multi_body(const MBwdArgs& a, cons
                 const float dscore = dv * m;
                 if (lane < S) {
                     dwl[rl][lane] = dscore;
-                    if (row < a.B) {
+                    if (slot < a.B) {
                         a.dscore[((size_t)row * T + t) * S + lane] = dscore;
                         a.weights[((size_t)row * T + t) * S + lane] = qv / Z;
                     }
@@ -868,7 +966,7 @@ __device__ __forceinline__ void attn_lstm_bwd_multi_body(const MBwdArgs& a, cons
         float sh = 0.f;
 #pragma unroll
         for (int m = 0; m < MEMBERS; ++m) sh += pv[m];
-        if (myrow0 + rl2 < a.B) a.dh0[(size_t)(myrow0 + rl2) * H + k] = sh + att;
+        if (myrow0 + rl2 < a.B) a.dh0[(size_t)grow(RW * part + rl2) * H + k] = sh + att;
     }
     cl.finish();
 }
@@ -878,6 +976,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     pnmn::cluster_coords<MEMBERS>(tile, part);
     if (tile >= a.tiles) return;
     attn_lstm_bwd_multi_body(a, tile, part);
+}
+
+// a pass with its rows grouped by length (ORD): a kernel of its own, as in the forward direction
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_lstm_bwd_multi_ordered_kernel(const MBwdArgs a,
+                                                                                                                    const OrdArgs ord) {
+    int tile, part;
+    pnmn::cluster_coords<MEMBERS>(tile, part);
+    if (tile >= a.tiles) return;
+    attn_lstm_bwd_multi_body<true>(a, tile, part, ord);
 }
 
 // the backward passes of two decoders in one launch (see attn_lstm_fwd_pair_kernel)
@@ -1063,6 +1170,48 @@ MBwdArgs kernel_args(const pnmn_decoder_bwd_job& j, size_t r, int rows, int* syn
                     (rows + ROWS - 1) / ROWS};
 }
 
+// The range of slots from r0 on (a multiple of 16) of a pass whose rows are grouped by length: its part of `order` and
+// `tile_steps`; the kernel's other arguments are those of the range's ROWS (kernel_args at r = 0 with the range's row count):
+// the pass's own base pointers -- a slot's row may lie anywhere in the pass
+OrdArgs ordered_range(size_t r0, int pass_rows, const int32_t* order, const int32_t* tile_steps) {
+    return OrdArgs{order + r0, tile_steps + r0 / ROWS, pass_rows};
+}
+
+// A lone teacher-forced pass with an order (the caller has checked both lists and the job's mode), in row ranges like any other.
+int launch_fwd_ordered(const pnmn_decoder_fwd_job& j, const int32_t* order, const int32_t* tile_steps, int hidden, void* workspace,
+                       hipStream_t st) {
+    if (j.B <= 0 || j.T <= 0) return 0;
+    if (const int e = check_job(j, hidden)) return e;
+    const int chunk = rows_per_launch();
+    if (chunk <= 0) return PNMN_ESHAPE;
+    const size_t base = FWD_FIXED_LDS + sizeof(float) * RW * j.S * H + ORDER_LDS;
+    const bool overlap = base + FWD_OVERLAP_LDS <= LDS_LIMIT;
+    const size_t lds = base + (overlap ? FWD_OVERLAP_LDS : 0);
+    const auto kernel = overlap ? attn_lstm_fwd_multi_ordered_kernel<true> : attn_lstm_fwd_multi_ordered_kernel<false>;
+    static std::atomic<uint64_t> cfg[2];  // (the opt-in is per device and per kernel: lds_optin.h)
+    if (const int e = pnmn::opt_in_lds(reinterpret_cast<const void*>(kernel), LDS_LIMIT, cfg[overlap])) return e;
+    int* sync = nullptr;
+    for (int r0 = 0; r0 < j.B; r0 += chunk) {
+        const int part = j.B - r0 < chunk ? j.B - r0 : chunk;
+        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
+        if (e != hipSuccess) return (int)e;
+        const MFwdArgs a = kernel_args(j, 0, part, sync, 0);
+        hipLaunchKernelGGL(kernel, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a,
+                           ordered_range((size_t)r0, j.B, order, tile_steps));
+        e = hipGetLastError();
+        if (e != hipSuccess) return (int)e;
+    }
+    return 0;
+}
+
+// Orders of a group call: null, or n entries of which entry i (may be null) belongs to job i
+inline bool any_order(const int32_t* const* order, int n) {
+    for (int i = 0; order && i < n; ++i)
+        if (order[i]) return true;
+    return false;
+}
+inline const int32_t* const* from(const int32_t* const* lists, int i) { return lists ? lists + i : nullptr; }
+
 // What a group of passes needs before its launch, the same in both directions: every job checked, the longest source
 // (the LDS size follows it), every pass's first tile (tile0[n] = all tiles).
 template <class Job>
@@ -1088,11 +1237,16 @@ int plan_group(const Job* j, int n, int hidden, int& smax, int& chunk, int* rows
 int launch_fwd_constrained(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, const pnmn::TokenAutomaton& au, int n,
                            int hidden, void* workspace, hipStream_t st);
 int launch_fwd(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, int n, int hidden, void* workspace, hipStream_t st,
-               const pnmn::TokenAutomaton* au = nullptr) {
-    if (n > 1 && !jobs_fit(j, n)) {
-        const int rc = launch_fwd(j, f, n - 1, hidden, workspace, st, au);
-        return rc != 0 ? rc : launch_fwd(j + n - 1, f ? f + n - 1 : nullptr, 1, hidden, workspace, st, au);
+               const pnmn::TokenAutomaton* au = nullptr, const int32_t* const* order = nullptr,
+               const int32_t* const* tile_steps = nullptr) {
+    // (`order` / `tile_steps`: see any_order.  A pass with an order goes out alone -- the kernels for passes side by side take
+    // none -- so a group that holds one falls back as a group that does not fit: identical results.)
+    if (n > 1 && (!jobs_fit(j, n) || any_order(order, n))) {
+        const int rc = launch_fwd(j, f, n - 1, hidden, workspace, st, au, order, tile_steps);
+        return rc != 0 ? rc : launch_fwd(j + n - 1, f ? f + n - 1 : nullptr, 1, hidden, workspace, st, au, from(order, n - 1),
+                                         from(tile_steps, n - 1));
     }
+    if (any_order(order, 1)) return launch_fwd_ordered(j[0], order[0], tile_steps[0], hidden, workspace, st);
     if (au && (j[0].sample != 0 || (n > 1 && j[1].sample != 0))) return launch_fwd_constrained(j, f, *au, n, hidden, workspace, st);
     if (j[0].B <= 0 || j[0].T <= 0) return 0;  // (a lone pass only: passes side by side have rows and steps, see jobs_fit)
     int smax, chunk, rows[MAX_JOBS], tile0[MAX_JOBS + 1];
@@ -1196,21 +1350,25 @@ int launch_fwd_constrained(const pnmn_decoder_fwd_job* j, const pnmn_sampling_fi
     return 0;
 }
 
-int launch_bwd(const pnmn_decoder_bwd_job* j, int n, int hidden, void* workspace, hipStream_t st) {
-    if (n > 1 && !jobs_fit(j, n)) {
-        const int rc = launch_bwd(j, n - 1, hidden, workspace, st);
-        return rc != 0 ? rc : launch_bwd(j + n - 1, 1, hidden, workspace, st);
+int launch_bwd(const pnmn_decoder_bwd_job* j, int n, int hidden, void* workspace, hipStream_t st,
+               const int32_t* const* order = nullptr, const int32_t* const* tile_steps = nullptr) {
+    if (n > 1 && (!jobs_fit(j, n) || any_order(order, n))) {  // (a pass with an order goes out alone: see launch_fwd)
+        const int rc = launch_bwd(j, n - 1, hidden, workspace, st, order, tile_steps);
+        return rc != 0 ? rc : launch_bwd(j + n - 1, 1, hidden, workspace, st, from(order, n - 1), from(tile_steps, n - 1));
     }
     if (j[0].B <= 0 || j[0].T <= 0) return 0;  // (a lone pass only: passes side by side have rows and steps, see jobs_fit)
     int smax, chunk, rows[MAX_JOBS], tile0[MAX_JOBS + 1];
     if (const int e = plan_group(j, n, hidden, smax, chunk, rows, tile0)) return e;
-    const size_t lds = BWD_FIXED_LDS + sizeof(float) * RW * smax * H;
+    const bool ordered = any_order(order, 1);  // (n == 1 then)
+    const size_t lds = BWD_FIXED_LDS + sizeof(float) * RW * smax * H + (ordered ? ORDER_LDS : 0);
     {
-        const void* const kernels[MAX_JOBS] = {reinterpret_cast<const void*>(attn_lstm_bwd_multi_kernel),
-                                               reinterpret_cast<const void*>(attn_lstm_bwd_pair_kernel),
-                                               reinterpret_cast<const void*>(attn_lstm_bwd_group3_kernel)};
-        static std::atomic<uint64_t> cfg[MAX_JOBS];  // (per kernel and device: lds_optin.h)
-        if (const int e = pnmn::opt_in_lds(kernels[n - 1], LDS_LIMIT, cfg[n - 1])) return e;
+        const void* const kernels[MAX_JOBS + 1] = {reinterpret_cast<const void*>(attn_lstm_bwd_multi_kernel),
+                                                   reinterpret_cast<const void*>(attn_lstm_bwd_pair_kernel),
+                                                   reinterpret_cast<const void*>(attn_lstm_bwd_group3_kernel),
+                                                   reinterpret_cast<const void*>(attn_lstm_bwd_multi_ordered_kernel)};
+        static std::atomic<uint64_t> cfg[MAX_JOBS + 1];  // (per kernel and device: lds_optin.h)
+        const int k = ordered ? MAX_JOBS : n - 1;
+        if (const int e = pnmn::opt_in_lds(kernels[k], LDS_LIMIT, cfg[k])) return e;
     }
     float* x1 = reinterpret_cast<float*>(static_cast<char*>(workspace) + pnmn::CLUSTER_SYNC_BYTES);
     float* x2 = x1 + (size_t)exchange_tiles(rows, n, chunk) * 2 * MEMBERS * 2 * ROWS * H;
@@ -1229,8 +1387,14 @@ int launch_bwd(const pnmn_decoder_bwd_job* j, int n, int hidden, void* workspace
         const int part = rows[0] - r0 < chunk ? rows[0] - r0 : chunk;
         hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
         if (e != hipSuccess) return (int)e;
-        const MBwdArgs a = kernel_args(j[0], (size_t)r0, part, sync, 0, x1, x2);
-        hipLaunchKernelGGL(attn_lstm_bwd_multi_kernel, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a);
+        if (ordered) {
+            const MBwdArgs a = kernel_args(j[0], 0, part, sync, 0, x1, x2);
+            hipLaunchKernelGGL(attn_lstm_bwd_multi_ordered_kernel, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a,
+                               ordered_range((size_t)r0, rows[0], order[0], tile_steps[0]));
+        } else {
+            const MBwdArgs a = kernel_args(j[0], (size_t)r0, part, sync, 0, x1, x2);
+            hipLaunchKernelGGL(attn_lstm_bwd_multi_kernel, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a);
+        }
         e = hipGetLastError();
         if (e != hipSuccess) return (int)e;
     }
@@ -1246,14 +1410,30 @@ int64_t pnmn_attn_lstm_group_workspace_bytes(const int32_t* rows, int n, int bac
     return workspace_bytes(rows, n, backward != 0);
 }
 
-int pnmn_attn_lstm_fwd_group(const pnmn_decoder_fwd_job* jobs, const pnmn_sampling_filter* filters, int end_index,
-                             const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left, int n_states,
-                             int n_classes, int n, int hidden, void* workspace, void* stream) {
+// a job with an order: both lists, a teacher-forced pass, shapes inside the kernels' limits
+static bool orders_valid(const int32_t* const* order, const int32_t* const* tile_steps, int n, int hidden, const int* S,
+                         const int* sample) {
+    if (!order != !tile_steps) return false;
+    for (int i = 0; order && i < n; ++i) {
+        if (!order[i] != !tile_steps[i]) return false;
+        if (order[i] && (sample[i] != 0 || hidden != H || S[i] < 1 || S[i] > MAXS)) return false;
+    }
+    return true;
+}
+
+int pnmn_attn_lstm_fwd_group_ordered(const pnmn_decoder_fwd_job* jobs, const pnmn_sampling_filter* filters, int end_index,
+                                     const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left, int n_states,
+                                     int n_classes, int n, int hidden, const int32_t* const* order,
+                                     const int32_t* const* tile_steps, void* workspace, void* stream) {
     if (!jobs || !workspace || n < 1 || n > 2) return PNMN_EINVAL;
     for (int i = 0; filters && i < n; ++i)
         if (!pnmn::filter_valid(filters + i)) return PNMN_EINVAL;
+    {
+        const int S[2] = {jobs[0].S, n > 1 ? jobs[1].S : 0}, sample[2] = {jobs[0].sample, n > 1 ? jobs[1].sample : 0};
+        if (!orders_valid(order, tile_steps, n, hidden, S, sample)) return PNMN_EINVAL;
+    }
     if (!token_class && !next_state && !min_left)
-        return launch_fwd(jobs, filters, n, hidden, workspace, static_cast<hipStream_t>(stream));
+        return launch_fwd(jobs, filters, n, hidden, workspace, static_cast<hipStream_t>(stream), nullptr, order, tile_steps);
     int V = 0, T = INT_MAX;  // of the free-running jobs: one automaton, one vocabulary; the fewest steps
     for (int i = 0; i < n; ++i) {
         if (jobs[i].sample == 0) continue;
@@ -1263,12 +1443,29 @@ int pnmn_attn_lstm_fwd_group(const pnmn_decoder_fwd_job* jobs, const pnmn_sampli
     }
     pnmn::TokenAutomaton au;
     if (const int e = pnmn::fill_automaton(au, token_class, next_state, min_left, n_states, n_classes, V, T, end_index)) return e;
-    return launch_fwd(jobs, filters, n, hidden, workspace, static_cast<hipStream_t>(stream), &au);
+    return launch_fwd(jobs, filters, n, hidden, workspace, static_cast<hipStream_t>(stream), &au, order, tile_steps);
+}
+
+int pnmn_attn_lstm_fwd_group(const pnmn_decoder_fwd_job* jobs, const pnmn_sampling_filter* filters, int end_index,
+                             const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left, int n_states,
+                             int n_classes, int n, int hidden, void* workspace, void* stream) {
+    return pnmn_attn_lstm_fwd_group_ordered(jobs, filters, end_index, token_class, next_state, min_left, n_states, n_classes, n,
+                                            hidden, nullptr, nullptr, workspace, stream);
+}
+
+int pnmn_attn_lstm_bwd_group_ordered(const pnmn_decoder_bwd_job* jobs, int n, int hidden, const int32_t* const* order,
+                                     const int32_t* const* tile_steps, void* workspace, void* stream) {
+    if (!jobs || !workspace || n < 1 || n > MAX_JOBS) return PNMN_EINVAL;
+    {
+        int S[MAX_JOBS], sample[MAX_JOBS];
+        for (int i = 0; i < n; ++i) S[i] = jobs[i].S, sample[i] = 0;
+        if (!orders_valid(order, tile_steps, n, hidden, S, sample)) return PNMN_EINVAL;
+    }
+    return launch_bwd(jobs, n, hidden, workspace, static_cast<hipStream_t>(stream), order, tile_steps);
 }
 
 int pnmn_attn_lstm_bwd_group(const pnmn_decoder_bwd_job* jobs, int n, int hidden, void* workspace, void* stream) {
-    if (!jobs || !workspace || n < 1 || n > MAX_JOBS) return PNMN_EINVAL;
-    return launch_bwd(jobs, n, hidden, workspace, static_cast<hipStream_t>(stream));
+    return pnmn_attn_lstm_bwd_group_ordered(jobs, n, hidden, nullptr, nullptr, workspace, stream);
 }
 
 }  // extern "C"

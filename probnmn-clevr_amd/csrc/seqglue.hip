@@ -158,6 +158,20 @@ __global__ __launch_bounds__(64) void length_order_kernel(const int32_t* __restr
     }
 }
 
+// ---- a decoder row's last step, for pnmn_length_order ------------------------------------------------------------------
+// steps_b as valid_rows_kernel counts a decoder segment's (1 + the last t whose mask token is not `pad`, 0 without one), as
+// last[b] = max(steps_b, 1) - 1: what pnmn_length_order takes.  A thread per row: no atomics, nothing depends on timing.
+__global__ __launch_bounds__(256) void decoder_last_kernel(const int64_t* __restrict__ mask, int64_t mask_stride, int pad, int rows,
+                                                           int T, int32_t* __restrict__ last) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= rows) return;
+    const int64_t* m = mask + (int64_t)b * mask_stride;
+    int steps = 0;
+    for (int t = 0; t < T; ++t)
+        if (m[t] != pad) steps = t + 1;
+    last[b] = max(steps, 1) - 1;
+}
+
 // ---- the valid (row, step) pairs of padded passes, as lists of storage rows ------------------------------------------------
 // What pnmn_gemm_rows contracts a weight gradient over (include/probnmn_hip.h: pnmn_valid_rows).  One workgroup per list:
 // 1024 sequences a round -- a thread finds its sequence's steps, a scan over the workgroup gives every sequence its first
@@ -517,6 +531,15 @@ extern "C" int pnmn_length_order(const int32_t* last, int B, int T, int32_t* ord
     if (T > LO_MAX_T) return PNMN_ESHAPE;
     hipLaunchKernelGGL(length_order_kernel, dim3(1), dim3(64), (size_t)(T + 1) * sizeof(int), static_cast<hipStream_t>(stream),
                        last, B, T, order, tile_steps);
+    return (int)hipGetLastError();
+}
+
+extern "C" int pnmn_decoder_last(const int64_t* mask_tokens, int64_t mask_stride, int pad, int rows, int T, int32_t* last,
+                                 void* stream) {
+    if (rows <= 0) return 0;
+    if (!mask_tokens || !last || T <= 0) return PNMN_EINVAL;
+    hipLaunchKernelGGL(decoder_last_kernel, dim3((rows + 255) / 256), dim3(256), 0, static_cast<hipStream_t>(stream), mask_tokens,
+                       mask_stride, pad, rows, T, last);
     return (int)hipGetLastError();
 }
 

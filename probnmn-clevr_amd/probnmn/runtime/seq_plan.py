@@ -57,6 +57,12 @@ LENGTH_ORDER_ABOVE_ROWS = 256
 #: step the decoders' gradients are 0 x finite -- so about half of the k rows of a 1024-question pass add nothing.  Below it
 #: the plan is call for call what it was.  PNMN_GEMM_VALID_PAIRS=0 (read when a plan is built) keeps every product whole.
 VALID_PAIRS_ABOVE_ROWS = LENGTH_ORDER_ABOVE_ROWS
+#: teacher-forced decoder passes above LENGTH_ORDER_ABOVE_ROWS rows run with their rows grouped by length, one order per pass for
+#: forward and backward (pnmn_decoder_last, pnmn_length_order, pnmn_attn_lstm_*_group_ordered): a row tile stops at its longest
+#: row's last weighted step.  The sampling pass never is (its lengths are known only as it runs); below the threshold the plan
+#: is call for call what it was.  PNMN_DECODER_LENGTH_ORDER (read when a plan is built): "0" keeps the unordered calls, "1"
+#: selects the ordered ones; unset, this default.
+DECODER_LENGTH_ORDER_DEFAULT = "1"
 #: the per-model decoder buffers, [flat sequence rows of all the model's passes][width]
 DECODER_BUFFERS = (("hs", 256), ("cs", 256), ("cx", 256), ("act", 1024), ("dhs", 256), ("dg", 1024), ("dctx", 256))
 
@@ -181,6 +187,8 @@ class _DecoderPass:
     trimmed: Optional[torch.Tensor]  # the sampling pass only: its samples cut at @end@ (what masks its loss)
     v: Dict[str, torch.Tensor]       # [rows][T][.] views of DECODER_BUFFERS, and the pass's own probs / dscore / weights
     loss: _Loss
+    order: Optional[torch.Tensor] = None       # rows grouped by length (``_decoder_order``): pnmn_length_order's lists, or None
+    tile_steps: Optional[torch.Tensor] = None
 
 
 @dataclass
@@ -235,6 +243,7 @@ class Seq2SeqPlan:
         self._keep_args: List[np.ndarray] = []  # plain host arrays the call tuples point into (per-problem / per-segment arguments)
         self._valid_lists: List = []  # segments of the (row, step) lists the weight gradients sum over (``_valid_list``)
         self.valid_pairs = os.environ.get("PNMN_GEMM_VALID_PAIRS", "1") != "0"
+        self.decoder_order = os.environ.get("PNMN_DECODER_LENGTH_ORDER", DECODER_LENGTH_ORDER_DEFAULT) != "0"
         self.anchor = torch.zeros((), device=dev, requires_grad=True)
         self.fwd_pg_enc, self.fwd_pg, self.fwd_pg_finish, self.fwd_qr, self.fwd_prior = (_Calls() for _ in range(5))
         self.bwd_a, self.bwd_b = _Calls(), _Calls()  # the decoders' backward / the encoders' and every parameter gradient
@@ -569,19 +578,43 @@ class Seq2SeqPlan:
             j["w_p"], j["b_p"], j["tokens"], j["V"], j["sample"] = mm.proj.weight.data_ptr(), mm.proj.bias.data_ptr(), p.tokens.data_ptr(), mm.proj.weight.size(0), 1
             j["pad_index"], j["unk_index"] = mm.model._pad_index, mm.model._unk_index
 
+    def _decoder_order(self, calls: _Calls, p: _DecoderPass) -> None:
+        """A large teacher-forced pass's rows grouped by length: its steps are the ones its loss weights (the mask tokens of
+        ``p.loss``, in place when this runs), one order for forward and backward."""
+        if not self.decoder_order or p.trimmed is not None or p.rows <= LENGTH_ORDER_ABOVE_ROWS:
+            return
+        f, i32 = self.buf, torch.int32
+        last = f(p.tag + ".last", p.rows, dtype=i32)
+        p.order, p.tile_steps = f(p.tag + ".order", p.rows, dtype=i32), f(p.tag + ".tile_steps", (p.rows + 15) // 16, dtype=i32)
+        calls.add("pnmn_decoder_last", p.loss.mask, p.loss.mask_stride, p.loss.pad, p.rows, p.T, last.data_ptr(), self.stream)
+        calls.add("pnmn_length_order", last.data_ptr(), p.rows, p.T, p.order.data_ptr(), p.tile_steps.data_ptr(), self.stream)
+
+    def _order_lists(self, passes: List[_DecoderPass]):
+        """() when no pass has an order, else the two host arrays of device pointers the ``_ordered`` calls take."""
+        if all(p.order is None for p in passes):
+            return ()
+        lists = np.array([[0 if t is None else t.data_ptr() for t in col] for col in
+                          ([p.order for p in passes], [p.tile_steps for p in passes])], np.uint64)
+        self._keep_args.append(lists)
+        return lists[0].ctypes.data, lists[1].ctypes.data
+
     def _decoder_forward(self, calls: _Calls, dec: _DecoderSet, source: torch.Tensor, tgt: torch.Tensor, ws_name: str) -> np.ndarray:
         """[@start@, source row, @end@] as the teacher-forced matrix ``tgt``, the token table, and the set's passes in one launch;
         returns the launch's job records, for the caller to keep."""
         model, rows = dec.mm.model, [p.rows for p in dec.passes]
         calls.add("pnmn_token_prep", source.data_ptr(), source.stride(0), source.size(0), source.size(1), model._pad_index, model._start_index,
                   model._end_index, 0, tgt.data_ptr(), None, None, self.stream)
+        for p in dec.passes:
+            self._decoder_order(calls, p)
         self._table_forward(calls, dec.table)
         jobs = np.zeros(len(dec.passes), _hip.DECODER_FWD_JOB)
         for j, p in zip(jobs, dec.passes):
             self._decoder_fwd_job(j, dec, p)
         ws = self.bytes_buf(ws_name, _hip.decoder_workspace_bytes(rows, False))
-        calls.add("pnmn_attn_lstm_fwd_group", jobs.ctypes.data, None, 0, None, None, None, 0, 0,  # (no filters, no automaton)
-                  len(jobs), 256, ws.data_ptr(), self.stream)
+        ordered = self._order_lists(dec.passes)
+        calls.add("pnmn_attn_lstm_fwd_group_ordered" if ordered else "pnmn_attn_lstm_fwd_group", jobs.ctypes.data,
+                  None, 0, None, None, None, 0, 0,  # (no filters, no automaton)
+                  len(jobs), 256, *ordered, ws.data_ptr(), self.stream)
         return jobs
 
     def _decoder_losses(self, calls: _Calls, dec: _DecoderSet) -> None:
@@ -698,7 +731,9 @@ class Seq2SeqPlan:
             j["B"], j["T"], j["S"] = p.rows, p.T, p.S
         self._keep.append(bj)
         gws = self.bytes_buf("group_ws", _hip.decoder_workspace_bytes([p.rows for _, p in passes], True))
-        c.add("pnmn_attn_lstm_bwd_group", bj.ctypes.data, len(bj), 256, gws.data_ptr(), st)
+        ordered = self._order_lists([p for _, p in passes])
+        c.add("pnmn_attn_lstm_bwd_group_ordered" if ordered else "pnmn_attn_lstm_bwd_group", bj.ctypes.data, len(bj), 256, *ordered,
+              gws.data_ptr(), st)
         for dec, p in passes:
             c.add("pnmn_attn_denc", p.v["weights"].data_ptr(), p.v["dscore"].data_ptr(), p.v["dctx"].data_ptr(), p.v["hs"].data_ptr(),
                   dec.enc["h"][p.enc_row0:].data_ptr(), dec.enc["denc"][p.enc_row0:].data_ptr(), p.rows, p.T, p.S, 256, st)
