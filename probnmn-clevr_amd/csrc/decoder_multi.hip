@@ -26,6 +26,8 @@
 #include <limits.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "../../include/probnmn_hip.h"
 #include "cluster.h"
 #include "lds_optin.h"
@@ -94,7 +96,8 @@ constexpr size_t FWD_OVERLAP_LDS = sizeof(float) * (ROWS * H + 64);  // (OVERLAP
 // scores' LDS reads and DPP reductions, the softmax and the context sums, which are latency, not issue slots -- and the
 // gates phase behind the context hand-off stages and contracts the context alone: half the matrix time of a step leaves
 // its critical path (cycle stamps before: gate MFMAs 42 % of a step, attention 23 %).  Each partial sum keeps its order
-// (k-blocks ascending, x y z w), so the result is bit-identical to the other path's.  Without OVERLAP (S > 59): both
+// (k-blocks ascending, x y z w); the two compilations still agree to round-off only (DESIGN, "Launches of the multi-CU
+// decoder"), so a pass must not change sides between two runs that are compared bit for bit.  Without OVERLAP (S > 59): both
 // products behind the hand-off, their A operands double buffered in the 16 KB that `cpart` and `logl` leave idle there.
 // SAMPLE: the free-running modes (the kernel picks each step's token); a teacher-forced pass compiles without the token
 // phase -- its logits tile, Philox draw and the pointers they keep live are what the register allocator spills.
@@ -1028,59 +1031,73 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
 }
 
-// the compiled variants of the forward kernels
-const void* fwd_multi_variant(bool overlap, bool sample) {
-    if (overlap) return sample ? reinterpret_cast<const void*>(attn_lstm_fwd_multi_kernel<true, true>)
-                               : reinterpret_cast<const void*>(attn_lstm_fwd_multi_kernel<true, false>);
-    return sample ? reinterpret_cast<const void*>(attn_lstm_fwd_multi_kernel<false, true>)
-                  : reinterpret_cast<const void*>(attn_lstm_fwd_multi_kernel<false, false>);
+// ---- the compiled kernels: every __global__ instantiation of this file, named once -----------------------------------
+// A launch finds its kernel by key.  Forward: passes side by side (1 or 2), OVERLAP, the kernel's M of either pass (0 teacher
+// forced, 1 free running, 2 sampling under a filter; m1 = 0 for a lone pass), under the automaton, rows grouped by length.
+// Backward: the passes (1 to 3) and the order.  `optin` is the row's own: the kernel's LDS opt-in per device (lds_optin.h).
+struct VariantKey {
+    int backward, passes, overlap, m0, m1, constrained, ordered;
+};
+struct Variant {
+    VariantKey key;
+    const void* kernel;
+    std::atomic<uint64_t> optin{0};
+};
+template <class... Args>
+const void* kernel_of(void (*kernel)(Args...)) {
+    return reinterpret_cast<const void*>(kernel);
 }
-template <bool OVERLAP>
-const void* fwd_pair_variant_of(bool s0, bool s1) {
-    if (s0) return s1 ? reinterpret_cast<const void*>(attn_lstm_fwd_pair_kernel<OVERLAP, true, true>)
-                      : reinterpret_cast<const void*>(attn_lstm_fwd_pair_kernel<OVERLAP, true, false>);
-    return s1 ? reinterpret_cast<const void*>(attn_lstm_fwd_pair_kernel<OVERLAP, false, true>)
-              : reinterpret_cast<const void*>(attn_lstm_fwd_pair_kernel<OVERLAP, false, false>);
-}
-const void* fwd_pair_variant(bool overlap, bool s0, bool s1) {
-    return overlap ? fwd_pair_variant_of<true>(s0, s1) : fwd_pair_variant_of<false>(s0, s1);
-}
-
-// the variants with a filter: m0 / m1 as the kernel's M0 / M1, at least one of them 2
-const void* fwd_multi_filtered_variant(bool overlap) {
-    return overlap ? reinterpret_cast<const void*>(attn_lstm_fwd_multi_filtered_kernel<true>)
-                   : reinterpret_cast<const void*>(attn_lstm_fwd_multi_filtered_kernel<false>);
-}
-template <bool OVERLAP>
-const void* fwd_pair_filtered_variant_of(int m0, int m1) {
-    if (m0 == 2) return m1 == 2 ? reinterpret_cast<const void*>(attn_lstm_fwd_pair_filtered_kernel<OVERLAP, 2, 2>)
-                       : m1 == 1 ? reinterpret_cast<const void*>(attn_lstm_fwd_pair_filtered_kernel<OVERLAP, 2, 1>)
-                                 : reinterpret_cast<const void*>(attn_lstm_fwd_pair_filtered_kernel<OVERLAP, 2, 0>);
-    return m0 == 1 ? reinterpret_cast<const void*>(attn_lstm_fwd_pair_filtered_kernel<OVERLAP, 1, 2>)
-                   : reinterpret_cast<const void*>(attn_lstm_fwd_pair_filtered_kernel<OVERLAP, 0, 2>);
-}
-const void* fwd_pair_filtered_variant(bool overlap, int m0, int m1) {
-    return overlap ? fwd_pair_filtered_variant_of<true>(m0, m1) : fwd_pair_filtered_variant_of<false>(m0, m1);
-}
-
-// the constrained variants: m / m0 <= m1 as the kernels' M, at least one of them not 0
-const void* fwd_multi_constrained_variant(bool overlap, int m) {
-    if (overlap) return m == 2 ? reinterpret_cast<const void*>(attn_lstm_fwd_multi_constrained_kernel<true, true>)
-                               : reinterpret_cast<const void*>(attn_lstm_fwd_multi_constrained_kernel<true, false>);
-    return m == 2 ? reinterpret_cast<const void*>(attn_lstm_fwd_multi_constrained_kernel<false, true>)
-                  : reinterpret_cast<const void*>(attn_lstm_fwd_multi_constrained_kernel<false, false>);
-}
-template <bool OVERLAP>
-const void* fwd_pair_constrained_variant_of(int m0, int m1) {
-    if (m0 == 0) return m1 == 2 ? reinterpret_cast<const void*>(attn_lstm_fwd_pair_constrained_kernel<OVERLAP, 0, 2>)
-                                : reinterpret_cast<const void*>(attn_lstm_fwd_pair_constrained_kernel<OVERLAP, 0, 1>);
-    if (m0 == 1) return m1 == 2 ? reinterpret_cast<const void*>(attn_lstm_fwd_pair_constrained_kernel<OVERLAP, 1, 2>)
-                                : reinterpret_cast<const void*>(attn_lstm_fwd_pair_constrained_kernel<OVERLAP, 1, 1>);
-    return reinterpret_cast<const void*>(attn_lstm_fwd_pair_constrained_kernel<OVERLAP, 2, 2>);
-}
-const void* fwd_pair_constrained_variant(bool overlap, int m0, int m1) {
-    return overlap ? fwd_pair_constrained_variant_of<true>(m0, m1) : fwd_pair_constrained_variant_of<false>(m0, m1);
-}
+Variant VARIANTS[] = {
+    // bwd n ov m0 m1 con ord
+    {{0, 1, 1, 1, 0, 0, 0}, kernel_of(attn_lstm_fwd_multi_kernel<true, true>)},
+    {{0, 1, 1, 0, 0, 0, 0}, kernel_of(attn_lstm_fwd_multi_kernel<true, false>)},
+    {{0, 1, 0, 1, 0, 0, 0}, kernel_of(attn_lstm_fwd_multi_kernel<false, true>)},
+    {{0, 1, 0, 0, 0, 0, 0}, kernel_of(attn_lstm_fwd_multi_kernel<false, false>)},
+    {{0, 2, 1, 1, 1, 0, 0}, kernel_of(attn_lstm_fwd_pair_kernel<true, true, true>)},
+    {{0, 2, 1, 1, 0, 0, 0}, kernel_of(attn_lstm_fwd_pair_kernel<true, true, false>)},
+    {{0, 2, 1, 0, 1, 0, 0}, kernel_of(attn_lstm_fwd_pair_kernel<true, false, true>)},
+    {{0, 2, 1, 0, 0, 0, 0}, kernel_of(attn_lstm_fwd_pair_kernel<true, false, false>)},
+    {{0, 2, 0, 1, 1, 0, 0}, kernel_of(attn_lstm_fwd_pair_kernel<false, true, true>)},
+    {{0, 2, 0, 1, 0, 0, 0}, kernel_of(attn_lstm_fwd_pair_kernel<false, true, false>)},
+    {{0, 2, 0, 0, 1, 0, 0}, kernel_of(attn_lstm_fwd_pair_kernel<false, false, true>)},
+    {{0, 2, 0, 0, 0, 0, 0}, kernel_of(attn_lstm_fwd_pair_kernel<false, false, false>)},
+    // with a filter: at least one M is 2
+    {{0, 1, 1, 2, 0, 0, 0}, kernel_of(attn_lstm_fwd_multi_filtered_kernel<true>)},
+    {{0, 1, 0, 2, 0, 0, 0}, kernel_of(attn_lstm_fwd_multi_filtered_kernel<false>)},
+    {{0, 2, 1, 2, 2, 0, 0}, kernel_of(attn_lstm_fwd_pair_filtered_kernel<true, 2, 2>)},
+    {{0, 2, 1, 2, 1, 0, 0}, kernel_of(attn_lstm_fwd_pair_filtered_kernel<true, 2, 1>)},
+    {{0, 2, 1, 2, 0, 0, 0}, kernel_of(attn_lstm_fwd_pair_filtered_kernel<true, 2, 0>)},
+    {{0, 2, 1, 1, 2, 0, 0}, kernel_of(attn_lstm_fwd_pair_filtered_kernel<true, 1, 2>)},
+    {{0, 2, 1, 0, 2, 0, 0}, kernel_of(attn_lstm_fwd_pair_filtered_kernel<true, 0, 2>)},
+    {{0, 2, 0, 2, 2, 0, 0}, kernel_of(attn_lstm_fwd_pair_filtered_kernel<false, 2, 2>)},
+    {{0, 2, 0, 2, 1, 0, 0}, kernel_of(attn_lstm_fwd_pair_filtered_kernel<false, 2, 1>)},
+    {{0, 2, 0, 2, 0, 0, 0}, kernel_of(attn_lstm_fwd_pair_filtered_kernel<false, 2, 0>)},
+    {{0, 2, 0, 1, 2, 0, 0}, kernel_of(attn_lstm_fwd_pair_filtered_kernel<false, 1, 2>)},
+    {{0, 2, 0, 0, 2, 0, 0}, kernel_of(attn_lstm_fwd_pair_filtered_kernel<false, 0, 2>)},
+    // under the automaton: at least one M is not 0, and m0 <= m1 in a pair (launch_fwd puts the passes in that order)
+    {{0, 1, 1, 2, 0, 1, 0}, kernel_of(attn_lstm_fwd_multi_constrained_kernel<true, true>)},
+    {{0, 1, 1, 1, 0, 1, 0}, kernel_of(attn_lstm_fwd_multi_constrained_kernel<true, false>)},
+    {{0, 1, 0, 2, 0, 1, 0}, kernel_of(attn_lstm_fwd_multi_constrained_kernel<false, true>)},
+    {{0, 1, 0, 1, 0, 1, 0}, kernel_of(attn_lstm_fwd_multi_constrained_kernel<false, false>)},
+    {{0, 2, 1, 0, 2, 1, 0}, kernel_of(attn_lstm_fwd_pair_constrained_kernel<true, 0, 2>)},
+    {{0, 2, 1, 0, 1, 1, 0}, kernel_of(attn_lstm_fwd_pair_constrained_kernel<true, 0, 1>)},
+    {{0, 2, 1, 1, 2, 1, 0}, kernel_of(attn_lstm_fwd_pair_constrained_kernel<true, 1, 2>)},
+    {{0, 2, 1, 1, 1, 1, 0}, kernel_of(attn_lstm_fwd_pair_constrained_kernel<true, 1, 1>)},
+    {{0, 2, 1, 2, 2, 1, 0}, kernel_of(attn_lstm_fwd_pair_constrained_kernel<true, 2, 2>)},
+    {{0, 2, 0, 0, 2, 1, 0}, kernel_of(attn_lstm_fwd_pair_constrained_kernel<false, 0, 2>)},
+    {{0, 2, 0, 0, 1, 1, 0}, kernel_of(attn_lstm_fwd_pair_constrained_kernel<false, 0, 1>)},
+    {{0, 2, 0, 1, 2, 1, 0}, kernel_of(attn_lstm_fwd_pair_constrained_kernel<false, 1, 2>)},
+    {{0, 2, 0, 1, 1, 1, 0}, kernel_of(attn_lstm_fwd_pair_constrained_kernel<false, 1, 1>)},
+    {{0, 2, 0, 2, 2, 1, 0}, kernel_of(attn_lstm_fwd_pair_constrained_kernel<false, 2, 2>)},
+    // rows grouped by length: a lone teacher-forced pass
+    {{0, 1, 1, 0, 0, 0, 1}, kernel_of(attn_lstm_fwd_multi_ordered_kernel<true>)},
+    {{0, 1, 0, 0, 0, 0, 1}, kernel_of(attn_lstm_fwd_multi_ordered_kernel<false>)},
+    // backward
+    {{1, 1, 0, 0, 0, 0, 0}, kernel_of(attn_lstm_bwd_multi_kernel)},
+    {{1, 1, 0, 0, 0, 0, 1}, kernel_of(attn_lstm_bwd_multi_ordered_kernel)},
+    {{1, 2, 0, 0, 0, 0, 0}, kernel_of(attn_lstm_bwd_pair_kernel)},
+    {{1, 3, 0, 0, 0, 0, 0}, kernel_of(attn_lstm_bwd_group3_kernel)},
+};
 
 // rows one launch can take: all tiles x 8 members resident, one workgroup per CU
 int rows_per_launch() {
@@ -1177,33 +1194,6 @@ OrdArgs ordered_range(size_t r0, int pass_rows, const int32_t* order, const int3
     return OrdArgs{order + r0, tile_steps + r0 / ROWS, pass_rows};
 }
 
-// A lone teacher-forced pass with an order (the caller has checked both lists and the job's mode), in row ranges like any other.
-int launch_fwd_ordered(const pnmn_decoder_fwd_job& j, const int32_t* order, const int32_t* tile_steps, int hidden, void* workspace,
-                       hipStream_t st) {
-    if (j.B <= 0 || j.T <= 0) return 0;
-    if (const int e = check_job(j, hidden)) return e;
-    const int chunk = rows_per_launch();
-    if (chunk <= 0) return PNMN_ESHAPE;
-    const size_t base = FWD_FIXED_LDS + sizeof(float) * RW * j.S * H + ORDER_LDS;
-    const bool overlap = base + FWD_OVERLAP_LDS <= LDS_LIMIT;
-    const size_t lds = base + (overlap ? FWD_OVERLAP_LDS : 0);
-    const auto kernel = overlap ? attn_lstm_fwd_multi_ordered_kernel<true> : attn_lstm_fwd_multi_ordered_kernel<false>;
-    static std::atomic<uint64_t> cfg[2];  // (the opt-in is per device and per kernel: lds_optin.h)
-    if (const int e = pnmn::opt_in_lds(reinterpret_cast<const void*>(kernel), LDS_LIMIT, cfg[overlap])) return e;
-    int* sync = nullptr;
-    for (int r0 = 0; r0 < j.B; r0 += chunk) {
-        const int part = j.B - r0 < chunk ? j.B - r0 : chunk;
-        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
-        if (e != hipSuccess) return (int)e;
-        const MFwdArgs a = kernel_args(j, 0, part, sync, 0);
-        hipLaunchKernelGGL(kernel, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a,
-                           ordered_range((size_t)r0, j.B, order, tile_steps));
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
-
 // Orders of a group call: null, or n entries of which entry i (may be null) belongs to job i
 inline bool any_order(const int32_t* const* order, int n) {
     for (int i = 0; order && i < n; ++i)
@@ -1228,131 +1218,104 @@ int plan_group(const Job* j, int n, int hidden, int& smax, int& chunk, int* rows
     return chunk > 0 ? 0 : PNMN_ESHAPE;
 }
 
+// The table's row of `key`, its kernel opted in to the LDS limit on this device (the limit itself, whatever the launch
+// uses).  A key without a row is PNMN_EINVAL: the launchers below form none.
+int find_variant(const VariantKey& key, const Variant*& out) {
+    for (Variant& v : VARIANTS) {
+        const VariantKey& k = v.key;
+        if (k.backward == key.backward && k.passes == key.passes && k.overlap == key.overlap && k.m0 == key.m0 && k.m1 == key.m1 &&
+            k.constrained == key.constrained && k.ordered == key.ordered) {
+            out = &v;
+            return pnmn::opt_in_lds(v.kernel, LDS_LIMIT, v.optin);
+        }
+    }
+    return PNMN_EINVAL;
+}
+
+// One launch of a row's kernel over `tiles` tiles.  `args`: the kernel's arguments in the order every signature follows -- the
+// pass records; with more than one pass tiles0 (and tiles01); a filter per pass (the filtered and the constrained kernels); the
+// automaton (constrained); OrdArgs (ordered) -- each null where the kernel takes none.
+int launch(const Variant& v, int tiles, size_t lds, hipStream_t st, std::initializer_list<const void*> args) {
+    void* argv[8];
+    int n = 0;
+    for (const void* a : args)
+        if (a) argv[n++] = const_cast<void*>(a);
+    (void)hipLaunchKernel(v.kernel, dim3(MEMBERS * tiles), dim3(512), argv, lds, st);
+    return (int)hipGetLastError();
+}
+
+// A lone pass runs in row ranges of at most `chunk` rows, each a launch behind the stream's counter block: issue(r0, rows, sync)
+template <class Issue>
+int for_row_ranges(int rows, int chunk, void* workspace, hipStream_t st, Issue issue) {
+    int* sync = nullptr;
+    for (int r0 = 0; r0 < rows; r0 += chunk) {
+        const hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
+        if (e != hipSuccess) return (int)e;
+        if (const int rc = issue(r0, rows - r0 < chunk ? rows - r0 : chunk, sync)) return rc;
+    }
+    return 0;
+}
+
 // Passes that fit the chip together go out as ONE launch; otherwise the first n - 1 by the same rule and then the last
-// alone (identical results).  A lone pass beyond one launch runs in row chunks.
+// alone.  A pass with an order goes out alone too -- the kernels for passes side by side take none -- so a group that holds
+// one falls back as a group that does not fit.  A lone pass beyond one launch runs in row ranges.
 // `f`: one filter per job (checked by the caller), or null: none.  A job runs under its filter when it samples (mode 1) and
-// the filter is not the identity; every other job, and every launch without such a job, takes the unfiltered kernels.
-// `au`: the checked automaton of a constrained call, or null.  It applies to every free-running job; a launch with such a job
-// takes the constrained kernels (launch_fwd_constrained), every other launch the kernels it always took.
-int launch_fwd_constrained(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, const pnmn::TokenAutomaton& au, int n,
-                           int hidden, void* workspace, hipStream_t st);
+// the filter is not the identity.  `au`: the checked automaton of a constrained call, or null.  It applies to every
+// free-running job, and a launch with such a job takes the constrained kernels.  Those pairs exist for M0 <= M1, so the passes
+// go out in that order (a pass's result does not depend on where its tiles sit in the grid).  `order` / `tile_steps`: see
+// any_order; the caller has checked the lists, and that a job with an order is teacher forced.
+// The LDS of a launch is the passes' own for the longest source plus what its family puts behind it -- the automaton's tables, or
+// the tile's row indices -- and OVERLAP is picked with that counted: S <= 59, under the automaton S <= 58.
 int launch_fwd(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, int n, int hidden, void* workspace, hipStream_t st,
-               const pnmn::TokenAutomaton* au = nullptr, const int32_t* const* order = nullptr,
-               const int32_t* const* tile_steps = nullptr) {
-    // (`order` / `tile_steps`: see any_order.  A pass with an order goes out alone -- the kernels for passes side by side take
-    // none -- so a group that holds one falls back as a group that does not fit: identical results.)
+               const pnmn::TokenAutomaton* au, const int32_t* const* order, const int32_t* const* tile_steps) {
     if (n > 1 && (!jobs_fit(j, n) || any_order(order, n))) {
         const int rc = launch_fwd(j, f, n - 1, hidden, workspace, st, au, order, tile_steps);
         return rc != 0 ? rc : launch_fwd(j + n - 1, f ? f + n - 1 : nullptr, 1, hidden, workspace, st, au, from(order, n - 1),
                                          from(tile_steps, n - 1));
     }
-    if (any_order(order, 1)) return launch_fwd_ordered(j[0], order[0], tile_steps[0], hidden, workspace, st);
-    if (au && (j[0].sample != 0 || (n > 1 && j[1].sample != 0))) return launch_fwd_constrained(j, f, *au, n, hidden, workspace, st);
     if (j[0].B <= 0 || j[0].T <= 0) return 0;  // (a lone pass only: passes side by side have rows and steps, see jobs_fit)
     int smax, chunk, rows[MAX_JOBS], tile0[MAX_JOBS + 1];
     if (const int e = plan_group(j, n, hidden, smax, chunk, rows, tile0)) return e;
-    const bool overlap = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + FWD_OVERLAP_LDS <= LDS_LIMIT;
-    const size_t lds = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + (overlap ? FWD_OVERLAP_LDS : 0);
-    const bool s0 = j[0].sample != 0, s1 = n > 1 && j[1].sample != 0;
     int m[2] = {0, 0};  // the kernels' M per pass
     pnmn::SamplingFilter ff[2] = {{1.f, 0, 1.f}, {1.f, 0, 1.f}};
     for (int i = 0; i < n; ++i) {
         m[i] = j[i].sample == 0 ? 0 : (f && j[i].sample == 1 && !pnmn::filter_is_identity(f[i])) ? 2 : 1;
         if (m[i] == 2) ff[i] = pnmn::SamplingFilter{f[i].temperature, f[i].top_k, f[i].top_p};
     }
-    const bool filtered = m[0] == 2 || m[1] == 2;
-    const void* kernel = filtered ? (n == 1 ? fwd_multi_filtered_variant(overlap) : fwd_pair_filtered_variant(overlap, m[0], m[1]))
-                                  : (n == 1 ? fwd_multi_variant(overlap, s0) : fwd_pair_variant(overlap, s0, s1));
-    {   // (the opt-in is per device and per kernel: lds_optin.h; the limit itself, whatever this launch uses)
-        static std::atomic<uint64_t> cfg[2][8], cfg_filtered[2][2][9];
-        std::atomic<uint64_t>& c = filtered ? cfg_filtered[n - 1][overlap][3 * m[0] + m[1]] : cfg[n - 1][4 * overlap + 2 * s0 + s1];
-        if (const int e = pnmn::opt_in_lds(kernel, LDS_LIMIT, c)) return e;
-    }
-    int* sync = nullptr;
+    const bool ordered = any_order(order, 1);  // (n == 1 then)
+    const bool constrained = au && (m[0] != 0 || m[1] != 0);
+    const bool filters = constrained || m[0] == 2 || m[1] == 2;  // (does the kernel take them?)
+    const int lo = n > 1 && constrained && m[0] > m[1] ? 1 : 0, hi = 1 - lo;  // the order the passes go out in
+    const size_t extras = constrained ? pnmn::AUTOMATON_LDS_BYTES : ordered ? ORDER_LDS : 0;
+    const size_t base = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + extras;
+    // A teacher-forced launch of a call with an automaton stages no tables, but takes OVERLAP where the call's constrained
+    // launches do: the two compilations of the body differ in the last bits, and a pass must compute the same bits alone
+    // (a group that does not fit) and beside a free-running pass.
+    const size_t as_pair = au && !constrained && !ordered ? pnmn::AUTOMATON_LDS_BYTES : 0;
+    const bool overlap = base + as_pair + FWD_OVERLAP_LDS <= LDS_LIMIT;
+    const size_t lds = base + (overlap ? FWD_OVERLAP_LDS : 0);
+    const Variant* v = nullptr;
+    if (const int e = find_variant({0, n, overlap, m[lo], n > 1 ? m[hi] : 0, constrained, ordered}, v)) return e;
+    const void* const f0 = filters ? &ff[lo] : nullptr;
     if (n > 1) {
-        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
+        int* sync = nullptr;
+        const hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
         if (e != hipSuccess) return (int)e;
-        const MFwdArgs a0 = kernel_args(j[0], 0, rows[0], sync, 0), a1 = kernel_args(j[1], 0, rows[1], sync, tile0[1]);
-        if (filtered) {
-            const auto pair = reinterpret_cast<void (*)(const MFwdArgs, const MFwdArgs, const int, const pnmn::SamplingFilter,
-                                                        const pnmn::SamplingFilter)>(const_cast<void*>(kernel));
-            hipLaunchKernelGGL(pair, dim3(MEMBERS * tile0[2]), dim3(512), lds, st, a0, a1, tile0[1], ff[0], ff[1]);
-        } else {
-            const auto pair = reinterpret_cast<void (*)(const MFwdArgs, const MFwdArgs, const int)>(const_cast<void*>(kernel));
-            hipLaunchKernelGGL(pair, dim3(MEMBERS * tile0[2]), dim3(512), lds, st, a0, a1, tile0[1]);
-        }
-        return (int)hipGetLastError();
+        const int tiles0 = padded_tiles(rows[lo]);
+        const MFwdArgs a0 = kernel_args(j[lo], 0, rows[lo], sync, 0), a1 = kernel_args(j[hi], 0, rows[hi], sync, tiles0);
+        return launch(*v, tile0[2], lds, st, {&a0, &a1, &tiles0, f0, filters ? &ff[hi] : nullptr, constrained ? au : nullptr});
     }
-    for (int r0 = 0; r0 < rows[0]; r0 += chunk) {
-        const int part = rows[0] - r0 < chunk ? rows[0] - r0 : chunk;
-        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
-        if (e != hipSuccess) return (int)e;
-        const MFwdArgs a = kernel_args(j[0], (size_t)r0, part, sync, 0);
-        if (filtered) {
-            const auto multi = reinterpret_cast<void (*)(const MFwdArgs, const pnmn::SamplingFilter)>(const_cast<void*>(kernel));
-            hipLaunchKernelGGL(multi, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a, ff[0]);
-        } else {
-            const auto multi = reinterpret_cast<void (*)(const MFwdArgs)>(const_cast<void*>(kernel));
-            hipLaunchKernelGGL(multi, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a);
-        }
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
+    return for_row_ranges(rows[0], chunk, workspace, st, [&](int r0, int part, int* sync) {
+        // (an ordered range is addressed from the pass's base pointers: ordered_range)
+        const MFwdArgs a = kernel_args(j[0], ordered ? 0 : (size_t)r0, part, sync, 0);
+        const OrdArgs ord = ordered ? ordered_range((size_t)r0, rows[0], order[0], tile_steps[0]) : OrdArgs{};
+        return launch(*v, padded_tiles(part), lds, st, {&a, f0, constrained ? au : nullptr, ordered ? &ord : nullptr});
+    });
 }
 
-// One launch of one or two passes that fit together (launch_fwd has seen to that), at least one of them free running: the
-// constrained kernels.  The pair kernels exist for M0 <= M1, so the passes go out in that order (a pass's result does not
-// depend on where its tiles sit in the grid).  The tables take AUTOMATON_LDS_BYTES behind the passes' own LDS, so OVERLAP is
-// picked with them counted: one source position earlier (S <= 58) than without the automaton, bit-identical either way.
-int launch_fwd_constrained(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, const pnmn::TokenAutomaton& au, int n,
-                           int hidden, void* workspace, hipStream_t st) {
-    if (j[0].B <= 0 || j[0].T <= 0) return 0;
-    int smax, chunk, rows[MAX_JOBS], tile0[MAX_JOBS + 1];
-    if (const int e = plan_group(j, n, hidden, smax, chunk, rows, tile0)) return e;
-    constexpr size_t TABLES = pnmn::AUTOMATON_LDS_BYTES;
-    const bool overlap = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + FWD_OVERLAP_LDS + TABLES <= LDS_LIMIT;
-    const size_t lds = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + (overlap ? FWD_OVERLAP_LDS : 0) + TABLES;
-    int m[2] = {0, 0};
-    pnmn::SamplingFilter ff[2] = {{1.f, 0, 1.f}, {1.f, 0, 1.f}};
-    for (int i = 0; i < n; ++i) {
-        m[i] = j[i].sample == 0 ? 0 : (f && j[i].sample == 1 && !pnmn::filter_is_identity(f[i])) ? 2 : 1;
-        if (m[i] == 2) ff[i] = pnmn::SamplingFilter{f[i].temperature, f[i].top_k, f[i].top_p};
-    }
-    int* sync = nullptr;
-    static std::atomic<uint64_t> cfg[2][2][9];  // (the opt-in is per device and per kernel: lds_optin.h)
-    if (n > 1) {
-        const int lo = m[0] <= m[1] ? 0 : 1, hi = 1 - lo;  // the order the passes go out in
-        const void* kernel = fwd_pair_constrained_variant(overlap, m[lo], m[hi]);
-        if (const int e = pnmn::opt_in_lds(kernel, LDS_LIMIT, cfg[1][overlap][3 * m[lo] + m[hi]])) return e;
-        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
-        if (e != hipSuccess) return (int)e;
-        const int tiles_lo = padded_tiles(rows[lo]);
-        const MFwdArgs a0 = kernel_args(j[lo], 0, rows[lo], sync, 0), a1 = kernel_args(j[hi], 0, rows[hi], sync, tiles_lo);
-        const auto pair = reinterpret_cast<void (*)(const MFwdArgs, const MFwdArgs, const int, const pnmn::SamplingFilter,
-                                                    const pnmn::SamplingFilter, const pnmn::TokenAutomaton)>(const_cast<void*>(kernel));
-        hipLaunchKernelGGL(pair, dim3(MEMBERS * tile0[2]), dim3(512), lds, st, a0, a1, tiles_lo, ff[lo], ff[hi], au);
-        return (int)hipGetLastError();
-    }
-    const void* kernel = fwd_multi_constrained_variant(overlap, m[0]);
-    if (const int e = pnmn::opt_in_lds(kernel, LDS_LIMIT, cfg[0][overlap][m[0]])) return e;
-    const auto multi = reinterpret_cast<void (*)(const MFwdArgs, const pnmn::SamplingFilter, const pnmn::TokenAutomaton)>(
-        const_cast<void*>(kernel));
-    for (int r0 = 0; r0 < rows[0]; r0 += chunk) {
-        const int part = rows[0] - r0 < chunk ? rows[0] - r0 : chunk;
-        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
-        if (e != hipSuccess) return (int)e;
-        const MFwdArgs a = kernel_args(j[0], (size_t)r0, part, sync, 0);
-        hipLaunchKernelGGL(multi, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a, ff[0], au);
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
-}
-
-int launch_bwd(const pnmn_decoder_bwd_job* j, int n, int hidden, void* workspace, hipStream_t st,
-               const int32_t* const* order = nullptr, const int32_t* const* tile_steps = nullptr) {
-    if (n > 1 && (!jobs_fit(j, n) || any_order(order, n))) {  // (a pass with an order goes out alone: see launch_fwd)
+int launch_bwd(const pnmn_decoder_bwd_job* j, int n, int hidden, void* workspace, hipStream_t st, const int32_t* const* order,
+               const int32_t* const* tile_steps) {
+    if (n > 1 && (!jobs_fit(j, n) || any_order(order, n))) {  // (as launch_fwd)
         const int rc = launch_bwd(j, n - 1, hidden, workspace, st, order, tile_steps);
         return rc != 0 ? rc : launch_bwd(j + n - 1, 1, hidden, workspace, st, from(order, n - 1), from(tile_steps, n - 1));
     }
@@ -1361,44 +1324,23 @@ int launch_bwd(const pnmn_decoder_bwd_job* j, int n, int hidden, void* workspace
     if (const int e = plan_group(j, n, hidden, smax, chunk, rows, tile0)) return e;
     const bool ordered = any_order(order, 1);  // (n == 1 then)
     const size_t lds = BWD_FIXED_LDS + sizeof(float) * RW * smax * H + (ordered ? ORDER_LDS : 0);
-    {
-        const void* const kernels[MAX_JOBS + 1] = {reinterpret_cast<const void*>(attn_lstm_bwd_multi_kernel),
-                                                   reinterpret_cast<const void*>(attn_lstm_bwd_pair_kernel),
-                                                   reinterpret_cast<const void*>(attn_lstm_bwd_group3_kernel),
-                                                   reinterpret_cast<const void*>(attn_lstm_bwd_multi_ordered_kernel)};
-        static std::atomic<uint64_t> cfg[MAX_JOBS + 1];  // (per kernel and device: lds_optin.h)
-        const int k = ordered ? MAX_JOBS : n - 1;
-        if (const int e = pnmn::opt_in_lds(kernels[k], LDS_LIMIT, cfg[k])) return e;
-    }
+    const Variant* v = nullptr;
+    if (const int e = find_variant({1, n, 0, 0, 0, 0, ordered}, v)) return e;
     float* x1 = reinterpret_cast<float*>(static_cast<char*>(workspace) + pnmn::CLUSTER_SYNC_BYTES);
     float* x2 = x1 + (size_t)exchange_tiles(rows, n, chunk) * 2 * MEMBERS * 2 * ROWS * H;
-    int* sync = nullptr;
     if (n > 1) {
-        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
+        int* sync = nullptr;
+        const hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
         if (e != hipSuccess) return (int)e;
         MBwdArgs a[MAX_JOBS];
         for (int i = 0; i < n; ++i) a[i] = kernel_args(j[i], 0, rows[i], sync, tile0[i], x1, x2);
-        const dim3 grid(MEMBERS * tile0[n]);
-        if (n == 2) hipLaunchKernelGGL(attn_lstm_bwd_pair_kernel, grid, dim3(512), lds, st, a[0], a[1], tile0[1]);
-        else hipLaunchKernelGGL(attn_lstm_bwd_group3_kernel, grid, dim3(512), lds, st, a[0], a[1], a[2], tile0[1], tile0[2]);
-        return (int)hipGetLastError();
+        return launch(*v, tile0[n], lds, st, {&a[0], &a[1], n > 2 ? &a[2] : nullptr, &tile0[1], n > 2 ? &tile0[2] : nullptr});
     }
-    for (int r0 = 0; r0 < rows[0]; r0 += chunk) {
-        const int part = rows[0] - r0 < chunk ? rows[0] - r0 : chunk;
-        hipError_t e = pnmn::cluster_sync_block(workspace, st, &sync);
-        if (e != hipSuccess) return (int)e;
-        if (ordered) {
-            const MBwdArgs a = kernel_args(j[0], 0, part, sync, 0, x1, x2);
-            hipLaunchKernelGGL(attn_lstm_bwd_multi_ordered_kernel, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a,
-                               ordered_range((size_t)r0, rows[0], order[0], tile_steps[0]));
-        } else {
-            const MBwdArgs a = kernel_args(j[0], (size_t)r0, part, sync, 0, x1, x2);
-            hipLaunchKernelGGL(attn_lstm_bwd_multi_kernel, dim3(MEMBERS * padded_tiles(part)), dim3(512), lds, st, a);
-        }
-        e = hipGetLastError();
-        if (e != hipSuccess) return (int)e;
-    }
-    return 0;
+    return for_row_ranges(rows[0], chunk, workspace, st, [&](int r0, int part, int* sync) {
+        const MBwdArgs a = kernel_args(j[0], ordered ? 0 : (size_t)r0, part, sync, 0, x1, x2);
+        const OrdArgs ord = ordered ? ordered_range((size_t)r0, rows[0], order[0], tile_steps[0]) : OrdArgs{};
+        return launch(*v, padded_tiles(part), lds, st, {&a, ordered ? &ord : nullptr});
+    });
 }
 
 }  // namespace
