@@ -387,6 +387,8 @@ typedef struct {
 int pnmn_token_prep(const int64_t* tokens, int64_t token_row_stride, int B, int T, int pad, int bos, int eos,
                     int drop_first, int64_t* out, float* fmask, int* last, void* stream);
 int pnmn_length_order(const int32_t* last, int B, int T, int32_t* order, int32_t* tile_steps, void* stream);
+/* The same lists from the rows' step counts: steps[b] = clamp(steps_in[b], 1, T)  (what pnmn_attn_lstm_fwd_group_stop writes). */
+int pnmn_length_order_steps(const int32_t* steps_in, int B, int T, int32_t* order, int32_t* tile_steps, void* stream);
 /* A decoder pass's rows for pnmn_length_order: last[b] = max(steps_b, 1) - 1 with steps_b as pnmn_valid_rows (below) defines a
  * decoder segment's, from the same mask tokens (the ones pnmn_seq_nll_fwd is given).  One launch, no atomics, no host
  * synchronisation. */
@@ -816,6 +818,31 @@ int pnmn_attn_lstm_fwd_group_ordered(const pnmn_decoder_fwd_job* jobs, const str
 int pnmn_attn_lstm_bwd_group_ordered(const pnmn_decoder_bwd_job* jobs, int n, int hidden,
                                      const int32_t* const* order /* HOST array, may be NULL */,
                                      const int32_t* const* tile_steps /* HOST array, may be NULL */, void* workspace, void* stream);
+/* Free-running tiles that stop: the forward call given, per job, `steps_out` [B] (device int32; a HOST array of n device pointers
+ * as `order` is, or NULL; entry i belongs to job i, NULL = the job runs as in pnmn_attn_lstm_fwd_group_ordered, which forwards
+ * here with NULL).  A job with steps_out must be free running (sample != 0) with end_index inside [0, V), and then
+ *   - a row that has chosen end_index chooses end_index at every later step (the finished row of the automaton rule), and
+ *     steps_out[b] = 1 + the step of row b's first end_index, T when it has none;
+ *   - a 16-row tile leaves its step loop behind the step at which the last of its rows has chosen end_index; which step that
+ *     is, every workgroup of the tile decides for itself from the tokens it has drawn itself -- the same tokens in all of
+ *     them, as they always were -- so no exchange is added;
+ *   - up to and including its first end_index (t < steps_out[b]) a row's tokens, hs, cs, act, ctx and probs are the bits the
+ *     call without steps_out writes there; between there and its tile's last step they are those of a row fed end_index;
+ *   - from its tile's last step on, a row holds end_index in tokens and ZEROS in hs, ctx (read by later calls over all T), cs,
+ *     act and probs (which a backward whose rows are grouped by steps_out may read at a step the row's tile here never ran:
+ *     there every gradient is 0 x these values, and with probs = 0 the attention's renormalisation stays finite);
+ *   - the job goes out in launches of its own, as a job with an order does; cut into row ranges, a range from row r0 takes
+ *     steps_out + r0.
+ * With steps_out - 1 as pnmn_length_order's `last` (pnmn_length_order_steps takes steps_out itself), the lists serve
+ * pnmn_attn_lstm_bwd_group_ordered for that job: its contract holds when dhs is zero from steps_out[b] on, as the loss over the
+ * trimmed samples makes it.  A teacher-forced job given steps_out, end_index outside [0, V), an automaton table or a
+ * non-identity filter of the job beside steps_out returns PNMN_EINVAL. */
+int pnmn_attn_lstm_fwd_group_stop(const pnmn_decoder_fwd_job* jobs, const struct pnmn_sampling_filter* filters /* HOST, may be NULL */,
+                                  int end_index, const uint8_t* token_class /* HOST */, const uint8_t* next_state /* HOST */,
+                                  const uint8_t* min_left /* HOST */, int n_states, int n_classes, int n, int hidden,
+                                  const int32_t* const* order /* HOST array, may be NULL */,
+                                  const int32_t* const* tile_steps /* HOST array, may be NULL */,
+                                  int32_t* const* steps_out /* HOST array, may be NULL */, void* workspace, void* stream);
 /* The encoder-output gradient from what pnmn_attn_lstm_bwd_group emits, in one bandwidth-bound launch instead of two
  * strided-batched library GEMMs of B tiny [S x T].[T x 256] products (allennlp SimpleSeq2Seq._prepare_attended_input /
  * DotProductAttention under autograd; seq2seq_base.py:201):

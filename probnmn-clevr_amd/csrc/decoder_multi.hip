@@ -87,6 +87,12 @@ struct OrdArgs {
     int Bfull;                  // rows of the whole pass: what an entry of `order` may address
 };
 
+// What a free-running launch that stops its tiles (STOP) takes besides: an argument of its own, as OrdArgs is.
+struct StopArgs {
+    int32_t* steps_out;  // [rows of the launch] steps of every row: 1 + the step of its first `end`, T without one
+    int end;
+};
+
 constexpr size_t FWD_FIXED_LDS = sizeof(float) * (4 * ROWS * GLD + RW * 4 * H + ROWS * MAXV + RW * MAXS) + sizeof(int) * ROWS;
 constexpr size_t FWD_OVERLAP_LDS = sizeof(float) * (ROWS * H + 64);  // (OVERLAP) the staged h_{t-1} tile + a sink for predicated stores
 
@@ -114,13 +120,33 @@ constexpr size_t FWD_OVERLAP_LDS = sizeof(float) * (ROWS * H + 64);  // (OVERLAP
 // What a later call reads over all T steps (hs: the logits product; ctx: the cell's input weight gradient) is zero filled from
 // there on; cs, act and probs, which only this pass's backward reads (over the same steps), stay unwritten.  Without ORD every
 // expression below is the one it was.
-template <bool OVERLAP, bool SAMPLE, bool FILT = false, bool CONSTR = false, bool ORD = false>
+// STOP (free running, no filter, no automaton): the tile leaves the step loop behind the step at which its last row has
+// chosen `end`.  A row that has chosen `end` chooses `end` from then on (the finished row of the constrained kernels), and its
+// steps -- 1 + the step of its first `end`, T without one -- go to steps_out.  Up to and including that step the row's tokens
+// and saved tensors are the bits of the kernel without STOP: the Philox counter is (row, step), and a row's arithmetic does
+// not depend on its neighbours.  From the tile's last step on its rows hold `end` in tokens and ZEROS in hs, ctx, cs, act
+// and probs: hs and ctx feed products over all T (the logits, the cell's input weight gradient); cs, act and probs are what
+// a backward with the rows grouped by their steps may read at a step the row's forward tile never ran (its tile there can be
+// longer than its tile here) -- every gradient of such a step is 0 x these values, so they must be finite, and with probs = 0
+// the softmax backward's renormalisation is 0 / 1e-13.
+// WHY THE MEMBERS CANNOT DISAGREE about the step they leave at (one that left early would let the others wait for good):
+// the decision is a function of the tile's 16 tokens per step alone.  Every member forms them itself, and forms the SAME
+// tokens: each reads the same h_t (complete in memory behind the step's second hand-off), the same w_p and b_p, and runs the
+// same instructions of the same code object over them, so the logits tile is bit-identical in all eight; the draw is a pure
+// function of those logits and (seed, row, step).  The kernels without STOP rest on the same fact -- a member's gate columns
+// take the token's table row, so members that disagreed would already compute a hidden state no single token sequence
+// explains.  The finished flags sit in LDS per member, are written in the token phase and read behind the barrier that ends
+// it: no exchange between workgroups is added, every member runs the same number of signal / wait pairs, and the counter
+// arithmetic of cluster.h holds as it is.
+template <bool OVERLAP, bool SAMPLE, bool FILT = false, bool CONSTR = false, bool ORD = false, bool STOP = false>
 __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, const int tile, const int part,
                                                          const pnmn::SamplingFilter& f = pnmn::SamplingFilter{1.f, 0, 1.f},
                                                          const pnmn::TokenAutomaton* aut = nullptr,
-                                                         const OrdArgs& ord = OrdArgs{nullptr, nullptr, 0}) {
+                                                         const OrdArgs& ord = OrdArgs{nullptr, nullptr, 0},
+                                                         const StopArgs& stop = StopArgs{nullptr, 0}) {
     static_assert(SAMPLE || !CONSTR, "the automaton constrains the free-running modes only");
     static_assert(!ORD || !SAMPLE, "a free-running pass knows its lengths only as it runs");
+    static_assert(!STOP || (SAMPLE && !FILT && !CONSTR), "only the plain free-running modes stop");
     extern __shared__ __attribute__((aligned(16))) char raw[];
     const int T = a.T, S = a.S;
     float* encl = reinterpret_cast<float*>(raw);                                       // [RW][S][H]
@@ -132,6 +158,7 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
     float* hst = &logl[ROWS][0];                                                       // (OVERLAP) [4 parts][16 rows][64]
     float* sink = hst + ROWS * H;                                                      // (OVERLAP) [64]
     int* rowl = reinterpret_cast<int*>(OVERLAP ? sink + 64 : hst);                     // (ORD) [16] batch row of every slot
+    int* stepl = rowl;                                                                 // (STOP) [16] steps of every finished row, else 0
 
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int row0 = tile * ROWS, myrow0 = row0 + RW * part, u0 = UW * part;
@@ -192,6 +219,10 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
         }
     }
     if (tid < ROWS) tokl[tid] = a.start;
+    if constexpr (STOP) {  // (a slot past the launch's last row counts as finished)
+        if (tid < ROWS) stepl[tid] = row0 + tid < a.B ? 0 : T;
+    }
+    int ran = T;  // (STOP) steps the tile ran
     // source mask of the row this wave attends for (constant over the steps)
     const float row_mask = lane < S ? a.mask[(size_t)(ORD ? mrow(wave >> 2) : min(myrow0 + (wave >> 2), a.B - 1)) * S + lane] : 0.f;
     float creg = 0.f;                       // cell state of (row tid / 32, unit u0 + tid % 32)
@@ -521,12 +552,47 @@ __device__ __forceinline__ void attn_lstm_fwd_multi_body(const MFwdArgs& a, cons
                     choice = pnmn::choose_row_token<FILT>(logl[rl], V, a.sample, a.pad, a.unk, a.start, a.seed,
                                                           a.row_offset + (uint64_t)row, (uint32_t)t, logl[rl], f);
                 }
+                if constexpr (STOP) {  // (only this wave touches the row's flag inside the phase)
+                    if (stepl[rl] != 0) choice = stop.end;
+                    else if (choice == stop.end && lane == 0) stepl[rl] = t + 1;
+                }
                 if (lane == 0) {
                     tokl[rl] = choice;
                     if (part == 0) a.tokens[(size_t)row * T + t] = choice;
                 }
             }
             __syncthreads();
+            if constexpr (STOP) {  // every row of the tile has ended: the same answer in every thread of every member (above)
+                int unfinished = 0;
+#pragma unroll
+                for (int r = 0; r < ROWS; ++r) unfinished += stepl[r] == 0;
+                if (unfinished == 0) {
+                    ran = t + 1;
+                    break;
+                }
+            }
+        }
+    }
+    if constexpr (STOP) {
+        // my rows from the tile's last step on: zeros in the saved tensors, `end` in the tokens; and their steps
+        const int nz = T - ran;
+        for (int rl = 0; rl < RW; ++rl) {
+            const int row = myrow0 + rl;
+            if (row >= a.B) continue;
+            const size_t o = (size_t)row * T + ran;
+            const f32x4 z4 = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int i = tid; i < nz * (H / 4); i += 512) {
+                *reinterpret_cast<f32x4*>(a.hs + o * H + 4 * (size_t)i) = z4;
+                *reinterpret_cast<f32x4*>(a.cs + o * H + 4 * (size_t)i) = z4;
+                *reinterpret_cast<f32x4*>(a.ctx + o * H + 4 * (size_t)i) = z4;
+            }
+            for (int i = tid; i < nz * (G4 / 4); i += 512) *reinterpret_cast<f32x4*>(a.act + o * G4 + 4 * (size_t)i) = z4;
+            for (int i = tid; i < nz * S; i += 512) a.probs[o * S + i] = 0.f;
+            for (int i = tid; i < nz; i += 512) a.tokens[o + i] = stop.end;
+            if (tid == 0) {
+                const int st = stepl[RW * part + rl];
+                stop.steps_out[row] = st != 0 ? st : T;
+            }
         }
     }
     cl.finish();
@@ -548,6 +614,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     pnmn::cluster_coords<MEMBERS>(tile, part);
     if (tile >= a.tiles) return;
     attn_lstm_fwd_multi_body<OVERLAP, false, false, false, true>(a, tile, part, pnmn::SamplingFilter{1.f, 0, 1.f}, nullptr, ord);
+}
+
+// A free-running pass whose tiles stop at their last row's `end` (STOP): a kernel of its own, so that the others keep their code.
+template <bool OVERLAP>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void attn_lstm_fwd_multi_stop_kernel(const MFwdArgs a,
+                                                                                                                 const StopArgs stop) {
+    int tile, part;
+    pnmn::cluster_coords<MEMBERS>(tile, part);
+    if (tile >= a.tiles) return;
+    attn_lstm_fwd_multi_body<OVERLAP, true, false, false, false, true>(a, tile, part, pnmn::SamplingFilter{1.f, 0, 1.f}, nullptr,
+                                                                       OrdArgs{nullptr, nullptr, 0}, stop);
 }
 
 // TWO independent decoder passes in one launch (the reconstructor's teacher-forced decode and the generator's
@@ -1034,9 +1111,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 // ---- the compiled kernels: every __global__ instantiation of this file, named once -----------------------------------
 // A launch finds its kernel by key.  Forward: passes side by side (1 or 2), OVERLAP, the kernel's M of either pass (0 teacher
 // forced, 1 free running, 2 sampling under a filter; m1 = 0 for a lone pass), under the automaton, rows grouped by length.
-// Backward: the passes (1 to 3) and the order.  `optin` is the row's own: the kernel's LDS opt-in per device (lds_optin.h).
+// Backward: the passes (1 to 3) and the order.  `stop`: a lone free-running pass whose tiles stop (last, so that the rows above
+// read as they did).  `optin` is the row's own: the kernel's LDS opt-in per device (lds_optin.h).
 struct VariantKey {
-    int backward, passes, overlap, m0, m1, constrained, ordered;
+    int backward, passes, overlap, m0, m1, constrained, ordered, stop;
 };
 struct Variant {
     VariantKey key;
@@ -1092,6 +1170,9 @@ Variant VARIANTS[] = {
     // rows grouped by length: a lone teacher-forced pass
     {{0, 1, 1, 0, 0, 0, 1}, kernel_of(attn_lstm_fwd_multi_ordered_kernel<true>)},
     {{0, 1, 0, 0, 0, 0, 1}, kernel_of(attn_lstm_fwd_multi_ordered_kernel<false>)},
+    // tiles that stop at their last row's end: a lone free-running pass (bwd n ov m0 m1 con ord stop)
+    {{0, 1, 1, 1, 0, 0, 0, 1}, kernel_of(attn_lstm_fwd_multi_stop_kernel<true>)},
+    {{0, 1, 0, 1, 0, 0, 0, 1}, kernel_of(attn_lstm_fwd_multi_stop_kernel<false>)},
     // backward
     {{1, 1, 0, 0, 0, 0, 0}, kernel_of(attn_lstm_bwd_multi_kernel)},
     {{1, 1, 0, 0, 0, 0, 1}, kernel_of(attn_lstm_bwd_multi_ordered_kernel)},
@@ -1224,7 +1305,7 @@ int find_variant(const VariantKey& key, const Variant*& out) {
     for (Variant& v : VARIANTS) {
         const VariantKey& k = v.key;
         if (k.backward == key.backward && k.passes == key.passes && k.overlap == key.overlap && k.m0 == key.m0 && k.m1 == key.m1 &&
-            k.constrained == key.constrained && k.ordered == key.ordered) {
+            k.constrained == key.constrained && k.ordered == key.ordered && k.stop == key.stop) {
             out = &v;
             return pnmn::opt_in_lds(v.kernel, LDS_LIMIT, v.optin);
         }
@@ -1234,7 +1315,7 @@ int find_variant(const VariantKey& key, const Variant*& out) {
 
 // One launch of a row's kernel over `tiles` tiles.  `args`: the kernel's arguments in the order every signature follows -- the
 // pass records; with more than one pass tiles0 (and tiles01); a filter per pass (the filtered and the constrained kernels); the
-// automaton (constrained); OrdArgs (ordered) -- each null where the kernel takes none.
+// automaton (constrained); OrdArgs (ordered); StopArgs (stop) -- each null where the kernel takes none.
 int launch(const Variant& v, int tiles, size_t lds, hipStream_t st, std::initializer_list<const void*> args) {
     void* argv[8];
     int n = 0;
@@ -1263,15 +1344,18 @@ int for_row_ranges(int rows, int chunk, void* workspace, hipStream_t st, Issue i
 // the filter is not the identity.  `au`: the checked automaton of a constrained call, or null.  It applies to every
 // free-running job, and a launch with such a job takes the constrained kernels.  Those pairs exist for M0 <= M1, so the passes
 // go out in that order (a pass's result does not depend on where its tiles sit in the grid).  `order` / `tile_steps`: see
-// any_order; the caller has checked the lists, and that a job with an order is teacher forced.
+// any_order; the caller has checked the lists, and that a job with an order is teacher forced.  `steps_out`: as `order`, one
+// entry per job; a job with one is free running without a filter or an automaton (checked by the caller), goes out alone as a
+// job with an order does, and takes the kernels that stop (`end`: their end token).  A range from row r0 takes steps_out + r0.
 // The LDS of a launch is the passes' own for the longest source plus what its family puts behind it -- the automaton's tables, or
 // the tile's row indices -- and OVERLAP is picked with that counted: S <= 59, under the automaton S <= 58.
 int launch_fwd(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, int n, int hidden, void* workspace, hipStream_t st,
-               const pnmn::TokenAutomaton* au, const int32_t* const* order, const int32_t* const* tile_steps) {
-    if (n > 1 && (!jobs_fit(j, n) || any_order(order, n))) {
-        const int rc = launch_fwd(j, f, n - 1, hidden, workspace, st, au, order, tile_steps);
+               const pnmn::TokenAutomaton* au, const int32_t* const* order, const int32_t* const* tile_steps,
+               int32_t* const* steps_out = nullptr, int end = 0) {
+    if (n > 1 && (!jobs_fit(j, n) || any_order(order, n) || any_order(steps_out, n))) {
+        const int rc = launch_fwd(j, f, n - 1, hidden, workspace, st, au, order, tile_steps, steps_out, end);
         return rc != 0 ? rc : launch_fwd(j + n - 1, f ? f + n - 1 : nullptr, 1, hidden, workspace, st, au, from(order, n - 1),
-                                         from(tile_steps, n - 1));
+                                         from(tile_steps, n - 1), steps_out ? steps_out + n - 1 : nullptr, end);
     }
     if (j[0].B <= 0 || j[0].T <= 0) return 0;  // (a lone pass only: passes side by side have rows and steps, see jobs_fit)
     int smax, chunk, rows[MAX_JOBS], tile0[MAX_JOBS + 1];
@@ -1283,10 +1367,11 @@ int launch_fwd(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, int
         if (m[i] == 2) ff[i] = pnmn::SamplingFilter{f[i].temperature, f[i].top_k, f[i].top_p};
     }
     const bool ordered = any_order(order, 1);  // (n == 1 then)
+    const bool stop = any_order(steps_out, 1);  // (n == 1, m[0] == 1 and no automaton then)
     const bool constrained = au && (m[0] != 0 || m[1] != 0);
     const bool filters = constrained || m[0] == 2 || m[1] == 2;  // (does the kernel take them?)
     const int lo = n > 1 && constrained && m[0] > m[1] ? 1 : 0, hi = 1 - lo;  // the order the passes go out in
-    const size_t extras = constrained ? pnmn::AUTOMATON_LDS_BYTES : ordered ? ORDER_LDS : 0;
+    const size_t extras = constrained ? pnmn::AUTOMATON_LDS_BYTES : ordered || stop ? ORDER_LDS : 0;  // (S <= 59 still: 192 bytes are left there)
     const size_t base = FWD_FIXED_LDS + sizeof(float) * RW * smax * H + extras;
     // A teacher-forced launch of a call with an automaton stages no tables, but takes OVERLAP where the call's constrained
     // launches do: the two compilations of the body differ in the last bits, and a pass must compute the same bits alone
@@ -1295,7 +1380,7 @@ int launch_fwd(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, int
     const bool overlap = base + as_pair + FWD_OVERLAP_LDS <= LDS_LIMIT;
     const size_t lds = base + (overlap ? FWD_OVERLAP_LDS : 0);
     const Variant* v = nullptr;
-    if (const int e = find_variant({0, n, overlap, m[lo], n > 1 ? m[hi] : 0, constrained, ordered}, v)) return e;
+    if (const int e = find_variant({0, n, overlap, m[lo], n > 1 ? m[hi] : 0, constrained, ordered, stop}, v)) return e;
     const void* const f0 = filters ? &ff[lo] : nullptr;
     if (n > 1) {
         int* sync = nullptr;
@@ -1309,7 +1394,8 @@ int launch_fwd(const pnmn_decoder_fwd_job* j, const pnmn_sampling_filter* f, int
         // (an ordered range is addressed from the pass's base pointers: ordered_range)
         const MFwdArgs a = kernel_args(j[0], ordered ? 0 : (size_t)r0, part, sync, 0);
         const OrdArgs ord = ordered ? ordered_range((size_t)r0, rows[0], order[0], tile_steps[0]) : OrdArgs{};
-        return launch(*v, padded_tiles(part), lds, st, {&a, f0, constrained ? au : nullptr, ordered ? &ord : nullptr});
+        const StopArgs sa = stop ? StopArgs{steps_out[0] + r0, end} : StopArgs{};
+        return launch(*v, padded_tiles(part), lds, st, {&a, f0, constrained ? au : nullptr, ordered ? &ord : nullptr, stop ? &sa : nullptr});
     });
 }
 
@@ -1325,7 +1411,7 @@ int launch_bwd(const pnmn_decoder_bwd_job* j, int n, int hidden, void* workspace
     const bool ordered = any_order(order, 1);  // (n == 1 then)
     const size_t lds = BWD_FIXED_LDS + sizeof(float) * RW * smax * H + (ordered ? ORDER_LDS : 0);
     const Variant* v = nullptr;
-    if (const int e = find_variant({1, n, 0, 0, 0, 0, ordered}, v)) return e;
+    if (const int e = find_variant({1, n, 0, 0, 0, 0, ordered, 0}, v)) return e;
     float* x1 = reinterpret_cast<float*>(static_cast<char*>(workspace) + pnmn::CLUSTER_SYNC_BYTES);
     float* x2 = x1 + (size_t)exchange_tiles(rows, n, chunk) * 2 * MEMBERS * 2 * ROWS * H;
     if (n > 1) {
@@ -1363,19 +1449,27 @@ static bool orders_valid(const int32_t* const* order, const int32_t* const* tile
     return true;
 }
 
-int pnmn_attn_lstm_fwd_group_ordered(const pnmn_decoder_fwd_job* jobs, const pnmn_sampling_filter* filters, int end_index,
-                                     const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left, int n_states,
-                                     int n_classes, int n, int hidden, const int32_t* const* order,
-                                     const int32_t* const* tile_steps, void* workspace, void* stream) {
+int pnmn_attn_lstm_fwd_group_stop(const pnmn_decoder_fwd_job* jobs, const pnmn_sampling_filter* filters, int end_index,
+                                  const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left, int n_states,
+                                  int n_classes, int n, int hidden, const int32_t* const* order, const int32_t* const* tile_steps,
+                                  int32_t* const* steps_out, void* workspace, void* stream) {
     if (!jobs || !workspace || n < 1 || n > 2) return PNMN_EINVAL;
     for (int i = 0; filters && i < n; ++i)
         if (!pnmn::filter_valid(filters + i)) return PNMN_EINVAL;
+    // a job with steps_out: free running, its end token inside the vocabulary, no filter of its own and no automaton
+    for (int i = 0; steps_out && i < n; ++i) {
+        if (!steps_out[i]) continue;
+        if (jobs[i].sample == 0 || end_index < 0 || end_index >= jobs[i].V) return PNMN_EINVAL;
+        if (token_class || next_state || min_left) return PNMN_EINVAL;
+        if (filters && jobs[i].sample == 1 && !pnmn::filter_is_identity(filters[i])) return PNMN_EINVAL;
+    }
     {
         const int S[2] = {jobs[0].S, n > 1 ? jobs[1].S : 0}, sample[2] = {jobs[0].sample, n > 1 ? jobs[1].sample : 0};
         if (!orders_valid(order, tile_steps, n, hidden, S, sample)) return PNMN_EINVAL;
     }
     if (!token_class && !next_state && !min_left)
-        return launch_fwd(jobs, filters, n, hidden, workspace, static_cast<hipStream_t>(stream), nullptr, order, tile_steps);
+        return launch_fwd(jobs, filters, n, hidden, workspace, static_cast<hipStream_t>(stream), nullptr, order, tile_steps,
+                          steps_out, end_index);
     int V = 0, T = INT_MAX;  // of the free-running jobs: one automaton, one vocabulary; the fewest steps
     for (int i = 0; i < n; ++i) {
         if (jobs[i].sample == 0) continue;
@@ -1386,6 +1480,14 @@ int pnmn_attn_lstm_fwd_group_ordered(const pnmn_decoder_fwd_job* jobs, const pnm
     pnmn::TokenAutomaton au;
     if (const int e = pnmn::fill_automaton(au, token_class, next_state, min_left, n_states, n_classes, V, T, end_index)) return e;
     return launch_fwd(jobs, filters, n, hidden, workspace, static_cast<hipStream_t>(stream), &au, order, tile_steps);
+}
+
+int pnmn_attn_lstm_fwd_group_ordered(const pnmn_decoder_fwd_job* jobs, const pnmn_sampling_filter* filters, int end_index,
+                                     const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left, int n_states,
+                                     int n_classes, int n, int hidden, const int32_t* const* order,
+                                     const int32_t* const* tile_steps, void* workspace, void* stream) {
+    return pnmn_attn_lstm_fwd_group_stop(jobs, filters, end_index, token_class, next_state, min_left, n_states, n_classes, n, hidden,
+                                         order, tile_steps, nullptr, workspace, stream);
 }
 
 int pnmn_attn_lstm_fwd_group(const pnmn_decoder_fwd_job* jobs, const pnmn_sampling_filter* filters, int end_index,

@@ -112,47 +112,75 @@ __global__ __launch_bounds__(256) void mask_last_fwd_kernel(const float* __restr
 // steps[b] = clamp(last[b] + 1, 1, T);  order = the rows sorted by steps, longest first, equal lengths in row order;
 // tile_steps[i] = steps of order[16 i], the longest row of the i-th 16-row tile of that order.  What the recurrent
 // layer kernels group their row tiles by (pnmn_lstm_seq_fwd_ordered), so that a tile stops at its rows' length.
-// A counting sort in ONE wave: the histogram's integer adds commute, and the placement walks the rows 64 at a time
-// in row order -- a row's slot is its bucket's next free one plus the rows of the same length on lower lanes, and
-// the last lane of a length moves the bucket on -- so the result does not depend on any timing.
-constexpr int LO_MAX_T = 4096;  // buckets (LDS words)
-__global__ __launch_bounds__(64) void length_order_kernel(const int32_t* __restrict__ last, int B, int T,
-                                                          int32_t* __restrict__ order, int32_t* __restrict__ tile_steps) {
-    extern __shared__ int first[];  // [T + 1]: rows of `s` steps, then the first free slot of their bucket
-    const int lane = threadIdx.x;
-    for (int s = lane; s <= T; s += 64) first[s] = 0;
+// A counting sort in ONE workgroup of up to 16 waves.  Wave w owns the rows [w C, (w + 1) C) -- C a multiple of 64 -- and a
+// histogram of its own: the integer adds commute.  One scan then gives every (length, wave) its first slot, lengths
+// descending and, within a length, waves ascending; and every wave places its own rows 64 at a time in row order -- a row's
+// slot is its (length, wave) bucket's next free one plus the rows of the same length on lower lanes, and the last lane of a
+// length moves the bucket on.  Equal lengths so stay in row order, no wave touches another's buckets, and the result does not
+// depend on any timing.  `bias`: 1 when the input is a row's last step, 0 when it is its step count.
+constexpr int LO_MAX_T = 4096;      // buckets
+constexpr int LO_MAX_WAVES = 16;
+constexpr int LO_LDS_WORDS = 16000;  // (waves + 1) x (T + 1) words must fit: 16 waves up to T = 940, 2 at T = 4096
+__global__ __launch_bounds__(64 * LO_MAX_WAVES) void length_order_kernel(const int32_t* __restrict__ last, int bias, int B, int T,
+                                                                        int32_t* __restrict__ order,
+                                                                        int32_t* __restrict__ tile_steps) {
+    extern __shared__ int lo_lds[];
+    int* first = lo_lds;            // [T + 1]: rows of `s` steps, then the first slot of their bucket
+    int* hist = lo_lds + (T + 1);   // [waves][T + 1]: wave w's rows of `s` steps, then the next free slot of (s, w) within the bucket
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, waves = blockDim.x >> 6;
+    const int C = 64 * ((B + 64 * waves - 1) / (64 * waves));  // rows of a wave
+    const int lo = min(wave * C, B), hi = min(lo + C, B);
+    auto steps_of = [&](const int b) { return min(max(last[b] + bias, 1), T); };
+    for (int i = tid; i < (waves + 1) * (T + 1); i += blockDim.x) lo_lds[i] = 0;
     __syncthreads();
-    for (int b = lane; b < B; b += 64) atomicAdd(&first[min(max(last[b] + 1, 1), T)], 1);
+    int* mine = hist + wave * (T + 1);
+    for (int b = lo + lane; b < hi; b += 64) atomicAdd(&mine[steps_of(b)], 1);
     __syncthreads();
-    int carry = 0;  // exclusive prefix sums from the longest bucket down, 64 buckets a round
-    for (int top = T; top >= 1; top -= 64) {
-        const int s = top - lane;
-        const int n = s >= 1 ? first[s] : 0;
-        int incl = n;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int v = __shfl_up(incl, o);
-            if (lane >= o) incl += v;
+    for (int s = 1 + tid; s <= T; s += blockDim.x) {  // within a length: the waves' counts -> their offsets; the length's total
+        int run = 0;
+        for (int w = 0; w < waves; ++w) {
+            const int n = hist[w * (T + 1) + s];
+            hist[w * (T + 1) + s] = run;
+            run += n;
         }
-        if (s >= 1) first[s] = carry + incl - n;
-        carry += __shfl(incl, 63);
+        first[s] = run;
     }
     __syncthreads();
-    for (int b0 = 0; b0 < B; b0 += 64) {
-        const int b = b0 + lane;
-        const int s = b < B ? min(max(last[b] + 1, 1), T) : 0;  // 0: no row on this lane
-        int before = 0, after = 0;
-        for (int j = 0; j < 64; ++j) {
-            const int sj = __shfl(s, j);
-            before += (sj == s && j < lane);
-            after += (sj == s && j > lane);
+    if (wave == 0) {
+        int carry = 0;  // exclusive prefix sums from the longest bucket down, 64 buckets a round
+        for (int top = T; top >= 1; top -= 64) {
+            const int s = top - lane;
+            const int n = s >= 1 ? first[s] : 0;
+            int incl = n;
+#pragma unroll
+            for (int o = 1; o < 64; o <<= 1) {
+                const int v = __shfl_up(incl, o);
+                if (lane >= o) incl += v;
+            }
+            if (s >= 1) first[s] = carry + incl - n;
+            carry += __shfl(incl, 63);
         }
-        const int pos = s ? first[s] + before : 0;
+    }
+    __syncthreads();
+    for (int b0 = 0; b0 < C; b0 += 64) {  // (the same trips in every wave: the barriers below are the workgroup's)
+        const int b = lo + b0 + lane;
+        const int s = b < hi ? steps_of(b) : 0;  // 0: no row on this lane
+        // the lanes that hold my length: one ballot per distinct length of the wave's 64 rows
+        unsigned long long same = 0;
+        bool pending = s != 0;
+        for (unsigned long long left = __ballot(pending); left != 0; left = __ballot(pending)) {
+            const int sv = __shfl(s, __ffsll(left) - 1);
+            const unsigned long long m = __ballot(s == sv);
+            if (s == sv) same = m, pending = false;
+        }
+        const int before = __popcll(same & ((1ull << lane) - 1ull));
+        const bool is_last = (same >> lane) == 1ull;
+        const int pos = s ? first[s] + mine[s] + before : 0;
         __syncthreads();  // every lane has read its bucket's slot before any bucket moves on
         if (s) {
             order[pos] = b;
             if ((pos & 15) == 0) tile_steps[pos >> 4] = s;
-            if (after == 0) first[s] = pos + 1;
+            if (is_last) mine[s] += before + 1;
         }
         __syncthreads();
     }
@@ -525,13 +553,26 @@ extern "C" int pnmn_token_prep(const int64_t* tokens, int64_t token_row_stride, 
     return (int)hipGetLastError();
 }
 
-extern "C" int pnmn_length_order(const int32_t* last, int B, int T, int32_t* order, int32_t* tile_steps, void* stream) {
+static int length_order(const int32_t* in, int bias, int B, int T, int32_t* order, int32_t* tile_steps, void* stream) {
     if (B <= 0) return 0;
-    if (!last || !order || !tile_steps || T <= 0) return PNMN_EINVAL;
+    if (!in || !order || !tile_steps || T <= 0) return PNMN_EINVAL;
     if (T > LO_MAX_T) return PNMN_ESHAPE;
-    hipLaunchKernelGGL(length_order_kernel, dim3(1), dim3(64), (size_t)(T + 1) * sizeof(int), static_cast<hipStream_t>(stream),
-                       last, B, T, order, tile_steps);
+    // as many waves as the rows can use and the histograms leave room for
+    int waves = LO_LDS_WORDS / (T + 1) - 1;
+    waves = waves > LO_MAX_WAVES ? LO_MAX_WAVES : waves;
+    waves = waves > (B + 63) / 64 ? (B + 63) / 64 : waves;
+    waves = waves < 1 ? 1 : waves;
+    hipLaunchKernelGGL(length_order_kernel, dim3(1), dim3(64 * waves), (size_t)(waves + 1) * (T + 1) * sizeof(int),
+                       static_cast<hipStream_t>(stream), in, bias, B, T, order, tile_steps);
     return (int)hipGetLastError();
+}
+
+extern "C" int pnmn_length_order(const int32_t* last, int B, int T, int32_t* order, int32_t* tile_steps, void* stream) {
+    return length_order(last, 1, B, T, order, tile_steps, stream);
+}
+
+extern "C" int pnmn_length_order_steps(const int32_t* steps_in, int B, int T, int32_t* order, int32_t* tile_steps, void* stream) {
+    return length_order(steps_in, 0, B, T, order, tile_steps, stream);
 }
 
 extern "C" int pnmn_decoder_last(const int64_t* mask_tokens, int64_t mask_stride, int pad, int rows, int T, int32_t* last,

@@ -59,10 +59,17 @@ LENGTH_ORDER_ABOVE_ROWS = 256
 VALID_PAIRS_ABOVE_ROWS = LENGTH_ORDER_ABOVE_ROWS
 #: teacher-forced decoder passes above LENGTH_ORDER_ABOVE_ROWS rows run with their rows grouped by length, one order per pass for
 #: forward and backward (pnmn_decoder_last, pnmn_length_order, pnmn_attn_lstm_*_group_ordered): a row tile stops at its longest
-#: row's last weighted step.  The sampling pass never is (its lengths are known only as it runs); below the threshold the plan
-#: is call for call what it was.  PNMN_DECODER_LENGTH_ORDER (read when a plan is built): "0" keeps the unordered calls, "1"
-#: selects the ordered ones; unset, this default.
+#: row's last weighted step.  The sampling pass's forward never is (its lengths are known only as it runs: see
+#: SAMPLED_PASS_STOP_ENV); below the threshold the plan is call for call what it was.  PNMN_DECODER_LENGTH_ORDER (read when a
+#: plan is built): "0" keeps the unordered calls, "1" selects the ordered ones; unset, this default.
 DECODER_LENGTH_ORDER_DEFAULT = "1"
+#: the sampling pass above LENGTH_ORDER_ABOVE_ROWS rows: its forward tiles stop once all their rows have emitted @end@
+#: (pnmn_attn_lstm_fwd_group_stop, which also counts every row's steps), and its backward runs with the rows grouped by those
+#: steps (pnmn_length_order_steps, pnmn_attn_lstm_bwd_group_ordered); the forward itself stays in batch order.  Who builds the
+#: plan asks for it (``Seq2SeqPlan(..., sampled_stop=True)``: the trainers do); a plan built without the argument, a pass at or
+#: below the threshold, and PNMN_SAMPLED_PASS_STOP=0 keep the calls as they were, call for call.  PNMN_SAMPLED_PASS_STOP (read
+#: when a plan is built) overrides the argument either way: "0" off, anything else on.
+SAMPLED_PASS_STOP_ENV = "PNMN_SAMPLED_PASS_STOP"
 #: the per-model decoder buffers, [flat sequence rows of all the model's passes][width]
 DECODER_BUFFERS = (("hs", 256), ("cs", 256), ("cx", 256), ("act", 1024), ("dhs", 256), ("dg", 1024), ("dctx", 256))
 
@@ -219,9 +226,9 @@ class _EncoderPass(NamedTuple):
 
 class Seq2SeqPlan:
     """See the module docstring.  ``n`` unsupervised (sampled) rows, ``m`` supervised rows, both > 0; ``tq`` / ``tp``: the
-    widths of the batch's question / program matrices."""
+    widths of the batch's question / program matrices.  ``sampled_stop``: see SAMPLED_PASS_STOP_ENV."""
 
-    def __init__(self, pg, qr, prior, dev: torch.device, n: int, m: int, tq: int, tp: int):
+    def __init__(self, pg, qr, prior, dev: torch.device, n: int, m: int, tq: int, tp: int, sampled_stop: bool = False):
         if not (_supported(pg) and _supported(qr)) or n <= 0 or m <= 0:
             raise PlanUnsupported("model shapes")
         pl = prior._encoder._module
@@ -244,6 +251,7 @@ class Seq2SeqPlan:
         self._valid_lists: List = []  # segments of the (row, step) lists the weight gradients sum over (``_valid_list``)
         self.valid_pairs = os.environ.get("PNMN_GEMM_VALID_PAIRS", "1") != "0"
         self.decoder_order = os.environ.get("PNMN_DECODER_LENGTH_ORDER", DECODER_LENGTH_ORDER_DEFAULT) != "0"
+        self.sampled_stop = os.environ[SAMPLED_PASS_STOP_ENV] != "0" if SAMPLED_PASS_STOP_ENV in os.environ else bool(sampled_stop)
         self.anchor = torch.zeros((), device=dev, requires_grad=True)
         self.fwd_pg_enc, self.fwd_pg, self.fwd_pg_finish, self.fwd_qr, self.fwd_prior = (_Calls() for _ in range(5))
         self.bwd_a, self.bwd_b = _Calls(), _Calls()  # the decoders' backward / the encoders' and every parameter gradient
@@ -612,9 +620,23 @@ class Seq2SeqPlan:
             self._decoder_fwd_job(j, dec, p)
         ws = self.bytes_buf(ws_name, _hip.decoder_workspace_bytes(rows, False))
         ordered = self._order_lists(dec.passes)
-        calls.add("pnmn_attn_lstm_fwd_group_ordered" if ordered else "pnmn_attn_lstm_fwd_group", jobs.ctypes.data,
-                  None, 0, None, None, None, 0, 0,  # (no filters, no automaton)
-                  len(jobs), 256, *ordered, ws.data_ptr(), self.stream)
+        stopping = [p for p in dec.passes if self.sampled_stop and p.trimmed is not None and p.rows > LENGTH_ORDER_ABOVE_ROWS]
+        if not stopping:
+            calls.add("pnmn_attn_lstm_fwd_group_ordered" if ordered else "pnmn_attn_lstm_fwd_group", jobs.ctypes.data,
+                      None, 0, None, None, None, 0, 0,  # (no filters, no automaton)
+                      len(jobs), 256, *ordered, ws.data_ptr(), self.stream)
+            return jobs
+        # a large sampling pass: its tiles stop at their rows' @end@ and count the rows' steps; its BACKWARD then runs with the
+        # rows grouped by those steps (the order is built behind the forward, which stays in batch order)
+        i32 = torch.int32
+        steps = {p.tag: self.buf(p.tag + ".steps", p.rows, dtype=i32) for p in stopping}
+        outs = np.array([steps[p.tag].data_ptr() if p.tag in steps else 0 for p in dec.passes], np.uint64)
+        self._keep_args.append(outs)
+        calls.add("pnmn_attn_lstm_fwd_group_stop", jobs.ctypes.data, None, model._end_index, None, None, None, 0, 0,
+                  len(jobs), 256, *(ordered or (None, None)), outs.ctypes.data, ws.data_ptr(), self.stream)
+        for p in stopping:
+            p.order, p.tile_steps = self.buf(p.tag + ".order", p.rows, dtype=i32), self.buf(p.tag + ".tile_steps", (p.rows + 15) // 16, dtype=i32)
+            calls.add("pnmn_length_order_steps", steps[p.tag].data_ptr(), p.rows, p.T, p.order.data_ptr(), p.tile_steps.data_ptr(), self.stream)
         return jobs
 
     def _decoder_losses(self, calls: _Calls, dec: _DecoderSet) -> None:

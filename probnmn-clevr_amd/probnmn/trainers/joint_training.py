@@ -123,7 +123,8 @@ class _TrainerBase(StepBase):
             plan = None
         if plan is None:
             try:
-                plan = Seq2SeqPlan(self.pg, self.qr, self.prior, dev, n, m, tq, tp)
+                # (sampled_stop: the sampling pass's tiles stop at their rows' @end@, above 256 rows; PNMN_SAMPLED_PASS_STOP=0 undoes it)
+                plan = Seq2SeqPlan(self.pg, self.qr, self.prior, dev, n, m, tq, tp, sampled_stop=True)
             except PlanUnsupported:
                 plan = False
             if len(plans) > 8:  # (a run with many batch shapes: keep the workspaces of the recent ones only)
