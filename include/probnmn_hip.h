@@ -348,6 +348,49 @@ int pnmn_answer_marginal(const float* logits /* [n_rows][num_answers] */, const 
                          int unknown_index, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Posterior over a question's program hypotheses (csrc/hypothesis_posterior.hip).  Not in the reference, which scores
+ * sampled programs with the prior and the reconstructor in training only (elbo.py:130-161) and answers from one sampled
+ * program (scripts/inference.py:76-91): the hypotheses of a question reranked by
+ *     score[r] = w_x log p(x | z_r) + w_z log p(z_r) + w_q log q(z_r | x)
+ * from the teacher-forced logits of the reconstructor (x) and of the prior (z) and the tokens they score.  Rows
+ * [group_start[g], group_start[g + 1]) are group g's, in that order, as for pnmn_answer_marginal.
+ * Per row, for a term k in {x, z} whose logits are given (row r's tokens are the T_k entries at k_tokens + r * k_token_stride):
+ *   lp_k[r] = sum over t with tok_k[r][t] != pad_k of (z_t[tok] - max_v z_t) - log sum_v exp(z_t[v] - max_v z_t),
+ *             z_t = k_logits[r][t][:]: every step rounded at its own size, summed over t in ascending order; 0 for a row
+ *             whose tokens are all padding; a true log-probability (a sum): with n scored tokens, -lp_k / n is
+ *             pnmn_seq_nll_fwd's loss for the same logits and tokens
+ *   a token that is neither pad_k nor in [0, V_k) is never used as an index: lp_k[r] = -inf
+ *   log_px[r] = lp_x[r], log_pz[r] = lp_z[r] (each written only when its logits are given; a term that neither is asked
+ *             for nor enters the score is not computed)
+ * A term ENTERS the score only when its input pointer (x_logits, z_logits, log_q) is not NULL and its coefficient is not
+ * exactly 0: a term that does not is left out entirely, no 0 * -inf is ever formed, and a NULL input gives the same bits as
+ * a zero coefficient.  Row r is USABLE when score[r] is finite.  Per group, over its usable rows:
+ *   support[g]       = their number
+ *   log_evidence[g]  = max + log sum exp(score - max), max being the largest usable score
+ *   log_posterior[r] = (score[r] - max) - log sum exp(score - max); -inf for a row that is not usable
+ *   best_row[g]      = the absolute index r of the first usable row with the largest score
+ *   support[g] == 0 (no rows, or none usable): log_evidence[g] = -inf, best_row[g] = -1, log_posterior = -inf over the rows
+ * Group bounds are clamped into [0, n_rows] with end >= start before use, so no group_start reads or writes outside the
+ * arrays; a row that no group covers is not written.  The scores of a group pass through its log_posterior slots, so groups
+ * that share a row (bounds that decrease) get unspecified values -- every other group keeps its own.  A group's outputs
+ * depend only on its own rows in their order: the same bits alone or inside a batch, and from run to run.  One launch, one
+ * 512-thread workgroup per group (its wavefronts take the rows in turn), no LDS, no atomics, no wait on another workgroup.
+ * n_groups == 0 returns 0 without a launch.  PNMN_EINVAL, with no launch and no HIP call: n_groups < 0 or n_rows < 0; a
+ * null group_start, log_posterior, log_evidence or best_row; logits without their tokens; x_logits, z_logits and log_q all
+ * null; T < 1 or V < 1 of a term whose logits are given; a coefficient that is not finite.  Vx or Vz > 1024 (of a term
+ * whose logits are given): PNMN_ESHAPE.
+ * ------------------------------------------------------------------------------------------- */
+int pnmn_hypothesis_posterior(const float* x_logits /* [n_rows][Tx][Vx], may be NULL */, const int64_t* x_tokens /* [n_rows] rows of Tx */,
+                              int64_t x_token_stride, const float* z_logits /* [n_rows][Tz][Vz], may be NULL */,
+                              const int64_t* z_tokens /* [n_rows] rows of Tz */, int64_t z_token_stride,
+                              const float* log_q /* [n_rows], may be NULL */, const int32_t* group_start /* DEVICE [n_groups + 1] */,
+                              float w_x, float w_z, float w_q, int pad_x, int pad_z, float* log_px /* [n_rows], may be NULL */,
+                              float* log_pz /* [n_rows], may be NULL */, float* log_posterior /* [n_rows] */,
+                              float* log_evidence /* [n_groups] */, int32_t* best_row /* [n_groups] */,
+                              int32_t* support /* [n_groups], may be NULL */, int n_groups, int n_rows, int Tx, int Vx, int Tz,
+                              int Vz, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Glue of the seq2seq passes (csrc/seqglue.hip): what the reference -- through AllenNLP 0.9.0 -- does with
  * chains of small tensor ops and per-row Python loops, one launch each.
  *

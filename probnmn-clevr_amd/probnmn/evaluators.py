@@ -12,7 +12,8 @@ Stand-alone layout only (when the models are grafted onto the reference's packag
     and lets the NMN answer without gold answers; with ``beam_size`` it beam-searches them instead (not in the
     reference) and can prefer the best-ranked hypothesis that is a valid program; with ``marginal`` / ``num_programs`` (not
     in the reference either) the answer is the MARGINAL over several programs, sum_z q(z | x) p(a | z, image), with its
-    probability and the hypotheses that voted;
+    probability and the hypotheses that voted; with ``rerank`` (not in the reference either) the hypotheses are weighted by
+    their posterior under the generative model, p(x | z) p(z), from the reconstructor and the prior (``hypothesis_posterior``);
   * ``explain`` (not in the reference either) adds to each answer where its program looked: the attention map of every
     step, and that map painted over the question's image (``attention_overlay``).
 Batches are dicts of DEVICE tensors with the reference's keys (a ``PrefetchingLoader`` yields them)."""
@@ -240,6 +241,135 @@ def _marginal_options(beam_size, marginal, num_programs, explain) -> bool:
     return bool(marginal) or num_programs is not None
 
 
+def _rerank_weights(weights):
+    """``(w_x, w_z, w_q)`` of ``hypothesis_posterior`` as three finite floats; ``ValueError`` otherwise."""
+    import math
+
+    try:
+        w = tuple(float(v) for v in weights)
+    except (TypeError, ValueError):
+        raise ValueError("weights must be three numbers (w_x, w_z, w_q), got %r" % (weights,))
+    if len(w) != 3 or not all(math.isfinite(v) for v in w):
+        raise ValueError("weights must be three finite numbers (w_x, w_z, w_q), got %r" % (weights,))
+    return w
+
+
+def _rerank_options(rerank, beam_size, num_programs, explain, question_reconstructor, program_prior, rerank_weights):
+    """The argument rules of ``rerank`` (``predict_answers`` states them), checked before any model is touched; the three
+    coefficients, or None when the hypotheses are not reranked."""
+    if not rerank:
+        return None
+    if beam_size is None and num_programs is None:
+        raise ValueError("rerank=True reranks several hypotheses per question: give a beam_size or num_programs")
+    if explain:
+        raise ValueError("explain=True explains the one program an answer came from; a reranked answer has several")
+    w = _rerank_weights(rerank_weights)
+    if question_reconstructor is None and w[0] != 0.0:
+        raise ValueError("rerank_weights[0] = %r weighs log p(x | z): give the question_reconstructor (or make it 0)" % (w[0],))
+    if program_prior is None and w[1] != 0.0:
+        raise ValueError("rerank_weights[1] = %r weighs log p(z): give the program_prior (or make it 0)" % (w[1],))
+    return w
+
+
+@torch.no_grad()
+def hypothesis_posterior(question_reconstructor, program_prior, questions: torch.Tensor, programs: torch.Tensor, question_rows,
+                         log_q=None, weights=(1.0, 1.0, 0.0), max_rows: int = 1024) -> Dict[str, torch.Tensor]:
+    """The posterior over each question's program hypotheses under the generative model (not in the reference, which
+    scores sampled programs with the three models in training only: modules/elbo.py):
+        log p(z_r | x) = w_x log p(x | z_r) + w_z log p(z_r) + w_q log q(z_r | x) - log of the sum over the question's rows
+    with ``weights`` = (w_x, w_z, w_q).  The default (1, 1, 0) is the exact posterior of p(x | z) p(z) restricted to the
+    candidate set; ``w_q`` mixes the generator's own weight back in.  Inference only, no gradient.
+
+    ``questions`` [G, Tq] on the device; ``programs`` [R, T] (host or device) with ``question_rows`` [R], non-decreasing, in
+    0 .. G - 1 -- the layout ``group_hypotheses`` returns; the programs as the decoders return them (trimmed behind their
+    @end@), fed as the ELBO passes feed sampled programs.  ``log_q`` [R] or None (then ``w_q`` must be 0).  Either model may
+    be None; its coefficient must then be 0 (``ValueError``), and its per-row output is NaN.  A term whose coefficient is 0
+    is left out of the score entirely.
+
+    Program row r is scored against ``questions[question_rows[r]]`` by ``QuestionReconstructor.teacher_forced_logits`` and
+    ``ProgramPrior.teacher_forced_logits`` in passes of at most ``max_rows`` rows -- scoring passes: no metric of either
+    model moves, no seed is drawn from the torch generator, and their ``train()`` / ``eval()`` state comes back as it was
+    -- then ONE ``pnmn_hypothesis_posterior`` launch (the rule: include/probnmn_hip.h).
+
+    Returns device tensors: ``"log_posterior"``, ``"log_reconstruction"`` (log p(x | z_r), a sum over the question's
+    tokens), ``"log_prior"`` (log p(z_r)) fp32 [R]; ``"log_evidence"`` fp32 [G] (log of the summed unnormalised scores; -inf
+    where no hypothesis has a finite score), ``"best_row"`` int32 [G] (the MAP hypothesis's row, first of equals; -1 there)
+    and ``"support"`` int32 [G] (hypotheses with a finite score)."""
+    w = _rerank_weights(weights)
+    if question_reconstructor is None and w[0] != 0.0:
+        raise ValueError("weights[0] = %r weighs log p(x | z): give the question_reconstructor (or make it 0)" % (w[0],))
+    if program_prior is None and w[1] != 0.0:
+        raise ValueError("weights[1] = %r weighs log p(z): give the program_prior (or make it 0)" % (w[1],))
+    if log_q is None and w[2] != 0.0:
+        raise ValueError("weights[2] = %r weighs log q(z | x): give log_q (or make it 0)" % (w[2],))
+    if question_reconstructor is None and program_prior is None and log_q is None:
+        raise ValueError("nothing to score the hypotheses with: no question_reconstructor, no program_prior and no log_q")
+    if max_rows < 1:
+        raise ValueError("max_rows must be at least 1, got %r" % (max_rows,))
+    dev = questions.device
+    if dev.type != "cuda":
+        raise _hip.HipLibraryError("hypothesis_posterior runs on the ROCm device the questions are on (got %s); there is no "
+                                   "CPU path" % dev)
+    G = int(questions.size(0))
+    qrows = np.ascontiguousarray(torch.as_tensor(question_rows).detach().cpu().numpy(), dtype=np.int64)
+    R = int(qrows.size)
+    if questions.dim() != 2 or programs.dim() != 2 or programs.size(0) != R or qrows.ndim != 1:
+        raise ValueError("questions [G, Tq], programs [R, T] and question_rows [R]; got %s, %s and %s"
+                         % (tuple(questions.shape), tuple(programs.shape), qrows.shape))
+    if R and (int(qrows.min()) < 0 or int(qrows.max()) >= G or bool((np.diff(qrows) < 0).any())):
+        raise ValueError("question_rows must be non-decreasing and in 0 .. %d" % (G - 1))
+    f = dict(dtype=torch.float32, device=dev)
+    out = {"log_posterior": torch.empty(R, **f), "log_reconstruction": torch.full((R,), float("nan"), **f),
+           "log_prior": torch.full((R,), float("nan"), **f), "log_evidence": torch.full((G,), -float("inf"), **f),
+           "best_row": torch.full((G,), -1, dtype=torch.int32, device=dev),
+           "support": torch.zeros(G, dtype=torch.int32, device=dev)}
+    if R == 0 or G == 0:  # (no row anywhere: what the kernel writes for a group without rows)
+        return out
+    q = None
+    if log_q is not None:
+        q = torch.as_tensor(log_q).detach().to(device=dev, dtype=torch.float32).contiguous()
+        if tuple(q.shape) != (R,):
+            raise ValueError("log_q [%d]; got %s" % (R, tuple(q.shape)))
+    programs = programs.detach().to(device=dev, dtype=torch.long)
+    rows_dev = _hip.to_device(qrows, dev).view(torch.long)
+    models = [m for m in (question_reconstructor, program_prior) if m is not None]
+    was_training = [m.training for m in models]
+    for m in models:
+        m.eval()
+    x = z = None  # (logits [R, T, V], tokens [R, T]) of each term, filled pass by pass
+    try:
+        for lo in range(0, R, max_rows):
+            hi = min(lo + max_rows, R)
+            if question_reconstructor is not None:
+                logits, tokens = question_reconstructor.teacher_forced_logits(programs[lo:hi],
+                                                                              questions.index_select(0, rows_dev[lo:hi]))
+                if x is None:
+                    x = (torch.empty((R,) + tuple(logits.shape[1:]), **f), torch.empty(R, tokens.size(1), dtype=torch.long, device=dev))
+                x[0][lo:hi], x[1][lo:hi] = logits, tokens
+            if program_prior is not None:
+                logits, tokens = program_prior.teacher_forced_logits(programs[lo:hi])
+                if z is None:
+                    z = (torch.empty((R,) + tuple(logits.shape[1:]), **f), torch.empty(R, tokens.size(1), dtype=torch.long, device=dev))
+                z[0][lo:hi], z[1][lo:hi] = logits, tokens
+    finally:
+        for m, training in zip(models, was_training):
+            m.train(training)
+    group_start = _hip.small_to_device(np.searchsorted(qrows, np.arange(G + 1)).tolist(), torch.int32, dev)
+
+    def term(t, model):
+        if t is None:
+            return (0, 0, 0), (0, 0, 0)
+        return (t[0].data_ptr(), t[1].data_ptr(), t[1].stride(0)), (t[0].size(1), t[0].size(2), model._pad_index)
+
+    (x_args, (Tx, Vx, pad_x)), (z_args, (Tz, Vz, pad_z)) = term(x, question_reconstructor), term(z, program_prior)
+    _hip.check(_hip.lib().pnmn_hypothesis_posterior(
+        *x_args, *z_args, 0 if q is None else q.data_ptr(), group_start.data_ptr(), w[0], w[1], w[2], pad_x, pad_z,
+        out["log_reconstruction"].data_ptr() if x is not None else 0, out["log_prior"].data_ptr() if z is not None else 0,
+        out["log_posterior"].data_ptr(), out["log_evidence"].data_ptr(), out["best_row"].data_ptr(), out["support"].data_ptr(),
+        G, R, Tx, Vx, Tz, Vz, _hip.stream_ptr(dev)), "hypothesis_posterior")
+    return out
+
+
 class _HostCopies:
     """Device tensors copied into page-locked buffers, two sets in turn (batch i + 1 is queued before batch i is read)."""
 
@@ -281,9 +411,13 @@ def _queue_hypotheses(program_generator, batch, iteration, copies, beam_size, nu
     return tokens, weights, copied
 
 
-def _finish_hypotheses(nmn, image, queued):
+def _finish_hypotheses(nmn, image, queued, rerank=None):
     """Second stage: wait for the copy, keep the valid hypotheses (merged), run the NMN over them and marginalise.
-    Returns (``marginal_answers``' dict as host numpy, programs [R, T], group_start [B + 1])."""
+    ``rerank`` = (question_reconstructor, program_prior, coefficients, questions [B, Tq]) or None: the hypotheses' weights
+    are their posterior under the generative model (``hypothesis_posterior``, the merged generator weight as its ``log_q``)
+    instead of the generator's own.  Returns (``marginal_answers``' dict as host numpy -- reranked: and
+    ``hypothesis_posterior``'s ``"log_reconstruction"``, ``"log_prior"`` and ``"best_row"`` --, programs [R, T], group_start
+    [B + 1])."""
     tokens, weights, copied = queued
     if copied is not None:
         copied.synchronize()
@@ -291,7 +425,15 @@ def _finish_hypotheses(nmn, image, queued):
     B, K, T = arr.shape
     valid = np.array([c.valid for c in nmn.engine.compiler.compile_batch(arr.reshape(B * K, T))], dtype=bool).reshape(B, K)
     programs, question_rows, log_weights, _ = group_hypotheses(arr, None if weights is None else weights.cpu().numpy(), valid)
+    scored = {}
+    if rerank is not None:
+        question_reconstructor, program_prior, coefficients, questions = rerank
+        posterior = hypothesis_posterior(question_reconstructor, program_prior, questions, torch.from_numpy(programs),
+                                         question_rows, log_q=log_weights, weights=coefficients)
+        log_weights = posterior["log_posterior"]
+        scored = {k: posterior[k] for k in ("log_reconstruction", "log_prior", "best_row")}
     out = nmn.marginal_answers(image, torch.from_numpy(programs), question_rows, log_weights)
+    out.update(scored)
     return ({k: v.cpu().numpy() for k, v in out.items()}, programs, np.searchsorted(question_rows, np.arange(B + 1)))
 
 
@@ -301,7 +443,8 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
                     constrained: bool = False, extractor=None, temperature: float = 1.0, top_k: int = 0,
                     top_p: float = 1.0, constrained_sampling: bool = False, explain: bool = False,
                     overlay_strength: int = 160, colormap: Optional[torch.Tensor] = None, marginal: bool = False,
-                    num_programs: Optional[int] = None) -> List[Dict[str, Any]]:
+                    num_programs: Optional[int] = None, rerank: bool = False, question_reconstructor=None, program_prior=None,
+                    rerank_weights=(1.0, 1.0, 0.0)) -> List[Dict[str, Any]]:
     """scripts/inference.py:76-91: sampled programs -> NMN -> answer strings, one record per question
     (``question_index`` from the batch when present, else a running index).
 
@@ -348,8 +491,22 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
     ``"answer_probability"`` (0.0 then), the ``"support"`` (how many distinct valid hypotheses voted) and the
     ``"hypotheses"``: ``{"program": token strings, "weight": its share, "answer": its own answer}`` each, in group order.
     ``marginal`` without ``beam_size``, ``num_programs`` with it, either with ``explain``, or a ``num_programs`` that is
-    not an int in range, are a ``ValueError``."""
-    marginalise = _marginal_options(beam_size, marginal, num_programs, explain)
+    not an int in range, are a ``ValueError``.
+
+    ``rerank`` (needs the hypotheses of ``beam_size`` or ``num_programs`` and implies the marginal answer): the generator only
+    PROPOSES the hypotheses; their weights are the posterior under the generative model, p(z | x) ~ p(x | z)^w_x p(z)^w_z
+    q(z | x)^w_q over the distinct valid hypotheses of a question, from ``question_reconstructor`` (p(x | z)), ``program_prior``
+    (p(z)) and ``rerank_weights`` = (w_x, w_z, w_q) (``hypothesis_posterior``; q is the merged weight of ``group_hypotheses``:
+    the beam score, or ``log count`` for samples).  The default (1, 1, 0) is the exact posterior restricted to the candidate
+    set; (0, 0, 1) gives the answers of ``rerank=False``.  A record's ``"weight"`` is then the posterior share, each
+    hypothesis also names its ``"log_reconstruction"`` (log p(x | z)) and ``"log_prior"`` (log p(z)) (None for a model that
+    was not given), and the record gains ``"map_program"`` and ``"map_answer"``: the hypothesis with the largest posterior
+    and its own answer (``[]`` and ``@@UNKNOWN@@`` when there is none).  The models are left as they were: no metric, no
+    seed, their ``train()`` / ``eval()`` state.  ``rerank`` without hypotheses, with ``explain``, with coefficients that are
+    not three finite numbers, or without a model whose coefficient is not 0, is a ``ValueError``, raised before any model
+    is touched."""
+    coefficients = _rerank_options(rerank, beam_size, num_programs, explain, question_reconstructor, program_prior, rerank_weights)
+    marginalise = _marginal_options(beam_size, marginal or (rerank and num_programs is None), num_programs, explain)
     if constrained and beam_size is None:
         raise ValueError("constrained=True constrains the beam search: give a beam_size")
     if constrained_sampling and beam_size is not None:
@@ -426,7 +583,8 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
 
         def finish_marginal(batch, queued):
             hypotheses, image = queued
-            out, programs, start = _finish_hypotheses(nmn, image, hypotheses)
+            reranked = None if coefficients is None else (question_reconstructor, program_prior, coefficients, batch["question"])
+            out, programs, start = _finish_hypotheses(nmn, image, hypotheses, reranked)
             B = len(start) - 1
             index = batch["question_index"].cpu().tolist() if "question_index" in batch else range(len(records), len(records) + B)
             for i, qi in enumerate(index):
@@ -437,6 +595,14 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
                     "hypotheses": [{"program": token_strings(programs[r]), "weight": float(out["hypothesis_weights"][r]),
                                     "answer": vocabulary.get_token_from_index(int(out["hypothesis_predictions"][r]), namespace="answers")}
                                    for r in range(start[i], start[i + 1])]})
+                if reranked is not None:
+                    for h, r in zip(records[-1]["hypotheses"], range(start[i], start[i + 1])):
+                        h["log_reconstruction"] = None if question_reconstructor is None else float(out["log_reconstruction"][r])
+                        h["log_prior"] = None if program_prior is None else float(out["log_prior"][r])
+                    best = int(out["best_row"][i])
+                    records[-1]["map_program"] = token_strings(programs[best]) if best >= 0 else []
+                    records[-1]["map_answer"] = vocabulary.get_token_from_index(
+                        int(out["hypothesis_predictions"][best]) if best >= 0 else nmn._unknown_answer, namespace="answers")
 
         def finish(batch, queued):
             if marginalise:
@@ -499,7 +665,8 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
 def evaluate_marginal_answer_accuracy(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary=None,
                                       beam_size: Optional[int] = None, num_programs: Optional[int] = None,
                                       constrained: bool = False, constrained_sampling: bool = False,
-                                      num_batches: Optional[int] = None) -> Dict[str, float]:
+                                      num_batches: Optional[int] = None, rerank: bool = False, question_reconstructor=None,
+                                      program_prior=None, rerank_weights=(1.0, 1.0, 0.0)) -> Dict[str, float]:
     """Answer accuracy of the MARGINAL answer over several programs per question -- the ``beam_size`` hypotheses of a beam
     search (``constrained``: under the validity rule), weighted by their probabilities, or ``num_programs`` sampled ones
     (``constrained_sampling``), uniformly weighted -- on batches with ``"answer"``; free-running decodes, unlike
@@ -507,9 +674,14 @@ def evaluate_marginal_answer_accuracy(program_generator, nmn, batches: Iterable[
     ``"single_answer_accuracy"`` (each question answered by its FIRST valid hypothesis alone -- the best beam, the first
     draw --, from the same pass), ``"average_support"`` (distinct valid hypotheses per question) and
     ``"average_rows_per_question"`` (NMN rows run per question).  ``vocabulary`` is not needed and only kept for symmetry
-    with ``predict_answers``; ``num_batches`` stops the loop as ``Evaluator.evaluate`` does."""
+    with ``predict_answers``; ``num_batches`` stops the loop as ``Evaluator.evaluate`` does.
+
+    ``rerank``, ``question_reconstructor``, ``program_prior``, ``rerank_weights``: as for ``predict_answers`` -- the hypotheses
+    are weighted by their posterior under the generative model -- and the result also holds ``"map_answer_accuracy"``: each
+    question answered by its MAP hypothesis alone."""
     if beam_size is None and num_programs is None:
         raise ValueError("give the hypotheses: beam_size (a beam search) or num_programs (samples)")
+    coefficients = _rerank_options(rerank, beam_size, num_programs, False, question_reconstructor, program_prior, rerank_weights)
     _marginal_options(beam_size, beam_size is not None, num_programs, False)
     if constrained and beam_size is None:
         raise ValueError("constrained=True constrains the beam search: give a beam_size")
@@ -523,10 +695,11 @@ def evaluate_marginal_answer_accuracy(program_generator, nmn, batches: Iterable[
         exclude = [getattr(program_generator, name) for name in ("_pad_index", "_unk_index", "_start_index", "_end_index")]
         constraint = nmn.engine.compiler.decoding_automaton(exclude=exclude)
     copies = _HostCopies()
-    totals = {"questions": 0, "correct": 0, "single": 0, "support": 0, "rows": 0}
+    totals = {"questions": 0, "correct": 0, "single": 0, "support": 0, "rows": 0, "map": 0}
 
     def finish(batch, queued):
-        out, programs, start = _finish_hypotheses(nmn, batch["image"], queued)
+        reranked = None if coefficients is None else (question_reconstructor, program_prior, coefficients, batch["question"])
+        out, programs, start = _finish_hypotheses(nmn, batch["image"], queued, reranked)
         answers = batch["answer"].cpu().numpy()
         has = start[1:] > start[:-1]
         single = np.full(answers.shape[0], nmn._unknown_answer, np.int64)
@@ -536,6 +709,11 @@ def evaluate_marginal_answer_accuracy(program_generator, nmn, batches: Iterable[
         totals["single"] += int((single == answers).sum())
         totals["support"] += int(out["support"].sum())
         totals["rows"] += int(programs.shape[0])
+        if reranked is not None:
+            best = out["best_row"]
+            by_map = np.full(answers.shape[0], nmn._unknown_answer, np.int64)
+            by_map[best >= 0] = out["hypothesis_predictions"][best[best >= 0]]
+            totals["map"] += int((by_map == answers).sum())
 
     try:
         pending = None
@@ -553,8 +731,11 @@ def evaluate_marginal_answer_accuracy(program_generator, nmn, batches: Iterable[
         program_generator.train(was_training[0])
         nmn.train(was_training[1])
     n = max(totals["questions"], 1)
-    return {"answer_accuracy": totals["correct"] / n, "single_answer_accuracy": totals["single"] / n,
-            "average_support": totals["support"] / n, "average_rows_per_question": totals["rows"] / n}
+    result = {"answer_accuracy": totals["correct"] / n, "single_answer_accuracy": totals["single"] / n,
+              "average_support": totals["support"] / n, "average_rows_per_question": totals["rows"] / n}
+    if coefficients is not None:
+        result["map_answer_accuracy"] = totals["map"] / n
+    return result
 
 
 @torch.no_grad()

@@ -151,6 +151,21 @@ class ProgramPrior(nn.Module):
         return {"predictions": predictions, "loss": loss}
 
     @torch.no_grad()
+    def teacher_forced_logits(self, program_tokens: torch.Tensor):
+        """The first half of ``forward``, for SCORING: (logits [R, T + 1, V], targets [R, T + 1]) -- step t's distribution over
+        the token that follows the first t ones and that token (the program's own, @end@ behind the last, padding after);
+        log p(z) is the sum over the non-padding targets of ``log_softmax(logits)[target]``.  No loss, no perplexity update,
+        no multinomial draw, no dropout whatever the mode and no seed drawn for it, no graph."""
+        if program_tokens.device.type != "cuda":
+            raise _hip.HipLibraryError("program prior input on %s: the HIP path needs a ROCm device" % program_tokens.device)
+        toks, fmask, _ = _TokenPrep.run(program_tokens, self._pad_index, self._start_index, self._end_index,
+                                        drop_first=False, want_mask=True)
+        encoded = self._encoder.forward_tokens(self._embedder.embedding, toks, fmask, derived=self._derived(),
+                                               row_offset=self.sample_row_offset, dropout=False)
+        logits = self._output_layer(self._projection_layer(encoded))
+        return logits[:, :-1], toks[:, 1:]
+
+    @torch.no_grad()
     def sample(self, num_samples: int = 1, max_sequence_length: int = 28, _forced=None, *, seed: Optional[int] = None,
                temperature: float = 1.0, top_k: int = 0, top_p: float = 1.0, constraint=None,
                greedy: bool = False) -> Dict[str, torch.Tensor]:

@@ -1511,9 +1511,10 @@ class Seq2SeqBase(nn.Module):
         predictions = self._trim_predictions(raw)
         return {"predictions": predictions, "loss": sequence_nll(logits_all, raw, predictions, self._pad_index, 1e-12)}, logits_all
 
-    def _decode_stepwise(self, enc, fmask, h, c, tgt, steps, greedy, seed):
+    def _decode_stepwise(self, enc, fmask, h, c, tgt, steps, greedy, seed, choose: bool = True):
         """Step-by-step decoding for shapes the persistent kernel is not built for (hidden != 256,
-        more than 64 source positions or 128 target tokens): a GEMM per step + the cell kernel."""
+        more than 64 source positions or 128 target tokens): a GEMM per step + the cell kernel.  ``choose=False`` (teacher
+        forcing only): no token is chosen from the distributions; the tokens and their log-probabilities come back None."""
         B = enc.size(0)
         pad, bos = self._pad_index, self._start_index
         last = fmask.new_full((B,), bos, dtype=torch.long)
@@ -1531,11 +1532,41 @@ class Seq2SeqBase(nn.Module):
             gates = torch.addmm(torch.addmm(bias, x, w_ih_t), h, w_hh_t)
             h, c = lstm_cell_pointwise(gates, c)
             logits = self._output_projection_layer(h)
+            step_logits.append(logits.unsqueeze(1))
+            if not choose:
+                continue
             last, _ = choose_tokens(logits, greedy, seed, self.sample_row_offset, t, pad, self._unk_index, bos)
             step_predictions.append(last.unsqueeze(1))
-            step_logits.append(logits.unsqueeze(1))
             step_logprobs.append(F.log_softmax(logits, dim=-1).gather(1, last.unsqueeze(1)))
+        if not choose:
+            return None, torch.cat(step_logits, 1), None
         return torch.cat(step_predictions, 1), torch.cat(step_logits, 1), torch.cat(step_logprobs, 1)
+
+    @torch.no_grad()
+    def teacher_forced_logits(self, source_tokens: torch.LongTensor, target_tokens: torch.LongTensor):
+        """The teacher-forced distributions of ``target_tokens`` given ``source_tokens``, for SCORING: (logits [R, T, V],
+        targets [R, T]), ``targets`` being the ``tgt[:, 1:]`` that ``decode`` scores them against (the targets after their
+        @start@, @end@ behind the last one, padding after) -- log p(target | source) is the sum over the non-padding targets
+        of ``log_softmax(logits)[target]``.
+
+        An inference pass that leaves the model as it was, unlike ``decode(state, targets)`` in ``eval()`` mode: no loss, no
+        predictions drawn from the distributions, no metric (perplexity, accuracy, BLEU) touched, no seed drawn from the
+        torch generator, no graph, the encoder without its dropout whatever the mode (``encode(dropout=False)``).  The
+        persistent decoder kernels of ``decode`` on their shapes; step by step (``_decode_stepwise``) on the others."""
+        state = self.encode(source_tokens, dropout=False)
+        tgt = _TokenPrep.run(target_tokens, self._pad_index, self._start_index, self._end_index, drop_first=False,
+                             want_mask=False)[0]
+        enc, h, fmask = state["enc"], state["h"], state["fmask"]
+        proj = self._output_projection_layer
+        if h.size(1) == 256 and enc.size(1) <= 64 and proj.weight.size(0) <= 128:
+            prep = self._fused_prep(state, tgt, False, 0, self._derived())
+            hs = _decoder_forward([_prep_tensors(prep)], [prep["meta"]]).outs[0]
+            logits = linear_rows(hs, proj.weight, proj.bias)
+        else:
+            _note_slow_path("decoder", "hidden size %d, %d source positions, %d target tokens (the persistent decoder kernel is "
+                            "built for 256 / <= 64 / <= 128)" % (h.size(1), enc.size(1), proj.weight.size(0)))
+            logits = self._decode_stepwise(enc, fmask, h, torch.zeros_like(h), tgt, tgt.size(1) - 1, True, 0, choose=False)[1]
+        return logits, tgt[:, 1:]
 
     def _trim_predictions(self, predictions: torch.LongTensor) -> torch.LongTensor:
         """Keep each row up to and including its first @end@; a row starting with @end@ becomes all
