@@ -799,6 +799,41 @@ int pnmn_attn_lstm_beam(const float* etable, const float* enc, const float* mask
                         const uint8_t* token_class /* HOST */, const uint8_t* next_state /* HOST */,
                         const uint8_t* min_left /* HOST */, int n_states, int n_classes, void* stream);
 
+/* Stochastic beam search (Kool, van Hoof and Welling, ICML 2019) on the same kernel (its second candidate stage): the `beam`
+ * hypotheses of a question are an exact sample WITHOUT replacement from the decoder's sequence distribution, in the order a
+ * sequential sample would draw them.  Every argument up to n_classes means what it means for pnmn_attn_lstm_beam; attention,
+ * gates, cell, logits, selection order, gather, early stop, back-track and the automaton rule are that call's.  Every slot
+ * carries phi (its log-probability, returned in `scores`) and G (its perturbed value).  Per question b:
+ *   phi[b][0] = G[b][0] = 0, phi[b][k>0] = G[b][k>0] = -inf, last[b][k] = start_index
+ *   each step t, hypothesis k that has not finished:
+ *     offered tokens    exactly those pnmn_attn_lstm_beam offers (never pad / unk / start; with tables, the automaton rule)
+ *     lse               log-sum-exp of the logits of the offered tokens whose logit is finite
+ *     phi(k,v)        = phi[b][k] + logit[k][v] - lse         (the softmax RESTRICTED to the offered tokens: the distribution
+ *                                                              the (constrained) sampling decode draws from)
+ *     u(k,v)          = (2 * (x0 >> 9) + 1) * 2^-24, x0 = word 0 of Philox4x32-10 with counter {row lo, row hi, t, 0x9E3779B9}
+ *                       and key {seed lo, seed hi} (the generator of pnmn_sample_tokens),
+ *                       row = ((question_offset + b) * 16 + k) * 128 + v: a draw depends on neither beam, V nor the batch
+ *     g(k,v)          = phi(k,v) - log(-log u(k,v));  Z = max of g(k,.) over the candidates with a finite phi
+ *     w               = G[b][k] - g(k,v) + log(1 - exp(g(k,v) - Z))
+ *     G~(k,v)         = G[b][k] - max(0, w) - log1p(exp(-|w|))           (the arg-max child: w = -inf, G~ = G[b][k])
+ *   a finished hypothesis offers only end_index, with phi and G unchanged; no uniform is drawn for it
+ *   a candidate whose phi or G~ is not finite counts as -inf
+ *   new beams = the `beam` largest G~, best first; equal G~: the smaller k*V+v first; a survivor takes phi(k,v) and G~(k,v);
+ *   a slot left without a finite candidate: token end_index, back-pointer 0, phi = G = -inf
+ * outputs: tokens, scores (= phi) and the three traces as pnmn_attn_lstm_beam; perturbed [B][beam] = G of every returned
+ * hypothesis; trace_perturbed [B][T][beam] = G of every slot at every step, given exactly when the three traces are.
+ * Checks and limits are those of pnmn_attn_lstm_beam; in addition a NULL `perturbed`, question_offset < 0, or some but not
+ * all of the four traces returns PNMN_EINVAL. */
+int pnmn_attn_lstm_beam_stochastic(const float* etable, const float* enc, const float* mask, const float* h0,
+                                   const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
+                                   int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
+                                   float* trace_scores, int B, int T, int S, int V, int hidden, int beam,
+                                   int pad_index, int unk_index, int start_index, int end_index,
+                                   const uint8_t* token_class /* HOST */, const uint8_t* next_state /* HOST */,
+                                   const uint8_t* min_left /* HOST */, int n_states, int n_classes,
+                                   float* perturbed, float* trace_perturbed, uint64_t seed, int64_t question_offset,
+                                   void* stream);
+
 /* Multi-CU variants of pnmn_attn_lstm_fwd / _bwd (decoder_multi.hip): eight workgroups per 16-row tile,
  * each keeping its rows' encoder outputs in LDS and its slices of W_c / W_hh in registers, two L2
  * hand-offs per step.  A job = the arguments and saved tensors of pnmn_attn_lstm_fwd / _bwd for one pass; every call

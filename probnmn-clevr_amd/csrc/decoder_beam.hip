@@ -26,6 +26,11 @@
 // a live hypothesis offers a token only if an accepting state stays reachable in the steps that remain, and @end@ only in
 // an accepting state.  Selection, gather, early stop and back-track are the unconstrained ones; the survivors' states
 // follow the back-pointers like their last tokens.
+//
+// Stochastic variant (pnmn_attn_lstm_beam_stochastic, template parameter ST, with or without C): every slot also carries G, its
+// perturbed log-probability.  Again the candidate stage alone differs (stochastic_candidates): log-probabilities renormalised
+// over the offered tokens, one Philox uniform per candidate, G~ conditioned on the parent's G; the selection ranks G~ and a
+// survivor takes its candidate's phi from a second [16][128] array.  The K survivors are a sample without replacement.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -80,13 +85,19 @@ struct ConstrainedBeamArgs : BeamArgs {
     int n_classes;
 };
 
-template <bool C>
-struct beam_args {
-    using type = BeamArgs;
+// stochastic beam search (pnmn_attn_lstm_beam_stochastic, template parameter ST): what it takes beyond the plain search's
+template <class Base>
+struct StochasticArgs : Base {
+    float* perturbed;        // [B][K] G of every returned hypothesis, best first
+    float* trace_perturbed;  // [B][T][K] or nullptr
+    uint64_t seed;
+    int64_t question_offset;
 };
-template <>
-struct beam_args<true> {
-    using type = ConstrainedBeamArgs;
+
+template <bool C, bool ST = false>
+struct beam_args {
+    using base = std::conditional_t<C, ConstrainedBeamArgs, BeamArgs>;
+    using type = std::conditional_t<ST, StochasticArgs<base>, base>;
 };
 
 // Attention of NH hypotheses that share one question's encoder rows (`er` = enc row 0 of the question + 4 * lane):
@@ -174,8 +185,73 @@ __device__ __forceinline__ void wave_top(float (&val)[N], const int (&idx)[N], f
     }
 }
 
-template <int K, bool C>
-__global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const typename beam_args<C>::type a) {
+// The candidates of rows 2w, 2w+1 under stochastic beam search (Kool, van Hoof and Welling 2019; the rule: include/probnmn_hip.h,
+// beside pnmn_attn_lstm_beam_stochastic), by wave w: logl[row] turns from logits into G~, the perturbed value the selection
+// ranks by, and phil[row] receives phi, the log-probability renormalised over the offered tokens.  `offered(row, j)`: the
+// plain search's test of a live hypothesis' token; `draw_row(row)`: (question_offset + question) * 16 + slot.  A lane
+// answers for tokens lane and lane + 64 of both rows: four Philox draws per lane and step, no LDS traffic beyond the two
+// stores, no barrier of its own.
+template <class Offered, class DrawRow>
+__device__ __forceinline__ void stochastic_candidates(float (*logl)[MAXV], float (*phil)[MAXV], const float* scorel, const float* gl,
+                                                      const int* tokl, int end, uint64_t seed, uint32_t t, Offered offered,
+                                                      DrawRow draw_row) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int rr = 0; rr < 2; ++rr) {
+        const int rl = 2 * wave + rr;
+        const float score = scorel[rl], G = gl[rl];
+        const bool finished = tokl[rl] == end;
+        float v[2], mx = -INFINITY;
+        bool in[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int j = lane + 64 * k;
+            v[k] = logl[rl][j];  // (-inf at and past V)
+            in[k] = !finished && offered(rl, j) && v[k] > -INFINITY && v[k] < INFINITY;  // offered, with a finite logit
+            if (in[k]) mx = fmaxf(mx, v[k]);
+        }
+        mx = wmax(mx);
+        float se = 0.f;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) se += in[k] ? expf(v[k] - mx) : 0.f;
+        const float lse = mx + logf(wsum(se));
+        float phi[2], gum[2], Z = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            phi[k] = in[k] ? score + (v[k] - lse) : -INFINITY;
+            if (!(phi[k] > -INFINITY && phi[k] < INFINITY)) phi[k] = -INFINITY;
+            gum[k] = -INFINITY;
+            if (phi[k] > -INFINITY) {
+                const float u = pnmn::philox_uniform_open(seed, draw_row(rl) * MAXV + (lane + 64 * k), t);
+                gum[k] = phi[k] - logf(-logf(u));
+            }
+            Z = fmaxf(Z, gum[k]);
+        }
+        Z = wmax(Z);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int j = lane + 64 * k;
+            float key = -INFINITY;
+            if (phi[k] > -INFINITY) {
+                // G~ = -log(exp(-G) - exp(-Z) + exp(-g)) without its cancellation: w = G - g + log(1 - exp(g - Z)),
+                // G~ = G - max(0, w) - log1p(exp(-|w|)); the arg-max child has w = -inf and keeps G
+                const float d = gum[k] - Z;  // <= 0
+                const float w = G - gum[k] + (d > -0.6931472f ? logf(-expm1f(d)) : log1pf(-expf(d)));
+                key = G - fmaxf(0.f, w) - log1pf(expf(-fabsf(w)));
+                if (!(key > -INFINITY && key < INFINITY)) key = phi[k] = -INFINITY;  // a non-finite candidate counts as -inf
+            }
+            if (finished && j == end && score > -INFINITY && G > -INFINITY && G < INFINITY) {
+                phi[k] = score;  // a finished hypothesis offers only @end@, phi and G unchanged; no uniform is drawn for it
+                key = G;
+            }
+            logl[rl][j] = key;
+            phil[rl][j] = phi[k];
+        }
+    }
+}
+
+template <int K, bool C, bool ST = false>
+__global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const typename beam_args<C, ST>::type a) {
     constexpr int Q = ROWS / K;  // questions per workgroup
     __shared__ __attribute__((aligned(16))) float hl[2][ROWS][LD];  // [0]: h the step reads, [1]: h the cell wrote
     __shared__ __attribute__((aligned(16))) float cl[ROWS][LD];     // ctx; after the cell: c on its way through the gather
@@ -189,6 +265,9 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const typename beam
     // constrained search only: the automaton, and the state of every slot ([0]: the step reads, [1]: the survivors')
     __shared__ unsigned char clsl[C ? MAXV : 1], nextl[C ? MAX_STATES * MAX_CLASSES : 1], leftl[C ? MAX_STATES : 1];
     __shared__ unsigned char statel[2][C ? ROWS : 1];
+    // stochastic search only: phi of every candidate beside its perturbed value in logl, and G of every slot
+    __shared__ float phil[ST ? ROWS : 1][ST ? MAXV : 1];
+    __shared__ float gl[ST ? ROWS : 1];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, g = lane >> 4;
     const int q0 = blockIdx.x * Q;  // first question of this tile
     const int T = a.T, S = a.S, V = a.V;
@@ -201,6 +280,7 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const typename beam
         const bool live = q0 + tid / K < a.B;
         tokl[tid] = live ? a.start : a.end;  // (a tile row past the batch counts as finished)
         scorel[tid] = (tid % K == 0) ? 0.f : -INFINITY;  // step 0 expands ONE state per question
+        if constexpr (ST) gl[tid] = (tid % K == 0) ? 0.f : -INFINITY;
     }
     int ncls = 1;
     if constexpr (C) {
@@ -284,41 +364,57 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const typename beam
         __syncthreads();
 
         // ---------------- candidates: wave w turns the logits of rows 2w, 2w+1 into score + log-probability ----------------
-#pragma unroll
-        for (int rr = 0; rr < 2; ++rr) {
-            const int rl = 2 * wave + rr;
-            float v[2], mx = -INFINITY;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                v[k] = logl[rl][lane + 64 * k];  // (-inf at and past V)
-                mx = fmaxf(mx, v[k]);
-            }
-            mx = wmax(mx);
-            float se = 0.f;
-#pragma unroll
-            for (int k = 0; k < 2; ++k) se += (lane + 64 * k < V) ? expf(v[k] - mx) : 0.f;
-            const float lse = mx + logf(wsum(se));
-            const float score = scorel[rl];
-            const bool finished = tokl[rl] == a.end;
-            int st = 0;
-            if constexpr (C) st = statel[0][rl];
-#pragma unroll
-            for (int k = 0; k < 2; ++k) {
-                const int j = lane + 64 * k;
-                float cand = -INFINITY;
-                if (finished) {
-                    if (j == a.end) cand = score;  // a finished hypothesis keeps its score
-                } else if (j < V && j != a.pad && j != a.unk && j != a.start) {
-                    cand = score + (v[k] - lse);
-                    if constexpr (C) {
-                        // @end@: only in an accepting state; any other token: an accepting state must stay reachable in
-                        // the T - 1 - t steps after this one (DEAD = 255 > any step count)
+        if constexpr (ST) {
+            const auto offered = [&](int rl, int j) {
+                bool ok = j < V && j != a.pad && j != a.unk && j != a.start;
+                if constexpr (C) {
+                    if (ok) {  // the constrained search's test, below
+                        const int st = statel[0][rl];
                         const int left = j == a.end ? (leftl[st] == 0 ? 0 : DEAD) : leftl[nextl[st * ncls + clsl[j]]];
-                        if (left > T - 1 - t) cand = -INFINITY;
+                        ok = left <= T - 1 - t;
                     }
                 }
-                if (!(cand > -INFINITY && cand < INFINITY)) cand = -INFINITY;  // a non-finite candidate counts as -inf
-                logl[rl][j] = cand;
+                return ok;
+            };
+            const auto draw_row = [&](int rl) { return ((uint64_t)a.question_offset + (uint64_t)(q0 + rl / K)) * ROWS + rl % K; };
+            stochastic_candidates(logl, phil, scorel, gl, tokl, a.end, a.seed, (uint32_t)t, offered, draw_row);
+        } else {
+#pragma unroll
+            for (int rr = 0; rr < 2; ++rr) {
+                const int rl = 2 * wave + rr;
+                float v[2], mx = -INFINITY;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    v[k] = logl[rl][lane + 64 * k];  // (-inf at and past V)
+                    mx = fmaxf(mx, v[k]);
+                }
+                mx = wmax(mx);
+                float se = 0.f;
+#pragma unroll
+                for (int k = 0; k < 2; ++k) se += (lane + 64 * k < V) ? expf(v[k] - mx) : 0.f;
+                const float lse = mx + logf(wsum(se));
+                const float score = scorel[rl];
+                const bool finished = tokl[rl] == a.end;
+                int st = 0;
+                if constexpr (C) st = statel[0][rl];
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const int j = lane + 64 * k;
+                    float cand = -INFINITY;
+                    if (finished) {
+                        if (j == a.end) cand = score;  // a finished hypothesis keeps its score
+                    } else if (j < V && j != a.pad && j != a.unk && j != a.start) {
+                        cand = score + (v[k] - lse);
+                        if constexpr (C) {
+                            // @end@: only in an accepting state; any other token: an accepting state must stay reachable in
+                            // the T - 1 - t steps after this one (DEAD = 255 > any step count)
+                            const int left = j == a.end ? (leftl[st] == 0 ? 0 : DEAD) : leftl[nextl[st * ncls + clsl[j]]];
+                            if (left > T - 1 - t) cand = -INFINITY;
+                        }
+                    }
+                    if (!(cand > -INFINITY && cand < INFINITY)) cand = -INFINITY;  // a non-finite candidate counts as -inf
+                    logl[rl][j] = cand;
+                }
             }
         }
         __syncthreads();
@@ -330,6 +426,10 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const typename beam
         const auto commit = [&](int rl, float score, int flat) {  // slot rl of the tile takes candidate `flat` of its question
             const int bp = flat < 0 ? 0 : flat / V;               // (flat < 0: a slot left without a finite candidate)
             const int tok = flat < 0 ? a.end : flat - bp * V;
+            if constexpr (ST) {  // ranked by G~: the survivor takes it, and its candidate's phi
+                gl[rl] = score;
+                score = flat < 0 ? -INFINITY : phil[(rl / K) * K + bp][tok];
+            }
             scorel[rl] = score;
             bpl[rl] = (rl / K) * K + bp;
             tokl[rl] = tok;
@@ -344,6 +444,7 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const typename beam
                 a.trace_tokens[o] = tok;
                 a.trace_backptr[o] = bp;
                 a.trace_scores[o] = score;
+                if constexpr (ST) a.trace_perturbed[o] = gl[rl];
             }
         };
 #pragma unroll
@@ -431,6 +532,7 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const typename beam
                 a.trace_tokens[o] = a.end;
                 a.trace_backptr[o] = bp;
                 a.trace_scores[o] = score;
+                if constexpr (ST) a.trace_perturbed[o] = gl[tid];
             }
         }
     }
@@ -445,41 +547,61 @@ __global__ __launch_bounds__(512) void attn_lstm_beam_kernel(const typename beam
             cur = bp_hist[t][base + cur];
         }
         a.scores[(size_t)q * K + tid % K] = scorel[tid];
+        if constexpr (ST) a.perturbed[(size_t)q * K + tid % K] = gl[tid];
     }
 }
 
-template <int K, bool C>
-int launch_beam(const typename beam_args<C>::type& a, hipStream_t stream) {
+template <int K, bool C, bool ST>
+int launch_beam(const typename beam_args<C, ST>::type& a, hipStream_t stream) {
     constexpr int Q = ROWS / K;
-    hipLaunchKernelGGL((attn_lstm_beam_kernel<K, C>), dim3((a.B + Q - 1) / Q), dim3(512), 0, stream, a);
+    hipLaunchKernelGGL((attn_lstm_beam_kernel<K, C, ST>), dim3((a.B + Q - 1) / Q), dim3(512), 0, stream, a);
     return (int)hipGetLastError();
 }
 
-template <bool C>
-int launch_beam_width(int beam, const typename beam_args<C>::type& a, hipStream_t stream) {
+template <bool C, bool ST>
+int launch_beam_width(int beam, const typename beam_args<C, ST>::type& a, hipStream_t stream) {
     switch (beam) {
-        case 1: return launch_beam<1, C>(a, stream);
-        case 2: return launch_beam<2, C>(a, stream);
-        case 4: return launch_beam<4, C>(a, stream);
-        case 8: return launch_beam<8, C>(a, stream);
-        case 16: return launch_beam<16, C>(a, stream);
+        case 1: return launch_beam<1, C, ST>(a, stream);
+        case 2: return launch_beam<2, C, ST>(a, stream);
+        case 4: return launch_beam<4, C, ST>(a, stream);
+        case 8: return launch_beam<8, C, ST>(a, stream);
+        case 16: return launch_beam<16, C, ST>(a, stream);
         default: return PNMN_EINVAL;
     }
 }
 
-}  // namespace
+// what pnmn_attn_lstm_beam_stochastic takes beyond pnmn_attn_lstm_beam
+struct StochasticPart {
+    float* perturbed;
+    float* trace_perturbed;
+    uint64_t seed;
+    int64_t question_offset;
+};
 
-extern "C" int pnmn_attn_lstm_beam(const float* etable, const float* enc, const float* mask, const float* h0,
-                                   const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
-                                   int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
-                                   float* trace_scores, int B, int T, int S, int V, int hidden, int beam, int pad_index,
-                                   int unk_index, int start_index, int end_index, const uint8_t* token_class,
-                                   const uint8_t* next_state, const uint8_t* min_left, int n_states, int n_classes,
-                                   void* stream) {
+// the plain search (st == nullptr) or the stochastic one over the same arguments
+template <bool C>
+int launch_search(int beam, const typename beam_args<C>::type& a, const StochasticPart* st, hipStream_t stream) {
+    if (!st) return launch_beam_width<C, false>(beam, a, stream);
+    typename beam_args<C, true>::type sa{};
+    static_cast<typename beam_args<C>::type&>(sa) = a;
+    sa.perturbed = st->perturbed;
+    sa.trace_perturbed = st->trace_perturbed;
+    sa.seed = st->seed;
+    sa.question_offset = st->question_offset;
+    return launch_beam_width<C, true>(beam, sa, stream);
+}
+
+// the checks and the launch both entry points share
+int beam_entry(const float* etable, const float* enc, const float* mask, const float* h0, const float* w_c, const float* w_hh,
+               const float* w_p, const float* b_p, int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
+               float* trace_scores, int B, int T, int S, int V, int hidden, int beam, int pad_index, int unk_index,
+               int start_index, int end_index, const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left,
+               int n_states, int n_classes, const StochasticPart* st, void* stream) {
     if (B < 0 || T < 0) return PNMN_EINVAL;
     if (!etable || !enc || !mask || !h0 || !w_c || !w_hh || !w_p || !b_p || !tokens || !scores) return PNMN_EINVAL;
     const int traced = (trace_tokens != nullptr) + (trace_backptr != nullptr) + (trace_scores != nullptr);
     if (traced != 0 && traced != 3) return PNMN_EINVAL;
+    if (st && (!st->perturbed || st->question_offset < 0 || (st->trace_perturbed != nullptr) != (traced == 3))) return PNMN_EINVAL;
     if (hidden != H || S < 1 || S > MAXS || V < 1 || V > MAXV || T > MAXT) return PNMN_EINVAL;
     // every index the kernel looks a table row up by, or writes as a token, is inside the vocabulary
     if (start_index < 0 || start_index >= V || end_index < 0 || end_index >= V) return PNMN_EINVAL;
@@ -487,7 +609,7 @@ extern "C" int pnmn_attn_lstm_beam(const float* etable, const float* enc, const 
     const BeamArgs plain{etable, enc, mask, h0, w_c, w_hh, w_p, b_p, tokens, scores, trace_tokens, trace_backptr, trace_scores,
                          B, T, S, V, pad_index, unk_index, start_index, end_index};
     if (!token_class && !next_state && !min_left)
-        return B == 0 || T == 0 ? 0 : launch_beam_width<false>(beam, plain, static_cast<hipStream_t>(stream));
+        return B == 0 || T == 0 ? 0 : launch_search<false>(beam, plain, st, static_cast<hipStream_t>(stream));
     if (!token_class || !next_state || !min_left) return PNMN_EINVAL;
     if (n_states < 1 || n_states > MAX_STATES || n_classes < 1 || n_classes > MAX_CLASSES) return PNMN_EINVAL;
     // every table entry the kernel indexes with stays inside the tables (min_left is only compared)
@@ -504,5 +626,33 @@ extern "C" int pnmn_attn_lstm_beam(const float* etable, const float* enc, const 
     if (B == 0 || T == 0) return 0;
     static_cast<BeamArgs&>(a) = plain;
     a.n_classes = n_classes;
-    return launch_beam_width<true>(beam, a, static_cast<hipStream_t>(stream));
+    return launch_search<true>(beam, a, st, static_cast<hipStream_t>(stream));
+}
+
+}  // namespace
+
+extern "C" int pnmn_attn_lstm_beam(const float* etable, const float* enc, const float* mask, const float* h0,
+                                   const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
+                                   int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
+                                   float* trace_scores, int B, int T, int S, int V, int hidden, int beam, int pad_index,
+                                   int unk_index, int start_index, int end_index, const uint8_t* token_class,
+                                   const uint8_t* next_state, const uint8_t* min_left, int n_states, int n_classes,
+                                   void* stream) {
+    return beam_entry(etable, enc, mask, h0, w_c, w_hh, w_p, b_p, tokens, scores, trace_tokens, trace_backptr, trace_scores, B, T, S,
+                      V, hidden, beam, pad_index, unk_index, start_index, end_index, token_class, next_state, min_left, n_states,
+                      n_classes, nullptr, stream);
+}
+
+extern "C" int pnmn_attn_lstm_beam_stochastic(const float* etable, const float* enc, const float* mask, const float* h0,
+                                              const float* w_c, const float* w_hh, const float* w_p, const float* b_p,
+                                              int64_t* tokens, float* scores, int32_t* trace_tokens, int32_t* trace_backptr,
+                                              float* trace_scores, int B, int T, int S, int V, int hidden, int beam,
+                                              int pad_index, int unk_index, int start_index, int end_index,
+                                              const uint8_t* token_class, const uint8_t* next_state, const uint8_t* min_left,
+                                              int n_states, int n_classes, float* perturbed, float* trace_perturbed,
+                                              uint64_t seed, int64_t question_offset, void* stream) {
+    const StochasticPart st{perturbed, trace_perturbed, seed, question_offset};
+    return beam_entry(etable, enc, mask, h0, w_c, w_hh, w_p, b_p, tokens, scores, trace_tokens, trace_backptr, trace_scores, B, T, S,
+                      V, hidden, beam, pad_index, unk_index, start_index, end_index, token_class, next_state, min_left, n_states,
+                      n_classes, &st, stream);
 }

@@ -44,7 +44,8 @@ __device__ __forceinline__ void philox_round(uint32_t (&ctr)[4], uint32_t k0, ui
     ctr[2] = hi0 ^ ctr[3] ^ k1;
     ctr[3] = lo0;
 }
-__device__ inline float philox_uniform(uint64_t seed, uint64_t row, uint32_t step) {  // same stream as pnmn_sample_tokens
+// word 0 of Philox4x32-10 for (seed, row, step): the one stream every draw of the library comes from
+__device__ inline uint32_t philox_word0(uint64_t seed, uint64_t row, uint32_t step) {
     uint32_t ctr[4] = {(uint32_t)row, (uint32_t)(row >> 32), step, 0x9E3779B9u};
     uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
 #pragma unroll
@@ -53,7 +54,14 @@ __device__ inline float philox_uniform(uint64_t seed, uint64_t row, uint32_t ste
         k0 += 0x9E3779B9u;
         k1 += 0xBB67AE85u;
     }
-    return (float)(ctr[0] >> 8) * (1.0f / 16777216.0f);
+    return ctr[0];
+}
+__device__ inline float philox_uniform(uint64_t seed, uint64_t row, uint32_t step) {  // same stream as pnmn_sample_tokens
+    return (float)(philox_word0(seed, row, step) >> 8) * (1.0f / 16777216.0f);
+}
+// the same word as an odd multiple of 2^-24: 0 < u < 1 exactly in fp32, so neither log u nor log(-log u) meets 0 or 1
+__device__ inline float philox_uniform_open(uint64_t seed, uint64_t row, uint32_t step) {
+    return (float)(2u * (philox_word0(seed, row, step) >> 9) + 1u) * (1.0f / 16777216.0f);
 }
 
 // Inverse-CDF scan of one row's weights `w` (chunk k of a lane = index lane + 64k, index order): the first index with

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from probnmn import _hip
-from probnmn.modules.seq2seq_base import sampling_filter
+from probnmn.modules.seq2seq_base import Seq2SeqBase, sampling_filter
 
 
 class Evaluator:
@@ -241,6 +241,87 @@ def _marginal_options(beam_size, marginal, num_programs, explain) -> bool:
     return bool(marginal) or num_programs is not None
 
 
+SAMPLE_WEIGHTS = ("probability", "importance")
+
+
+def _scaled_exp1(c: torch.Tensor) -> torch.Tensor:
+    """exp(c) E1(c) = int_0^inf exp(-x) / (x + c) dx for c > 0 (float64): the power series of E1 up to c = 1, the continued
+    fraction 1 / (c + 1 - 1 / (c + 3 - 4 / (c + 5 - ...))) above (evaluated bottom up, 80 levels: 1e-15 at c = 1)."""
+    small = c.clamp(min=1e-300, max=1.0)
+    term, series = torch.ones_like(small), torch.zeros_like(small)
+    for k in range(1, 26):
+        term = term * (-small) / k  # (-c)^k / k!
+        series = series - term / k
+    low = torch.exp(small) * (-0.5772156649015329 - torch.log(small) + series)
+    big = c.clamp(min=1.0, max=1e300)
+    tail = big + (2 * 80 + 1)
+    for k in range(80, 0, -1):
+        tail = big + (2 * k - 1) - k * k / tail
+    return torch.where(c <= 1.0, low, 1.0 / tail)
+
+
+_LAGUERRE = np.polynomial.laguerre.laggauss(48)  # nodes and weights of int_0^inf exp(-x) f(x) dx
+
+
+def without_replacement_weights(log_probabilities: torch.Tensor, perturbed: torch.Tensor) -> torch.Tensor:
+    """Log importance weights of a sample without replacement (Kool, van Hoof and Welling 2019, section 4.2), from what
+    ``Seq2SeqBase.decode_stochastic_beam`` returns: ``log_probabilities`` = phi and ``perturbed`` = G, both [B, K], best
+    first: sum_i w_i f(z_i) is an unbiased estimate of E_p[f], and divided by sum_i w_i (what
+    ``NeuralModuleNetwork.marginal_answers`` does with any weights) it is the paper's normalised estimator.  The K-th
+    perturbed value is the threshold kappa = G[:, K-1]; slot K-1 gets -inf.
+
+    The paper's w_i = p_i / q_i(kappa), q_i(kappa) = 1 - exp(-exp(phi_i - kappa)), holds for UNCONDITIONED Gumbels.  The search
+    starts from G = 0 at the root, so its G are conditioned on the largest being 0, and that formula would come out biased
+    low (sum_i w_i averages 0.75 at K = 2).  The root's free value M ~ Gumbel(0) is independent of the sample, and given M
+    the unconditioned values follow from the returned ones: exp(-G'_i) = exp(-M) - 1 + exp(-G_i).  With E = exp(-M) ~ Exp(1)
+    and c = exp(-kappa) - 1, the threshold becomes exp(-kappa') = E + c, and the weight is the paper's, averaged over E:
+
+        w_i = p_i  int_0^inf exp(-x) / (1 - exp(-p_i (x + c))) dx          for i < K-1,      p_i = exp(phi_i)
+
+    -- a function of (phi_i, kappa) alone, unbiased, and of smaller variance than a drawn M.  Evaluated as
+    exp(c) E1(c) + p_i int exp(-x) r(p_i (x + c)) dx with r(y) = 1 / (1 - exp(-y)) - 1 / y, which is smooth and lies in
+    [1/2, 1): a 48-point Gauss-Laguerre rule; the first term carries the logarithmic singularity of c -> 0.
+    kappa = -inf (fewer than K sequences exist: the whole support was enumerated): log w_i = phi_i for every finite slot.  A
+    slot without a sequence (phi = -inf) gets -inf.  Pure torch, any device, computed in float64 and returned in the dtype of
+    ``log_probabilities``; no overflow or NaN for any finite phi_i and kappa < 0."""
+    phi, g = log_probabilities, perturbed
+    if phi.dim() != 2 or phi.shape != g.shape:
+        raise ValueError("log_probabilities and perturbed are [B, K] each; got %s and %s" % (tuple(phi.shape), tuple(g.shape)))
+    phi64, kappa = phi.double(), g[:, -1:].double()
+    finite = torch.isfinite(phi64)
+    p = torch.exp(torch.where(finite, phi64, torch.zeros_like(phi64)))
+    c = torch.expm1(-kappa).clamp(min=1e-300).expand_as(p)  # (+inf where kappa = -inf; kappa = 0: the only slot, K = 1)
+    whole = torch.isinf(c)
+    c_ = torch.where(whole, torch.ones_like(c), c)
+    nodes = torch.as_tensor(_LAGUERRE[0], dtype=torch.float64, device=phi.device)
+    weights = torch.as_tensor(_LAGUERRE[1], dtype=torch.float64, device=phi.device)
+    y = (p * c_).unsqueeze(-1) + p.unsqueeze(-1) * nodes  # p (x + c), the product first: c may be 1e300
+    y_ = y.clamp(min=1e-4)
+    r = torch.where(y < 1e-4, 0.5 + y / 12.0, -1.0 / torch.expm1(-y_) - 1.0 / y_)
+    w = _scaled_exp1(c_) + p * (r * weights).sum(-1)
+    out = torch.where(finite, torch.where(whole, phi64, torch.log(w)), torch.full_like(phi64, float("-inf")))
+    out[:, -1] = float("-inf")
+    return out.to(phi.dtype)
+
+
+def _without_replacement_options(without_replacement, sample_weights, beam_size, num_programs) -> Optional[str]:
+    """The argument rules of ``without_replacement`` / ``sample_weights`` (``predict_answers`` states them): None, or the
+    weights a without-replacement sample hands on."""
+    if sample_weights not in SAMPLE_WEIGHTS:
+        raise ValueError("sample_weights must be one of %s, got %r" % (SAMPLE_WEIGHTS, sample_weights))
+    if not without_replacement:
+        if sample_weights != "probability":
+            raise ValueError("sample_weights=%r weighs a sample without replacement: give without_replacement=True" % (sample_weights,))
+        return None
+    if beam_size is not None:
+        raise ValueError("without_replacement=True samples num_programs hypotheses; with beam_size they are searched")
+    sizes = tuple(k for k in Seq2SeqBase.BEAM_SIZES if k >= 2)
+    if isinstance(num_programs, bool) or not isinstance(num_programs, int) or num_programs not in sizes:
+        raise ValueError("without_replacement=True draws num_programs hypotheses in one stochastic beam search: num_programs must be "
+                         "one of %s, got %r" % (sizes, num_programs))
+    return sample_weights
+
+
 def _rerank_weights(weights):
     """``(w_x, w_z, w_q)`` of ``hypothesis_posterior`` as three finite floats; ``ValueError`` otherwise."""
     import math
@@ -385,11 +466,20 @@ class _HostCopies:
 
 
 def _queue_hypotheses(program_generator, batch, iteration, copies, beam_size, num_programs, constraint, constrained_sampling,
-                      sampling, on_device):
+                      sampling, on_device, without_replacement=None):
     """First stage of a marginal batch: the generator pass that yields K hypotheses per question and the asynchronous copy
-    of them to the host.  Returns (tokens [B, K, T], log-weights [B, K] or None, event or None)."""
+    of them to the host.  Returns (tokens [B, K, T], log-weights [B, K] or None, event or None, perturbed [B, K] or None).
+    ``without_replacement`` ("probability" / "importance", or None): the ``num_programs`` hypotheses are ONE stochastic beam
+    search's, weighted by their log-probabilities or by ``without_replacement_weights``."""
     question = batch["question"]
-    if num_programs is not None:  # every question num_programs times in ONE call: the rows draw independently
+    perturbed = None
+    if without_replacement is not None:
+        extra = {} if constraint is None else {"constraint": constraint}
+        out = program_generator(question, decoding_strategy="stochastic_beam", beam_size=num_programs, **extra)
+        tokens, weights, perturbed = out["beam_predictions"], out["beam_log_probabilities"], out["beam_perturbed"]
+        if without_replacement == "importance":
+            weights = without_replacement_weights(weights, perturbed)
+    elif num_programs is not None:  # every question num_programs times in ONE call: the rows draw independently
         repeated = question.repeat_interleave(num_programs, 0)
         if constrained_sampling:
             out = program_generator(repeated, decoding_strategy="constrained_sampling", constraint=constraint, **sampling)
@@ -402,13 +492,15 @@ def _queue_hypotheses(program_generator, batch, iteration, copies, beam_size, nu
         out = program_generator(question, decoding_strategy="beam", beam_size=beam_size, **extra)
         tokens, weights = out["beam_predictions"], out["beam_log_probabilities"]
     if not (tokens.is_cuda and on_device):
-        return tokens, weights, None
+        return tokens, weights, None, perturbed
     tokens = copies.copy("tokens", iteration, tokens)
     if weights is not None:
         weights = copies.copy("weights", iteration, weights)
+    if perturbed is not None:
+        perturbed = copies.copy("perturbed", iteration, perturbed)
     copied = torch.cuda.Event()
     copied.record()
-    return tokens, weights, copied
+    return tokens, weights, copied, perturbed
 
 
 def _finish_hypotheses(nmn, image, queued, rerank=None):
@@ -416,15 +508,16 @@ def _finish_hypotheses(nmn, image, queued, rerank=None):
     ``rerank`` = (question_reconstructor, program_prior, coefficients, questions [B, Tq]) or None: the hypotheses' weights
     are their posterior under the generative model (``hypothesis_posterior``, the merged generator weight as its ``log_q``)
     instead of the generator's own.  Returns (``marginal_answers``' dict as host numpy -- reranked: and
-    ``hypothesis_posterior``'s ``"log_reconstruction"``, ``"log_prior"`` and ``"best_row"`` --, programs [R, T], group_start
-    [B + 1])."""
-    tokens, weights, copied = queued
+    ``hypothesis_posterior``'s ``"log_reconstruction"``, ``"log_prior"`` and ``"best_row"``; a sample without replacement: and
+    ``"perturbed"`` [R], G of every row's first slot --, programs [R, T], group_start [B + 1])."""
+    tokens, weights, copied, perturbed = queued
     if copied is not None:
         copied.synchronize()
     arr = tokens.cpu().numpy()
     B, K, T = arr.shape
     valid = np.array([c.valid for c in nmn.engine.compiler.compile_batch(arr.reshape(B * K, T))], dtype=bool).reshape(B, K)
-    programs, question_rows, log_weights, _ = group_hypotheses(arr, None if weights is None else weights.cpu().numpy(), valid)
+    programs, question_rows, log_weights, first_slot = group_hypotheses(arr, None if weights is None else weights.cpu().numpy(),
+                                                                        valid)
     scored = {}
     if rerank is not None:
         question_reconstructor, program_prior, coefficients, questions = rerank
@@ -434,6 +527,8 @@ def _finish_hypotheses(nmn, image, queued, rerank=None):
         scored = {k: posterior[k] for k in ("log_reconstruction", "log_prior", "best_row")}
     out = nmn.marginal_answers(image, torch.from_numpy(programs), question_rows, log_weights)
     out.update(scored)
+    if perturbed is not None:
+        out["perturbed"] = perturbed.cpu()[torch.from_numpy(question_rows), torch.from_numpy(first_slot)]
     return ({k: v.cpu().numpy() for k, v in out.items()}, programs, np.searchsorted(question_rows, np.arange(B + 1)))
 
 
@@ -444,7 +539,8 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
                     top_p: float = 1.0, constrained_sampling: bool = False, explain: bool = False,
                     overlay_strength: int = 160, colormap: Optional[torch.Tensor] = None, marginal: bool = False,
                     num_programs: Optional[int] = None, rerank: bool = False, question_reconstructor=None, program_prior=None,
-                    rerank_weights=(1.0, 1.0, 0.0)) -> List[Dict[str, Any]]:
+                    rerank_weights=(1.0, 1.0, 0.0), without_replacement: bool = False,
+                    sample_weights: str = "probability") -> List[Dict[str, Any]]:
     """scripts/inference.py:76-91: sampled programs -> NMN -> answer strings, one record per question
     (``question_index`` from the batch when present, else a running index).
 
@@ -504,7 +600,18 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
     and its own answer (``[]`` and ``@@UNKNOWN@@`` when there is none).  The models are left as they were: no metric, no
     seed, their ``train()`` / ``eval()`` state.  ``rerank`` without hypotheses, with ``explain``, with coefficients that are
     not three finite numbers, or without a model whose coefficient is not 0, is a ``ValueError``, raised before any model
-    is touched."""
+    is touched.
+
+    ``without_replacement`` (with ``num_programs`` = N in 2, 4, 8 or 16): the N hypotheses of a question are a sample WITHOUT
+    replacement from the generator -- N distinct programs from ONE stochastic beam search
+    (``decoding_strategy="stochastic_beam"``) instead of N independent decodes that mostly repeat each other; with
+    ``constrained_sampling`` they are drawn under the validity rule.  ``sample_weights``: ``"probability"`` hands their
+    log-probabilities to ``group_hypotheses`` / ``marginal_answers`` exactly as the beam path hands its scores;
+    ``"importance"`` hands ``without_replacement_weights`` (the N-th hypothesis sets the threshold and weighs nothing).
+    Everything downstream, ``rerank`` included, is unchanged; each hypothesis of a record also names its ``"perturbed"``
+    log-probability.  ``without_replacement`` with ``beam_size``, with a ``num_programs`` outside those sizes or with a
+    sampling filter, and ``sample_weights`` without ``without_replacement``, are a ``ValueError``."""
+    draw = _without_replacement_options(without_replacement, sample_weights, beam_size, num_programs)
     coefficients = _rerank_options(rerank, beam_size, num_programs, explain, question_reconstructor, program_prior, rerank_weights)
     marginalise = _marginal_options(beam_size, marginal or (rerank and num_programs is None), num_programs, explain)
     if constrained and beam_size is None:
@@ -514,6 +621,8 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
     filt = sampling_filter(temperature, top_k, top_p)
     if filt is not None and beam_size is not None:
         raise ValueError("temperature / top_k / top_p filter sampled programs; with beam_size the programs are searched, not drawn")
+    if filt is not None and draw is not None:
+        raise ValueError("temperature / top_k / top_p filter independent draws; a sample without replacement takes no filter")
     sampling = {} if filt is None else dict(temperature=filt[0], top_k=filt[1], top_p=filt[2])
     was_training = (program_generator.training, nmn.training)
     program_generator.eval()
@@ -543,7 +652,7 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
             image = features(batch)
             if marginalise:
                 return _queue_hypotheses(program_generator, batch, iteration, copies, beam_size, num_programs, constraint,
-                                         constrained_sampling, sampling, image.is_cuda), image
+                                         constrained_sampling, sampling, image.is_cuda, draw), image
             if constrained_sampling:
                 programs = program_generator(batch["question"], decoding_strategy="constrained_sampling", constraint=constraint,
                                              **sampling)["predictions"]
@@ -595,6 +704,9 @@ def predict_answers(program_generator, nmn, batches: Iterable[Dict[str, torch.Te
                     "hypotheses": [{"program": token_strings(programs[r]), "weight": float(out["hypothesis_weights"][r]),
                                     "answer": vocabulary.get_token_from_index(int(out["hypothesis_predictions"][r]), namespace="answers")}
                                    for r in range(start[i], start[i + 1])]})
+                if draw is not None:
+                    for h, r in zip(records[-1]["hypotheses"], range(start[i], start[i + 1])):
+                        h["perturbed"] = float(out["perturbed"][r])
                 if reranked is not None:
                     for h, r in zip(records[-1]["hypotheses"], range(start[i], start[i + 1])):
                         h["log_reconstruction"] = None if question_reconstructor is None else float(out["log_reconstruction"][r])
@@ -666,7 +778,8 @@ def evaluate_marginal_answer_accuracy(program_generator, nmn, batches: Iterable[
                                       beam_size: Optional[int] = None, num_programs: Optional[int] = None,
                                       constrained: bool = False, constrained_sampling: bool = False,
                                       num_batches: Optional[int] = None, rerank: bool = False, question_reconstructor=None,
-                                      program_prior=None, rerank_weights=(1.0, 1.0, 0.0)) -> Dict[str, float]:
+                                      program_prior=None, rerank_weights=(1.0, 1.0, 0.0), without_replacement: bool = False,
+                                      sample_weights: str = "probability") -> Dict[str, float]:
     """Answer accuracy of the MARGINAL answer over several programs per question -- the ``beam_size`` hypotheses of a beam
     search (``constrained``: under the validity rule), weighted by their probabilities, or ``num_programs`` sampled ones
     (``constrained_sampling``), uniformly weighted -- on batches with ``"answer"``; free-running decodes, unlike
@@ -678,7 +791,11 @@ def evaluate_marginal_answer_accuracy(program_generator, nmn, batches: Iterable[
 
     ``rerank``, ``question_reconstructor``, ``program_prior``, ``rerank_weights``: as for ``predict_answers`` -- the hypotheses
     are weighted by their posterior under the generative model -- and the result also holds ``"map_answer_accuracy"``: each
-    question answered by its MAP hypothesis alone."""
+    question answered by its MAP hypothesis alone.
+
+    ``without_replacement``, ``sample_weights``: as for ``predict_answers`` -- the ``num_programs`` hypotheses are one
+    stochastic beam search's, a sample without replacement."""
+    draw = _without_replacement_options(without_replacement, sample_weights, beam_size, num_programs)
     if beam_size is None and num_programs is None:
         raise ValueError("give the hypotheses: beam_size (a beam search) or num_programs (samples)")
     coefficients = _rerank_options(rerank, beam_size, num_programs, False, question_reconstructor, program_prior, rerank_weights)
@@ -719,7 +836,7 @@ def evaluate_marginal_answer_accuracy(program_generator, nmn, batches: Iterable[
         pending = None
         for iteration, batch in enumerate(batches):
             queued = _queue_hypotheses(program_generator, batch, iteration, copies, beam_size, num_programs, constraint,
-                                       constrained_sampling, {}, batch["image"].is_cuda)
+                                       constrained_sampling, {}, batch["image"].is_cuda, draw)
             if pending is not None:
                 finish(*pending)
             pending = (batch, queued)

@@ -20,7 +20,8 @@ performs no host synchronisation.
 
 Not in the reference: ``decoding_strategy="beam"`` (``Seq2SeqBase.decode_beam``), beam search for inference as one launch
 of a persistent kernel that keeps the K hypotheses of a question in one workgroup (``pnmn_attn_lstm_beam``,
-csrc/decoder_beam.hip).
+csrc/decoder_beam.hip), and ``decoding_strategy="stochastic_beam"`` (``Seq2SeqBase.decode_stochastic_beam``), the same
+kernel's stochastic candidate stage: K programs sampled without replacement (``pnmn_attn_lstm_beam_stochastic``).
 """
 import math
 import os
@@ -1148,7 +1149,9 @@ class Seq2SeqBase(nn.Module):
         top_p: float = 1.0,
     ) -> Dict[str, torch.Tensor]:
         """``decoding_strategy``: "sampling" / "greedy" as the reference; "beam": beam search of width ``beam_size`` (free
-        running only, no gradients -- see ``decode_beam``); "constrained_sampling" / "constrained_greedy": a sampled / arg-max
+        running only, no gradients -- see ``decode_beam``); "stochastic_beam": ``beam_size`` hypotheses sampled without
+        replacement, accepted wherever "beam" is, with the same argument rules (see ``decode_stochastic_beam``; it draws one
+        seed from the torch CPU generator); "constrained_sampling" / "constrained_greedy": a sampled / arg-max
         decode under the token automaton ``constraint`` (free running, inference only -- see ``decode_constrained``).
         ``beam_size`` is ignored by the other strategies; ``constraint`` (a token automaton) is required by the constrained
         strategies, optional for "beam" and refused by "sampling" / "greedy".  ``temperature``, ``top_k``, ``top_p``: the
@@ -1160,12 +1163,15 @@ class Seq2SeqBase(nn.Module):
                 return self.decode_constrained(self.encode(source_tokens, dropout=False), constraint,
                                                greedy=decoding_strategy == "constrained_greedy", temperature=temperature,
                                                top_k=top_k, top_p=top_p)
-        if decoding_strategy == "beam":
-            self._check_beam_arguments(target_tokens, beam_size)
+        if decoding_strategy in ("beam", "stochastic_beam"):
+            self._check_beam_arguments(target_tokens, beam_size, decoding_strategy)
             with torch.no_grad():  # (the encoder without its dropout: the search is the same in train() and eval() mode)
-                return self.decode_beam(self.encode(source_tokens, dropout=False), beam_size, constraint=constraint)
+                state = self.encode(source_tokens, dropout=False)
+                if decoding_strategy == "stochastic_beam":
+                    return self.decode_stochastic_beam(state, beam_size, constraint=constraint)
+                return self.decode_beam(state, beam_size, constraint=constraint)
         if constraint is not None:
-            raise ValueError("constraint: only decoding_strategy='beam' decodes under a token automaton")
+            raise ValueError("constraint: only decoding_strategy='beam' / 'stochastic_beam' decode under a token automaton")
         return self.decode(self.encode(source_tokens), target_tokens, decoding_strategy, need_predictions,
                            temperature=temperature, top_k=top_k, top_p=top_p)
 
@@ -1236,11 +1242,15 @@ class Seq2SeqBase(nn.Module):
         if decoding_strategy == "beam":
             self._check_beam_arguments(target_tokens, beam_size)
             return self.decode_beam(state, beam_size, constraint=constraint)
+        if decoding_strategy == "stochastic_beam":
+            self._check_beam_arguments(target_tokens, beam_size, decoding_strategy)
+            return self.decode_stochastic_beam(state, beam_size, seed=seed, constraint=constraint)
         if constraint is not None:
-            raise ValueError("constraint: decoding_strategy='beam', 'constrained_sampling' and 'constrained_greedy' decode under a "
-                             "token automaton; %r does not" % (decoding_strategy,))
+            raise ValueError("constraint: decoding_strategy='beam', 'stochastic_beam', 'constrained_sampling' and "
+                             "'constrained_greedy' decode under a token automaton; %r does not" % (decoding_strategy,))
         if decoding_strategy not in ("sampling", "greedy"):
-            raise ValueError("decoding_strategy must be 'sampling', 'greedy', 'beam', 'constrained_sampling' or 'constrained_greedy'")
+            raise ValueError("decoding_strategy must be 'sampling', 'greedy', 'beam', 'stochastic_beam', 'constrained_sampling' "
+                             "or 'constrained_greedy'")
         pad, bos, eos = self._pad_index, self._start_index, self._end_index
         enc, h, fmask = state["enc"], state["h"], state["fmask"]
         tgt = None
@@ -1359,9 +1369,9 @@ class Seq2SeqBase(nn.Module):
     BEAM_SIZES = (1, 2, 4, 8, 16)
 
     @staticmethod
-    def _check_beam_arguments(target_tokens, beam_size) -> None:
+    def _check_beam_arguments(target_tokens, beam_size, strategy="beam") -> None:
         if target_tokens is not None:
-            raise ValueError("decoding_strategy='beam' is free running: it takes no target_tokens")
+            raise ValueError("decoding_strategy=%r is free running: it takes no target_tokens" % (strategy,))
         if isinstance(beam_size, bool) or not isinstance(beam_size, int) or beam_size not in Seq2SeqBase.BEAM_SIZES:
             raise ValueError("beam_size must be one of %s, got %r" % (Seq2SeqBase.BEAM_SIZES, beam_size))
 
@@ -1382,6 +1392,11 @@ class Seq2SeqBase(nn.Module):
         [n_states] as uint8 numpy arrays -- ``ProgramCompiler.decoding_automaton``).  The same call then gets its tables:
         a hypothesis offers a token only while an accepted completion stays reachable in the steps that remain, so every
         hypothesis with a finite score is accepted by the automaton.  The same keys come back.  ``None``: unconstrained."""
+        return self._beam_launch(state, beam_size, trace, constraint, None)
+
+    def _beam_launch(self, state, beam_size, trace, constraint, stochastic) -> Dict[str, torch.Tensor]:
+        """``decode_beam`` (``stochastic`` None) or ``decode_stochastic_beam`` (``stochastic`` = the seed): one launch of the
+        beam kernel and the trimming of what it returns."""
         self._check_beam_arguments(None, beam_size)
         tables = None
         if constraint is not None:
@@ -1411,29 +1426,65 @@ class Seq2SeqBase(nn.Module):
         enc, h, fmask, w_p, b_p = enc.contiguous(), h.contiguous(), fmask.contiguous(), w_p.contiguous(), b_p.contiguous()
         raw = torch.empty(B, K, T, dtype=torch.long, device=dev)
         scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+        perturbed = torch.empty(B, K, dtype=torch.float32, device=dev) if stochastic is not None else None
         tr = None
         if trace:
             tr = (torch.empty(B, T, K, dtype=torch.int32, device=dev), torch.empty(B, T, K, dtype=torch.int32, device=dev),
                   torch.empty(B, T, K, dtype=torch.float32, device=dev))
+            if stochastic is not None:
+                tr += (torch.empty(B, T, K, dtype=torch.float32, device=dev),)
         if B > 0 and T > 0:
             automaton = (0, 0, 0, 0, 0)  # (null tables: unconstrained)
             if tables is not None:  # (the tables are host arrays: the library checks every entry and passes them by value)
                 automaton = (tables[0].ctypes.data, tables[1].ctypes.data, tables[2].ctypes.data, *tables[1].shape)
-            _hip.check(_hip.lib().pnmn_attn_lstm_beam(
-                etable.data_ptr(), enc.data_ptr(), fmask.data_ptr(), h.data_ptr(), w_c_p.data_ptr(), w_hh_p.data_ptr(),
-                w_p.data_ptr(), b_p.data_ptr(), raw.data_ptr(), scores.data_ptr(),
-                tr[0].data_ptr() if tr else None, tr[1].data_ptr() if tr else None, tr[2].data_ptr() if tr else None,
-                B, T, S, V, Hd, K, self._pad_index, self._unk_index, self._start_index, self._end_index, *automaton,
-                _hip.stream_ptr(dev)), "attn_lstm_beam")
+            args = (etable.data_ptr(), enc.data_ptr(), fmask.data_ptr(), h.data_ptr(), w_c_p.data_ptr(), w_hh_p.data_ptr(),
+                    w_p.data_ptr(), b_p.data_ptr(), raw.data_ptr(), scores.data_ptr(),
+                    tr[0].data_ptr() if tr else None, tr[1].data_ptr() if tr else None, tr[2].data_ptr() if tr else None,
+                    B, T, S, V, Hd, K, self._pad_index, self._unk_index, self._start_index, self._end_index, *automaton)
+            if stochastic is None:
+                _hip.check(_hip.lib().pnmn_attn_lstm_beam(*args, _hip.stream_ptr(dev)), "attn_lstm_beam")
+            else:
+                _hip.check(_hip.lib().pnmn_attn_lstm_beam_stochastic(
+                    *args, perturbed.data_ptr(), tr[3].data_ptr() if tr else None, stochastic, self.sample_row_offset,
+                    _hip.stream_ptr(dev)), "attn_lstm_beam_stochastic")
         beams = self._trim_predictions(raw.view(B * K, T)).view(B, K, T)
         best = beams[:, 0]
         n = (best != self._pad_index).sum(-1).to(scores.dtype)
         # (an empty best hypothesis, n = 0: the sampled path sums no log-probability and returns 0)
         loss = torch.where(n > 0, -scores[:, 0] / (n + 1e-12), torch.zeros_like(n))
         out = {"predictions": best, "loss": loss, "beam_predictions": beams, "beam_log_probabilities": scores}
+        if stochastic is not None:
+            out["beam_perturbed"] = perturbed
         if tr:
             out["beam_trace"] = {"tokens": tr[0], "backpointers": tr[1], "scores": tr[2]}
+            if stochastic is not None:
+                out["beam_trace"]["perturbed"] = tr[3]
         return out
+
+    @torch.no_grad()
+    def decode_stochastic_beam(self, state: Dict[str, torch.Tensor], beam_size: int = 4, seed: Optional[int] = None,
+                               trace: bool = False, constraint=None) -> Dict[str, torch.Tensor]:
+        """Stochastic beam search (Kool, van Hoof and Welling 2019) in ONE launch of the beam kernel's second candidate stage
+        (``pnmn_attn_lstm_beam_stochastic``; the rule is stated in include/probnmn_hip.h): the K hypotheses of a question
+        are an exact sample WITHOUT replacement from the decoder's sequence distribution -- K distinct sequences, in the
+        order a sequential sample would draw them, so ``predictions`` (hypothesis 0) is an ordinary sample.  The
+        distribution is the one the sampling decode draws from: every step's softmax restricted to the tokens that may be
+        offered (never pad / unk / start; with ``constraint``, the automaton's rule, as ``decode_constrained``).
+
+        Returns what ``decode_beam`` returns -- ``beam_predictions`` [B, K, T], ``beam_log_probabilities`` [B, K] (phi, the
+        log-probability under that distribution), ``predictions``, ``loss`` -- and ``beam_perturbed`` [B, K], the perturbed
+        log-probability G of every hypothesis (best first; ``evaluators.without_replacement_weights`` turns the two into
+        importance weights).  A slot left without a sequence (the support is smaller than K) holds -inf in both.
+        ``trace=True``: ``beam_trace`` gains ``"perturbed"``.
+
+        ``seed``: None draws ONE seed from the torch CPU generator, exactly as the sampling decode does, so
+        ``torch.manual_seed`` reproduces a run; the uniform of (question, slot, token, step) depends on the seed and on
+        ``sample_row_offset`` + the question's row only, so a question draws the same hypotheses alone or in a batch.
+        Inference only, no dropout, no graph; the refusals are ``decode_beam``'s and there is no CPU or step-by-step path."""
+        self._check_beam_arguments(None, beam_size)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # CPU generator: no device sync
+        return self._beam_launch(state, beam_size, trace, constraint, int(seed))
 
     # ---- two teacher-forced decodes of a training iteration side by side -------------------------------------------
     def decode_prepare(self, state: Dict[str, torch.Tensor], target_tokens: Optional[torch.LongTensor] = None,
