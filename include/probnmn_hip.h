@@ -391,6 +391,54 @@ int pnmn_hypothesis_posterior(const float* x_logits /* [n_rows][Tx][Vx], may be 
                               int Vz, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Posterior over a question's program hypotheses given its ANSWER (csrc/answer_posterior.hip).  Not in the reference,
+ * which uses p(a | z, image) only to answer from one sampled program (nmn.py:245-269, scripts/inference.py:76-91) and
+ * never to judge the program: the hypotheses of a question reranked by
+ *     score[r] = log_w[r] + w_a log p(a | z_r, image)
+ * from the answer logits of every hypothesis row, the given answer answers[g] of each question and the log-weight a row
+ * has before the answer is seen -- log q(z_r | x), or pnmn_hypothesis_posterior's log_posterior, with which (w_a = 1) the
+ * result is p(z | x, a, image) on the candidate set.  Rows [group_start[g], group_start[g + 1]) are group g's, in that
+ * order, as for pnmn_answer_marginal.
+ *   row r is BASE-USABLE when (valid == NULL or valid[r] != 0) and (log_weight == NULL or log_weight[r] is finite)
+ *   log_w[r]           = log_weight[r] - logsumexp of log_weight over the group's base-usable rows; log_weight == NULL:
+ *                        -log of their number
+ *   log_answer[r]      = (z[a] - max z) - log sum exp(z - max z), z = logits[r], a = answers[g]; written for every covered
+ *                        row, base-usable or not; an answer outside [0, num_answers) is never used as an index:
+ *                        log_answer[r] = -inf
+ *   row_predictions[r] = first arg-max of logits[r]; unknown_index where valid[r] == 0 (pnmn_answer_marginal's rule)
+ *   score[r]           = log_w[r] + w_a * log_answer[r]; when w_a is exactly 0 the answer term is left out entirely -- no
+ *                        0 * -inf is formed -- and log_answer is still reported
+ * Row r is USABLE when it is base-usable and score[r] is finite.  Per group, over its usable rows:
+ *   support[g]          = their number
+ *   log_evidence[g]     = max + log sum exp(score - max), max being the largest usable score; with w_a = 1 it is
+ *                         log p(a | x, image) on the candidate set: pnmn_answer_marginal's log_marginal[g][answers[g]]
+ *   log_posterior[r]    = (score[r] - max) - log sum exp(score - max); -inf for a covered row that is not usable
+ *   best_row[g]         = the absolute index r of the first usable row with the largest score
+ *   consistent_count[g] = number of usable rows whose row_predictions equals answers[g]
+ *   first_consistent[g] = the absolute index of the first such row, -1 when there is none
+ *   support[g] == 0 (no rows, or none usable): log_evidence[g] = -inf, best_row[g] = -1, consistent_count[g] = 0,
+ *                         first_consistent[g] = -1
+ * Group bounds are clamped into [0, n_rows] with end >= start before use, so no group_start reads or writes outside the
+ * arrays; a row that no group covers is not written.  The scores of a group pass through its log_posterior slots, so groups
+ * that share a row (bounds that decrease) get unspecified values -- every other group keeps its own.  A group's outputs
+ * depend only on its own rows in their order: the same bits alone or inside a batch, and from run to run.  One launch, one
+ * wavefront (a 64-thread workgroup) per group, no LDS, no atomics, no wait on another workgroup.
+ * n_groups == 0 returns 0 without a launch.  PNMN_EINVAL, with no launch and no HIP call: n_groups < 0 or n_rows < 0;
+ * num_answers < 1; a null group_start, answers, log_posterior, log_evidence or best_row; a null logits (n_rows > 0); a w_a
+ * that is not finite.  num_answers > 1024: PNMN_ESHAPE.  The checks run in this order: the counts and num_answers < 1; then
+ * the empty case -- n_groups == 0 returns 0 whatever the pointers and w_a are --; then the pointers and w_a; then the shape.
+ * ------------------------------------------------------------------------------------------- */
+int pnmn_answer_posterior(const float* logits /* [n_rows][num_answers] */, const int32_t* valid /* [n_rows], may be NULL */,
+                          const float* log_weight /* [n_rows], may be NULL */, const int64_t* answers /* DEVICE [n_groups] */,
+                          const int32_t* group_start /* DEVICE [n_groups + 1] */, float w_a,
+                          float* log_answer /* [n_rows], may be NULL */, int64_t* row_predictions /* [n_rows], may be NULL */,
+                          float* log_posterior /* [n_rows] */, float* log_evidence /* [n_groups] */,
+                          int32_t* best_row /* [n_groups] */, int32_t* support /* [n_groups], may be NULL */,
+                          int32_t* consistent_count /* [n_groups], may be NULL */,
+                          int32_t* first_consistent /* [n_groups], may be NULL */, int n_groups, int n_rows, int num_answers,
+                          int unknown_index, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Glue of the seq2seq passes (csrc/seqglue.hip): what the reference -- through AllenNLP 0.9.0 -- does with
  * chains of small tensor ops and per-row Python loops, one launch each.
  *

@@ -14,6 +14,9 @@ Stand-alone layout only (when the models are grafted onto the reference's packag
     in the reference either) the answer is the MARGINAL over several programs, sum_z q(z | x) p(a | z, image), with its
     probability and the hypotheses that voted; with ``rerank`` (not in the reference either) the hypotheses are weighted by
     their posterior under the generative model, p(x | z) p(z), from the reconstructor and the prior (``hypothesis_posterior``);
+  * ``infer_programs`` (not in the reference either) asks the reverse question on batches that carry the answer: which of a
+    question's hypotheses explains the question AND its known answer, p(z | x, a, image) over the candidates
+    (``NeuralModuleNetwork.answer_posterior``); ``evaluate_program_inference`` and ``mine_supervision`` are built on it;
   * ``explain`` (not in the reference either) adds to each answer where its program looked: the attention map of every
     step, and that map painted over the question's image (``attention_overlay``).
 Batches are dicts of DEVICE tensors with the reference's keys (a ``PrefetchingLoader`` yields them)."""
@@ -503,14 +506,14 @@ def _queue_hypotheses(program_generator, batch, iteration, copies, beam_size, nu
     return tokens, weights, copied, perturbed
 
 
-def _finish_hypotheses(nmn, image, queued, rerank=None):
-    """Second stage: wait for the copy, keep the valid hypotheses (merged), run the NMN over them and marginalise.
-    ``rerank`` = (question_reconstructor, program_prior, coefficients, questions [B, Tq]) or None: the hypotheses' weights
-    are their posterior under the generative model (``hypothesis_posterior``, the merged generator weight as its ``log_q``)
-    instead of the generator's own.  Returns (``marginal_answers``' dict as host numpy -- reranked: and
-    ``hypothesis_posterior``'s ``"log_reconstruction"``, ``"log_prior"`` and ``"best_row"``; a sample without replacement: and
-    ``"perturbed"`` [R], G of every row's first slot --, programs [R, T], group_start [B + 1])."""
-    tokens, weights, copied, perturbed = queued
+def _awaited_hypotheses(nmn, queued, rerank=None):
+    """What ``_queue_hypotheses`` queued, awaited and grouped: wait for the copy, keep the valid hypotheses (merged:
+    ``group_hypotheses``) and, with ``rerank`` = (question_reconstructor, program_prior, coefficients, questions [B, Tq]),
+    replace their weights by their posterior under the generative model (``hypothesis_posterior``, the merged generator
+    weight as its ``log_q``).  Returns (B, programs [R, T], question_rows [R], log-weights [R] -- host float64, or reranked
+    the device ``"log_posterior"`` --, first_slot [R], reranked ``hypothesis_posterior``'s ``"log_reconstruction"``,
+    ``"log_prior"`` and ``"best_row"`` as device tensors, else ``{}``)."""
+    tokens, weights, copied, _ = queued
     if copied is not None:
         copied.synchronize()
     arr = tokens.cpu().numpy()
@@ -525,6 +528,18 @@ def _finish_hypotheses(nmn, image, queued, rerank=None):
                                          question_rows, log_q=log_weights, weights=coefficients)
         log_weights = posterior["log_posterior"]
         scored = {k: posterior[k] for k in ("log_reconstruction", "log_prior", "best_row")}
+    return B, programs, question_rows, log_weights, first_slot, scored
+
+
+def _finish_hypotheses(nmn, image, queued, rerank=None):
+    """Second stage: wait for the copy, keep the valid hypotheses (merged), run the NMN over them and marginalise.
+    ``rerank`` = (question_reconstructor, program_prior, coefficients, questions [B, Tq]) or None: the hypotheses' weights
+    are their posterior under the generative model (``hypothesis_posterior``, the merged generator weight as its ``log_q``)
+    instead of the generator's own.  Returns (``marginal_answers``' dict as host numpy -- reranked: and
+    ``hypothesis_posterior``'s ``"log_reconstruction"``, ``"log_prior"`` and ``"best_row"``; a sample without replacement: and
+    ``"perturbed"`` [R], G of every row's first slot --, programs [R, T], group_start [B + 1])."""
+    perturbed = queued[3]
+    B, programs, question_rows, log_weights, first_slot, scored = _awaited_hypotheses(nmn, queued, rerank)
     out = nmn.marginal_answers(image, torch.from_numpy(programs), question_rows, log_weights)
     out.update(scored)
     if perturbed is not None:
@@ -853,6 +868,301 @@ def evaluate_marginal_answer_accuracy(program_generator, nmn, batches: Iterable[
     if coefficients is not None:
         result["map_answer_accuracy"] = totals["map"] / n
     return result
+
+
+def _program_inference_options(beam_size, num_programs, constrained, constrained_sampling, without_replacement, sample_weights,
+                               answer_weight, rerank, question_reconstructor, program_prior, rerank_weights):
+    """The argument rules of ``infer_programs`` and what is built on it, checked before any model is touched: (the weights a
+    without-replacement sample hands on or None, the rerank coefficients or None, ``answer_weight`` as a finite float)."""
+    import math
+
+    _marginal_options(beam_size, beam_size is not None, num_programs, False)
+    draw = _without_replacement_options(without_replacement, sample_weights, beam_size, num_programs)
+    coefficients = _rerank_options(rerank, beam_size, num_programs, False, question_reconstructor, program_prior, rerank_weights)
+    if beam_size is None and num_programs is None:
+        raise ValueError("give the hypotheses: beam_size (a beam search) or num_programs (samples)")
+    if constrained and beam_size is None:
+        raise ValueError("constrained=True constrains the beam search: give a beam_size")
+    if constrained_sampling and beam_size is not None:
+        raise ValueError("constrained_sampling=True samples the programs; with beam_size they are searched (constrained=True)")
+    try:
+        w_a = float(answer_weight)
+    except (TypeError, ValueError):
+        raise ValueError("answer_weight must be a finite number, got %r" % (answer_weight,))
+    if isinstance(answer_weight, bool) or not math.isfinite(w_a):
+        raise ValueError("answer_weight must be a finite number, got %r" % (answer_weight,))
+    return draw, coefficients, w_a
+
+
+# the options of ``infer_programs`` and their defaults (what ``mine_supervision`` hands on)
+_INFERENCE_OPTIONS = dict(beam_size=None, num_programs=None, constrained=False, constrained_sampling=False, without_replacement=False,
+                          sample_weights="probability", answer_weight=1.0, rerank=False, question_reconstructor=None,
+                          program_prior=None, rerank_weights=(1.0, 1.0, 0.0))
+
+
+def _group_log_softmax(values, group_of, n_groups):
+    """Host numpy, no loop over the groups: ``values`` [R] float64 normalised over the finite entries of each group
+    (``group_of`` [R], non-decreasing, in 0 .. n_groups - 1) -- -inf for an entry that is not finite -- and per group the
+    index of its first largest finite entry (-1 for a group without one)."""
+    values = np.asarray(values, dtype=np.float64)
+    ok = np.isfinite(values)
+    kept = np.where(ok, values, -np.inf)
+    top = np.full(n_groups, -np.inf)
+    np.maximum.at(top, group_of, kept)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        shifted = np.where(ok, kept - top[group_of], -np.inf)
+        log_norm = np.log(np.bincount(group_of, weights=np.exp(shifted), minlength=n_groups))
+        out = np.where(ok, shifted - log_norm[group_of], -np.inf)
+    first = np.full(n_groups, values.size, np.int64)
+    leads = np.nonzero(ok & (kept == top[group_of]))[0]
+    np.minimum.at(first, group_of[leads], leads)
+    return out, np.where(first < values.size, first, -1)
+
+
+def _inferred_batches(program_generator, nmn, batches, beam_size, num_programs, constrained, constrained_sampling, draw,
+                      coefficients, w_a, question_reconstructor, program_prior, num_batches=None):
+    """The loop under ``infer_programs``, ``evaluate_program_inference`` and ``mine_supervision``: a generator of (batch, out,
+    programs [R, T], group_start [B + 1]) per input batch, pipelined as ``predict_answers`` is -- batch i + 1's generator pass
+    is queued before batch i's hypotheses are awaited.  ``out``: ``NeuralModuleNetwork.answer_posterior``'s dict as host numpy,
+    and ``"log_prior_weight"`` [R] (the weight of a row before the answer, normalised over its question's rows),
+    ``"prior_best_row"`` [B] (the MAP row without the answer term, -1 where there is none), ``"answers"`` [B] and, reranked,
+    ``hypothesis_posterior``'s ``"log_reconstruction"`` and ``"log_prior"``.  The generator and the NMN are in ``eval()`` while
+    the loop runs and get their state back when it ends, is closed or raises."""
+    was_training = (program_generator.training, nmn.training)
+    program_generator.eval()
+    nmn.eval()
+    try:
+        constraint = None
+        if constrained or constrained_sampling:
+            exclude = [getattr(program_generator, name) for name in ("_pad_index", "_unk_index", "_start_index", "_end_index")]
+            constraint = nmn.engine.compiler.decoding_automaton(exclude=exclude)
+        copies = _HostCopies()
+
+        def finish(batch, queued):
+            reranked = None if coefficients is None else (question_reconstructor, program_prior, coefficients, batch["question"])
+            B, programs, question_rows, base, _, scored = _awaited_hypotheses(nmn, queued, reranked)
+            out = nmn.answer_posterior(batch["image"], torch.from_numpy(programs), question_rows, batch["answer"], base, w_a)
+            out = {k: v.cpu().numpy() for k, v in out.items()}
+            start = np.searchsorted(question_rows, np.arange(B + 1))
+            if reranked is not None:  # (hypothesis_posterior's log_posterior is normalised over the question's rows already)
+                out.update({k: scored[k].cpu().numpy() for k in ("log_reconstruction", "log_prior")})
+                out["log_prior_weight"] = base.cpu().numpy().astype(np.float64)
+                out["prior_best_row"] = scored["best_row"].cpu().numpy().astype(np.int64)
+            else:
+                out["log_prior_weight"], out["prior_best_row"] = _group_log_softmax(base, question_rows, B)
+            out["answers"] = batch["answer"].cpu().numpy()
+            return batch, out, programs, start
+
+        pending = None
+        for iteration, batch in enumerate(batches):
+            queued = _queue_hypotheses(program_generator, batch, iteration, copies, beam_size, num_programs, constraint,
+                                       constrained_sampling, {}, batch["image"].is_cuda, draw)
+            if pending is not None:
+                yield finish(*pending)
+            pending = (batch, queued)
+            if num_batches is not None and iteration > num_batches:
+                break
+        if pending is not None:
+            yield finish(*pending)
+    finally:
+        program_generator.train(was_training[0])
+        nmn.train(was_training[1])
+
+
+@torch.no_grad()
+def infer_programs(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary, beam_size: Optional[int] = None,
+                   num_programs: Optional[int] = None, constrained: bool = False, constrained_sampling: bool = False,
+                   without_replacement: bool = False, sample_weights: str = "probability", answer_weight: float = 1.0,
+                   rerank: bool = False, question_reconstructor=None, program_prior=None,
+                   rerank_weights=(1.0, 1.0, 0.0)) -> List[Dict[str, Any]]:
+    """Which program explains a question AND its known answer (not in the reference, which uses p(a | z, image) only to answer):
+    the posterior over each question's program hypotheses given the answer, p(z | x, a, image) ~ w(z) p(a | z, image)^answer_weight,
+    on batches with ``"question"``, ``"image"`` and ``"answer"``, one record per question.
+
+    The hypotheses are those of ``predict_answers`` with the same options and rules: the ``beam_size`` hypotheses of a beam
+    search (``constrained``: under the validity rule) or ``num_programs`` sampled ones (``constrained_sampling``;
+    ``without_replacement`` / ``sample_weights``: one stochastic beam search's), invalid ones dropped and identical ones merged
+    (``group_hypotheses``); one of the two is required.  The weight w(z) of a hypothesis before the answer is seen is its merged
+    generator weight; with ``rerank`` (``question_reconstructor``, ``program_prior``, ``rerank_weights``: as for
+    ``predict_answers``) it is ``hypothesis_posterior``'s, so that the default coefficients give the posterior under the whole
+    generative model, p(x | z) p(z) p(a | z, image)^answer_weight normalised over the candidates.  ``answer_weight`` is a finite
+    number; 0 leaves the answer out.  A wrong combination is a ``ValueError`` before any model is touched.
+
+    A record holds ``"question_index"``, ``"answer"`` (the GIVEN one, as a string), ``"support"`` (hypotheses that count),
+    ``"log_answer_evidence"`` (log of the summed scores: with ``answer_weight`` 1, log p(a | x, image) on the candidate set; -inf
+    without support), ``"consistent_count"`` (counting hypotheses whose own answer is the given one), ``"map_program"`` and
+    ``"map_answer"`` (the hypothesis with the largest posterior and its own answer; ``[]`` and ``@@UNKNOWN@@`` when there is
+    none), ``"map_consistent"``, ``"first_consistent_rank"`` (position of the first consistent hypothesis among the question's
+    hypotheses, None when there is none) and the ``"hypotheses"`` in group order: ``{"program", "prior_weight"`` (its share
+    before the answer) ``, "weight"`` (its posterior share) ``, "log_answer_likelihood", "answer"`` (its own) ``, "consistent"}``;
+    reranked, each also names its ``"log_reconstruction"`` and ``"log_prior"`` (None for a model that was not given).  The
+    models are left in the ``train()`` / ``eval()`` state they were in."""
+    draw, coefficients, w_a = _program_inference_options(beam_size, num_programs, constrained, constrained_sampling,
+                                                         without_replacement, sample_weights, answer_weight, rerank,
+                                                         question_reconstructor, program_prior, rerank_weights)
+    pad = getattr(program_generator, "_pad_index", 0)
+    records: List[Dict[str, Any]] = []
+
+    def token_strings(row):
+        return [vocabulary.get_token_from_index(int(t), namespace="programs") for t in row if t != pad]
+
+    def answer_string(a):
+        return vocabulary.get_token_from_index(int(a), namespace="answers")
+
+    for batch, out, programs, start in _inferred_batches(program_generator, nmn, batches, beam_size, num_programs, constrained,
+                                                         constrained_sampling, draw, coefficients, w_a, question_reconstructor,
+                                                         program_prior):
+        B = len(start) - 1
+        index = batch["question_index"].cpu().tolist() if "question_index" in batch else range(len(records), len(records) + B)
+        for i, qi in enumerate(index):
+            given, best, first = int(out["answers"][i]), int(out["best_row"][i]), int(out["first_consistent_row"][i])
+            hypotheses = []
+            for r in range(start[i], start[i + 1]):
+                own, counts = int(out["hypothesis_predictions"][r]), bool(np.isfinite(out["log_posterior"][r]))
+                h = {"program": token_strings(programs[r]), "prior_weight": float(np.exp(out["log_prior_weight"][r])),
+                     "weight": float(np.exp(out["log_posterior"][r])),
+                     "log_answer_likelihood": float(out["log_answer_likelihood"][r]), "answer": answer_string(own),
+                     "consistent": counts and own == given}
+                if coefficients is not None:
+                    h["log_reconstruction"] = None if question_reconstructor is None else float(out["log_reconstruction"][r])
+                    h["log_prior"] = None if program_prior is None else float(out["log_prior"][r])
+                hypotheses.append(h)
+            map_answer = int(out["hypothesis_predictions"][best]) if best >= 0 else nmn._unknown_answer
+            records.append({
+                "question_index": int(qi), "answer": answer_string(given), "support": int(out["support"][i]),
+                "log_answer_evidence": float(out["log_evidence"][i]), "consistent_count": int(out["consistent_count"][i]),
+                "map_program": token_strings(programs[best]) if best >= 0 else [], "map_answer": answer_string(map_answer),
+                "map_consistent": best >= 0 and map_answer == given,
+                "first_consistent_rank": first - int(start[i]) if first >= 0 else None, "hypotheses": hypotheses})
+    return records
+
+
+@torch.no_grad()
+def evaluate_program_inference(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary=None,
+                               beam_size: Optional[int] = None, num_programs: Optional[int] = None, constrained: bool = False,
+                               constrained_sampling: bool = False, without_replacement: bool = False,
+                               sample_weights: str = "probability", answer_weight: float = 1.0, rerank: bool = False,
+                               question_reconstructor=None, program_prior=None, rerank_weights=(1.0, 1.0, 0.0),
+                               num_batches: Optional[int] = None) -> Dict[str, float]:
+    """Was a program that answers correctly among the hypotheses, and does the answer posterior find it?  The options are
+    ``infer_programs``'; ``vocabulary`` is not needed and only kept for symmetry; ``num_batches`` stops the loop as
+    ``Evaluator.evaluate`` does.  Returns, as fractions of the questions, ``"answer_recall"`` (at least one counting hypothesis
+    whose own answer is the given one), ``"map_consistency"`` (the MAP hypothesis under the answer posterior answers correctly)
+    and ``"proposal_consistency"`` (the question's FIRST hypothesis does: ``evaluate_marginal_answer_accuracy``'s
+    ``"single_answer_accuracy"``); and ``"average_support"``, ``"average_consistent"`` and ``"average_rows_per_question"`` (NMN
+    rows run per question).  Where batches carry ``"program"``, also ``"program_accuracy_with_answer"`` and
+    ``"program_accuracy_without_answer"``: the fraction of those questions whose MAP program -- with the answer term, and by the
+    weights before it -- is the annotated one, token for token, padding, @start@ and @end@ left out."""
+    draw, coefficients, w_a = _program_inference_options(beam_size, num_programs, constrained, constrained_sampling,
+                                                         without_replacement, sample_weights, answer_weight, rerank,
+                                                         question_reconstructor, program_prior, rerank_weights)
+    skip = [getattr(program_generator, name, default) for name, default in (("_pad_index", 0), ("_start_index", 2), ("_end_index", 3))]
+    totals = {"questions": 0, "recall": 0, "map": 0, "proposal": 0, "support": 0, "consistent": 0, "rows": 0, "annotated": 0,
+              "with": 0, "without": 0}
+
+    def same_program(row, annotated):
+        return [t for t in row.tolist() if t not in skip] == [t for t in annotated.tolist() if t not in skip]
+
+    for batch, out, programs, start in _inferred_batches(program_generator, nmn, batches, beam_size, num_programs, constrained,
+                                                         constrained_sampling, draw, coefficients, w_a, question_reconstructor,
+                                                         program_prior, num_batches):
+        answers, best, own = out["answers"], out["best_row"], out["hypothesis_predictions"]
+        has = start[1:] > start[:-1]
+        by_map = np.full(answers.shape[0], nmn._unknown_answer, np.int64)
+        by_map[best >= 0] = own[best[best >= 0]]
+        proposal = np.full(answers.shape[0], nmn._unknown_answer, np.int64)
+        proposal[has] = own[start[:-1][has]]
+        totals["questions"] += answers.shape[0]
+        totals["recall"] += int((out["consistent_count"] > 0).sum())
+        totals["map"] += int(((by_map == answers) & (best >= 0)).sum())
+        totals["proposal"] += int((proposal == answers).sum())
+        totals["support"] += int(out["support"].sum())
+        totals["consistent"] += int(out["consistent_count"].sum())
+        totals["rows"] += int(programs.shape[0])
+        if "program" in batch:
+            annotated = batch["program"].cpu().numpy()
+            totals["annotated"] += annotated.shape[0]
+            for i in range(annotated.shape[0]):
+                totals["with"] += int(best[i] >= 0 and same_program(programs[best[i]], annotated[i]))
+                before = int(out["prior_best_row"][i])
+                totals["without"] += int(before >= 0 and same_program(programs[before], annotated[i]))
+    n = max(totals["questions"], 1)
+    result = {"answer_recall": totals["recall"] / n, "map_consistency": totals["map"] / n,
+              "proposal_consistency": totals["proposal"] / n, "average_support": totals["support"] / n,
+              "average_consistent": totals["consistent"] / n, "average_rows_per_question": totals["rows"] / n}
+    if totals["annotated"]:
+        result["program_accuracy_with_answer"] = totals["with"] / totals["annotated"]
+        result["program_accuracy_without_answer"] = totals["without"] / totals["annotated"]
+    return result
+
+
+def mine_supervision(program_generator, nmn, batches: Iterable[Dict[str, torch.Tensor]], vocabulary=None, min_posterior: float = 0.9,
+                     require_consistent: bool = True, **options):
+    """Pseudo-supervision for the questions without a program annotation: programs that explain the question and answer it
+    correctly.  A generator over ``batches`` (``"question"``, ``"image"``, ``"answer"``; ``"program"`` [B, T] and
+    ``"supervision"`` [B] where some rows are annotated); ``options`` are ``infer_programs``' own, checked here -- before any
+    model is touched and before the first batch is asked for.  Each batch is yielded as a shallow copy whose ``"program"`` and
+    ``"supervision"`` also cover the mined rows, plus ``"mined"`` (bool [B], beside ``"supervision"``):
+      * a row that is already supervised keeps its program bit for bit and is not mined;
+      * an unsupervised row gets its MAP program under the answer posterior when that program's posterior share is at least
+        ``min_posterior`` and -- with ``require_consistent`` -- its own answer is the given one: in the layout of the
+        annotated programs (no @start@, no @end@, padding behind), padded to ``batch["program"].size(1)``; a longer one is not
+        mined.  A batch without ``"program"`` gets one as wide as the decoded hypotheses; without ``"supervision"`` none of
+        its rows counts as supervised.
+    The input tensors are not written.  The generator and the NMN are in ``eval()`` while a batch is worked on and in the state
+    they were in whenever the caller holds a batch and when the loop ends; batch i + 1's generator pass is queued before batch i
+    is yielded.  ``vocabulary`` is not needed and only kept for symmetry."""
+    unknown = sorted(set(options) - set(_INFERENCE_OPTIONS))
+    if unknown:
+        raise TypeError("mine_supervision() got options that infer_programs does not take: %s" % ", ".join(unknown))
+    o = dict(_INFERENCE_OPTIONS, **options)
+    draw, coefficients, w_a = _program_inference_options(
+        o["beam_size"], o["num_programs"], o["constrained"], o["constrained_sampling"], o["without_replacement"], o["sample_weights"],
+        o["answer_weight"], o["rerank"], o["question_reconstructor"], o["program_prior"], o["rerank_weights"])
+    pad = getattr(program_generator, "_pad_index", 0)
+    skip = (pad, getattr(program_generator, "_start_index", 2), getattr(program_generator, "_end_index", 3))
+
+    @torch.no_grad()
+    def mined_batches():
+        was_training = (program_generator.training, nmn.training)
+        for batch, out, programs, start in _inferred_batches(program_generator, nmn, batches, o["beam_size"], o["num_programs"],
+                                                             o["constrained"], o["constrained_sampling"], draw, coefficients, w_a,
+                                                             o["question_reconstructor"], o["program_prior"]):
+            B = len(start) - 1
+            if "program" in batch:
+                program = batch["program"].clone()
+            else:
+                program = torch.full((B, programs.shape[1]), pad, dtype=torch.long, device=batch["question"].device)
+            if "supervision" in batch:
+                supervision = batch["supervision"].clone()
+            else:
+                supervision = torch.zeros(B, dtype=torch.long, device=batch["question"].device)
+            supervised = supervision.cpu().numpy() != 0
+            width = int(program.size(1))
+            at, rows = [], []
+            for i in np.nonzero(~supervised)[0].tolist():
+                best = int(out["best_row"][i])
+                if best < 0 or not float(np.exp(out["log_posterior"][best])) >= min_posterior:
+                    continue
+                if require_consistent and int(out["hypothesis_predictions"][best]) != int(out["answers"][i]):
+                    continue
+                tokens = [t for t in programs[best].tolist() if t not in skip]
+                if len(tokens) <= width:
+                    at.append(i)
+                    rows.append(tokens + [pad] * (width - len(tokens)))
+            mined = torch.zeros(B, dtype=torch.bool)
+            if at:
+                where = torch.tensor(at, dtype=torch.long)
+                mined[where] = True
+                program[where.to(program.device)] = torch.tensor(rows, dtype=program.dtype).to(program.device)
+                supervision[where.to(supervision.device)] = 1
+            result = dict(batch)
+            result.update(program=program, supervision=supervision, mined=mined.to(supervision.device))
+            program_generator.train(was_training[0]), nmn.train(was_training[1])
+            yield result
+            program_generator.eval(), nmn.eval()
+
+    return mined_batches()
 
 
 @torch.no_grad()

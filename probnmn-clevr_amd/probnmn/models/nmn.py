@@ -416,25 +416,11 @@ class NeuralModuleNetwork(nn.Module):
             output_dict["metrics"] = self.get_metrics(reset=True)
         return output_dict
 
-    @torch.no_grad()
-    def marginal_answers(self, features, programs: torch.Tensor, question_rows, log_weights=None, max_rows: int = 1024):
-        """The answer of every question from SEVERAL programs: p(a | x, image) = sum_z q(z | x) p(a | z, image) over the
-        hypotheses given for it (not in the reference, which answers from one program: nmn.py:245-269).  Evaluation only,
-        no gradient.
-
-        ``features``: the G questions' feature maps -- an NCHW or ``channels_last`` tensor, or a ``ResidentRows`` batch.
-        ``programs`` [R, T] (host or device): the hypotheses.  ``question_rows`` [R], non-decreasing, in 0 .. G - 1:
-        hypothesis r belongs to question ``question_rows[r]``; a question may have none.  ``log_weights`` [R]:
-        unnormalised log q(z | x) of each hypothesis (None: uniform); the weights are renormalised over the hypotheses of
-        a question that are valid programs and have a finite weight.
-
-        The NMN runs over the R hypothesis rows in passes of at most ``max_rows`` (the engine has ONE activation arena),
-        reading each row's feature map where it lies (``rows=`` / ``ResidentRows.subset``: nothing is gathered, but the
-        stem runs once per hypothesis row, not once per question); then ONE ``pnmn_answer_marginal`` launch.
-
-        Returns ``"predictions"`` int64 [G] (@@UNKNOWN@@ where no hypothesis counts), ``"log_probabilities"`` fp32 [G, A]
-        (-inf there), ``"hypothesis_predictions"`` int64 [R] (each hypothesis's own answer), ``"hypothesis_weights"``
-        fp32 [R] (0 for one that does not count) and ``"support"`` int32 [G] (how many count)."""
+    def _hypothesis_logits(self, features, programs: torch.Tensor, question_rows, max_rows: int):
+        """The row loop of ``marginal_answers`` and ``answer_posterior``: their argument checks, then the NMN over the R
+        hypothesis rows in passes of at most ``max_rows``, each row reading its question's feature map where it lies
+        (``rows=`` / ``ResidentRows.subset``).  Returns (device, G, R, A, question_rows as host int64 [R], answer logits
+        fp32 [R, A], validity int32 [R] -- both on the device)."""
         import numpy as np
 
         from probnmn import _hip
@@ -463,6 +449,32 @@ class NeuralModuleNetwork(nn.Module):
             else:
                 trunk = self.forward_trunk(features, programs[lo:hi], rows=rows_dev[lo:hi])
             logits[lo:hi], _, valid[lo:hi] = self._answer_logits(trunk)
+        return dev, G, R, A, qrows, logits, valid
+
+    @torch.no_grad()
+    def marginal_answers(self, features, programs: torch.Tensor, question_rows, log_weights=None, max_rows: int = 1024):
+        """The answer of every question from SEVERAL programs: p(a | x, image) = sum_z q(z | x) p(a | z, image) over the
+        hypotheses given for it (not in the reference, which answers from one program: nmn.py:245-269).  Evaluation only,
+        no gradient.
+
+        ``features``: the G questions' feature maps -- an NCHW or ``channels_last`` tensor, or a ``ResidentRows`` batch.
+        ``programs`` [R, T] (host or device): the hypotheses.  ``question_rows`` [R], non-decreasing, in 0 .. G - 1:
+        hypothesis r belongs to question ``question_rows[r]``; a question may have none.  ``log_weights`` [R]:
+        unnormalised log q(z | x) of each hypothesis (None: uniform); the weights are renormalised over the hypotheses of
+        a question that are valid programs and have a finite weight.
+
+        The NMN runs over the R hypothesis rows in passes of at most ``max_rows`` (the engine has ONE activation arena),
+        reading each row's feature map where it lies (``rows=`` / ``ResidentRows.subset``: nothing is gathered, but the
+        stem runs once per hypothesis row, not once per question); then ONE ``pnmn_answer_marginal`` launch.
+
+        Returns ``"predictions"`` int64 [G] (@@UNKNOWN@@ where no hypothesis counts), ``"log_probabilities"`` fp32 [G, A]
+        (-inf there), ``"hypothesis_predictions"`` int64 [R] (each hypothesis's own answer), ``"hypothesis_weights"``
+        fp32 [R] (0 for one that does not count) and ``"support"`` int32 [G] (how many count)."""
+        import numpy as np
+
+        from probnmn import _hip
+
+        dev, G, R, A, qrows, logits, valid = self._hypothesis_logits(features, programs, question_rows, max_rows)
         weights = None
         if log_weights is not None:
             weights = torch.as_tensor(log_weights).detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -479,6 +491,74 @@ class NeuralModuleNetwork(nn.Module):
             out["log_probabilities"].data_ptr(), out["predictions"].data_ptr(), out["hypothesis_predictions"].data_ptr(),
             out["hypothesis_weights"].data_ptr(), out["support"].data_ptr(), G, R, A, self._unknown_answer,
             _hip.stream_ptr(dev)), "answer_marginal")
+        return out
+
+    @torch.no_grad()
+    def answer_posterior(self, features, programs: torch.Tensor, question_rows, answers, log_weights=None,
+                         answer_weight: float = 1.0, max_rows: int = 1024):
+        """The posterior over every question's program hypotheses GIVEN ITS ANSWER (not in the reference, which uses
+        p(a | z, image) to answer from one program and never to judge the program):
+            log p(z_r | x, a, image) = log w_r + answer_weight * log p(a | z_r, image) - log of the sum over the question's rows
+        with w_r the renormalised weight a hypothesis has before the answer is seen.  Inference only, no gradient.
+
+        ``features``, ``programs`` [R, T], ``question_rows`` [R], ``max_rows``: as for ``marginal_answers``.  ``answers`` [G]
+        (host or device, int64): the given answer of each question; one that is no index into the answers rules every
+        hypothesis out (unless ``answer_weight`` is 0).  ``log_weights`` [R]: unnormalised log q(z | x) of each hypothesis, or
+        ``hypothesis_posterior``'s ``"log_posterior"`` -- with which, and ``answer_weight`` 1, the result is the posterior
+        under the whole generative model p(z) p(x | z) p(a | z, image) on the candidate set -- (None: uniform), renormalised
+        over the hypotheses of a question that are valid programs and have a finite weight.  ``answer_weight``: a finite
+        number; exactly 0 leaves the answer term out.
+
+        The NMN runs over the R hypothesis rows exactly as in ``marginal_answers`` (the stem runs once per hypothesis row);
+        then ONE ``pnmn_answer_posterior`` launch (the rule: include/probnmn_hip.h).  No metric moves, and the ``train()`` /
+        ``eval()`` state is not touched.
+
+        Returns device tensors: ``"log_answer_likelihood"`` fp32 [R] (log p(a | z_r, image), of every row), ``"log_posterior"``
+        fp32 [R] (-inf for a hypothesis that does not count: an invalid program, a weight or a score that is not finite),
+        ``"hypothesis_predictions"`` int64 [R] (each hypothesis's own answer; @@UNKNOWN@@ for an invalid program);
+        ``"log_evidence"`` fp32 [G] (with ``answer_weight`` 1: log p(a | x, image) on the candidate set; -inf where no
+        hypothesis counts), ``"best_row"`` int32 [G] (the MAP hypothesis's row, first of equals; -1 there),
+        ``"first_consistent_row"`` int32 [G] (the first counting hypothesis whose own answer is the given one; -1 when there
+        is none), ``"consistent_count"`` int32 [G] (how many there are) and ``"support"`` int32 [G] (how many count)."""
+        import math
+
+        import numpy as np
+
+        from probnmn import _hip
+
+        try:
+            w_a = float(answer_weight)
+        except (TypeError, ValueError):
+            raise ValueError("answer_weight must be a finite number, got %r" % (answer_weight,))
+        if not math.isfinite(w_a):
+            raise ValueError("answer_weight must be a finite number, got %r" % (answer_weight,))
+        given = torch.as_tensor(answers).detach()
+        if given.dim() != 1 or given.size(0) != int(features.size(0)) or given.dtype.is_floating_point or given.dtype == torch.bool:
+            raise ValueError("answers int64 [%d]; got %s %s" % (int(features.size(0)), given.dtype, tuple(given.shape)))
+        dev, G, R, A, qrows, logits, valid = self._hypothesis_logits(features, programs, question_rows, max_rows)
+        weights = None
+        if log_weights is not None:
+            weights = torch.as_tensor(log_weights).detach().to(device=dev, dtype=torch.float32).contiguous()
+            if tuple(weights.shape) != (R,):
+                raise ValueError("log_weights [%d]; got %s" % (R, tuple(weights.shape)))
+        given = given.to(device=dev, dtype=torch.long).contiguous()
+        group_start = _hip.small_to_device(np.searchsorted(qrows, np.arange(G + 1)).tolist(), torch.int32, dev)
+        f, i = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        out = {"log_answer_likelihood": torch.empty(R, **f), "log_posterior": torch.empty(R, **f),
+               "hypothesis_predictions": torch.empty(R, dtype=torch.long, device=dev), "log_evidence": torch.empty(G, **f),
+               "best_row": torch.empty(G, **i), "first_consistent_row": torch.empty(G, **i),
+               "consistent_count": torch.empty(G, **i), "support": torch.empty(G, **i)}
+        if R == 0 or G == 0:  # (no row anywhere: what the kernel writes for a group without rows)
+            out["log_evidence"].fill_(-float("inf"))
+            out["best_row"].fill_(-1), out["first_consistent_row"].fill_(-1)
+            out["consistent_count"].zero_(), out["support"].zero_()
+            return out
+        _hip.check(_hip.lib().pnmn_answer_posterior(
+            logits.data_ptr(), valid.data_ptr(), 0 if weights is None else weights.data_ptr(), given.data_ptr(),
+            group_start.data_ptr(), w_a, out["log_answer_likelihood"].data_ptr(), out["hypothesis_predictions"].data_ptr(),
+            out["log_posterior"].data_ptr(), out["log_evidence"].data_ptr(), out["best_row"].data_ptr(), out["support"].data_ptr(),
+            out["consistent_count"].data_ptr(), out["first_consistent_row"].data_ptr(), G, R, A, self._unknown_answer,
+            _hip.stream_ptr(dev)), "answer_posterior")
         return out
 
     def begin(self, features: torch.Tensor, rows: Optional[torch.Tensor] = None):
