@@ -14,15 +14,13 @@
 //               one wave in a fixed order, so which wave took it cannot change the bits.  (The work is latency: a row is a
 //               chain of dependent wave reductions.  Measured at 256 groups x 8 rows with the CLEVR shapes: four waves and one
 //               step at a time 115 us, four steps at a time 64 us, eight waves and eight steps 38 us.)
-//   lanes       run over the vocabulary: lane l holds columns l, l + 64, ... (NPER = ceil(V / 64) registers per step), so a
-//               step's logits are one coalesced segment
+//   lanes       run over the vocabulary (hypothesis_group.h: the column layout, the group bounds, the wave reductions), so
+//               a step's logits are one coalesced segment
 //   steps       a row's tokens are read 64 at a time, one per lane; the scored ones form a wave-uniform bit set, so padding
 //               costs nothing, and the rest is taken U at a time (8 for V <= 128, 4 / 2 / 1 up to 256 / 512 / 1024): their butterflies
 //               overlap, and the next U steps' logits are loaded before these are reduced
 //   score       the wave's lane 0 writes score[r] into log_posterior[r]; ONE __syncthreads(); wave 0 then sweeps the group's
-//               scores (64 at a time): the usable rows, the largest score and its first row; the sum of exp(score - largest);
-//               log_posterior[r] = (score[r] - largest) - log(sum) over the slots the scores were in
-// Wave reductions are xor butterflies: every lane ends with the same bits, in an order that depends on nothing but the lane.
+//               scores (64 at a time): the usable rows, the largest score and its first row; then score_normaliser()
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -30,13 +28,14 @@
 #include <algorithm>
 
 #include "../../include/probnmn_hip.h"
+#include "hypothesis_group.h"
 
 namespace {
 
+using namespace pnmn::hypothesis;
+
 constexpr int THREADS = 512;
-constexpr int WAVE = 64;
 constexpr int WAVES = THREADS / WAVE;
-constexpr int MAX_VOCAB = 1024;  // NPER <= 16 registers per step and lane
 
 struct Term {  // one likelihood term: teacher-forced logits and the tokens they score
     const float* logits;    // [n_rows][T][V], null: the term is not computed
@@ -60,42 +59,6 @@ struct PosteriorArgs {
     int n_groups, n_rows;
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) v += __shfl_xor(v, d, WAVE);
-    return v;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) v += __shfl_xor(v, d, WAVE);
-    return v;
-}
-
-// the largest value and the lowest index that holds it (the first maximum), in every lane
-__device__ __forceinline__ void wave_argmax(float& v, int& i) {
-#pragma unroll
-    for (int d = 1; d < WAVE; d <<= 1) {
-        const float ov = __shfl_xor(v, d, WAVE);
-        const int oi = __shfl_xor(i, d, WAVE);
-        if (ov > v || (ov == v && oi < i)) {
-            v = ov;
-            i = oi;
-        }
-    }
-}
-
-__device__ __forceinline__ bool finite(float x) { return fabsf(x) < INFINITY; }  // (false for a NaN)
-
-template <int NPER>
-__device__ __forceinline__ void load_step(const float* __restrict__ step, int V, int lane, float (&z)[NPER]) {
-#pragma unroll
-    for (int k = 0; k < NPER; ++k) {
-        const int v = lane + WAVE * k;
-        z[k] = v < V ? step[v] : -INFINITY;
-    }
-}
-
 // Up to U scored steps taken off the (wave-uniform) set `steps` in ascending order, their logits requested: step[u] = the
 // step's index within its block of 64 (-1: none), z[u] = its logits.
 template <int NPER, int U>
@@ -106,7 +69,7 @@ __device__ __forceinline__ void take_steps(uint64_t& steps, const float* __restr
         if (steps) {
             step[u] = __ffsll((unsigned long long)steps) - 1;
             steps &= steps - 1;
-            load_step<NPER>(block + (size_t)step[u] * V, V, lane, z[u]);
+            load_columns<NPER>(block + (size_t)step[u] * V, V, lane, z[u]);
         } else {
             step[u] = -1;
 #pragma unroll
@@ -163,15 +126,10 @@ __device__ float row_log_likelihood(const Term& k, int r, int lane) {
             for (int u = 0; u < U; ++u) {
                 // (an empty slot: step 0's token stands in, its result is not used)
                 const int token = __builtin_amdgcn_readlane(mine, step[u] >= 0 ? step[u] : 0);
-                const int reg = token >> 6;
-                float held = 0.f;
+                at[u] = lane_held<NPER>(z[u], token);
                 se[u] = 0.f;
 #pragma unroll
-                for (int j = 0; j < NPER; ++j) {
-                    se[u] += expf(z[u][j] - top[u]);  // (columns beyond V hold -inf: exp gives 0)
-                    if (j == reg) held = z[u][j];
-                }
-                at[u] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(held), token & (WAVE - 1)));
+                for (int j = 0; j < NPER; ++j) se[u] += expf(z[u][j] - top[u]);  // (columns beyond V hold -inf: exp gives 0)
             }
 #pragma unroll
             for (int d = 1; d < WAVE; d <<= 1)
@@ -191,9 +149,8 @@ __global__ __launch_bounds__(THREADS) void hypothesis_posterior_kernel(const Pos
     const int lane = threadIdx.x & (WAVE - 1);
     const int wave = threadIdx.x >> 6;
     const int g = blockIdx.x;
-    // the group's rows, clamped into the arrays whatever group_start says
-    const int start = min(max(p.group_start[g], 0), p.n_rows);
-    const int end = max(min(max(p.group_start[g + 1], 0), p.n_rows), start);
+    const Rows rows = group_rows(p.group_start, g, p.n_rows);
+    const int start = rows.start, end = rows.end;
 
     // ---- every wave: the likelihood terms and the score of its rows ----
     for (int r = start + wave; r < end; r += WAVES) {
@@ -226,31 +183,12 @@ __global__ __launch_bounds__(THREADS) void hypothesis_posterior_kernel(const Pos
     }
     count = wave_sum(count);
     wave_argmax(top, at);  // (a lane without a usable row holds (-inf, int max) and never wins a tie)
-    float log_norm = 0.f;
-    if (count > 0) {
-        float se = 0.f;
-        for (int r = start + lane; r < end; r += WAVE) {
-            const float s = p.log_posterior[r];
-            if (finite(s)) se += expf(s - top);
-        }
-        log_norm = logf(wave_sum(se));
-    }
-    for (int r = start + lane; r < end; r += WAVE) {
-        const float s = p.log_posterior[r];
-        p.log_posterior[r] = finite(s) ? (s - top) - log_norm : -INFINITY;
-    }
+    const float log_norm = score_normaliser(p.log_posterior, rows, lane, count, top);
     if (lane == 0) {
         p.log_evidence[g] = count > 0 ? top + log_norm : -INFINITY;
         p.best_row[g] = count > 0 ? at : -1;
         if (p.support) p.support[g] = count;
     }
-}
-
-template <int NPER>
-int launch(const PosteriorArgs& a, void* stream) {
-    hipLaunchKernelGGL(hypothesis_posterior_kernel<NPER>, dim3((unsigned)a.n_groups), dim3(THREADS), 0,
-                       static_cast<hipStream_t>(stream), a);
-    return (int)hipGetLastError();
 }
 
 }  // namespace
@@ -267,7 +205,7 @@ extern "C" int pnmn_hypothesis_posterior(const float* x_logits, const int64_t* x
     if ((x_logits && !x_tokens) || (z_logits && !z_tokens) || (!x_logits && !z_logits && !log_q)) return PNMN_EINVAL;
     if ((x_logits && (Tx < 1 || Vx < 1)) || (z_logits && (Tz < 1 || Vz < 1))) return PNMN_EINVAL;
     if (!(fabsf(w_x) < INFINITY) || !(fabsf(w_z) < INFINITY) || !(fabsf(w_q) < INFINITY)) return PNMN_EINVAL;
-    if ((x_logits && Vx > MAX_VOCAB) || (z_logits && Vz > MAX_VOCAB)) return PNMN_ESHAPE;
+    if ((x_logits && Vx > MAX_COLUMNS) || (z_logits && Vz > MAX_COLUMNS)) return PNMN_ESHAPE;
     PosteriorArgs a;
     // (a term that neither enters the score nor is asked for is not computed)
     const bool score_x = x_logits && w_x != 0.f, score_z = z_logits && w_z != 0.f;
@@ -282,10 +220,9 @@ extern "C" int pnmn_hypothesis_posterior(const float* x_logits, const int64_t* x
     a.support = support;
     a.n_groups = n_groups;
     a.n_rows = n_rows;
-    const int nper = (std::max(a.x.logits ? Vx : 1, a.z.logits ? Vz : 1) + WAVE - 1) / WAVE;
-    if (nper <= 1) return launch<1>(a, stream);
-    if (nper <= 2) return launch<2>(a, stream);
-    if (nper <= 4) return launch<4>(a, stream);
-    if (nper <= 8) return launch<8>(a, stream);
-    return launch<16>(a, stream);
+    return with_nper(std::max(a.x.logits ? Vx : 1, a.z.logits ? Vz : 1), [&](auto nper) {
+        hipLaunchKernelGGL(hypothesis_posterior_kernel<decltype(nper)::value>, dim3((unsigned)n_groups), dim3(THREADS), 0,
+                           static_cast<hipStream_t>(stream), a);
+        return (int)hipGetLastError();
+    });
 }

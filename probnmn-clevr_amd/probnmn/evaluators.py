@@ -25,7 +25,7 @@ from typing import Any, Callable, Dict, Iterable, List, Optional
 import numpy as np
 import torch
 
-from probnmn import _hip
+from probnmn import _hip, hypothesis_rows
 from probnmn.modules.seq2seq_base import Seq2SeqBase, sampling_filter
 
 
@@ -395,13 +395,12 @@ def hypothesis_posterior(question_reconstructor, program_prior, questions: torch
         raise _hip.HipLibraryError("hypothesis_posterior runs on the ROCm device the questions are on (got %s); there is no "
                                    "CPU path" % dev)
     G = int(questions.size(0))
-    qrows = np.ascontiguousarray(torch.as_tensor(question_rows).detach().cpu().numpy(), dtype=np.int64)
+    qrows = hypothesis_rows.on_host(question_rows)
     R = int(qrows.size)
     if questions.dim() != 2 or programs.dim() != 2 or programs.size(0) != R or qrows.ndim != 1:
         raise ValueError("questions [G, Tq], programs [R, T] and question_rows [R]; got %s, %s and %s"
                          % (tuple(questions.shape), tuple(programs.shape), qrows.shape))
-    if R and (int(qrows.min()) < 0 or int(qrows.max()) >= G or bool((np.diff(qrows) < 0).any())):
-        raise ValueError("question_rows must be non-decreasing and in 0 .. %d" % (G - 1))
+    hypothesis_rows.check(qrows, G)
     f = dict(dtype=torch.float32, device=dev)
     out = {"log_posterior": torch.empty(R, **f), "log_reconstruction": torch.full((R,), float("nan"), **f),
            "log_prior": torch.full((R,), float("nan"), **f), "log_evidence": torch.full((G,), -float("inf"), **f),
@@ -409,11 +408,7 @@ def hypothesis_posterior(question_reconstructor, program_prior, questions: torch
            "support": torch.zeros(G, dtype=torch.int32, device=dev)}
     if R == 0 or G == 0:  # (no row anywhere: what the kernel writes for a group without rows)
         return out
-    q = None
-    if log_q is not None:
-        q = torch.as_tensor(log_q).detach().to(device=dev, dtype=torch.float32).contiguous()
-        if tuple(q.shape) != (R,):
-            raise ValueError("log_q [%d]; got %s" % (R, tuple(q.shape)))
+    q = None if log_q is None else hypothesis_rows.row_vector(log_q, "log_q", R, dev)
     programs = programs.detach().to(device=dev, dtype=torch.long)
     rows_dev = _hip.to_device(qrows, dev).view(torch.long)
     models = [m for m in (question_reconstructor, program_prior) if m is not None]
@@ -438,7 +433,7 @@ def hypothesis_posterior(question_reconstructor, program_prior, questions: torch
     finally:
         for m, training in zip(models, was_training):
             m.train(training)
-    group_start = _hip.small_to_device(np.searchsorted(qrows, np.arange(G + 1)).tolist(), torch.int32, dev)
+    group_start = hypothesis_rows.group_start_on_device(qrows, G, dev)
 
     def term(t, model):
         if t is None:
@@ -544,7 +539,7 @@ def _finish_hypotheses(nmn, image, queued, rerank=None):
     out.update(scored)
     if perturbed is not None:
         out["perturbed"] = perturbed.cpu()[torch.from_numpy(question_rows), torch.from_numpy(first_slot)]
-    return ({k: v.cpu().numpy() for k, v in out.items()}, programs, np.searchsorted(question_rows, np.arange(B + 1)))
+    return ({k: v.cpu().numpy() for k, v in out.items()}, programs, hypothesis_rows.group_start(question_rows, B))
 
 
 @torch.no_grad()
@@ -943,7 +938,7 @@ def _inferred_batches(program_generator, nmn, batches, beam_size, num_programs, 
             B, programs, question_rows, base, _, scored = _awaited_hypotheses(nmn, queued, reranked)
             out = nmn.answer_posterior(batch["image"], torch.from_numpy(programs), question_rows, batch["answer"], base, w_a)
             out = {k: v.cpu().numpy() for k, v in out.items()}
-            start = np.searchsorted(question_rows, np.arange(B + 1))
+            start = hypothesis_rows.group_start(question_rows, B)
             if reranked is not None:  # (hypothesis_posterior's log_posterior is normalised over the question's rows already)
                 out.update({k: scored[k].cpu().numpy() for k in ("log_reconstruction", "log_prior")})
                 out["log_prior_weight"] = base.cpu().numpy().astype(np.float64)

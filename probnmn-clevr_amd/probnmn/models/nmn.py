@@ -421,9 +421,7 @@ class NeuralModuleNetwork(nn.Module):
         hypothesis rows in passes of at most ``max_rows``, each row reading its question's feature map where it lies
         (``rows=`` / ``ResidentRows.subset``).  Returns (device, G, R, A, question_rows as host int64 [R], answer logits
         fp32 [R, A], validity int32 [R] -- both on the device)."""
-        import numpy as np
-
-        from probnmn import _hip
+        from probnmn import _hip, hypothesis_rows
         from probnmn.data.feature_store import ResidentRows
 
         if max_rows < 1:
@@ -431,12 +429,11 @@ class NeuralModuleNetwork(nn.Module):
         dev = features.device
         G = int(features.size(0))
         programs = programs.detach().cpu()
-        qrows = np.ascontiguousarray(torch.as_tensor(question_rows).detach().cpu().numpy(), dtype=np.int64)
+        qrows = hypothesis_rows.on_host(question_rows)
         R = int(qrows.size)
         if programs.dim() != 2 or programs.size(0) != R or qrows.ndim != 1:
             raise ValueError("programs [R, T] and question_rows [R]; got %s and %s" % (tuple(programs.shape), qrows.shape))
-        if R and (int(qrows.min()) < 0 or int(qrows.max()) >= G or bool((np.diff(qrows) < 0).any())):
-            raise ValueError("question_rows must be non-decreasing and in 0 .. %d" % (G - 1))
+        hypothesis_rows.check(qrows, G)
         A = self.classifier[6].out_features
         logits = torch.empty(R, A, dtype=torch.float32, device=dev)
         valid = torch.empty(R, dtype=torch.int32, device=dev)
@@ -470,17 +467,11 @@ class NeuralModuleNetwork(nn.Module):
         Returns ``"predictions"`` int64 [G] (@@UNKNOWN@@ where no hypothesis counts), ``"log_probabilities"`` fp32 [G, A]
         (-inf there), ``"hypothesis_predictions"`` int64 [R] (each hypothesis's own answer), ``"hypothesis_weights"``
         fp32 [R] (0 for one that does not count) and ``"support"`` int32 [G] (how many count)."""
-        import numpy as np
-
-        from probnmn import _hip
+        from probnmn import _hip, hypothesis_rows
 
         dev, G, R, A, qrows, logits, valid = self._hypothesis_logits(features, programs, question_rows, max_rows)
-        weights = None
-        if log_weights is not None:
-            weights = torch.as_tensor(log_weights).detach().to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(weights.shape) != (R,):
-                raise ValueError("log_weights [%d]; got %s" % (R, tuple(weights.shape)))
-        group_start = _hip.small_to_device(np.searchsorted(qrows, np.arange(G + 1)).tolist(), torch.int32, dev)
+        weights = None if log_weights is None else hypothesis_rows.row_vector(log_weights, "log_weights", R, dev)
+        group_start = hypothesis_rows.group_start_on_device(qrows, G, dev)
         out = {"predictions": torch.empty(G, dtype=torch.long, device=dev),
                "log_probabilities": torch.empty(G, A, dtype=torch.float32, device=dev),
                "hypothesis_predictions": torch.empty(R, dtype=torch.long, device=dev),
@@ -522,9 +513,7 @@ class NeuralModuleNetwork(nn.Module):
         is none), ``"consistent_count"`` int32 [G] (how many there are) and ``"support"`` int32 [G] (how many count)."""
         import math
 
-        import numpy as np
-
-        from probnmn import _hip
+        from probnmn import _hip, hypothesis_rows
 
         try:
             w_a = float(answer_weight)
@@ -536,13 +525,9 @@ class NeuralModuleNetwork(nn.Module):
         if given.dim() != 1 or given.size(0) != int(features.size(0)) or given.dtype.is_floating_point or given.dtype == torch.bool:
             raise ValueError("answers int64 [%d]; got %s %s" % (int(features.size(0)), given.dtype, tuple(given.shape)))
         dev, G, R, A, qrows, logits, valid = self._hypothesis_logits(features, programs, question_rows, max_rows)
-        weights = None
-        if log_weights is not None:
-            weights = torch.as_tensor(log_weights).detach().to(device=dev, dtype=torch.float32).contiguous()
-            if tuple(weights.shape) != (R,):
-                raise ValueError("log_weights [%d]; got %s" % (R, tuple(weights.shape)))
+        weights = None if log_weights is None else hypothesis_rows.row_vector(log_weights, "log_weights", R, dev)
         given = given.to(device=dev, dtype=torch.long).contiguous()
-        group_start = _hip.small_to_device(np.searchsorted(qrows, np.arange(G + 1)).tolist(), torch.int32, dev)
+        group_start = hypothesis_rows.group_start_on_device(qrows, G, dev)
         f, i = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
         out = {"log_answer_likelihood": torch.empty(R, **f), "log_posterior": torch.empty(R, **f),
                "hypothesis_predictions": torch.empty(R, dtype=torch.long, device=dev), "log_evidence": torch.empty(G, **f),

@@ -6,11 +6,14 @@ FIXED_SIZES = [0, 1, 2, 3, 16, 17, 64, 65, 5, 1, 0, 7]
 DEAD_GROUP = 5           # (the 17 rows: every weight is -inf)
 BEYOND_GROUP = 8         # (the 5 rows: the given answer is A + 3)
 NEGATIVE_GROUP = 11      # (the 7 rows: the given answer is -2)
-ANSWERS = (1, 2, 28, 64, 65, 130)   # NPER 1, 2 and 4, and both sides of a lane boundary
+# NPER 1, 2 and 4 and both sides of a lane boundary; 257 and 513, the first widths of the NPER 8 and 16 kernels (one live
+# column in their register 4 and 8); 1024, the full width
+ANSWERS = (1, 2, 28, 64, 65, 130, 257, 513, 1024)
 # one seed per number of answers at which, on the reference alone, the two best scores of every supported group differ by
 # 100 x the group's tolerance in every variant ``variants`` lists, and at least 28 groups are supported (searched on the CPU
-# with ``ragged_inputs`` and the reference, seeds 0 .. 39: 38 and 32 of them do at A = 1 and 2, 13 to 23 from A = 28 on)
-SEEDS = {1: 0, 2: 0, 28: 0, 64: 0, 65: 2, 130: 0}
+# with ``ragged_inputs`` and the reference, seeds 0 .. 39: 38 and 32 of them do at A = 1 and 2, 13 to 23 from A = 28 to 130,
+# 9, 13 and 18 at A = 257, 513 and 1024, where the first that does is taken)
+SEEDS = {1: 0, 2: 0, 28: 0, 64: 0, 65: 2, 130: 0, 257: 4, 513: 0, 1024: 5}
 
 
 def variants(A, log_weight):

@@ -27,8 +27,10 @@ GUARD = 64     # guard words on either side of every output buffer
 FIXED_SIZES = [0, 1, 2, 3, 16, 17, 64, 65, 5, 1, 0, 7]
 INVALID_GROUP = 5  # (the 17 rows)
 # one seed per number of answers at which, on the reference alone, every supported group's best answer leads by MARGIN,
-# with valid / log_weight given and with both null (searched on the CPU; most seeds do)
-SEEDS = {1: 0, 2: 2, 28: 0, 29: 1, 64: 3, 65: 4, 130: 6}
+# with valid / log_weight given and with both null (searched on the CPU; most seeds do).  257 and 513 are the first widths
+# of the NPER 8 and 16 kernels (one live column in their register 4 and 8), 1024 the full width: of the seeds 0 .. 39, 27, 20
+# and 11 hold there (and leave at least 30 groups supported); the first of each is taken
+SEEDS = {1: 0, 2: 2, 28: 0, 29: 1, 64: 3, 65: 4, 130: 6, 257: 0, 513: 0, 1024: 1}
 
 
 def ragged_inputs(A: int, seed: int):
@@ -211,6 +213,18 @@ def test_group_bounds_are_clamped_into_the_arrays():
     assert np.array_equal(bits(got["row_weight"])[outside], bits(base["row_weight"])[outside])
     assert np.array_equal(got["row_predictions"], base["row_predictions"])  # (a row's own arg-max: whoever writes it)
     np.testing.assert_allclose(got["row_weight"][3:22], ref["row_weight"][3:22], **TOL)
+
+
+def test_more_answers_than_the_widest_kernel_holds_return_without_a_launch():
+    from probnmn import _hip
+
+    dev = torch.device("cuda:0")
+    out = torch.full((2 * 1025,), -777.0, device=dev)
+    p = out.data_ptr()
+    # (one group of two rows of 1025 answers: every buffer the kernel would touch lies inside ``out``)
+    assert _hip.lib().pnmn_answer_marginal(p, 0, 0, p, p, p, 0, 0, 0, 1, 2, 1025, 0, _hip.stream_ptr(dev)) == _hip.ESHAPE
+    torch.cuda.synchronize()
+    assert (out == -777).all()  # nothing ran
 
 
 # ---- the network and the evaluators ------------------------------------------------------------------------------------

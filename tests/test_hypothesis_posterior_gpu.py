@@ -31,8 +31,10 @@ WEIGHTS = (1.0, 0.75, 0.5)
 # one seed per (Vx, Vz) at which, on the reference alone, the two best scores of every supported group differ by 100 x the
 # group's tolerance, with WEIGHTS and -- but for (1, 1), see ``variants`` -- with (1, 1, 0) and no log_q (searched on the CPU
 # with ``ragged_inputs`` and the reference; about one seed in two does, one in thirty at (3, 2), whose few distinct scores
-# tie often)
-SEEDS = {(1, 1): 0, (3, 2): 32, (64, 45): 1, (65, 64): 0, (130, 129): 1}
+# tie often).  The kernel variant follows the larger vocabulary: 257 and 513 are the first widths of the NPER 8 and 16 kernels
+# (one live column in their register 4 and 8), 1024 the full width; of the seeds 0 .. 39, 16, 21 and 17 hold at those pairs,
+# and the first of each is taken
+SEEDS = {(1, 1): 0, (3, 2): 32, (64, 45): 1, (65, 64): 0, (130, 129): 1, (257, 256): 4, (513, 512): 0, (1024, 1023): 0}
 
 
 def variants(V, log_q):
@@ -311,6 +313,20 @@ def test_group_bounds_are_clamped_into_the_arrays():
     assert np.array_equal(bits(got["log_posterior"])[outside], bits(base["log_posterior"])[outside])
     for name in ("log_px", "log_pz"):
         assert np.array_equal(bits(got[name]), bits(base[name])), name
+
+
+def test_a_wider_vocabulary_than_the_widest_kernel_holds_returns_without_a_launch():
+    from probnmn import _hip
+
+    dev = torch.device("cuda:0")
+    out = torch.full((2 * 3 * 1025,), -777.0, device=dev)
+    p = out.data_ptr()
+    # (one group of two rows of three steps: every buffer the kernel would touch lies inside ``out``)
+    for Vx, Vz in ((1025, 4), (4, 1025)):
+        assert _hip.lib().pnmn_hypothesis_posterior(p, p, 3, p, p, 3, 0, p, 1.0, 1.0, 0.0, 0, 0, 0, 0, p, p, p, 0, 1, 2, 3, Vx, 3, Vz,
+                                                    _hip.stream_ptr(dev)) == _hip.ESHAPE
+    torch.cuda.synchronize()
+    assert (out == -777).all()  # nothing ran
 
 
 # ---- the models and the evaluators -------------------------------------------------------------------------------------
