@@ -579,7 +579,25 @@ int pnmn_elbo_rows(const float* pg_loss, const float* qr_loss, const float* prio
  *            process; under data parallelism the caller all-reduces stats[5] = sum(c) and stats[9] = n first)
  *   stats    [10] = mean(-qr), mean(kl), mean(elbo), mean(R), mean(nmn), sum(c), mean(pg_sup), mean(qr_sup), J, n
  *   objective [1] = J again (its own tensor on the autograd side)
- *   d_pg [n], d_qr [n + m], d_nmn [n] (NULL with nmn == NULL), d_pg_sup [m] = dJ / d(row loss) */
+ *   d_pg [n], d_qr [n + m], d_nmn [n] (NULL with nmn == NULL), d_pg_sup [m] = dJ / d(row loss)
+ *
+ * baseline == NULL: the LEAVE-ONE-OUT baseline in the moving one's place (no state: nothing is read or written for it,
+ * decay is ignored).  `update_baseline` then holds K, the programs drawn per question, 2 .. 64; the n sampled rows are
+ * n / K questions of K rows each, question-major (row i = q K + k), and each sample's reward is centred by the mean reward
+ * of the question's OTHER K - 1 samples (Kool et al. 2019, "Buy 4 REINFORCE samples, get a baseline for free"): per
+ * question and independent of the sample it centres, so the score-function gradient stays unbiased.  Per row as above
+ * but for c:   S_q = sum of the question's R, added in the order k = 0 .. K-1 ;  c_i = R_i - (S_q - R_i) / (K - 1)
+ *   stats    [11] = the ten above (stats[5] = sum(c): zero up to rounding) and
+ *            stats[10] = reward_variance = mean over questions of sum_k (R_k - S_q / K)^2 / (K - 1)
+ *   d_pg [n] = -s (c - beta), d_qr [0..n) = s, d_nmn [n] = s gamma, with the ONE factor s = w_unsup * (1 / n): a row sees
+ *            the batch through s alone, so its derivative has the same bits alone and in a batch of any size whenever s is
+ *            the same, whichever thread takes its question.  d_qr [n..n+m) and d_pg_sup [m] as above.
+ * Its own kernel (the moving baseline is not folded into it); no atomics; every loop is bounded by the arguments; n == 0
+ * with m > 0 is a batch without sampled rows.
+ *
+ * PNMN_EINVAL: a negative count, stats or objective NULL, a NULL row pointer where rows exist (pg, qr, d_pg, d_qr with
+ * n > 0; pg_sup, qr, d_pg_sup, d_qr with m > 0), nmn without d_nmn or the reverse; with baseline == NULL also K outside
+ * [2, 64] (so every call that was refused for its missing baseline still is: the flag was 0 or 1) and n no multiple of K. */
 int pnmn_joint_objective(const float* pg, const float* qr, const float* prior, const float* nmn, const float* pg_sup,
                          float* baseline, const float* w_unsup, const float* w_sup, float alpha, float beta, float gamma,
                          float decay, int update_baseline, int n, int m, float* stats, float* objective, float* d_pg,

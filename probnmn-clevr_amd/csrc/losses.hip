@@ -182,6 +182,88 @@ __global__ __launch_bounds__(256) void joint_objective_kernel(
     }
 }
 
+// ... with K = samples programs per question, question-major (row i = q K + k), and the leave-one-out baseline: a sample's
+// reward is centred by the mean reward of the question's other K - 1 samples,
+//     S_q = sum_k R_k (k = 0 .. K-1, in that order) ;  c_i = R_i - (S_q - R_i) / (K - 1)
+// and no moving baseline exists.  One THREAD per question: it forms the question's sum itself, in the one fixed order, so a
+// row's c depends on its question's K rows and on nothing else -- neither on n_questions nor on which thread took it -- and
+// with the single factor s = w_u / N its derivatives have the same bits alone and in a batch of equal s.  (R is parked in
+// d_pg between the two passes over a question: the second pass reads back what the first one rounded.)
+//   stats[11] = the ten above (sum c is zero up to rounding, stats[9] = N) and the reward variance
+//               mean_q sum_k (R_k - S_q / K)^2 / (K - 1), which is what the baseline removes
+__global__ __launch_bounds__(256) void joint_objective_loo_kernel(
+    const float* __restrict__ pg, const float* __restrict__ qr, const float* __restrict__ pr, const float* __restrict__ nmn,
+    const float* __restrict__ pgs, const float* __restrict__ w_u_ptr, const float* __restrict__ w_s_ptr, float alpha, float beta,
+    float gamma, int n_questions, int samples, int m, float* __restrict__ stats, float* __restrict__ objective, float* d_pg,
+    float* __restrict__ d_qr, float* __restrict__ d_nmn, float* __restrict__ d_pgs) {
+    __shared__ float red[9][4];
+    const int n = n_questions * samples;
+    const float w_u = w_u_ptr ? w_u_ptr[0] : 1.f, w_s = w_s_ptr ? w_s_ptr[0] : 1.f;
+    const float inv_n = n > 0 ? 1.f / (float)n : 0.f, inv_m = m > 0 ? 1.f / (float)m : 0.f;
+    const float inv_q = n_questions > 0 ? 1.f / (float)n_questions : 0.f;
+    const float s = w_u * inv_n;
+    const float others = (float)(samples - 1), all = (float)samples;
+    float acc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int q = threadIdx.x; q < n_questions; q += 256) {
+        const int at = q * samples;
+        float S = 0.f;
+        for (int k = 0; k < samples; ++k) {
+            const int i = at + k;
+            const float prior = pr ? -pr[i] : 0.f;
+            const float ans = nmn ? -nmn[i] : 0.f;
+            const float logq = -pg[i], rec = -qr[i];
+            const float R = rec + beta * prior - beta * logq + gamma * ans;
+            d_pg[i] = R;
+            S += R;
+        }
+        const float centre = S / all;
+        float var = 0.f;
+        for (int k = 0; k < samples; ++k) {
+            const int i = at + k;
+            const float logq = -pg[i], rec = -qr[i];
+            const float R = d_pg[i];
+            const float c = R - (S - R) / others;
+            const float kl = logq * c - beta * logq;
+            acc[0] += rec;
+            acc[1] += kl;
+            acc[2] += rec - kl;
+            acc[3] += R;
+            acc[4] += nmn ? nmn[i] : 0.f;
+            acc[5] += c;
+            var += (R - centre) * (R - centre);
+            d_pg[i] = -s * (c - beta);
+            d_qr[i] = s;
+            if (d_nmn) d_nmn[i] = s * gamma;
+        }
+        acc[8] += var / others;
+    }
+    for (int j = threadIdx.x; j < m; j += 256) {
+        acc[6] += pgs[j];
+        acc[7] += qr[n + j];
+        d_pgs[j] = w_s * alpha * inv_m;
+        d_qr[n + j] = w_s * alpha * inv_m;
+    }
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        const float t = wsum(acc[k]);
+        if (lane == 0) red[k][wave] = t;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) t[k] = (red[k][0] + red[k][1]) + (red[k][2] + red[k][3]);
+        stats[0] = t[0] * inv_n, stats[1] = t[1] * inv_n, stats[2] = t[2] * inv_n, stats[3] = t[3] * inv_n;
+        stats[4] = t[4] * inv_n, stats[5] = t[5];
+        stats[6] = t[6] * inv_m, stats[7] = t[7] * inv_m;
+        stats[8] = w_u * (gamma * t[4] * inv_n - t[2] * inv_n) + w_s * alpha * (t[6] * inv_m + t[7] * inv_m);
+        stats[9] = (float)n;
+        stats[10] = t[8] * inv_q;
+        objective[0] = stats[8];
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -190,10 +272,18 @@ int pnmn_joint_objective(const float* pg, const float* qr, const float* prior, c
                          float* baseline, const float* w_unsup, const float* w_sup, float alpha, float beta, float gamma,
                          float decay, int update_baseline, int n, int m, float* stats, float* objective, float* d_pg,
                          float* d_qr, float* d_nmn, float* d_pg_sup, void* stream) {
-    if (n < 0 || m < 0 || !baseline || !stats || !objective) return PNMN_EINVAL;
+    if (n < 0 || m < 0 || !stats || !objective) return PNMN_EINVAL;
     if (n > 0 && (!pg || !qr || !d_pg || !d_qr)) return PNMN_EINVAL;
     if (m > 0 && (!pg_sup || !qr || !d_pg_sup || !d_qr)) return PNMN_EINVAL;
     if ((nmn != nullptr) != (d_nmn != nullptr)) return PNMN_EINVAL;
+    if (!baseline) {  // the leave-one-out baseline: update_baseline is K, the samples per question
+        const int samples = update_baseline;
+        if (samples < 2 || samples > 64 || n % samples != 0) return PNMN_EINVAL;
+        hipLaunchKernelGGL(joint_objective_loo_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), pg, qr, prior,
+                           nmn, pg_sup, w_unsup, w_sup, alpha, beta, gamma, n / samples, samples, m, stats, objective, d_pg, d_qr,
+                           d_nmn, d_pg_sup);
+        return (int)hipGetLastError();
+    }
     hipLaunchKernelGGL(joint_objective_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), pg, qr, prior, nmn,
                        pg_sup, baseline, w_unsup, w_sup, alpha, beta, gamma, decay, update_baseline, n, m, stats, objective, d_pg,
                        d_qr, d_nmn, d_pg_sup);

@@ -9,6 +9,11 @@ Data parallelism: every loss term is a mean over a data-dependent subset, so a m
 would weight shards wrongly; each local mean is rescaled by (n_local * world / n_global) before
 backward, which makes the averaged all-reduced gradient equal the single-process gradient
 (SURVEY.md 8e).
+
+``num_samples=K`` draws K programs per unsupervised question: the unsupervised index list is replicated K-fold,
+question-major, and every pass, the answers, the image rows and the NMN then run over n K sampled rows as they are.
+``baseline`` picks what centres a sample's reward: the reference's moving scalar, or (the default for K > 1) the mean
+reward of the question's other samples -- ``probnmn.modules.elbo``.
 """
 import os
 import time
@@ -17,7 +22,7 @@ from typing import Any, Dict
 import torch
 
 from probnmn import _hip, parallel
-from probnmn.modules.elbo import JointTrainingElbo, QuestionCodingElbo
+from probnmn.modules.elbo import JointTrainingElbo, QuestionCodingElbo, check_estimator
 from probnmn.optim import ClampAdam
 from ._base import StepBase
 
@@ -39,6 +44,20 @@ def _index_to_device(index: torch.Tensor, dev: torch.device) -> torch.Tensor:
 
 
 _dp_weight = parallel.mean_weight  # (n_local * world / n_global, see probnmn.parallel)
+
+
+def _estimator(num_samples, baseline):
+    """(K, baseline) of a step that draws K programs per unsupervised question: ``baseline=None`` is the leave-one-out
+    baseline where there is another sample to take it from, the reference's moving scalar otherwise."""
+    if baseline is None:
+        baseline = "leave_one_out" if num_samples > 1 else "moving"
+    return check_estimator(num_samples, baseline), baseline  # (the one rule: probnmn.modules.elbo)
+
+
+def _replicate(nosup: torch.Tensor, num_samples: int) -> torch.Tensor:
+    """The unsupervised index list with every question K times, question-major (sampled row q * K + k): every pass gathers
+    its rows through this list, and the sampling decoder draws per row POSITION, so the replicas get different programs."""
+    return nosup.repeat_interleave(num_samples) if num_samples > 1 else nosup
 
 
 def _cat_padded(a: torch.Tensor, b: torch.Tensor, pad: int = 0) -> torch.Tensor:
@@ -383,6 +402,10 @@ class _TrainerBase(StepBase):
         if "pg_sup_rows" in p:
             p["pg_sup"] = p["pg_sup_rows"].mean()
 
+    def _elbo_keys(self):
+        keys = ("reconstruction_likelihood", "kl_divergence", "elbo", "reinforce_reward")
+        return keys + ("reward_variance",) if self.elbo.leave_one_out else keys
+
     def _fused_objective(self, p, nmn_rows, w_sup, w_nosup, alpha, gamma):
         """(J, detached statistics) through ``pnmn_joint_objective`` -- one launch forward, one multiply backward."""
         n, m = p["n_nosup"], p["n_sup"]
@@ -393,13 +416,18 @@ class _TrainerBase(StepBase):
 class QuestionCodingStep(_TrainerBase):
     def __init__(self, program_generator, question_reconstructor, program_prior, objective: str = "ours",
                  alpha: float = 100.0, beta: float = 0.1, delta: float = 0.99, lr: float = 1e-3,
-                 weight_decay: float = 0.0, lr_gamma: float = 0.5, lr_patience: int = 3):
+                 weight_decay: float = 0.0, lr_gamma: float = 0.5, lr_patience: int = 3, num_samples: int = 1,
+                 baseline=None):
         if objective not in ("ours", "baseline"):
             raise ValueError("objective must be 'ours' or 'baseline'")
+        self.num_samples, self.baseline = _estimator(num_samples, baseline)
+        if objective == "baseline" and self.num_samples > 1:
+            raise ValueError("the 'baseline' objective samples no programs: num_samples must be 1")
         self.pg, self.qr, self.prior = program_generator, question_reconstructor, program_prior
         self.objective, self.alpha = objective, alpha
         self.prior.eval()
-        self.elbo = QuestionCodingElbo(self.pg, self.qr, self.prior, beta=beta, baseline_decay=delta)
+        self.elbo = QuestionCodingElbo(self.pg, self.qr, self.prior, beta=beta, baseline_decay=delta,
+                                       num_samples=self.num_samples, baseline=self.baseline)
         self.models = {"program_generator": self.pg, "question_reconstructor": self.qr}
         self.optimizer = self._make_optimizer([self.pg, self.qr], lr, weight_decay)
         self._init_schedule(lr_gamma, lr_patience)
@@ -412,10 +440,11 @@ class QuestionCodingStep(_TrainerBase):
                 m.train()
         dev = batch["question"].device
         sup, nosup = _split_supervision(batch["supervision"])
+        nosup = _replicate(nosup, self.num_samples)
         sup_d, nosup_d = _index_to_device(sup, dev), _index_to_device(nosup, dev)
         ours = self.objective == "ours"
         p = self._seq2seq_passes(batch, sup_d, nosup_d, supervised=True, sampled=ours, prior=True)
-        out: Dict[str, Any] = {}
+        out: Dict[str, Any] = {"samples_per_question": self.num_samples}
         loss = torch.zeros((), device=dev)
         # Data parallel: both weights are computed (one collective each) and the REINFORCE baseline is
         # synchronised on EVERY rank, whatever this rank's shard holds -- a rank without supervised (or
@@ -426,7 +455,7 @@ class QuestionCodingStep(_TrainerBase):
             if p["n_sup"]:
                 out["loss"] = {k: stats[k] for k in ("program_generation_gt", "question_reconstruction_gt")}
             if p["n_nosup"]:
-                out["elbo"] = {k: stats[k] for k in ("reconstruction_likelihood", "kl_divergence", "elbo", "reinforce_reward")}
+                out["elbo"] = {k: stats[k] for k in self._elbo_keys()}
                 out["programs"] = p["programs"]
             self._finish(loss)
             out["objective"] = loss.detach()
@@ -440,7 +469,7 @@ class QuestionCodingStep(_TrainerBase):
             loss = loss - w_nosup * elbo_out["elbo"]
             out["elbo"] = {k: v.detach() for k, v in elbo_out.items()}
             out["programs"] = p["programs"]
-        elif ours and parallel.world() > 1:
+        elif ours and parallel.world() > 1 and not self.elbo.leave_one_out:  # (leave-one-out: no rank has a collective to join)
             self.elbo._reinforce.idle(dev)
         self._finish(loss)
         out["objective"] = loss.detach()
@@ -450,14 +479,19 @@ class QuestionCodingStep(_TrainerBase):
 class JointTrainingStep(_TrainerBase):
     def __init__(self, program_generator, question_reconstructor, program_prior, nmn, objective: str = "ours",
                  alpha: float = 100.0, beta: float = 0.1, gamma: float = 1.0, delta: float = 0.99,
-                 lr: float = 1e-6, weight_decay: float = 0.0, lr_gamma: float = 0.5, lr_patience: int = 3):
+                 lr: float = 1e-6, weight_decay: float = 0.0, lr_gamma: float = 0.5, lr_patience: int = 3,
+                 num_samples: int = 1, baseline=None):
         if objective not in ("ours", "baseline"):
             raise ValueError("objective must be 'ours' or 'baseline'")
+        self.num_samples, self.baseline = _estimator(num_samples, baseline)
+        if objective == "baseline" and self.num_samples > 1:
+            raise ValueError("the reference's 'baseline' objective draws one program per question: num_samples must be 1")
         self.pg, self.qr, self.prior, self.nmn = program_generator, question_reconstructor, program_prior, nmn
         self.objective, self.alpha, self.gamma = objective, alpha, gamma
         self.prior.eval()
         self.elbo = JointTrainingElbo(self.pg, self.qr, self.prior, self.nmn, beta=beta, gamma=gamma,
-                                      baseline_decay=delta, objective=objective)
+                                      baseline_decay=delta, objective=objective, num_samples=self.num_samples,
+                                      baseline=self.baseline)
         self.models = {"program_generator": self.pg, "question_reconstructor": self.qr, "nmn": self.nmn}
         self.optimizer = self._make_optimizer([self.pg, self.qr, self.nmn], lr, weight_decay)
         self._init_schedule(lr_gamma, lr_patience)
@@ -512,6 +546,7 @@ class JointTrainingStep(_TrainerBase):
         self.nmn.report_batch_metrics = False
         dev = batch["question"].device
         sup, nosup = _split_supervision(batch["supervision"])
+        nosup = _replicate(nosup, self.num_samples)
         sup_d, nosup_d = _index_to_device(sup, dev), _index_to_device(nosup, dev)
         if nosup.numel() == 0 and parallel.world() == 1:
             raise ValueError("joint training needs at least one example without program supervision in the batch")
@@ -519,8 +554,13 @@ class JointTrainingStep(_TrainerBase):
         # Data parallel: every rank issues the same collectives in the same order (both loss weights, the
         # REINFORCE baseline, the gradient all-reduces) whatever its shard holds; a shard without
         # unsupervised rows contributes zeros to the terms it has no rows for.
+        # (with K samples per question the weights count n K sampled rows; K is the same on every rank, so their ratio is
+        # what it was)
         w_sup, w_nosup = _dp_weight(sup.numel(), dev), _dp_weight(nosup.numel(), dev)
-        out: Dict[str, Any] = {"loss": {}}
+        out: Dict[str, Any] = {"loss": {}, "samples_per_question": self.num_samples}
+        # rows the passes of this step run over (the batch's questions; with K samples each unsupervised one K times): what
+        # the schedule rules below go by
+        passes_rows = int(sup.numel() + nosup.numel())
         if nosup.numel():
             answers = batch["answer"][nosup_d]
             main = torch.cuda.current_stream(dev) if dev.type == "cuda" else None
@@ -529,7 +569,7 @@ class JointTrainingStep(_TrainerBase):
             # conv launches of a trunk that shares the chip are cut for the CUs it can count on (engine.conv_cus)
             engine = getattr(self.nmn, "engine", None)
             if engine is not None:
-                rows = int(batch["question"].size(0))
+                rows = passes_rows
                 # (28x28 maps: four band units per item, launches four times as large -- the whole chip, as for the large
                 # batches: 35.6-36.1 ms at 256 against 36.2-38.0 at 192, profiles/ab/r04r_c5.txt)
                 free = self.shared_conv_cus or shared_conv_cus(rows, getattr(engine, "banded", False))
@@ -550,7 +590,7 @@ class JointTrainingStep(_TrainerBase):
                 token = {}
 
                 stem_mode = (self.stem_after_encode if self.stem_after_encode is not None
-                             else stem_waits_for_encoder(int(batch["question"].size(0))))
+                             else stem_waits_for_encoder(passes_rows))
 
                 def launch_stem():
                     if stem_mode == 2:  # (the stem also WAITS for the encoder pass on the GPU)
@@ -585,7 +625,7 @@ class JointTrainingStep(_TrainerBase):
                     return self.nmn.forward_trunk(images, host, started=token["started"], trunk_stream=side, rows=rows_d)
 
                 before_prior = (self.trunk_before_prior if self.trunk_before_prior is not None
-                                else trunk_before_prior(int(batch["question"].size(0))))
+                                else trunk_before_prior(passes_rows))
                 p = self._seq2seq_passes(batch, sup_d, nosup_d, supervised=ours, sampled=True, prior=ours,
                                          reconstruct=ours, host_programs=True,
                                          before_prior=launch_trunk if before_prior else None,
@@ -610,7 +650,7 @@ class JointTrainingStep(_TrainerBase):
                 loss, stats = self._fused_objective(p, nmn_out["loss"], w_sup, w_nosup, self.alpha, self.gamma)
                 _hip.mark("objective combined")
                 out["loss"]["nmn"] = stats["nmn_loss"]
-                out["elbo"] = {k: stats[k] for k in ("reconstruction_likelihood", "kl_divergence", "elbo", "reinforce_reward")}
+                out["elbo"] = {k: stats[k] for k in self._elbo_keys()}
                 out["programs"] = p["programs"]
                 if p["n_sup"]:
                     out["loss"]["program_generation_gt"] = stats["program_generation_gt"]
@@ -629,7 +669,8 @@ class JointTrainingStep(_TrainerBase):
         else:
             p = self._seq2seq_passes(batch, sup_d, nosup_d, supervised=ours, sampled=False, prior=False)
             self._split_means(p)
-            self.elbo._reinforce.idle(dev)
+            if not self.elbo.leave_one_out:  # (leave-one-out: no rank has a baseline collective to join)
+                self.elbo._reinforce.idle(dev)
             for a in self.optimizer.arenas:  # no NMN backward on this rank, which is what zeroes them
                 a.grad.zero_()
             loss = torch.zeros((), device=dev)
