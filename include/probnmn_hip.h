@@ -427,6 +427,24 @@ int pnmn_hypothesis_posterior(const float* x_logits /* [n_rows][Tx][Vx], may be 
  * num_answers < 1; a null group_start, answers, log_posterior, log_evidence or best_row; a null logits (n_rows > 0); a w_a
  * that is not finite.  num_answers > 1024: PNMN_ESHAPE.  The checks run in this order: the counts and num_answers < 1; then
  * the empty case -- n_groups == 0 returns 0 whatever the pointers and w_a are --; then the pointers and w_a; then the shape.
+ *
+ * GRADIENT MODE: best_row == NULL and log_answer != NULL.  The marginal-likelihood loss of group g over its candidate
+ * programs is -log_evidence[g] = -log sum_r w_r p(a_g | z_r, image)^w_a; this mode computes it together with its gradient
+ * with respect to the logits -- a row's cross-entropy gradient scaled by the row's posterior share.  The log_answer slot is
+ * then read as d_logits, fp32 [n_rows][num_answers]; log_answer itself is not reported and best_row is not written.
+ * log_posterior, log_evidence, row_predictions, support, consistent_count and first_consistent keep their rules and are the
+ * same bits as a launch with best_row on the same inputs.  Over a fourth sweep of the group's rows:
+ *   d_logits[r][c] = w_a * exp(log_posterior[r]) * (softmax(logits[r])[c] - [c == answers[g]])      for a usable row r
+ *                  = d(-log_evidence[g]) / d logits[r][c]; a logit of -inf gets exactly 0
+ *   d_logits[r][c] = 0 exactly for every covered row that is not usable -- so for every row of a group without support --,
+ *                    and for every covered row when w_a is exactly 0
+ * A row that no group covers is not written; the given answer's column is found by comparing c, never by indexing with an
+ * unchecked answer.  A group's d_logits rows depend only on its own rows in their order: the same bits alone or inside a
+ * batch, and from run to run.  The checks, their order and their codes are those above with "best_row" read as "best_row or
+ * (in its absence) log_answer": log_posterior and log_evidence remain required.  No call that was accepted before this
+ * mode existed changes its meaning or its bits: every such call passed a best_row, and a call without one was refused
+ * with PNMN_EINVAL -- a call with neither best_row nor log_answer still is.  The derivative with respect to log_weight,
+ * exp(log_w[r]) - exp(log_posterior[r]), has no slot and is not computed.
  * ------------------------------------------------------------------------------------------- */
 int pnmn_answer_posterior(const float* logits /* [n_rows][num_answers] */, const int32_t* valid /* [n_rows], may be NULL */,
                           const float* log_weight /* [n_rows], may be NULL */, const int64_t* answers /* DEVICE [n_groups] */,

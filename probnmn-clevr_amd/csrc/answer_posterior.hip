@@ -21,6 +21,17 @@
 //               so the support, the largest score and its first row and the consistent rows are counted in scalars; lane 0
 //               writes score[r] (-inf for a row that is not usable) into log_posterior[r]
 //   sweep 3     ONE __syncthreads() (the scores lane 0 stored are visible to the other lanes), then score_normaliser()
+//
+// GRADIENT MODE (pnmn_answer_posterior without best_row and with a log_answer pointer, which is then d_logits [n_rows][A]):
+// the same kernel body with GRAD set -- so the outputs the two modes share are the same bits -- and one more sweep.  The
+// marginal-likelihood loss of a group is -log_evidence[g]; its gradient with respect to a row's logits is the row's
+// cross-entropy gradient scaled by the row's posterior share:
+//   sweep 4     a second __syncthreads() (the posteriors sweep 3 stored, a lane per row, are visible to every lane), then one
+//               row at a time as in sweep 2 (the logits are in L2; the next row is loaded before this one is reduced):
+//               row_softmax_stats() again -- the bits of sweep 2 --, share = w_a exp(log_posterior[r]), and
+//               d_logits[r][c] = share (softmax_c - [c == answer]), one coalesced segment per register; the answer's column
+//               is found by comparing c, never by indexing.  A row that is not usable, and every row when w_a is 0, is
+//               written as zeros; no d_logits word outside the group's clamped rows is touched.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -42,6 +53,7 @@ struct AnswerPosteriorArgs {
     const int32_t* group_start;
     float w_a;
     float* log_answer;
+    float* d_logits;  // (gradient mode only: it arrives in log_answer's place)
     int64_t* row_predictions;
     float* log_posterior;
     float* log_evidence;
@@ -52,7 +64,7 @@ struct AnswerPosteriorArgs {
     int n_groups, n_rows, A, unknown_index;
 };
 
-template <int NPER>
+template <int NPER, bool GRAD>
 __global__ __launch_bounds__(THREADS) void answer_posterior_kernel(const AnswerPosteriorArgs p) {
     const int lane = threadIdx.x;
     const int g = blockIdx.x;
@@ -123,10 +135,50 @@ __global__ __launch_bounds__(THREADS) void answer_posterior_kernel(const AnswerP
     const float log_norm = score_normaliser(p.log_posterior, rows, lane, count, top);
     if (lane == 0) {
         p.log_evidence[g] = count > 0 ? top + log_norm : -INFINITY;
-        p.best_row[g] = count > 0 ? best : -1;
+        if constexpr (!GRAD) p.best_row[g] = count > 0 ? best : -1;
         if (p.support) p.support[g] = count;
         if (p.consistent_count) p.consistent_count[g] = consistent;
         if (p.first_consistent) p.first_consistent[g] = first_consistent;
+    }
+
+    // ---- sweep 4 (gradient mode): d(-log_evidence[g]) / d logits of every row of the group ----
+    if constexpr (GRAD) {
+        __syncthreads();  // (the posteriors sweep 3 stored, a lane per row, are visible to every lane of the wave)
+        float lp_nxt = -INFINITY;
+        if (start < end) {
+            load_columns<NPER>(p.logits + (size_t)start * A, A, lane, nxt);
+            lp_nxt = p.log_posterior[start];
+        }
+        for (int r = start; r < end; ++r) {
+#pragma unroll
+            for (int k = 0; k < NPER; ++k) z[k] = nxt[k];
+            const float lp = lp_nxt;
+            if (r + 1 < end) {
+                load_columns<NPER>(p.logits + (size_t)(r + 1) * A, A, lane, nxt);
+                lp_nxt = p.log_posterior[r + 1];
+            }
+            float* __restrict__ d_row = p.d_logits + (size_t)r * A;
+            // (a usable row has a finite maximum and a finite logit at the answer; every value here is wave-uniform)
+            const bool use = finite(lp) && p.w_a != 0.f;
+            float row_max = 0.f, log_z = 0.f, share = 0.f;
+            if (use) {
+                int at;
+                log_z = row_softmax_stats<NPER>(z, lane, row_max, at);
+                share = p.w_a * expf(lp);
+            }
+#pragma unroll
+            for (int k = 0; k < NPER; ++k) {
+                const int c = lane + WAVE * k;
+                if (c < A) {
+                    float d = 0.f;
+                    if (use && z[k] > -INFINITY) {  // (a logit of -inf: probability 0, gradient 0)
+                        const float prob = expf((z[k] - row_max) - log_z);  // (<= 1: both terms are <= 0)
+                        d = share * (prob - ((answer_known && c == answer_at) ? 1.f : 0.f));
+                    }
+                    d_row[c] = d;
+                }
+            }
+        }
     }
 }
 
@@ -139,15 +191,19 @@ extern "C" int pnmn_answer_posterior(const float* logits, const int32_t* valid, 
                                      int num_answers, int unknown_index, void* stream) {
     if (n_groups < 0 || n_rows < 0 || num_answers < 1) return PNMN_EINVAL;
     if (n_groups == 0) return 0;  // (nothing to read or to write)
-    if (!group_start || !answers || !log_posterior || !log_evidence || !best_row || (n_rows > 0 && !logits)) return PNMN_EINVAL;
+    // gradient mode: no best_row, and log_answer's place holds d_logits (refused until this mode existed: best_row was null)
+    const bool grad = !best_row && log_answer;
+    if (!group_start || !answers || !log_posterior || !log_evidence || (!best_row && !grad) || (n_rows > 0 && !logits))
+        return PNMN_EINVAL;
     if (!(fabsf(w_a) < INFINITY)) return PNMN_EINVAL;
     if (num_answers > MAX_COLUMNS) return PNMN_ESHAPE;
-    const AnswerPosteriorArgs a{logits, valid, log_weight, answers, group_start, w_a, log_answer, row_predictions, log_posterior,
-                                log_evidence, best_row, support, consistent_count, first_consistent, n_groups, n_rows, num_answers,
-                                unknown_index};
+    const AnswerPosteriorArgs a{logits, valid, log_weight, answers, group_start, w_a, grad ? nullptr : log_answer,
+                                grad ? log_answer : nullptr, row_predictions, log_posterior, log_evidence, best_row, support,
+                                consistent_count, first_consistent, n_groups, n_rows, num_answers, unknown_index};
     return with_nper(num_answers, [&](auto nper) {
-        hipLaunchKernelGGL(answer_posterior_kernel<decltype(nper)::value>, dim3((unsigned)n_groups), dim3(THREADS), 0,
-                           static_cast<hipStream_t>(stream), a);
+        constexpr int NPER = decltype(nper)::value;
+        const auto kernel = grad ? answer_posterior_kernel<NPER, true> : answer_posterior_kernel<NPER, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n_groups), dim3(THREADS), 0, static_cast<hipStream_t>(stream), a);
         return (int)hipGetLastError();
     });
 }

@@ -242,6 +242,54 @@ class _AnswerLoss(torch.autograd.Function):
         return dlogits * dloss.unsqueeze(1), None, None, None
 
 
+class _MarginalAnswerLoss(torch.autograd.Function):
+    """The marginal likelihood of each question's answer over its program hypotheses,
+        loss[g] = -log sum_r w_r p(a_g | z_r, image)^answer_weight       over the rows r of question g,
+    and d loss / d logits in ONE launch: ``pnmn_answer_posterior`` in gradient mode (include/probnmn_hip.h) -- a row's
+    cross-entropy gradient scaled by the row's posterior share.  ``logits`` fp32 [R, A], ``answers`` int64 [G], ``valid`` int32
+    [R], ``log_weights`` fp32 [R] or None (uniform), ``group_start`` int32 [G + 1] (``hypothesis_rows.group_start``: from 0 to
+    R, non-decreasing), all on the device.  Returns ``loss`` [G] -- ``INVALID_PROGRAM_LOSS``, without a gradient, where no
+    row of the question counts -- and, not differentiable, ``log_posterior`` fp32 [R], the rows' own answers int64 [R],
+    ``support`` and ``consistent_count`` int32 [G].  The weights get no gradient (the kernel has no slot for it): a
+    ``log_weights`` that requires one is an error."""
+
+    @staticmethod
+    def forward(ctx, logits, answers, valid, log_weights, group_start, answer_weight, unknown_index):
+        from probnmn import _hip
+
+        if log_weights is not None and ctx.needs_input_grad[3]:
+            raise ValueError("the marginal answer loss gives no gradient to log_weights (module training holds the program "
+                             "generator frozen): detach them")
+        logits = logits.contiguous()
+        R, A = logits.shape
+        G = answers.numel()
+        dev = logits.device
+        f, i = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        d_logits = torch.zeros(R, A, **f)  # (a row that no group covers is not written)
+        log_posterior, log_evidence = torch.full((R,), -float("inf"), **f), torch.empty(G, **f)
+        predictions = torch.full((R,), unknown_index, dtype=torch.long, device=dev)
+        support, consistent = torch.empty(G, **i), torch.empty(G, **i)
+        if R == 0 or G == 0:  # (no row anywhere: what the kernel writes for a group without rows)
+            log_evidence.fill_(-float("inf")), support.zero_(), consistent.zero_()
+        else:
+            _hip.check(_hip.lib().pnmn_answer_posterior(
+                logits.data_ptr(), valid.data_ptr(), 0 if log_weights is None else log_weights.data_ptr(), answers.data_ptr(),
+                group_start.data_ptr(), float(answer_weight), d_logits.data_ptr(), predictions.data_ptr(),
+                log_posterior.data_ptr(), log_evidence.data_ptr(), 0, support.data_ptr(), consistent.data_ptr(), 0, G, R, A,
+                unknown_index, _hip.stream_ptr(dev)), "answer_posterior (gradient mode)")
+        loss = torch.where(support > 0, -log_evidence, torch.full_like(log_evidence, INVALID_PROGRAM_LOSS))
+        # the question of every row: how many groups end at or before it
+        question_of_row = torch.searchsorted(group_start[1:].long(), torch.arange(R, device=dev), right=True).clamp_(max=max(G - 1, 0))
+        ctx.save_for_backward(d_logits, question_of_row)
+        ctx.mark_non_differentiable(log_posterior, predictions, support, consistent)
+        return loss, log_posterior, predictions, support, consistent
+
+    @staticmethod
+    def backward(ctx, dloss, *_):
+        d_logits, question_of_row = ctx.saved_tensors
+        return d_logits * dloss[question_of_row].unsqueeze(1), None, None, None, None, None, None
+
+
 class NeuralModuleNetwork(nn.Module):
     def __init__(
         self,
@@ -416,16 +464,11 @@ class NeuralModuleNetwork(nn.Module):
             output_dict["metrics"] = self.get_metrics(reset=True)
         return output_dict
 
-    def _hypothesis_logits(self, features, programs: torch.Tensor, question_rows, max_rows: int):
-        """The row loop of ``marginal_answers`` and ``answer_posterior``: their argument checks, then the NMN over the R
-        hypothesis rows in passes of at most ``max_rows``, each row reading its question's feature map where it lies
-        (``rows=`` / ``ResidentRows.subset``).  Returns (device, G, R, A, question_rows as host int64 [R], answer logits
-        fp32 [R, A], validity int32 [R] -- both on the device)."""
-        from probnmn import _hip, hypothesis_rows
-        from probnmn.data.feature_store import ResidentRows
+    def _hypothesis_arguments(self, features, programs: torch.Tensor, question_rows):
+        """The argument checks ``marginal_answers``, ``answer_posterior`` and ``marginal_answer_loss`` share.  Returns (device,
+        G, R, A, programs [R, T] on the host, question_rows as host int64 [R])."""
+        from probnmn import hypothesis_rows
 
-        if max_rows < 1:
-            raise ValueError("max_rows must be at least 1, got %r" % (max_rows,))
         dev = features.device
         G = int(features.size(0))
         programs = programs.detach().cpu()
@@ -434,7 +477,36 @@ class NeuralModuleNetwork(nn.Module):
         if programs.dim() != 2 or programs.size(0) != R or qrows.ndim != 1:
             raise ValueError("programs [R, T] and question_rows [R]; got %s and %s" % (tuple(programs.shape), qrows.shape))
         hypothesis_rows.check(qrows, G)
-        A = self.classifier[6].out_features
+        return dev, G, R, self.classifier[6].out_features, programs, qrows
+
+    @staticmethod
+    def _given_answers(features, answers, answer_weight):
+        """The ``answers`` / ``answer_weight`` checks of ``answer_posterior`` and ``marginal_answer_loss``: (the weight as a
+        finite float, the given answers as a detached integer tensor [G])."""
+        import math
+
+        try:
+            w_a = float(answer_weight)
+        except (TypeError, ValueError):
+            raise ValueError("answer_weight must be a finite number, got %r" % (answer_weight,))
+        if not math.isfinite(w_a):
+            raise ValueError("answer_weight must be a finite number, got %r" % (answer_weight,))
+        given = torch.as_tensor(answers).detach()
+        if given.dim() != 1 or given.size(0) != int(features.size(0)) or given.dtype.is_floating_point or given.dtype == torch.bool:
+            raise ValueError("answers int64 [%d]; got %s %s" % (int(features.size(0)), given.dtype, tuple(given.shape)))
+        return w_a, given
+
+    def _hypothesis_logits(self, features, programs: torch.Tensor, question_rows, max_rows: int):
+        """The row loop of ``marginal_answers`` and ``answer_posterior``: their argument checks, then the NMN over the R
+        hypothesis rows in passes of at most ``max_rows``, each row reading its question's feature map where it lies
+        (``rows=`` / ``ResidentRows.subset``).  Returns (device, G, R, A, question_rows as host int64 [R], answer logits
+        fp32 [R, A], validity int32 [R] -- both on the device)."""
+        from probnmn import _hip
+        from probnmn.data.feature_store import ResidentRows
+
+        if max_rows < 1:
+            raise ValueError("max_rows must be at least 1, got %r" % (max_rows,))
+        dev, G, R, A, programs, qrows = self._hypothesis_arguments(features, programs, question_rows)
         logits = torch.empty(R, A, dtype=torch.float32, device=dev)
         valid = torch.empty(R, dtype=torch.int32, device=dev)
         resident = isinstance(features, ResidentRows)
@@ -511,19 +583,9 @@ class NeuralModuleNetwork(nn.Module):
         hypothesis counts), ``"best_row"`` int32 [G] (the MAP hypothesis's row, first of equals; -1 there),
         ``"first_consistent_row"`` int32 [G] (the first counting hypothesis whose own answer is the given one; -1 when there
         is none), ``"consistent_count"`` int32 [G] (how many there are) and ``"support"`` int32 [G] (how many count)."""
-        import math
-
         from probnmn import _hip, hypothesis_rows
 
-        try:
-            w_a = float(answer_weight)
-        except (TypeError, ValueError):
-            raise ValueError("answer_weight must be a finite number, got %r" % (answer_weight,))
-        if not math.isfinite(w_a):
-            raise ValueError("answer_weight must be a finite number, got %r" % (answer_weight,))
-        given = torch.as_tensor(answers).detach()
-        if given.dim() != 1 or given.size(0) != int(features.size(0)) or given.dtype.is_floating_point or given.dtype == torch.bool:
-            raise ValueError("answers int64 [%d]; got %s %s" % (int(features.size(0)), given.dtype, tuple(given.shape)))
+        w_a, given = self._given_answers(features, answers, answer_weight)
         dev, G, R, A, qrows, logits, valid = self._hypothesis_logits(features, programs, question_rows, max_rows)
         weights = None if log_weights is None else hypothesis_rows.row_vector(log_weights, "log_weights", R, dev)
         given = given.to(device=dev, dtype=torch.long).contiguous()
@@ -545,6 +607,56 @@ class NeuralModuleNetwork(nn.Module):
             out["consistent_count"].data_ptr(), out["first_consistent_row"].data_ptr(), G, R, A, self._unknown_answer,
             _hip.stream_ptr(dev)), "answer_posterior")
         return out
+
+    def marginal_answer_loss(self, features, programs: torch.Tensor, question_rows, answers, log_weights=None,
+                             answer_weight: float = 1.0):
+        """The marginal likelihood of every question's answer over its program hypotheses, as a loss to TRAIN the modules on
+        (the maximum marginal likelihood objective of weakly supervised semantic parsing; not in the reference, which pays
+        the cross entropy of one sampled program: nmn.py:245-269):
+            loss[g] = -log sum_r w_r p(a_g | z_r, image)^answer_weight        over the hypothesis rows r of question g
+        with w_r the renormalised weight of a hypothesis.  Its gradient reaches a row's answer logits as that row's
+        cross-entropy gradient scaled by its posterior share p(z_r | x, a, image): a hypothesis that explains the answer is
+        trained on, one that does not is left alone.
+
+        ``features``, ``programs`` [R, T], ``question_rows`` [R], ``answers`` [G], ``log_weights`` [R], ``answer_weight``: the
+        arguments of ``answer_posterior``, under its rules.  The weights receive NO gradient (a ``log_weights`` tensor that
+        requires one is a ``ValueError``): the candidate set and its weights are given.
+
+        The NMN runs over the R hypothesis rows in ONE pass with gradient tracking -- there is no ``max_rows``: the engine
+        has one activation arena and backward needs it intact -- each row reading its question's feature map where it lies
+        (``rows=`` / ``ResidentRows.subset``; the stem runs once per hypothesis row); then ONE ``pnmn_answer_posterior``
+        launch in gradient mode gives the loss and d loss / d logits.  No metric moves, and the ``train()`` / ``eval()``
+        state is not touched.
+
+        Returns ``"loss"`` fp32 [G] (differentiable; ``INVALID_PROGRAM_LOSS`` = 3.33, without a gradient, for a question
+        none of whose hypotheses counts) and, detached, ``"log_posterior"`` fp32 [R] (-inf for a hypothesis that does not
+        count), ``"hypothesis_predictions"`` int64 [R], ``"support"`` and ``"consistent_count"`` int32 [G]."""
+        from probnmn import _hip, hypothesis_rows
+        from probnmn.data.feature_store import ResidentRows
+
+        w_a, given = self._given_answers(features, answers, answer_weight)
+        if torch.is_tensor(log_weights) and log_weights.requires_grad:
+            raise ValueError("marginal_answer_loss gives no gradient to log_weights (the candidate set and its weights are "
+                             "given): detach them")
+        dev, G, R, A, programs, qrows = self._hypothesis_arguments(features, programs, question_rows)
+        weights = None if log_weights is None else hypothesis_rows.row_vector(log_weights, "log_weights", R, dev)
+        if R == 0 or G == 0:  # (no row anywhere: nothing to run the network on, every question pays the constant)
+            i = dict(dtype=torch.int32, device=dev)
+            return {"loss": torch.full((G,), INVALID_PROGRAM_LOSS, dtype=torch.float32, device=dev),
+                    "log_posterior": torch.empty(0, dtype=torch.float32, device=dev),
+                    "hypothesis_predictions": torch.empty(0, dtype=torch.long, device=dev),
+                    "support": torch.zeros(G, **i), "consistent_count": torch.zeros(G, **i)}
+        given = given.to(device=dev, dtype=torch.long).contiguous()
+        group_start = hypothesis_rows.group_start_on_device(qrows, G, dev)
+        if isinstance(features, ResidentRows):
+            trunk = self.forward_trunk(features.subset(qrows), programs)
+        else:
+            trunk = self.forward_trunk(features, programs, rows=_hip.to_device(qrows, dev).view(torch.long))
+        logits, _, valid = self._answer_logits(trunk)
+        loss, log_posterior, predictions, support, consistent = _MarginalAnswerLoss.apply(
+            logits, given, valid, weights, group_start, w_a, self._unknown_answer)
+        return {"loss": loss, "log_posterior": log_posterior, "hypothesis_predictions": predictions, "support": support,
+                "consistent_count": consistent}
 
     def begin(self, features: torch.Tensor, rows: Optional[torch.Tensor] = None):
         """Launch the program-independent part of ``forward`` (feature layout + stem) ahead of time;
