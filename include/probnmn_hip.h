@@ -378,7 +378,33 @@ int pnmn_answer_marginal(const float* logits /* [n_rows][num_answers] */, const 
  * n_groups == 0 returns 0 without a launch.  PNMN_EINVAL, with no launch and no HIP call: n_groups < 0 or n_rows < 0; a
  * null group_start, log_posterior, log_evidence or best_row; logits without their tokens; x_logits, z_logits and log_q all
  * null; T < 1 or V < 1 of a term whose logits are given; a coefficient that is not finite.  Vx or Vz > 1024 (of a term
- * whose logits are given): PNMN_ESHAPE.
+ * whose logits are given): PNMN_ESHAPE.  The checks run in this order: the counts; then the empty case -- n_groups == 0
+ * returns 0 whatever else is given --; then the pointers, the sizes of the given terms and the coefficients; then the shape.
+ *
+ * GRADIENT MODE: best_row == NULL and at least one of log_px, log_pz != NULL.  The marginal-likelihood loss of group g over
+ * its candidate rows is -log_evidence[g] = -log sum_r p(x | z_r)^w_x p(z_r)^w_z q(z_r | x)^w_q; this mode computes it together
+ * with its gradient with respect to the logits of every sequence term -- a row's per-step cross-entropy gradient scaled by
+ * the row's posterior share.  The log_px slot is then read as d_x_logits, fp32 [n_rows][Tx][Vx], and requires x_logits; the
+ * log_pz slot is read as d_z_logits, fp32 [n_rows][Tz][Vz], and requires z_logits (PNMN_EINVAL otherwise).  lp_x and lp_z
+ * themselves are not reported and best_row is not written.  log_posterior, log_evidence and support keep their rules and
+ * are the same bits as a launch with best_row on the same inputs.  For a term k in {x, z} whose slot is given, over a
+ * second sweep of the group's rows, with share_k[r] = w_k * exp(log_posterior[r]):
+ *   d_k_logits[r][t][v] = share_k[r] * (softmax(k_logits[r][t])[v] - [v == tok_k[r][t]])   for a usable row r and a scored
+ *                         step t (tok_k[r][t] != pad_k)
+ *                       = d(-log_evidence[g]) / d k_logits[r][t][v]; a logit of -inf gets exactly 0
+ *   d_k_logits[r][t][v] = 0 exactly for every padding step of a covered row; for every step of a covered row that is not
+ *                         usable (a row with a token that is no index, whose lp is -inf, among them) -- so for every row of
+ *                         a group without support --; and for every covered row of a term that does not enter the score
+ *                         (w_k exactly 0), whose logits are then not read
+ * A row that no group covers is not written; the target's column is found by comparing v, never by indexing with an
+ * unchecked token.  A group's d_logits rows depend only on its own rows in their order: the same bits alone or inside a
+ * batch, and from run to run.  One launch, no LDS, no atomics, no wait on another workgroup; every wavefront of the
+ * workgroup reaches both of its barriers.  The checks, their order and their codes are those above with "best_row" read as
+ * "best_row or (in its absence) a log_px / log_pz slot": log_posterior and log_evidence remain required.  No call that was
+ * accepted before this mode existed changes its meaning or its bits: every such call passed a best_row, and a call without
+ * one was refused with PNMN_EINVAL -- a call with none of best_row, log_px and log_pz still is.  The derivative with respect
+ * to log_q, d(-log_evidence[g]) / d log_q[r] = -w_q * exp(log_posterior[r]), is a function of an output and has no slot:
+ * the caller forms it.
  * ------------------------------------------------------------------------------------------- */
 int pnmn_hypothesis_posterior(const float* x_logits /* [n_rows][Tx][Vx], may be NULL */, const int64_t* x_tokens /* [n_rows] rows of Tx */,
                               int64_t x_token_stride, const float* z_logits /* [n_rows][Tz][Vz], may be NULL */,

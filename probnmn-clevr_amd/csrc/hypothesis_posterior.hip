@@ -21,6 +21,19 @@
 //               overlap, and the next U steps' logits are loaded before these are reduced
 //   score       the wave's lane 0 writes score[r] into log_posterior[r]; ONE __syncthreads(); wave 0 then sweeps the group's
 //               scores (64 at a time): the usable rows, the largest score and its first row; then score_normaliser()
+//
+// GRADIENT MODE (pnmn_hypothesis_posterior without best_row and with a log_px / log_pz pointer, which is then d_x_logits
+// [n_rows][Tx][Vx] / d_z_logits [n_rows][Tz][Vz]): the same kernel body with GRAD set -- so the outputs the two modes share
+// are the same bits -- and one more sweep.  The loss of a group is -log_evidence[g]; its gradient with respect to a row's
+// logits of term k is the row's per-step cross-entropy gradient scaled by the row's posterior share:
+//   barriers    NO wave returns before the second __syncthreads(): waves 1..7 skip wave 0's epilogue and wait at it, so the
+//               posteriors wave 0 stored (a lane per row) are visible to every wave
+//   sweep       every wave takes ITS OWN rows again (w, w + 8, ...; the logits are in L2): share_k = w_k exp(log_posterior[r]);
+//               a row that is not usable, and every row of a term that does not enter the score, is one run of zeros; of a
+//               usable row the scored steps go U at a time as in row_log_likelihood() -- the same maximum and sum, the next
+//               U steps' logits loaded before these are reduced -- and d[t][v] = share_k (softmax_v - [v == token]) leaves as
+//               one coalesced segment per register column, the target's column found by comparing v, never by indexing;
+//               the padding steps leave as zeros the same way.  No word outside the group's clamped rows is touched.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -42,6 +55,7 @@ struct Term {  // one likelihood term: teacher-forced logits and the tokens they
     const int64_t* tokens;  // row r at tokens + r * stride, T entries
     int64_t stride;
     float* out;             // [n_rows] or null
+    float* d;               // gradient mode: [n_rows][T][V] or null (it arrives in out's place)
     float w;
     int T, V, pad;
     bool scored;            // the term enters the score (logits given and w != 0)
@@ -143,7 +157,100 @@ __device__ float row_log_likelihood(const Term& k, int r, int lane) {
     return lp;
 }
 
-template <int NPER>
+// Gradient mode: d(-log_evidence[g]) / d logits of row r's term k into k.d, every one of the row's T * V words written.
+// `use`: the row is usable and the term enters the score (wave-uniform); share = w_k exp(log_posterior[r]).  A row that is
+// not used is one run of zeros and its logits are not read.  Of a used row the scored steps are taken U at a time exactly as
+// row_log_likelihood() takes them (the same maximum and the same sum of exponentials, so log softmax is the one the score was
+// built from), and each leaves as one coalesced segment per register column; the target's column is found by comparing v.
+// A logit of -inf gets exactly 0; the padding steps leave as zeros.
+template <int NPER, int U>
+__device__ void row_gradient(const Term& k, int r, int lane, bool use, float share) {
+    const int T = k.T, V = k.V;
+    float* __restrict__ d_row = k.d + (size_t)r * T * V;
+    if (!use) {
+        for (size_t i = lane; i < (size_t)T * V; i += WAVE) d_row[i] = 0.f;
+        return;
+    }
+    const float* row = k.logits + (size_t)r * T * V;
+    const int64_t* tok = k.tokens + (int64_t)r * k.stride;
+    for (int t0 = 0; t0 < T; t0 += WAVE) {
+        const bool inside = t0 + lane < T;
+        int mine = -1;  // (as in row_log_likelihood)
+        if (inside) {
+            const int64_t t = tok[t0 + lane];
+            mine = t == (int64_t)k.pad ? -1 : (t < 0 || t >= (int64_t)V) ? -2 : (int)t;
+        }
+        // (a usable row has no token that is no index; rows that malformed bounds let two groups share may: such a step is
+        // written as zeros, and its token is never an index)
+        uint64_t steps = __ballot(mine >= 0);
+        uint64_t zeros = __ballot(inside && mine < 0);
+        float* __restrict__ d_block = d_row + (size_t)t0 * V;
+        while (zeros) {
+            const int s = __ffsll((unsigned long long)zeros) - 1;
+            zeros &= zeros - 1;
+#pragma unroll
+            for (int j = 0; j < NPER; ++j) {
+                const int c = lane + WAVE * j;
+                if (c < V) d_block[(size_t)s * V + c] = 0.f;
+            }
+        }
+        const float* block = row + (size_t)t0 * V;
+        int step[U], ahead[U];
+        float z[U][NPER], nxt[U][NPER];
+        take_steps<NPER, U>(steps, block, V, lane, ahead, nxt);
+        while (ahead[0] >= 0) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                step[u] = ahead[u];
+#pragma unroll
+                for (int j = 0; j < NPER; ++j) z[u][j] = nxt[u][j];
+            }
+            take_steps<NPER, U>(steps, block, V, lane, ahead, nxt);
+            float top[U], se[U];
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                top[u] = z[u][0];
+#pragma unroll
+                for (int j = 1; j < NPER; ++j) top[u] = fmaxf(top[u], z[u][j]);
+            }
+#pragma unroll
+            for (int d = 1; d < WAVE; d <<= 1)
+#pragma unroll
+                for (int u = 0; u < U; ++u) top[u] = fmaxf(top[u], __shfl_xor(top[u], d, WAVE));
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                se[u] = 0.f;
+#pragma unroll
+                for (int j = 0; j < NPER; ++j) se[u] += expf(z[u][j] - top[u]);
+            }
+#pragma unroll
+            for (int d = 1; d < WAVE; d <<= 1)
+#pragma unroll
+                for (int u = 0; u < U; ++u) se[u] += __shfl_xor(se[u], d, WAVE);
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                if (step[u] < 0) continue;
+                const int token = __builtin_amdgcn_readlane(mine, step[u]);
+                const float log_z = logf(se[u]);
+                float* __restrict__ d_step = d_block + (size_t)step[u] * V;
+#pragma unroll
+                for (int j = 0; j < NPER; ++j) {
+                    const int c = lane + WAVE * j;
+                    if (c < V) {
+                        float g = 0.f;
+                        if (z[u][j] > -INFINITY) {  // (a logit of -inf: probability 0, gradient 0)
+                            const float prob = expf((z[u][j] - top[u]) - log_z);  // (<= 1: both terms are <= 0)
+                            g = share * (prob - (c == token ? 1.f : 0.f));
+                        }
+                        d_step[c] = g;
+                    }
+                }
+            }
+        }
+    }
+}
+
+template <int NPER, bool GRAD>
 __global__ __launch_bounds__(THREADS) void hypothesis_posterior_kernel(const PosteriorArgs p) {
     constexpr int U = NPER <= 2 ? 8 : 16 / NPER;  // steps in flight per wave: at most 16 registers of logits, twice
     const int lane = threadIdx.x & (WAVE - 1);
@@ -169,25 +276,41 @@ __global__ __launch_bounds__(THREADS) void hypothesis_posterior_kernel(const Pos
         if (lane == 0) p.log_posterior[r] = score;
     }
     __syncthreads();  // (workgroup scope: the scores the other waves stored are visible to wave 0)
-    if (wave != 0) return;
+    if constexpr (!GRAD) {
+        if (wave != 0) return;
+    }
 
     // ---- wave 0: the group's usable rows, the largest score and its first row ----
-    int count = 0, at = 0x7fffffff;
-    float top = -INFINITY;
-    for (int r = start + lane; r < end; r += WAVE) {
-        const float s = p.log_posterior[r];
-        if (finite(s)) {
-            ++count;
-            if (s > top || at == 0x7fffffff) top = s, at = r;  // (rows grow: the lane's first maximum)
+    if (!GRAD || wave == 0) {  // (gradient mode: the other waves go on to the second barrier, none returns before it)
+        int count = 0, at = 0x7fffffff;
+        float top = -INFINITY;
+        for (int r = start + lane; r < end; r += WAVE) {
+            const float s = p.log_posterior[r];
+            if (finite(s)) {
+                ++count;
+                if (s > top || at == 0x7fffffff) top = s, at = r;  // (rows grow: the lane's first maximum)
+            }
+        }
+        count = wave_sum(count);
+        wave_argmax(top, at);  // (a lane without a usable row holds (-inf, int max) and never wins a tie)
+        const float log_norm = score_normaliser(p.log_posterior, rows, lane, count, top);
+        if (lane == 0) {
+            p.log_evidence[g] = count > 0 ? top + log_norm : -INFINITY;
+            if constexpr (!GRAD) p.best_row[g] = count > 0 ? at : -1;
+            if (p.support) p.support[g] = count;
         }
     }
-    count = wave_sum(count);
-    wave_argmax(top, at);  // (a lane without a usable row holds (-inf, int max) and never wins a tie)
-    const float log_norm = score_normaliser(p.log_posterior, rows, lane, count, top);
-    if (lane == 0) {
-        p.log_evidence[g] = count > 0 ? top + log_norm : -INFINITY;
-        p.best_row[g] = count > 0 ? at : -1;
-        if (p.support) p.support[g] = count;
+
+    // ---- gradient mode, every wave: d(-log_evidence[g]) / d logits of its rows ----
+    if constexpr (GRAD) {
+        __syncthreads();  // (the posteriors wave 0 stored, a lane per row, are visible to every wave; all 512 threads arrive)
+        for (int r = start + wave; r < end; r += WAVES) {
+            const float lp = p.log_posterior[r];
+            const bool use = finite(lp);  // (wave-uniform; -inf for a row that is not usable, so for a group without support)
+            const float weight = use ? expf(lp) : 0.f;
+            if (p.x.d) row_gradient<NPER, U>(p.x, r, lane, use && p.x.scored, p.x.w * weight);
+            if (p.z.d) row_gradient<NPER, U>(p.z, r, lane, use && p.z.scored, p.z.w * weight);
+        }
     }
 }
 
@@ -201,7 +324,11 @@ extern "C" int pnmn_hypothesis_posterior(const float* x_logits, const int64_t* x
                                          int Tx, int Vx, int Tz, int Vz, void* stream) {
     if (n_groups < 0 || n_rows < 0) return PNMN_EINVAL;
     if (n_groups == 0) return 0;  // (nothing to read or to write)
-    if (!group_start || !log_posterior || !log_evidence || !best_row) return PNMN_EINVAL;
+    // gradient mode: no best_row, and log_px's / log_pz's place holds d_x_logits / d_z_logits (refused until this mode
+    // existed: best_row was null)
+    const bool grad = !best_row && (log_px || log_pz);
+    if (!group_start || !log_posterior || !log_evidence || (!best_row && !grad)) return PNMN_EINVAL;
+    if (grad && ((log_px && !x_logits) || (log_pz && !z_logits))) return PNMN_EINVAL;
     if ((x_logits && !x_tokens) || (z_logits && !z_tokens) || (!x_logits && !z_logits && !log_q)) return PNMN_EINVAL;
     if ((x_logits && (Tx < 1 || Vx < 1)) || (z_logits && (Tz < 1 || Vz < 1))) return PNMN_EINVAL;
     if (!(fabsf(w_x) < INFINITY) || !(fabsf(w_z) < INFINITY) || !(fabsf(w_q) < INFINITY)) return PNMN_EINVAL;
@@ -209,8 +336,13 @@ extern "C" int pnmn_hypothesis_posterior(const float* x_logits, const int64_t* x
     PosteriorArgs a;
     // (a term that neither enters the score nor is asked for is not computed)
     const bool score_x = x_logits && w_x != 0.f, score_z = z_logits && w_z != 0.f;
-    a.x = Term{score_x || log_px ? x_logits : nullptr, x_tokens, x_token_stride, log_px, w_x, Tx, Vx, pad_x, score_x};
-    a.z = Term{score_z || log_pz ? z_logits : nullptr, z_tokens, z_token_stride, log_pz, w_z, Tz, Vz, pad_z, score_z};
+    if (grad) {  // (lp_x and lp_z are not reported; a term that does not enter the score is not read, its gradient is zeros)
+        a.x = Term{score_x ? x_logits : nullptr, x_tokens, x_token_stride, nullptr, log_px, w_x, Tx, Vx, pad_x, score_x};
+        a.z = Term{score_z ? z_logits : nullptr, z_tokens, z_token_stride, nullptr, log_pz, w_z, Tz, Vz, pad_z, score_z};
+    } else {
+        a.x = Term{score_x || log_px ? x_logits : nullptr, x_tokens, x_token_stride, log_px, nullptr, w_x, Tx, Vx, pad_x, score_x};
+        a.z = Term{score_z || log_pz ? z_logits : nullptr, z_tokens, z_token_stride, log_pz, nullptr, w_z, Tz, Vz, pad_z, score_z};
+    }
     a.log_q = log_q;
     a.w_q = log_q ? w_q : 0.f;
     a.group_start = group_start;
@@ -221,8 +353,9 @@ extern "C" int pnmn_hypothesis_posterior(const float* x_logits, const int64_t* x
     a.n_groups = n_groups;
     a.n_rows = n_rows;
     return with_nper(std::max(a.x.logits ? Vx : 1, a.z.logits ? Vz : 1), [&](auto nper) {
-        hipLaunchKernelGGL(hypothesis_posterior_kernel<decltype(nper)::value>, dim3((unsigned)n_groups), dim3(THREADS), 0,
-                           static_cast<hipStream_t>(stream), a);
+        constexpr int NPER = decltype(nper)::value;
+        const auto kernel = grad ? hypothesis_posterior_kernel<NPER, true> : hypothesis_posterior_kernel<NPER, false>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)n_groups), dim3(THREADS), 0, static_cast<hipStream_t>(stream), a);
         return (int)hipGetLastError();
     });
 }

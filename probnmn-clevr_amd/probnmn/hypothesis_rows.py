@@ -4,8 +4,8 @@ is what ``group_hypotheses`` returns and what ``pnmn_answer_marginal``, ``pnmn_h
 ``pnmn_answer_posterior`` read as ``group_start`` [G + 1]: question g owns rows group_start[g] .. group_start[g + 1].
 ``NeuralModuleNetwork.marginal_answers`` / ``answer_posterior`` and ``evaluators.hypothesis_posterior`` take their arguments
 through here.  ``queue_hypotheses`` / ``awaited_hypotheses`` are the two stages that turn a generator pass into such rows --
-the evaluators (``probnmn.evaluators``) and marginal-likelihood module training (``probnmn.trainers.module_training``) share
-them.  Of the layout functions only ``group_start_on_device`` and ``row_vector`` touch a device."""
+the evaluators (``probnmn.evaluators``), marginal-likelihood module training (``probnmn.trainers.module_training``) and joint
+marginal-likelihood training (``probnmn.trainers.marginal_training``) share them.  Of the layout functions only ``group_start_on_device`` and ``row_vector`` touch a device."""
 from typing import Any, Dict
 
 import numpy as np

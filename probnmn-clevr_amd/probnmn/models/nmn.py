@@ -658,6 +658,39 @@ class NeuralModuleNetwork(nn.Module):
         return {"loss": loss, "log_posterior": log_posterior, "hypothesis_predictions": predictions, "support": support,
                 "consistent_count": consistent}
 
+    def answer_log_likelihood(self, features, programs: torch.Tensor, question_rows, answers):
+        """log p(a_g | z_r, image_g) of every hypothesis row r of question g, WITH a graph: what a loss over a question's
+        candidate programs that also trains the program generator (``sequence_marginal_loss``, ``MarginalJointStep``) takes
+        as a row's answer term (not in the reference, which scores one sampled program per question: nmn.py:245-269).
+
+        ``features``, ``programs`` [R, T], ``question_rows`` [R], ``answers`` [G]: the arguments of ``marginal_answer_loss``,
+        under its rules.  The NMN runs over the R hypothesis rows in ONE pass with gradient tracking, as there: each row
+        reads its question's feature map where it lies, the stem runs once per hypothesis row.  The row's value is the
+        negative of the loss ``forward`` computes for that program and its question's answer (``pnmn_answer_loss``: the
+        same launch, the same gradient); a row whose program is invalid gets -inf and no gradient -- it is no candidate.
+        No metric moves, and the ``train()`` / ``eval()`` state is not touched.
+
+        Returns ``"log_answer"`` fp32 [R] (differentiable) and, detached, ``"hypothesis_predictions"`` int64 [R] (each
+        hypothesis's own answer; @@UNKNOWN@@ for an invalid program)."""
+        from probnmn import _hip
+        from probnmn.data.feature_store import ResidentRows
+
+        _, given = self._given_answers(features, answers, 1.0)
+        dev, G, R, A, programs, qrows = self._hypothesis_arguments(features, programs, question_rows)
+        if R == 0 or G == 0:  # (no row anywhere: nothing to run the network on)
+            return {"log_answer": torch.empty(0, dtype=torch.float32, device=dev),
+                    "hypothesis_predictions": torch.empty(0, dtype=torch.long, device=dev)}
+        rows_dev = _hip.to_device(qrows, dev).view(torch.long)
+        row_answers = given.to(device=dev, dtype=torch.long).index_select(0, rows_dev).contiguous()
+        if isinstance(features, ResidentRows):
+            trunk = self.forward_trunk(features.subset(qrows), programs)
+        else:
+            trunk = self.forward_trunk(features, programs, rows=rows_dev)
+        logits, _, valid = self._answer_logits(trunk)
+        loss, predictions = _AnswerLoss.apply(logits, row_answers, valid, self._unknown_answer)
+        log_answer = torch.where(valid != 0, -loss, torch.full_like(loss, -float("inf")))
+        return {"log_answer": log_answer, "hypothesis_predictions": predictions}
+
     def begin(self, features: torch.Tensor, rows: Optional[torch.Tensor] = None):
         """Launch the program-independent part of ``forward`` (feature layout + stem) ahead of time;
         pass the returned token as ``forward(..., started=token)`` with the same ``features``.  ``rows`` (int64

@@ -1593,8 +1593,8 @@ class Seq2SeqBase(nn.Module):
             return None, torch.cat(step_logits, 1), None
         return torch.cat(step_predictions, 1), torch.cat(step_logits, 1), torch.cat(step_logprobs, 1)
 
-    @torch.no_grad()
-    def teacher_forced_logits(self, source_tokens: torch.LongTensor, target_tokens: torch.LongTensor):
+    def teacher_forced_logits(self, source_tokens: torch.LongTensor, target_tokens: torch.LongTensor, *,
+                              differentiable: bool = False):
         """The teacher-forced distributions of ``target_tokens`` given ``source_tokens``, for SCORING: (logits [R, T, V],
         targets [R, T]), ``targets`` being the ``tgt[:, 1:]`` that ``decode`` scores them against (the targets after their
         @start@, @end@ behind the last one, padding after) -- log p(target | source) is the sum over the non-padding targets
@@ -1603,7 +1603,35 @@ class Seq2SeqBase(nn.Module):
         An inference pass that leaves the model as it was, unlike ``decode(state, targets)`` in ``eval()`` mode: no loss, no
         predictions drawn from the distributions, no metric (perplexity, accuracy, BLEU) touched, no seed drawn from the
         torch generator, no graph, the encoder without its dropout whatever the mode (``encode(dropout=False)``).  The
-        persistent decoder kernels of ``decode`` on their shapes; step by step (``_decode_stepwise``) on the others."""
+        persistent decoder kernels of ``decode`` on their shapes; step by step (``_decode_stepwise``) on the others.
+
+        ``differentiable=True``: the same logits WITH a graph, to train the model on a loss of its sequence scores
+        (``sequence_marginal_loss``): the persistent decoder runs through the autograd node ``decode`` uses for teacher
+        forcing (``_AttnLSTMDecoderGroup``, then ``linear_rows``), step by step on the other shapes, and the encoder's
+        dropout follows the module's mode as in ``forward`` (``train()`` mode with LSTM dropout draws one seed; in ``eval()``
+        mode the logits are the plain call's).  Still no loss, no predictions, no metric and no BLEU."""
+        if differentiable:
+            return self._teacher_forced_logits_with_graph(source_tokens, target_tokens)
+        with torch.no_grad():
+            return self._teacher_forced_logits(source_tokens, target_tokens)
+
+    def _teacher_forced_logits_with_graph(self, source_tokens, target_tokens):
+        state = self.encode(source_tokens)
+        tgt = _TokenPrep.run(target_tokens, self._pad_index, self._start_index, self._end_index, drop_first=False,
+                             want_mask=False)[0]
+        enc, h, fmask = state["enc"], state["h"], state["fmask"]
+        proj = self._output_projection_layer
+        if h.size(1) == 256 and enc.size(1) <= 64 and proj.weight.size(0) <= 128:
+            prep = self._fused_prep(state, tgt, False, 0, self._derived())
+            hs, _ = _AttnLSTMDecoderGroup.apply(*_prep_tensors(prep), [prep["meta"]], None)
+            logits = linear_rows(hs, proj.weight, proj.bias)
+        else:
+            _note_slow_path("decoder", "hidden size %d, %d source positions, %d target tokens (the persistent decoder kernel is "
+                            "built for 256 / <= 64 / <= 128)" % (h.size(1), enc.size(1), proj.weight.size(0)))
+            logits = self._decode_stepwise(enc, fmask, h, torch.zeros_like(h), tgt, tgt.size(1) - 1, True, 0, choose=False)[1]
+        return logits, tgt[:, 1:]
+
+    def _teacher_forced_logits(self, source_tokens, target_tokens):
         state = self.encode(source_tokens, dropout=False)
         tgt = _TokenPrep.run(target_tokens, self._pad_index, self._start_index, self._end_index, drop_first=False,
                              want_mask=False)[0]

@@ -1,0 +1,12 @@
+"""The training iterations.  Each lives in its own module; ``MarginalJointStep`` is also reachable from here (resolved on
+first use, so importing the package stays as cheap as it was)."""
+
+__all__ = ["MarginalJointStep"]
+
+
+def __getattr__(name):
+    if name == "MarginalJointStep":
+        from .marginal_training import MarginalJointStep
+
+        return MarginalJointStep
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
