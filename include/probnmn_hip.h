@@ -105,10 +105,12 @@ int pnmn_conv_nhwc_cus(const pnmn_conv_item* items, int n_items, int H, int W, i
 /* Kernel launches one pnmn_conv_nhwc call with these sizes makes (1 since round 3: the segments of different splits
  * go out as one launch; 0 for an empty call or an unsupported map size) -- for per-launch accounting. */
 int pnmn_conv_nhwc_launches(int n_items, int H, int W, int cin_chunks, int ntaps, int cout_blocks);
-/* Tuning / test hook: every later convolution launch of this process uses ONE split -- 1, 2, 4 or 8 workgroups per
- * (item, 128-channel output block), each computing 128/split output channels; the results do not depend on it (every
- * output sums all its input channels in one wave, in one order).  0 = the launch planner decides again.
- * Also settable as PNMN_CONV_KSPLIT before the first launch. */
+/* Tuning / test hook: every later convolution launch of this process uses ONE split -- 1, 2, 4, 6, 8, 14 or 26 workgroups
+ * per (item, 128-channel output block), which share its 128 output channels (and from 4 on its pixel tiles); 6, 14 and 26
+ * exist for 3x3 launches only: a 1x1 launch under one of them is planned as if none were forced.  The results do not
+ * depend on it (every output sums all its input channels in one wave, in one order).  0 = the launch planner decides
+ * again; any other value returns PNMN_EINVAL and changes nothing.  Also settable as PNMN_CONV_KSPLIT before the first
+ * launch. */
 int pnmn_conv_force_split(int split);
 
 /* ---------------------------------------------------------------------------------------------

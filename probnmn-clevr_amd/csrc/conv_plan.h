@@ -16,9 +16,10 @@ struct LaunchPlan {
     int split[3], count[3];
 };
 
-// One split for every launch (0 = the planner decides): PNMN_CONV_KSPLIT=<1|2|4|8> or pnmn_conv_force_split() --
-// scripts/conv_modes.py measures the splits with it, and tests/test_nmn_gpu.py pins each to show that the results do not
-// depend on the split.  One instance per library (inline, C++17).
+// One split for every launch (0 = the planner decides): PNMN_CONV_KSPLIT=<1|2|4|6|8|14|26> or pnmn_conv_force_split()
+// (6, 14 and 26 hold for 3x3 launches only: plan_launch plans a 1x1 launch itself under them) -- scripts/conv_modes.py
+// measures the splits with it, and tests/test_nmn_gpu.py and tests/test_conv_stream_gpu.py pin each to show that the
+// results do not depend on the split.  One instance per library (inline, C++17).
 inline int& forced_split() {
     static int forced = [] {
         const char* e = getenv("PNMN_CONV_KSPLIT");
