@@ -826,8 +826,9 @@ typedef struct pnmn_decoder_fwd_job {
     int32_t B, T, S, V, sample, pad_index, unk_index, start_index;
 } pnmn_decoder_fwd_job;    /* 184 bytes */
 /* The automaton rule: sampling and greedy decoding under a token automaton.  The free-running modes of pnmn_attn_lstm_fwd /
- * _fwd_group emit only strings the automaton accepts.  INFERENCE ONLY: a constrained draw is not a draw from the model's
- * distribution, and no trainer uses it.  The tables (token_class, next_state, min_left, n_states, n_classes, state 0 = start,
+ * _fwd_group emit only strings the automaton accepts.  A constrained draw is not a draw from the model's distribution q
+ * but from q_c, q renormalised over A_c step by step: a loss on such tokens is scored under q_c (pnmn_grammar_logits,
+ * include/probnmn_grammar.h, masks the logits to the same sets), never under the logprobs below.  The tables (token_class, next_state, min_left, n_states, n_classes, state 0 = start,
  * 255 = no completion) and the test of a candidate are those of pnmn_attn_lstm_beam below: HOST pointers, every entry checked,
  * passed by value in the launch arguments and staged into LDS once per workgroup -- no device allocation, no copy, no
  * synchronisation.
@@ -847,8 +848,9 @@ typedef struct pnmn_decoder_fwd_job {
  *   state:       unchanged on end_index, otherwise s <- next_state[s][token_class[token]]
  * By induction min_left[s] <= T - t before every step, so A_c is never empty, and every row, cut at its first end_index, is
  * accepted by the automaton.  With one state, one class and min_left = {0} a sampling pass emits what the unconstrained pass
- * emits up to and including each row's first end_index.  logprobs, and any loss built from the tokens, stay
- * log_softmax(z)[token] of the UNMODIFIED distribution, exactly as for the filtered draw.
+ * emits up to and including each row's first end_index.  logprobs, and the loss the inference decodes report, stay
+ * log_softmax(z)[token] of the UNMODIFIED distribution, exactly as for the filtered draw; the trainers that sample under the
+ * automaton take log_softmax over A_c instead (pnmn_grammar_logits), which is the distribution of the unfiltered draw.
  * A filter (null or the identity: the unfiltered draw) applies to sample == 1 within A_c, as stated.
  * pnmn_attn_lstm_fwd_group: the automaton applies to every job with sample != 0, which share one vocabulary size V; for a job
  * with sample == 0 it is checked as far as it can be without a vocabulary, and ignored.

@@ -1155,8 +1155,14 @@ class Seq2SeqBase(nn.Module):
         decode under the token automaton ``constraint`` (free running, inference only -- see ``decode_constrained``).
         ``beam_size`` is ignored by the other strategies; ``constraint`` (a token automaton) is required by the constrained
         strategies, optional for "beam" and refused by "sampling" / "greedy".  ``temperature``, ``top_k``, ``top_p``: the
-        sampling filter, "sampling" and "constrained_sampling" only (see ``decode``)."""
+        sampling filter, "sampling" and "constrained_sampling" only (see ``decode``).  "grammar_sampling": the TRAINING twin of
+        "sampling" under ``constraint`` (required) -- sampled, or teacher forced on ``target_tokens``, with a graph and the
+        encoder's dropout following the module's mode, scored under the grammar-normalised distribution (``decode_grammar``)."""
         self._check_filter(decoding_strategy, temperature, top_k, top_p)
+        if decoding_strategy == "grammar_sampling":
+            if constraint is None:
+                raise ValueError("decoding_strategy='grammar_sampling' needs constraint= (a token automaton)")
+            return self.decode_grammar(self.encode(source_tokens), constraint, target_tokens)
         if decoding_strategy in self.CONSTRAINED_STRATEGIES:
             self._check_constrained_arguments(target_tokens, constraint)
             with torch.no_grad():  # (the encoder without its dropout, as for "beam": the same in train() and eval() mode)
@@ -1227,7 +1233,8 @@ class Seq2SeqBase(nn.Module):
         paired and unpaired schedules sample the same programs from the same torch seed.  ``decoding_strategy="beam"``:
         ``decode_beam`` with ``beam_size`` (which the other strategies ignore) and ``constraint``.
         ``decoding_strategy="constrained_sampling"`` / ``"constrained_greedy"``: ``decode_constrained`` under ``constraint``
-        (required; "sampling" / "greedy" refuse one).
+        (required; "sampling" / "greedy" refuse one).  ``decoding_strategy="grammar_sampling"``: ``decode_grammar`` under
+        ``constraint`` (required), free running or teacher forced, with a graph; it takes no filter.
         ``temperature``, ``top_k``, ``top_p`` (``decoding_strategy="sampling"`` / ``"constrained_sampling"`` only; anything but
         (1, 0, 1) with another strategy is a ``ValueError``): the tokens -- the free-running decode's, and the predictions drawn from teacher-forced
         distributions -- are drawn from the distribution sharpened by the temperature and cut to its ``top_k`` most likely
@@ -1239,6 +1246,10 @@ class Seq2SeqBase(nn.Module):
             self._check_constrained_arguments(target_tokens, constraint)
             return self.decode_constrained(state, constraint, greedy=decoding_strategy == "constrained_greedy", seed=seed,
                                            temperature=temperature, top_k=top_k, top_p=top_p)
+        if decoding_strategy == "grammar_sampling":
+            if constraint is None:
+                raise ValueError("decoding_strategy='grammar_sampling' needs constraint= (a token automaton)")
+            return self.decode_grammar(state, constraint, target_tokens, seed=seed)
         if decoding_strategy == "beam":
             self._check_beam_arguments(target_tokens, beam_size)
             return self.decode_beam(state, beam_size, constraint=constraint)
@@ -1246,11 +1257,12 @@ class Seq2SeqBase(nn.Module):
             self._check_beam_arguments(target_tokens, beam_size, decoding_strategy)
             return self.decode_stochastic_beam(state, beam_size, seed=seed, constraint=constraint)
         if constraint is not None:
-            raise ValueError("constraint: decoding_strategy='beam', 'stochastic_beam', 'constrained_sampling' and "
-                             "'constrained_greedy' decode under a token automaton; %r does not" % (decoding_strategy,))
+            raise ValueError("constraint: decoding_strategy='beam', 'stochastic_beam', 'constrained_sampling', "
+                             "'constrained_greedy' and 'grammar_sampling' decode under a token automaton; %r does not"
+                             % (decoding_strategy,))
         if decoding_strategy not in ("sampling", "greedy"):
-            raise ValueError("decoding_strategy must be 'sampling', 'greedy', 'beam', 'stochastic_beam', 'constrained_sampling' "
-                             "or 'constrained_greedy'")
+            raise ValueError("decoding_strategy must be 'sampling', 'greedy', 'beam', 'stochastic_beam', 'constrained_sampling', "
+                             "'constrained_greedy' or 'grammar_sampling'")
         pad, bos, eos = self._pad_index, self._start_index, self._end_index
         enc, h, fmask = state["enc"], state["h"], state["fmask"]
         tgt = None
@@ -1332,7 +1344,8 @@ class Seq2SeqBase(nn.Module):
         uniforms are those of an unconstrained sampling decode from the same seed.
 
         INFERENCE ONLY, no graph, the same in ``train()`` and ``eval()`` mode: a constrained draw is not a draw from the
-        generator's distribution, so no trainer calls this.  Returns ``predictions`` [B, T] (trimmed: padding after a row's
+        generator's distribution, so no trainer calls this (a trainer samples AND scores under the automaton through
+        ``decode_grammar``, whose loss is under the distribution the draw comes from).  Returns ``predictions`` [B, T] (trimmed: padding after a row's
         first @end@) and ``loss`` [B], the length-normalised negative log-probability of the trimmed row as the sampling
         decode reports it -- ``log_softmax(z)[token]`` of the UNMODIFIED distribution, not of the restricted one.
         ``seed``: None draws ONE seed from the torch CPU generator, exactly as the sampling decode does; a greedy call
@@ -1364,6 +1377,66 @@ class Seq2SeqBase(nn.Module):
             prep["meta"]["filter"] = filt
         hs, raw = _AttnLSTMDecoderGroup.apply(*_prep_tensors(prep), [prep["meta"]], None)
         return self._finish(prep, hs, raw)[0]
+
+    # ---- training under a token automaton: the grammar-normalised distribution ---------------------------------------------
+    def decode_grammar(self, state: Dict[str, torch.Tensor], constraint, target_tokens: Optional[torch.LongTensor] = None,
+                       seed: Optional[int] = None) -> Dict[str, torch.Tensor]:
+        """``decoding_strategy="grammar_sampling"``: a decode WITH a graph on ``state`` as it is (the encoder's dropout as
+        ``encode`` applied it), scored under q_c -- the generator's step distributions renormalised over the allowed sets
+        of the token automaton ``constraint``, which is the distribution ``decode_constrained`` (unfiltered) draws from.
+        ``loss`` is then a differentiable function of the model that the REINFORCE and likelihood estimators of the
+        trainers may use with every sample a valid program (``probnmn.modules.grammar``).  The horizon of the rule is
+        ``max_decoding_steps`` in both modes, never the batch's padded length.
+
+        Without ``target_tokens``: the free-running sampled pass -- the launch ``decode_constrained`` makes, through the
+        autograd node of the sampling decode.  ``predictions`` [B, T] (trimmed) and ``loss`` [B] =
+        ``sequence_nll(grammar_logits(logits, raw)[0], raw, predictions, pad, 1e-12)``: the reference's length-normalised
+        negative log-probability, under q_c.  With ``target_tokens``: teacher forced, ``loss`` [B] the cross entropy of
+        ``decode`` over the masked logits (a target the grammar does not allow stays finite: it is added to its step's set,
+        and counted); no predictions are drawn.  Both return ``grammar_log_mass`` [B] (the sum over the row's scored steps
+        of the log share of the unconstrained step distribution inside the grammar: log q - log q_c of the row) and
+        ``grammar_outside`` [B] (int32: scored tokens outside their allowed set; 0 for every sampled row).
+
+        No metric is recorded.  One seed is drawn from the torch CPU generator when ``seed`` is None, exactly as "sampling"
+        draws it, teacher forced or not.  ``ValueError``: no constraint, tables of another vocabulary size, an automaton
+        whose shortest accepted string is longer than ``max_decoding_steps``.  Shapes outside the persistent kernels raise
+        ``NotImplementedError``."""
+        from probnmn.modules.grammar import check_horizon, grammar_logits, scored_log_mass
+
+        if constraint is None:
+            raise ValueError("decode_grammar needs a token automaton")
+        enc, h = state["enc"], state["h"]
+        proj = self._output_projection_layer
+        n_vocab, T = proj.weight.size(0), self._max_decoding_steps
+        tables = constraint_tables(constraint, n_vocab, self._end_index)
+        check_horizon(tables, T)
+        Hd = h.size(1)
+        if not (Hd == 256 and enc.size(1) <= 64 and n_vocab <= 128):
+            raise NotImplementedError("grammar_sampling: hidden size %d, %d source positions, %d target tokens -- it exists in the "
+                                      "persistent decoder kernels only (256 / <= 64 / <= 128)" % (Hd, enc.size(1), n_vocab))
+        pad, bos, eos = self._pad_index, self._start_index, self._end_index
+        tgt = None
+        if target_tokens is not None:
+            tgt = _TokenPrep.run(target_tokens, pad, bos, eos, drop_first=False, want_mask=False)[0]
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())  # CPU generator: no device sync
+        prep = self._fused_prep(state, tgt, False, seed, self._derived())
+        if tgt is None:
+            prep["meta"]["constraint"] = tables
+        hs, raw = _AttnLSTMDecoderGroup.apply(*_prep_tensors(prep), [prep["meta"]], None)
+        logits_all = linear_rows(hs, proj.weight, proj.bias)
+        if tgt is None:
+            predictions = self._trim_predictions(raw)
+            scored, weighted, eps = raw, predictions, 1e-12
+        else:
+            scored = weighted = tgt[:, 1:]
+            eps = 1e-13
+        masked, log_mass, outside = grammar_logits(logits_all, scored, tables, T, pad, self._unk_index, bos, eos)
+        out = {"loss": sequence_nll(masked, scored, weighted, pad, eps),
+               "grammar_log_mass": scored_log_mass(log_mass, weighted, pad), "grammar_outside": outside}
+        if tgt is None:
+            out["predictions"] = predictions
+        return out
 
     # ---- beam search (inference) ---------------------------------------------------------------------------------------
     BEAM_SIZES = (1, 2, 4, 8, 16)
@@ -1594,7 +1667,7 @@ class Seq2SeqBase(nn.Module):
         return torch.cat(step_predictions, 1), torch.cat(step_logits, 1), torch.cat(step_logprobs, 1)
 
     def teacher_forced_logits(self, source_tokens: torch.LongTensor, target_tokens: torch.LongTensor, *,
-                              differentiable: bool = False):
+                              differentiable: bool = False, constraint=None):
         """The teacher-forced distributions of ``target_tokens`` given ``source_tokens``, for SCORING: (logits [R, T, V],
         targets [R, T]), ``targets`` being the ``tgt[:, 1:]`` that ``decode`` scores them against (the targets after their
         @start@, @end@ behind the last one, padding after) -- log p(target | source) is the sum over the non-padding targets
@@ -1609,11 +1682,22 @@ class Seq2SeqBase(nn.Module):
         (``sequence_marginal_loss``): the persistent decoder runs through the autograd node ``decode`` uses for teacher
         forcing (``_AttnLSTMDecoderGroup``, then ``linear_rows``), step by step on the other shapes, and the encoder's
         dropout follows the module's mode as in ``forward`` (``train()`` mode with LSTM dropout draws one seed; in ``eval()``
-        mode the logits are the plain call's).  Still no loss, no predictions, no metric and no BLEU."""
-        if differentiable:
-            return self._teacher_forced_logits_with_graph(source_tokens, target_tokens)
-        with torch.no_grad():
-            return self._teacher_forced_logits(source_tokens, target_tokens)
+        mode the logits are the plain call's).  Still no loss, no predictions, no metric and no BLEU.
+
+        ``constraint`` (a token automaton): the logits come back masked to the allowed set of every step
+        (``probnmn.modules.grammar.grammar_logits`` along the targets, horizon ``max_decoding_steps``), in both calls:
+        ``log_softmax`` of them scores the targets under the grammar-normalised distribution q_c."""
+        with torch.set_grad_enabled(torch.is_grad_enabled() and differentiable):
+            if differentiable:
+                logits, targets = self._teacher_forced_logits_with_graph(source_tokens, target_tokens)
+            else:
+                logits, targets = self._teacher_forced_logits(source_tokens, target_tokens)
+            if constraint is not None:
+                from probnmn.modules.grammar import grammar_logits
+
+                logits = grammar_logits(logits, targets, constraint, self._max_decoding_steps, self._pad_index,
+                                        self._unk_index, self._start_index, self._end_index)[0]
+        return logits, targets
 
     def _teacher_forced_logits_with_graph(self, source_tokens, target_tokens):
         state = self.encode(source_tokens)

@@ -54,6 +54,15 @@ def _estimator(num_samples, baseline):
     return check_estimator(num_samples, baseline), baseline  # (the one rule: probnmn.modules.elbo)
 
 
+def check_constraint(constraint):
+    """The ``constraint`` argument of the trainers: None, or a token automaton (``ProgramCompiler.decoding_automaton``:
+    ``token_class``, ``next_state`` and ``min_left`` tables); ``ValueError`` for anything else.  Touches no model."""
+    if constraint is not None and not all(hasattr(constraint, name) for name in ("token_class", "next_state", "min_left")):
+        raise ValueError("constraint must be a token automaton with token_class, next_state and min_left tables, got %r"
+                         % (constraint,))
+    return constraint
+
+
 def _replicate(nosup: torch.Tensor, num_samples: int) -> torch.Tensor:
     """The unsupervised index list with every question K times, question-major (sampled row q * K + k): every pass gathers
     its rows through this list, and the sampling decoder draws per row POSITION, so the replicas get different programs."""
@@ -130,6 +139,10 @@ class _TrainerBase(StepBase):
     # False, or anything else: the eager passes below (one autograd node per kernel -- the plan's reference in
     # tests/test_seq_plan_gpu.py)
     use_plan = os.environ.get("PNMN_SEQ_PLAN", "1") != "0"
+    # a token automaton (``check_constraint``): the generator samples and is scored under the grammar-normalised
+    # distribution q_c (``decoding_strategy="grammar_sampling"``).  The plan runs fixed launch lists without the grammar
+    # kernels, so such an iteration takes the eager passes, its two generator decodes as single launches.  None: as ever
+    constraint = None
 
     def _plan(self, dev, n: int, m: int, tq: int, tp: int):
         """The cached plan for this shape signature (None: not plannable -- remembered, so the check is paid once)."""
@@ -154,7 +167,8 @@ class _TrainerBase(StepBase):
     def _planned_encoder_workgroups(self, batch, sup, nosup) -> int:
         """Workgroups of the generator's encoder launch of this batch's plan (0: no plan, or a launch per layer)."""
         dev = batch["question"].device
-        if not (self.use_plan and sup.numel() and nosup.numel() and dev.type == "cuda" and batch["program"].device == dev):
+        if not (self.use_plan and self.constraint is None and sup.numel() and nosup.numel() and dev.type == "cuda"
+                and batch["program"].device == dev):
             return 0
         plan = self._plan(dev, int(nosup.numel()), int(sup.numel()), int(batch["question"].size(1)), int(batch["program"].size(1)))
         return plan.pg_encoder_workgroups if plan is not None else 0
@@ -299,8 +313,12 @@ class _TrainerBase(StepBase):
             out["n_nosup"], out["n_sup"] = 0, 0
             return out
         question = batch["question"]
-        if (self.use_plan and n_sup and n_nosup and prior and reconstruct and dev.type == "cuda" and torch.is_grad_enabled()
-                and self.pg.training and self.qr.training and batch["program"].device == dev):
+        grammar = self.constraint
+        # the generator's decodes: under a grammar, sampled from and scored under q_c
+        pg_decode = dict(decoding_strategy="sampling") if grammar is None else dict(decoding_strategy="grammar_sampling",
+                                                                                    constraint=grammar)
+        if (self.use_plan and grammar is None and n_sup and n_nosup and prior and reconstruct and dev.type == "cuda"
+                and torch.is_grad_enabled() and self.pg.training and self.qr.training and batch["program"].device == dev):
             plan = self._plan(dev, n_nosup, n_sup, int(question.size(1)), int(batch["program"].size(1)))
             if plan is not None:
                 return self._planned_passes(plan, batch, sup_d, nosup_d, host_programs, after_sampling, before_prior, after_encode)
@@ -328,7 +346,7 @@ class _TrainerBase(StepBase):
         group = None  # (the generator's prepared decodes and their launch: their graph node is created with the reconstructor's)
         if n_nosup:
             prep_s = None
-            if n_sup and dev.type == "cuda":
+            if n_sup and dev.type == "cuda" and grammar is None:
                 # the generator's sampling decode and its supervised (teacher-forced) decode start from the same encoder
                 # pass and are independent: one launch each way for both -- the persistent decoder kernels are latency
                 # bound, so the supervised pass rides along for free while the sampling pass, which the step's critical
@@ -351,7 +369,7 @@ class _TrainerBase(StepBase):
                     paired = True
             if not paired:
                 drawn = prep_s["meta"]["seed"] if prep_s is not None else None  # (a prepared pass has drawn its seed)
-                out["pg"] = self.pg.decode(state_nosup, None, "sampling", seed=drawn)
+                out["pg"] = self.pg.decode(state_nosup, None, seed=drawn, **pg_decode)
             if group is None:
                 z = out["pg"]["predictions"]
             out["programs"] = z
@@ -361,7 +379,13 @@ class _TrainerBase(StepBase):
                 out["after_sampling"] = after_sampling()
         # per-row losses; "qr_rows" = the sampled rows' reconstruction losses followed by the supervised rows'
         if n_sup and not paired:
-            out["pg_sup_rows"] = self.pg.decode(state_sup, prog_sup, "sampling", need_predictions=False)["loss"]
+            o_sup = self.pg.decode(state_sup, prog_sup, need_predictions=False, **pg_decode)
+            out["pg_sup_rows"] = o_sup["loss"]
+        if grammar is not None:
+            # (device scalars: no synchronisation) how much of q the grammar keeps on the samples; supervised targets it refuses
+            zero = torch.zeros((), device=dev)
+            out["grammar"] = {"log_mass": out["pg"]["grammar_log_mass"].mean() if n_nosup else zero,
+                              "outside": o_sup["grammar_outside"].sum() if n_sup else zero.int()}
         if group is not None:
             from probnmn.modules.seq2seq_base import decode_group
 
@@ -417,12 +441,13 @@ class QuestionCodingStep(_TrainerBase):
     def __init__(self, program_generator, question_reconstructor, program_prior, objective: str = "ours",
                  alpha: float = 100.0, beta: float = 0.1, delta: float = 0.99, lr: float = 1e-3,
                  weight_decay: float = 0.0, lr_gamma: float = 0.5, lr_patience: int = 3, num_samples: int = 1,
-                 baseline=None):
+                 baseline=None, constraint=None):
         if objective not in ("ours", "baseline"):
             raise ValueError("objective must be 'ours' or 'baseline'")
         self.num_samples, self.baseline = _estimator(num_samples, baseline)
         if objective == "baseline" and self.num_samples > 1:
             raise ValueError("the 'baseline' objective samples no programs: num_samples must be 1")
+        self.constraint = check_constraint(constraint)
         self.pg, self.qr, self.prior = program_generator, question_reconstructor, program_prior
         self.objective, self.alpha = objective, alpha
         self.prior.eval()
@@ -457,10 +482,14 @@ class QuestionCodingStep(_TrainerBase):
             if p["n_nosup"]:
                 out["elbo"] = {k: stats[k] for k in self._elbo_keys()}
                 out["programs"] = p["programs"]
+            if "grammar" in p:
+                out["grammar"] = p["grammar"]
             self._finish(loss)
             out["objective"] = loss.detach()
             return out
         self._split_means(p)
+        if "grammar" in p:
+            out["grammar"] = p["grammar"]
         if "pg_sup" in p:
             loss = loss + w_sup * (self.alpha if ours else 1.0) * (p["pg_sup"] + p["qr_sup"])
             out["loss"] = {"program_generation_gt": p["pg_sup"].detach(), "question_reconstruction_gt": p["qr_sup"].detach()}
@@ -480,12 +509,13 @@ class JointTrainingStep(_TrainerBase):
     def __init__(self, program_generator, question_reconstructor, program_prior, nmn, objective: str = "ours",
                  alpha: float = 100.0, beta: float = 0.1, gamma: float = 1.0, delta: float = 0.99,
                  lr: float = 1e-6, weight_decay: float = 0.0, lr_gamma: float = 0.5, lr_patience: int = 3,
-                 num_samples: int = 1, baseline=None):
+                 num_samples: int = 1, baseline=None, constraint=None):
         if objective not in ("ours", "baseline"):
             raise ValueError("objective must be 'ours' or 'baseline'")
         self.num_samples, self.baseline = _estimator(num_samples, baseline)
         if objective == "baseline" and self.num_samples > 1:
             raise ValueError("the reference's 'baseline' objective draws one program per question: num_samples must be 1")
+        self.constraint = check_constraint(constraint)
         self.pg, self.qr, self.prior, self.nmn = program_generator, question_reconstructor, program_prior, nmn
         self.objective, self.alpha, self.gamma = objective, alpha, gamma
         self.prior.eval()
@@ -646,6 +676,8 @@ class JointTrainingStep(_TrainerBase):
                 copied.synchronize()  # waits for the sampling decode only, not for the work queued after it
                 self.blocked_seconds += time.perf_counter() - t0
                 nmn_out = self.nmn(images, programs_host, answers, started=started, trunk_stream=side, rows=rows_d)
+            if "grammar" in p:
+                out["grammar"] = p["grammar"]
             if ours and dev.type == "cuda":
                 loss, stats = self._fused_objective(p, nmn_out["loss"], w_sup, w_nosup, self.alpha, self.gamma)
                 _hip.mark("objective combined")
@@ -669,6 +701,8 @@ class JointTrainingStep(_TrainerBase):
         else:
             p = self._seq2seq_passes(batch, sup_d, nosup_d, supervised=ours, sampled=False, prior=False)
             self._split_means(p)
+            if "grammar" in p:
+                out["grammar"] = p["grammar"]
             if not self.elbo.leave_one_out:  # (leave-one-out: no rank has a baseline collective to join)
                 self.elbo._reinforce.idle(dev)
             for a in self.optimizer.arenas:  # no NMN backward on this rank, which is what zeroes them

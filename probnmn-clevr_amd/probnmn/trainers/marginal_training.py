@@ -21,15 +21,20 @@ from probnmn.modules.seq2seq_base import Seq2SeqBase
 from .joint_training import _TrainerBase
 
 
-def marginal_joint_options(beam_size, constrained, without_replacement, answer_weight, train_modules) -> float:
+def marginal_joint_options(beam_size, constrained, without_replacement, answer_weight, train_modules,
+                           grammar_normalised=False) -> float:
     """The argument rules of ``MarginalJointStep``; touches no device and no model.  Returns ``answer_weight`` as a float;
-    ``ValueError`` otherwise.  ``beam_size``: one of ``Seq2SeqBase.BEAM_SIZES``; ``constrained``, ``without_replacement`` and
-    ``train_modules``: booleans; ``answer_weight``: a finite number."""
+    ``ValueError`` otherwise.  ``beam_size``: one of ``Seq2SeqBase.BEAM_SIZES``; ``constrained``, ``without_replacement``,
+    ``train_modules`` and ``grammar_normalised``: booleans; ``answer_weight``: a finite number.  ``grammar_normalised``
+    scores the candidates under the automaton the search ran under: it needs ``constrained``."""
     if isinstance(beam_size, bool) or not isinstance(beam_size, int) or beam_size not in Seq2SeqBase.BEAM_SIZES:
         raise ValueError("beam_size must be one of %s, got %r" % (Seq2SeqBase.BEAM_SIZES, beam_size))
-    for name, flag in (("constrained", constrained), ("without_replacement", without_replacement), ("train_modules", train_modules)):
+    for name, flag in (("constrained", constrained), ("without_replacement", without_replacement), ("train_modules", train_modules),
+                       ("grammar_normalised", grammar_normalised)):
         if not isinstance(flag, bool):
             raise ValueError("%s must be True or False, got %r" % (name, flag))
+    if grammar_normalised and not constrained:
+        raise ValueError("grammar_normalised=True scores the candidates under the validity rule: it needs constrained=True")
     try:
         w_a = float(answer_weight)
     except (TypeError, ValueError):
@@ -64,6 +69,10 @@ class MarginalJointStep(_TrainerBase):
     5. backward, the data-parallel gradient all-reduce, the clamp to [-5, 5] and Adam over both models (the generator alone
        without ``train_modules``), as ``ModuleTrainingStep`` runs them.
 
+    ``grammar_normalised`` (needs ``constrained``): step 2 passes the search's automaton to ``teacher_forced_logits``, so
+    q above is q_c, the generator's distribution renormalised over the valid programs (``probnmn.modules.grammar``), and L_g
+    sums q_c over the candidates: mass the generator puts on invalid programs no longer counts against the candidate set.
+
     ``step`` reports ``"loss"``, ``"support"`` (the mean number of candidates that count per question), ``"rows"`` (R) and
     ``"posterior_on_map"`` (the mean over the supported questions of the largest posterior share: how peaked the answer
     makes the candidates; NaN without a supported question).  Candidates are searched, never sampled with replacement:
@@ -71,9 +80,11 @@ class MarginalJointStep(_TrainerBase):
 
     def __init__(self, program_generator, nmn, beam_size: int = 4, constrained: bool = False, without_replacement: bool = False,
                  answer_weight: float = 1.0, train_modules: bool = True, lr: float = 1e-4, weight_decay: float = 0.0,
-                 lr_gamma: float = 0.5, lr_patience: int = 1000000):
-        self.answer_weight = marginal_joint_options(beam_size, constrained, without_replacement, answer_weight, train_modules)
+                 lr_gamma: float = 0.5, lr_patience: int = 1000000, grammar_normalised: bool = False):
+        self.answer_weight = marginal_joint_options(beam_size, constrained, without_replacement, answer_weight, train_modules,
+                                                    grammar_normalised)
         self.beam_size, self.constrained, self.without_replacement = beam_size, constrained, without_replacement
+        self.grammar_normalised = grammar_normalised
         self.train_modules = train_modules
         self._constraint = None
         self._copies = hypothesis_rows.HostCopies()
@@ -134,7 +145,8 @@ class MarginalJointStep(_TrainerBase):
                     "posterior_on_map": torch.full((), float("nan"), dtype=torch.float32, device=dev)}
         rows_dev = _hip.to_device(question_rows, dev).view(torch.long)
         logits, targets = self.pg.teacher_forced_logits(question.index_select(0, rows_dev),
-                                                        candidate_targets(programs.to(dev), self.pg), differentiable=True)
+                                                        candidate_targets(programs.to(dev), self.pg), differentiable=True,
+                                                        constraint=self._constraint if self.grammar_normalised else None)
         with torch.set_grad_enabled(self.train_modules):
             log_answer = self.nmn.answer_log_likelihood(batch["image"], programs, question_rows, batch["answer"])["log_answer"]
         group_start = hypothesis_rows.group_start_on_device(question_rows, G, dev)
