@@ -183,7 +183,7 @@ int pnmn_dot1_sigmoid_bwd(const pnmn_dot1_item* items, int n_items, int HW, void
  * SameModule                                         nmn_modules.py:200-208
  *   j = argmax_p attn[p] (first maximum, as max_pool2d); v[c] = feats[j][c]
  *   out[p] = sigmoid(b + sum_c w[c]*feats[p][c]*v[c] + w[128]*attn[p])
- * backward accumulates dfeats (+=), writes dattn, accumulates dw[129]/db with atomics.
+ * backward accumulates dfeats (+=) and dattn (+=; may be NULL), accumulates dw[129]/db with atomics.
  * ------------------------------------------------------------------------------------------- */
 typedef struct pnmn_same_item {
     const float* feats;  /* [HW][128] */
@@ -193,7 +193,7 @@ typedef struct pnmn_same_item {
     float*       out;    /* [HW]      */
     const float* dout;   /* bwd */
     float*       dfeats; /* bwd, += */
-    float*       dattn;  /* bwd, written */
+    float*       dattn;  /* bwd, += (may be NULL) */
     float*       dw;     /* bwd, atomics */
     float*       db;     /* bwd, atomics */
 } pnmn_same_item;        /* 80 bytes */
@@ -219,7 +219,7 @@ int pnmn_minmax_fwd(const pnmn_minmax_item* items, int n_items, int HW, int C, v
 int pnmn_minmax_bwd(const pnmn_minmax_item* items, int n_items, int HW, int C, void* stream);
 
 /* Backward of `feats * attn.repeat(1,C,1,1)` (nmn_modules.py:83,120,161):
- *   dattn[p] = sum_c dx[p][c]*feats[p][c]  (written);  dfeats[p][c] += dx[p][c]*attn[p]
+ *   dattn[p] += sum_c dx[p][c]*feats[p][c];  dfeats[p][c] += dx[p][c]*attn[p]   (both with atomics: items may share maps)
  * attn == NULL means the all-ones attention `scene` produces: dfeats += dx, no dattn. */
 typedef struct pnmn_maskbwd_item {
     const float* dx;
@@ -312,7 +312,7 @@ int pnmn_maxpool2_flatten_bwd(const float* in, const float* dout, float* din, in
 /* ---------------------------------------------------------------------------------------------
  * Answer loss                                                          nmn.py:245-269
  *   logprobs = log_softmax(logits[b]); pred[b] = argmax (first); loss[b] = -logprobs[answer[b]]
- *   (answers == NULL: loss[b] = -max logprob); invalid rows: pred = unknown_index, loss = 3.33
+ *   (answers == NULL: loss[b] = -max logprob, dlogits = 0); invalid rows: pred = unknown_index, loss = 3.33
  *   dlogits[b] = (softmax - onehot) * scale for valid rows, 0 for invalid rows.
  * ------------------------------------------------------------------------------------------- */
 int pnmn_answer_loss(const float* logits, const int64_t* answers, const int32_t* valid,
@@ -654,6 +654,9 @@ int pnmn_joint_objective(const float* pg, const float* qr, const float* prior, c
  * module_training_trainer.py:94-96, joint_training_trainer.py:182-188, _trainer.py:103-108,193
  * torch.optim.Adam semantics (no amsgrad): g = clamp(g) + wd*p; m,v EMA; bias correction per
  * item; p -= lr * mhat / (sqrt(vhat) + eps).
+ * lr, beta1, beta2, eps, weight_decay and clamp are rounded to float32 on entry and the update is this formula AT THE
+ * ROUNDED VALUES, in float32: the weight of g^2 is 1 - (float)beta2 (for 0.999: 0.99998713e-3, where torch rounds 1 - beta2
+ * itself: 1.3e-5 of the weight apart -- the same update for a beta2 that differs by 1.3e-8).
  * ------------------------------------------------------------------------------------------- */
 typedef struct pnmn_adam_item {
     float*       param;

@@ -13,6 +13,7 @@
 #include "lds_optin.h"
 #include "global_ptr.h"
 #include "pointwise_body.h"
+#include "pointwise_plan.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -165,25 +166,28 @@ __global__ __launch_bounds__(256) void transpose_weights_kernel(const pnmn_wtran
     const int tiles_ci = (it.cin + 31) / 32;
     const int tiles_co = (it.cout + 31) / 32;
     const int per_tap = tiles_ci * tiles_co;
-    // blockIdx.x enumerates (tap, co tile, ci tile); items may have fewer tiles than the grid
-    if ((int)blockIdx.x >= per_tap * it.ntaps) return;
-    const int tap = blockIdx.x / per_tap;
-    const int rem = blockIdx.x % per_tap;
-    const int co0 = (rem / tiles_ci) * 32;
-    const int ci0 = (rem % tiles_ci) * 32;
     const int tx = threadIdx.x & 31;
     const int ty = threadIdx.x >> 5;  // 0..7
-    for (int r = ty; r < 32; r += 8) {
-        const int co = co0 + r, ci = ci0 + tx;
-        if (co < it.cout && ci < it.cin)
-            tile[r][tx] = it.src[((size_t)co * it.ntaps + tap) * it.cin + ci];
-    }
-    __syncthreads();
-    const int rt = it.ntaps - 1 - tap;
-    for (int r = ty; r < 32; r += 8) {
-        const int ci = ci0 + r, co = co0 + tx;
-        if (co < it.cout && ci < it.cin)
-            it.dst[((size_t)ci * it.ntaps + rt) * it.cout + co] = tile[tx][r];
+    // a tile index enumerates (tap, co tile, ci tile); the workgroups of an item walk its tiles with the stride of the
+    // grid -- an item may have fewer tiles than the grid or more (the index is uniform in the workgroup: so are the barriers)
+    for (int t = blockIdx.x; t < per_tap * it.ntaps; t += gridDim.x) {
+        const int tap = t / per_tap;
+        const int rem = t % per_tap;
+        const int co0 = (rem / tiles_ci) * 32;
+        const int ci0 = (rem % tiles_ci) * 32;
+        for (int r = ty; r < 32; r += 8) {
+            const int co = co0 + r, ci = ci0 + tx;
+            if (co < it.cout && ci < it.cin)
+                tile[r][tx] = it.src[((size_t)co * it.ntaps + tap) * it.cin + ci];
+        }
+        __syncthreads();
+        const int rt = it.ntaps - 1 - tap;
+        for (int r = ty; r < 32; r += 8) {
+            const int ci = ci0 + r, co = co0 + tx;
+            if (co < it.cout && ci < it.cin)
+                it.dst[((size_t)ci * it.ntaps + rt) * it.cout + co] = tile[tx][r];
+        }
+        __syncthreads();  // (the next tile overwrites `tile`)
     }
 }
 
@@ -454,13 +458,9 @@ inline int last_error() { return (int)hipGetLastError(); }
 
 #define STREAM(s) static_cast<hipStream_t>(s)
 
-// pixels per workgroup of the layout kernels: the whole map when 64 channels of it fit the LDS
-// budget (14x14), otherwise the smallest number of equal chunks that do (28x28: two of 392)
-static int layout_chunk(int HW) {
-    int parts = 1;
-    while ((size_t)64 * ((HW + parts - 1) / parts + 1) * sizeof(float) > 112 * 1024) ++parts;
-    return (HW + parts - 1) / parts;
-}
+// (the launch shapes -- layout_chunk, pool_band, the even backward's band, the gather's parts: pointwise_plan.h)
+using pnmn::layout_chunk;
+using pnmn::pool_band;
 
 template <bool TO_NHWC>
 static int launch_layout(const float* src, float* dst, int n, int Cn, int HW, void* stream, const int64_t* rows) {
@@ -473,13 +473,6 @@ static int launch_layout(const float* src, float* dst, int n, int Cn, int HW, vo
     hipLaunchKernelGGL(layout_kernel<TO_NHWC>, dim3((Cn + 63) / 64, n, (HW + PT - 1) / PT), dim3(256), lds,
                        STREAM(stream), src, dst, Cn, HW, PT, rows);
     return last_error();
-}
-
-// image rows per workgroup of the max-pool kernels (even; [rows*W][65] floats within the LDS budget)
-static int pool_band(int H, int W) {
-    int rb = (H + 1) & ~1;
-    while (rb > 2 && (size_t)rb * W * 65 * sizeof(float) > 112 * 1024) rb = ((rb / 2) + 1) & ~1;
-    return rb;
 }
 
 // Backward of the ReLU-gated 2x2 max-pool for EVEN maps (14x14, 28x28 -- every shape the engine runs): only the pooled
@@ -543,10 +536,10 @@ template <bool BWD>
 static int launch_pool(const float* in, const float* dout, float* out, int n, int H, int W, int Cn, void* stream) {
     if (n <= 0) return 0;
     if (!in || !out || (BWD && !dout) || (Cn % 64) != 0 || H < 2 || W < 2) return PNMN_EINVAL;
-    if (BWD && (H % 2) == 0 && (W % 2) == 0) {
-        const int PRB = (H / 2) * (W / 2) <= 64 ? H / 2 : 7;  // pooled rows per workgroup: 14x14 all 7, 28x28 two bands of 7
+    if (BWD && pnmn::pool_bwd_takes_even(H, W)) {  // (an even map whose band outgrows 64 KB of LDS takes the generic kernel)
+        const int PRB = pnmn::pool_bwd_even_rows(H, W);  // pooled rows per workgroup: 14x14 all 7, 28x28 two bands of 7
         hipLaunchKernelGGL(maxpool_bwd_even_kernel, dim3(Cn / 64, n, (H / 2 + PRB - 1) / PRB), dim3(256),
-                           (size_t)PRB * (W / 2) * 65 * sizeof(float), STREAM(stream), in, dout, out, H, W, Cn, PRB);
+                           pnmn::pool_bwd_even_lds(H, W), STREAM(stream), in, dout, out, H, W, Cn, PRB);
         return last_error();
     }
     const int RB = pool_band(H, W);
@@ -615,9 +608,7 @@ int pnmn_mask_bwd(const pnmn_maskbwd_item* items, int n_items, int HW, void* str
 int pnmn_feat_grad_gather(const pnmn_maskbwd_item* items, float* gfeat, int n_items, int n_examples, int HW, void* stream) {
     if (n_items <= 0 || n_examples <= 0) return 0;
     if (!items || !gfeat || HW <= 0) return PNMN_EINVAL;
-    // enough workgroups to fill the chip at small batches: pixel ranges of >= 14 rows' worth
-    int parts = 1;
-    while (n_examples * parts < 512 && parts < 8 && HW / (parts * 2) >= 24) parts *= 2;
+    const int parts = pnmn::gather_parts(n_examples, HW);
     hipLaunchKernelGGL(feat_grad_gather_kernel, dim3(n_examples, parts), dim3(256), 0, STREAM(stream), items, n_items, gfeat, HW);
     return last_error();
 }
@@ -639,10 +630,9 @@ int pnmn_set_rows(const pnmn_axpy_item* items, int n_items, void* stream) {
 int pnmn_transpose_weights(const pnmn_wtrans_item* items, int n_items, void* stream) {
     if (n_items <= 0) return 0;
     if (!items) return PNMN_EINVAL;
-    // grid.x covers the largest supported weight: 9 taps x (1024/32) x (1024/32) tiles would be
-    // wasteful; the caller's weights are at most [1024][1][128] / [128][9][128] / [128][1][256].
-    const int max_tiles = 9 * 4 * 4 > 32 * 8 ? 9 * 4 * 4 : 32 * 8;
-    hipLaunchKernelGGL(transpose_weights_kernel, dim3(max_tiles, 1, n_items), dim3(256), 0,
+    // grid.x covers the engine's weights ([1024][1][128]: 256 tiles, [128][9][128]: 144, [128][1][256]: 32) in one pass;
+    // the items live in device memory, so a larger weight cannot be sized for here: its workgroups walk the rest.
+    hipLaunchKernelGGL(transpose_weights_kernel, dim3(pnmn::WTRANS_GRID, 1, n_items), dim3(256), 0,
                        STREAM(stream), items);
     return last_error();
 }
