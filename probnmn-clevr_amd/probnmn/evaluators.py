@@ -1082,3 +1082,78 @@ def sample_programs(program_prior, vocabulary, num_samples: int, max_sequence_le
             record["program_valid"] = bool(valid[i])
         records.append(record)
     return records
+
+
+@torch.no_grad()
+def evaluate_question_evidence(program_generator, question_reconstructor, program_prior, batches: Iterable[Dict[str, torch.Tensor]],
+                               num_samples: int = 8, constraint=None) -> Dict[str, Any]:
+    """A lower bound on log p(x) of every question under the generative model p(x | z) p(z), importance sampled with the
+    generator (not in the reference, which has no figure that compares checkpoints' evidence):
+        bound_g = logsumexp_k(log w_k) - log K,   log w_k = log p(x_g | z_k) + log p(z_k) - log q(z_k | x_g),   z_k ~ q(. | x_g)
+    with every term a true SUM over tokens (``probnmn.modules.importance_weighted``, beta = 1): E[bound_g] <= log p(x_g), it
+    tightens as ``num_samples`` = K (1 .. 64) grows, and K = 1 is the ELBO.
+
+    Per batch (``"question"`` on the device): ONE sampling decode of the generator over the questions replicated K-fold,
+    question-major (``"sampling"``; with ``constraint``, a token automaton, ``"constrained_sampling"``, scored under the
+    grammar-normalised q_c it draws from), the three scoring passes (``teacher_forced_logits``) and one plain
+    ``pnmn_importance_bound`` launch.  No gradient; the models run in ``eval()`` mode and come back in the mode they were in;
+    no metric of any model moves.  The draw takes its seed from the torch CPU generator (``torch.manual_seed`` makes the
+    call reproducible).
+
+    Returns ``"log_evidence_bound"`` (the mean bound over the questions that count: all K rows with a finite weight),
+    ``"elbo"`` (the mean log w over the same samples: the K = 1 bound), ``"effective_sample_size"`` (mean 1 / sum share^2),
+    ``"questions"`` (how many were evaluated), ``"unsupported"`` (how many of them do not count), ``"bound"`` (fp32, one
+    entry per question in batch order; -inf for a question that does not count) and ``"log_weight"`` (fp32 [questions, K]:
+    log w of every sample)."""
+    from probnmn.modules.importance_weighted import check_samples, importance_weighted_bound
+    from probnmn.trainers.joint_training import check_constraint
+    from probnmn.trainers.marginal_training import candidate_targets
+
+    K = check_samples(num_samples)
+    constraint = check_constraint(constraint)
+    pg, qr, prior = program_generator, question_reconstructor, program_prior
+    models = (pg, qr, prior)
+    was_training = [m.training for m in models]
+    for m in models:
+        m.eval()
+    bounds, weights, sums = [], [], None
+    try:
+        for batch in batches:
+            question = batch["question"]
+            if question.device.type != "cuda":
+                raise _hip.HipLibraryError("evaluate_question_evidence runs on the ROCm device the questions are on (got %s); "
+                                           "there is no CPU path" % question.device)
+            questions = question.repeat_interleave(K, 0) if K > 1 else question
+            if constraint is None:
+                programs = pg(questions, decoding_strategy="sampling")["predictions"]
+            else:
+                programs = pg(questions, decoding_strategy="constrained_sampling", constraint=constraint)["predictions"]
+            targets = candidate_targets(programs, pg)
+            q_logits, q_targets = pg.teacher_forced_logits(questions, targets, constraint=constraint)
+            x_logits, x_targets = qr.teacher_forced_logits(targets, questions)
+            p_logits, p_targets = prior.teacher_forced_logits(targets)
+            loss, stats = importance_weighted_bound((x_logits, x_targets, qr._pad_index), (q_logits, q_targets, pg._pad_index),
+                                                    (p_logits, p_targets, prior._pad_index), samples=K, beta=1.0)
+            counts = stats["support"] == K
+            bound = torch.where(counts, -loss, torch.full_like(loss, -float("inf")))
+            bounds.append(bound)
+            weights.append(stats["log_weight"].view(-1, K))
+            zero = torch.zeros_like(loss)
+            log_w = torch.where(counts.repeat_interleave(K), stats["log_weight"], torch.zeros_like(stats["log_weight"]))
+            part = torch.stack((torch.where(counts, bound, zero).sum().double(), log_w.sum().double() / K,
+                                stats["ess"].sum().double(), counts.sum().double()))
+            sums = part if sums is None else sums + part
+    finally:
+        for m, training in zip(models, was_training):
+            m.train(training)
+    if sums is None:
+        nan = float("nan")
+        return {"log_evidence_bound": nan, "elbo": nan, "effective_sample_size": nan, "questions": 0, "unsupported": 0,
+                "bound": torch.zeros(0), "log_weight": torch.zeros(0, K)}
+    total, elbo, ess, n = sums.tolist()
+    bound = torch.cat(bounds)
+    n = int(n)
+    div = lambda v: v / n if n else float("nan")  # noqa: E731
+    return {"log_evidence_bound": div(total), "elbo": div(elbo), "effective_sample_size": div(ess),
+            "questions": int(bound.numel()), "unsupported": int(bound.numel()) - n, "bound": bound,
+            "log_weight": torch.cat(weights)}

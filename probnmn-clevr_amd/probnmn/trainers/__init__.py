@@ -1,7 +1,7 @@
-"""The training iterations.  Each lives in its own module; ``MarginalJointStep`` is also reachable from here (resolved on
-first use, so importing the package stays as cheap as it was)."""
+"""The training iterations.  Each lives in its own module; ``MarginalJointStep`` and ``ImportanceWeightedCodingStep`` are also
+reachable from here (resolved on first use, so importing the package stays as cheap as it was)."""
 
-__all__ = ["MarginalJointStep"]
+__all__ = ["MarginalJointStep", "ImportanceWeightedCodingStep"]
 
 
 def __getattr__(name):
@@ -9,4 +9,8 @@ def __getattr__(name):
         from .marginal_training import MarginalJointStep
 
         return MarginalJointStep
+    if name == "ImportanceWeightedCodingStep":
+        from .importance_weighted import ImportanceWeightedCodingStep
+
+        return ImportanceWeightedCodingStep
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
