@@ -1157,3 +1157,118 @@ def evaluate_question_evidence(program_generator, question_reconstructor, progra
     return {"log_evidence_bound": div(total), "elbo": div(elbo), "effective_sample_size": div(ess),
             "questions": int(bound.numel()), "unsupported": int(bound.numel()) - n, "bound": bound,
             "log_weight": torch.cat(weights)}
+
+
+@torch.no_grad()
+def evaluate_joint_evidence(program_generator, question_reconstructor, program_prior, nmn, batches: Iterable[Dict[str, torch.Tensor]],
+                            vocabulary=None, num_samples: int = 8, constraint=None, answer_weight: float = 1.0) -> Dict[str, Any]:
+    """A lower bound on log p(x, a | image) of every question and its answer under the generative model
+    p(x | z) p(a | z, image) p(z), importance sampled with the generator, and the answers of that model's POSTERIOR over
+    programs (not in the reference, which answers from the proposal: one program of the generator per question):
+        bound_g = logsumexp_k(log w_k) - log K,   z_k ~ q(. | x_g),
+        log w_k = log p(x_g | z_k) + answer_weight log p(a_g | z_k, image_g) + log p(z_k) - log q(z_k | x_g)
+    with every sequence term a true SUM over tokens (``probnmn.modules.importance_weighted``, beta = 1; an invalid program
+    answers uniformly: log p(a | z) = -log A).  With ``answer_weight`` 1, E[bound_g] <= log p(x_g, a_g | image_g), and it
+    tightens as ``num_samples`` = K (1 .. 64) grows.
+
+    Per batch (``"question"``, ``"answer"`` and ``"image"`` -- feature maps or a ``ResidentRows`` batch -- on the device): ONE
+    sampling decode of the generator over the questions replicated K-fold, question-major (``"sampling"``; with
+    ``constraint``, a token automaton, ``"constrained_sampling"``, scored under the grammar-normalised q_c it draws from),
+    the three scoring passes, ONE module-network pass over the K n sampled rows (``nmn.hypothesis_answer_logits``: each row
+    reads its question's feature map in place), two plain ``pnmn_importance_bound_joint`` launches -- the joint weights, and
+    with the answer's weight 0 the question-only ones, log w^x_k -- and two ``pnmn_answer_marginal`` launches over each
+    question's rows: with log w^x as the row weights, the self-normalised importance-sampling estimate of the generative
+    model's answer  p(a | x, image) ~= sum_k share^x_k p(a | z_k, image), and with uniform weights the proposal's (invalid
+    programs are left out of both sums).  No gradient; the models run in ``eval()`` mode and come back in the mode they were
+    in; no metric of any model moves.  The draw takes its seed from the torch CPU generator.  ``vocabulary`` is not needed
+    and only kept for symmetry with ``predict_answers``.
+
+    Returns ``"log_joint_evidence_bound"`` (the mean bound on log p(x, a | image) over the questions whose K rows all have a
+    finite joint weight), ``"log_evidence_bound"`` (the mean bound on log p(x) from the same samples, over the same
+    questions), ``"log_answer_given_question"`` (their difference: an ESTIMATE of log p(a | x, image), the difference of two
+    lower bounds, not itself a bound), ``"effective_sample_size"`` (of the joint weights), ``"posterior_answer_accuracy"``
+    (the arg-max of sum_k share^x_k p(. | z_k, image) against the answer), ``"proposal_answer_accuracy"`` (the same with
+    uniform weights) -- both over ALL the questions asked, those that do not count included, where the three figures before
+    them are means over the questions that count --, ``"questions"``, ``"unsupported"`` (questions that do not count), ``"bound"`` (fp32, one entry per
+    question in batch order; -inf for one that does not count) and ``"log_weight"`` (fp32 [questions, K]: the joint log w of
+    every sample)."""
+    from probnmn.modules.importance_weighted import check_answer_weight, check_samples, joint_importance_weighted_bound
+    from probnmn.trainers.joint_training import check_constraint
+    from probnmn.trainers.marginal_training import candidate_targets
+
+    K = check_samples(num_samples)
+    constraint = check_constraint(constraint)
+    gamma = check_answer_weight(answer_weight)
+    pg, qr, prior = program_generator, question_reconstructor, program_prior
+    models = (pg, qr, prior, nmn)
+    was_training = [m.training for m in models]
+    for m in models:
+        m.eval()
+    bounds, weights, sums = [], [], None
+    try:
+        for batch in batches:
+            question = batch["question"]
+            if question.device.type != "cuda":
+                raise _hip.HipLibraryError("evaluate_joint_evidence runs on the ROCm device the questions are on (got %s); "
+                                           "there is no CPU path" % question.device)
+            dev, n = question.device, int(question.size(0))
+            questions = question.repeat_interleave(K, 0) if K > 1 else question
+            if constraint is None:
+                programs = pg(questions, decoding_strategy="sampling")["predictions"]
+            else:
+                programs = pg(questions, decoding_strategy="constrained_sampling", constraint=constraint)["predictions"]
+            targets = candidate_targets(programs, pg)
+            q_logits, q_targets = pg.teacher_forced_logits(questions, targets, constraint=constraint)
+            x_logits, x_targets = qr.teacher_forced_logits(targets, questions)
+            p_logits, p_targets = prior.teacher_forced_logits(targets)
+            qrows = np.repeat(np.arange(n, dtype=np.int64), K)
+            answered = nmn.hypothesis_answer_logits(batch["image"], programs, qrows)
+            logits, valid = answered["answer_logits"].contiguous(), answered["valid"]
+            answers = batch["answer"].to(device=dev, dtype=torch.long)
+            terms = ((x_logits, x_targets, qr._pad_index), (q_logits, q_targets, pg._pad_index), (p_logits, p_targets, prior._pad_index))
+            loss, stats = joint_importance_weighted_bound(*terms, answer=(logits, answers, valid), samples=K, beta=1.0,
+                                                          answer_weight=gamma, unknown_index=int(nmn._unknown_answer))
+            x_loss, x_stats = joint_importance_weighted_bound(*terms, answer=(logits, answers, valid), samples=K, beta=1.0,
+                                                              answer_weight=0.0, unknown_index=int(nmn._unknown_answer))
+            # the answers of the posterior (rows weighed by the question-only log w) and of the proposal (uniform weights)
+            A = int(logits.size(1))
+            group_start = hypothesis_rows.group_start_on_device(qrows, n, dev)
+            answered_by = {}
+            for name, row_weights in (("posterior", x_stats["log_weight"]), ("proposal", None)):
+                m_out = {"predictions": torch.empty(n, dtype=torch.long, device=dev),
+                         "log_probabilities": torch.empty(n, A, dtype=torch.float32, device=dev),
+                         "hypothesis_predictions": torch.empty(n * K, dtype=torch.long, device=dev),
+                         "hypothesis_weights": torch.empty(n * K, dtype=torch.float32, device=dev),
+                         "support": torch.empty(n, dtype=torch.int32, device=dev)}
+                _hip.check(_hip.lib().pnmn_answer_marginal(
+                    logits.data_ptr(), valid.data_ptr(), 0 if row_weights is None else row_weights.data_ptr(), group_start.data_ptr(),
+                    m_out["log_probabilities"].data_ptr(), m_out["predictions"].data_ptr(), m_out["hypothesis_predictions"].data_ptr(),
+                    m_out["hypothesis_weights"].data_ptr(), m_out["support"].data_ptr(), n, n * K, A, nmn._unknown_answer,
+                    _hip.stream_ptr(dev)), "answer_marginal")
+                answered_by[name] = (m_out["predictions"] == answers).sum().double()
+            counts = stats["support"] == K
+            bound = torch.where(counts, -loss, torch.full_like(loss, -float("inf")))
+            bounds.append(bound)
+            weights.append(stats["log_weight"].view(-1, K))
+            zero = torch.zeros_like(loss)
+            # (a question whose joint weights are finite has finite question-only weights: the same terms, one fewer)
+            part = torch.stack((torch.where(counts, bound, zero).sum().double(), torch.where(counts, -x_loss, zero).sum().double(),
+                                stats["ess"].sum().double(), counts.sum().double(), answered_by["posterior"],
+                                answered_by["proposal"]))
+            sums = part if sums is None else sums + part
+    finally:
+        for m, training in zip(models, was_training):
+            m.train(training)
+    if sums is None:
+        nan = float("nan")
+        return {"log_joint_evidence_bound": nan, "log_evidence_bound": nan, "log_answer_given_question": nan,
+                "effective_sample_size": nan, "posterior_answer_accuracy": nan, "proposal_answer_accuracy": nan, "questions": 0,
+                "unsupported": 0, "bound": torch.zeros(0), "log_weight": torch.zeros(0, K)}
+    joint, evidence, ess, n, posterior, proposal = sums.tolist()
+    bound = torch.cat(bounds)
+    n, asked = int(n), int(bound.numel())
+    div = lambda v: v / n if n else float("nan")  # noqa: E731
+    return {"log_joint_evidence_bound": div(joint), "log_evidence_bound": div(evidence),
+            "log_answer_given_question": div(joint) - div(evidence), "effective_sample_size": div(ess),
+            "posterior_answer_accuracy": posterior / max(asked, 1), "proposal_answer_accuracy": proposal / max(asked, 1),
+            "questions": asked, "unsupported": asked - n, "bound": bound, "log_weight": torch.cat(weights)}

@@ -691,6 +691,32 @@ class NeuralModuleNetwork(nn.Module):
         log_answer = torch.where(valid != 0, -loss, torch.full_like(loss, -float("inf")))
         return {"log_answer": log_answer, "hypothesis_predictions": predictions}
 
+    def hypothesis_answer_logits(self, features, programs: torch.Tensor, question_rows):
+        """The answer logits of every hypothesis row, WITH a graph and without a loss: what a loss that weighs a question's
+        programs itself takes (``joint_importance_weighted_bound``, whose kernel computes log p(a | z, image) and its
+        gradient from them).  Not in the reference, which scores one sampled program per question (nmn.py:245-269).
+
+        ``features``, ``programs`` [R, T], ``question_rows`` [R]: the arguments of ``marginal_answer_loss``, under its rules.
+        The NMN runs over the R hypothesis rows in ONE trunk pass with gradient tracking, as in ``answer_log_likelihood``:
+        each row reads its question's feature map where it lies, the stem runs once per hypothesis row.  No metric moves,
+        and the ``train()`` / ``eval()`` state is not touched.
+
+        Returns ``"answer_logits"`` fp32 [R, A] (differentiable) and ``"valid"`` int32 [R] (0 for a row whose program is
+        invalid: its logits mean nothing)."""
+        from probnmn import _hip
+        from probnmn.data.feature_store import ResidentRows
+
+        dev, G, R, A, programs, qrows = self._hypothesis_arguments(features, programs, question_rows)
+        if R == 0 or G == 0:  # (no row anywhere: nothing to run the network on)
+            return {"answer_logits": torch.empty(0, A, dtype=torch.float32, device=dev),
+                    "valid": torch.empty(0, dtype=torch.int32, device=dev)}
+        if isinstance(features, ResidentRows):
+            trunk = self.forward_trunk(features.subset(qrows), programs)
+        else:
+            trunk = self.forward_trunk(features, programs, rows=_hip.to_device(qrows, dev).view(torch.long))
+        logits, _, valid = self._answer_logits(trunk)
+        return {"answer_logits": logits, "valid": valid}
+
     def begin(self, features: torch.Tensor, rows: Optional[torch.Tensor] = None):
         """Launch the program-independent part of ``forward`` (feature layout + stem) ahead of time;
         pass the returned token as ``forward(..., started=token)`` with the same ``features``.  ``rows`` (int64

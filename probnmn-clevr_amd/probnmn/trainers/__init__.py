@@ -1,7 +1,8 @@
-"""The training iterations.  Each lives in its own module; ``MarginalJointStep`` and ``ImportanceWeightedCodingStep`` are also
-reachable from here (resolved on first use, so importing the package stays as cheap as it was)."""
+"""The training iterations.  Each lives in its own module; ``MarginalJointStep``, ``ImportanceWeightedCodingStep`` and
+``ImportanceWeightedJointStep`` are also reachable from here (resolved on first use, so importing the package stays as cheap
+as it was)."""
 
-__all__ = ["MarginalJointStep", "ImportanceWeightedCodingStep"]
+__all__ = ["MarginalJointStep", "ImportanceWeightedCodingStep", "ImportanceWeightedJointStep"]
 
 
 def __getattr__(name):
@@ -13,4 +14,8 @@ def __getattr__(name):
         from .importance_weighted import ImportanceWeightedCodingStep
 
         return ImportanceWeightedCodingStep
+    if name == "ImportanceWeightedJointStep":
+        from .importance_weighted import ImportanceWeightedJointStep
+
+        return ImportanceWeightedJointStep
     raise AttributeError("module %r has no attribute %r" % (__name__, name))
